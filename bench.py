@@ -17,11 +17,18 @@ sway -1, seeded random-init weights (AdaLN-zero tensors re-randomised, SURVEY F8
 Inputs are resident in HBM when the timed region starts; every pass ends with the asynchronous copy of its waveform into
 pinned host memory (wall = mel front-end -> ODE loop -> Vocos -> host copy).
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times --steps passes and prints ONE JSON line (rank 0) with the contract fields (`metric`,
+`value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).  --dump-outputs DIR then also writes what the last timed
+pass returned (the stitched mel and the waveform) as DIR/<name>.npy, float32; inputs and weights are seeded, so two builds
+run with the same arguments can be compared output for output.
+
+--full adds every other leg to the line (each as before; --no-* switches still drop single legs):
+  concurrent     -- (1 GPU, C2 / C3 / C5) --streams host threads sampling batch-1 utterances concurrently on one model;
+  scaling_c4     -- (C2) the fixed-total C4 strong-scaling leg (--c4-total utterances, --c4-workers threads per rank);
   roofline       -- the dominant kernel of the workload (bf16 MFMA GEMM class chosen by total time) timed per launch with
                     HIP events on the launch stream during an eager, in-situ pass of the same workload; `traffic` from the
                     committed rocprofv3 --pmc summary, only when it was measured on the kernel sources that run here;
-  roofline_c3    -- (default C2 run, 1 GPU) one pass of BASELINE config C3 (batch 32 x 10 s) with the same in-situ timer on
+  roofline_c3    -- (C2, 1 GPU) one pass of BASELINE config C3 (batch 32 x 10 s) with the same in-situ timer on
                     the four block GEMMs and attention: per-op us / TFLOP/s / fraction of the 2.5 PFLOP/s dense bf16 peak
                     and the flop-weighted fraction the north star's ">= 40 % MFMA on attention + MLP GEMMs" refers to;
   cpu_baseline   -- the CPU oracle ("port") on the same workload on this box's host cores: 1 warm-up + median of 3;
@@ -117,6 +124,29 @@ def median(v):
     return s[len(s) // 2]
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each tensor of `arrays` as out_dir/<name>.npy in float32.  Past 64 MB in all, every array is cut
+    to the same fraction of its elements, drawn by a fixed seed (flat indices, ascending), so the files stay comparable
+    run to run.  -> {name: [shape written, shape computed]}."""
+    import numpy as np
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for k, a in host.items():
+        full_shape = list(a.shape)
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(a.size * DUMP_BUDGET_BYTES // total))
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{k}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        written[k] = [list(a.shape), full_shape]
+    return written
+
+
 def c4_fixed_total(total, rank, world, dist, make_input, run_one, sync, device, workers=1):
     """Strong-scaling leg on BASELINE's scaling config (C4: eval_infer_batch-style stream, NFE 16): a FIXED total of `total`
     utterances (lengths from tests/golden/c4_durations.csv), LPT-split over the ranks on the analytic FLOP cost (SURVEY
@@ -177,7 +207,7 @@ def stub_main(args, rank, world, distributed):
     elapsed = time.perf_counter() - t0
     red = reduce_job_totals(d, args.steps * N_TOTAL * BATCH, args.steps * BATCH * (N_TOTAL - N_REF), elapsed, "cpu")
     c4 = None
-    if args.c4_total > 0:
+    if args.full and args.c4_total > 0:
         c4 = c4_fixed_total(args.c4_total, rank, world, d, lambda r, t: (r, t), lambda x: time.sleep(0.0005),
                             lambda: None, "cpu", workers=args.c4_workers)
     if rank == 0:
@@ -227,7 +257,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--c4-total", type=int, default=2048,
-                    help="utterances of the fixed-total C4 leg (`scaling_c4`: strong scaling on BASELINE's scaling "
+                    help="utterances of the fixed-total C4 leg of --full (`scaling_c4`: strong scaling on BASELINE's scaling "
                          "config -- 2048 utterances, NFE 16 -- LPT-split over the ranks); 0 skips it")
     ap.add_argument("--c4-workers", type=int, default=4,
                     help="host threads per rank in the C4 legs, one stream each (eval_infer_batch --workers); 1 = sequential")
@@ -236,20 +266,28 @@ def main():
                          "line says data = stub.  Exercises the rank launch, partition and reductions on CPU")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: concurrent streams, scaling_c4, roofline, "
+                         "roofline_c3, cpu_baseline and the oracle parity of the timed workload (off: set up, warm up, "
+                         "time --steps passes, print the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed pass returned (mel, wave) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-c3", action="store_true", help="skip the roofline_c3 leg of the default run")
+    ap.add_argument("--no-c3", action="store_true", help="skip the roofline_c3 leg of a --full run")
     ap.add_argument("--batch", type=int, default=0, help="override the workload's batch size (experiments; the line says so)")
     ap.add_argument("--eager", action="store_true",
                     help="launch every kernel eagerly (no hipGraph): for rocprofv3 --pmc passes, which have hung on graph replays")
     ap.add_argument("--streams", type=int, default=4,
-                    help="extra leg (1 GPU only, reported as `concurrent`, never as `value`): this many host threads sample "
+                    help="extra leg of --full (1 GPU only, reported as `concurrent`, never as `value`): this many host threads sample "
                          "batch-1 utterances concurrently on one model; 0 skips it")
     ap.add_argument("--workload", default="C2", choices=["C2", "C3", "C4", "C5"],
                     help="C2 (default, the graded line): batch 1, 2 s ref / 5 s total; C3: batch 32, 4 s / 10 s; "
                          "C4: eval_infer_batch-style stream of single utterances (LibriSpeech-PC length mix, NFE 16, "
                          "LPT-sharded over the ranks, a step = one utterance); C5: Small + PPG config, sample_vc, NFE 32")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench: --steps must be >= 1")
     global N_REF, N_TOTAL, BATCH, NFE
     if args.workload == "C3":
         N_REF, N_TOTAL, BATCH = 375, 938, 32
@@ -367,6 +405,7 @@ def main():
             w, ids, r, t = inputs[cursor[0] % len(inputs)]
             cursor[0] += 1
             mel, _ = cfm.sample(w, ids, duration=t, steps=NFE, cfg_strength=CFG, sway_sampling_coef=SWAY, seed=0)
+            last_mel[0] = mel
             return to_host(voc.decode(mel[:, r:t, :].permute(0, 2, 1)))
 
     log(f"model ready on cuda:{local_rank}, world {world}")
@@ -403,11 +442,15 @@ def main():
     if step_frames is None and not torch.equal(host_tls.last, last_out.cpu()):
         raise SystemExit("bench: the pinned host copy of the last pass differs from the device result")
     log(f"timed region: {args.steps} steps in {elapsed:.3f} s")
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed pass receives: the stitched mel of CFM.sample and the decoded waveform
+        shapes = dump_outputs(args.dump_outputs, {"mel": gpu_mel, "wave": last_out})
+        log(f"outputs of the last timed step -> {args.dump_outputs}: {shapes}")
 
     # Concurrency leg: the batch-1 chain is latency-bound, so independent utterances in flight on separate
     # capture streams overlap each other's launch gaps.  Throughput only -- each pass takes longer -- and kept out of `value`.
     concurrent = None
-    if world == 1 and args.streams > 1 and step_frames is None:
+    if args.full and world == 1 and args.streams > 1 and step_frames is None:
         from f5e_tts_amd.eval.eval_infer_batch import RankWorkers
         n_conc = -(-max(args.steps, 8 * args.streams) // args.streams) * args.streams   # a whole number of rounds
 
@@ -450,7 +493,7 @@ def main():
     assert red["world_size"] == world and len(rank_frames) == world, (red["world_size"], world, rank_frames)
 
     scaling_c4 = None
-    if args.workload == "C2" and args.c4_total > 0 and not args.eager:
+    if args.full and args.workload == "C2" and args.c4_total > 0 and not args.eager:
         def run_utt(x):
             w, ids, r, t = x
             mel, _ = cfm.sample(w, ids, duration=t, steps=16, cfg_strength=CFG, sway_sampling_coef=SWAY, seed=0)
@@ -495,7 +538,7 @@ def main():
         return round(fl / tm_ / 1e12 / PEAK_BF16_TFLOPS, 4) if tm_ > 0 else None
 
     roofline = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # in-situ per-launch timing: eager launches of the SAME kernels in the SAME order
         n_chains = getattr(dit.engine(), "last_n_chains", 1)
         M = 2 * N_TOTAL * BATCH // n_chains          # rows per launch (the CFG branches may run as parallel chains)
@@ -549,7 +592,7 @@ def main():
                     "pmc_mfma_note": pm_note}
 
     roofline_c3 = None
-    if (rank == 0 and world == 1 and args.workload == "C2" and not args.no_roofline and not args.no_c3):
+    if args.full and rank == 0 and world == 1 and args.workload == "C2" and not args.no_roofline and not args.no_c3:
         # BASELINE config C3 (batch 32 x 10 s prompts, NFE 32) is where "MFMA utilisation on the attention + MLP GEMMs" is
         # defined: one graph pass for its throughput, one eager pass with the in-situ timer for the kernels
         B3, R3, N3 = 32, 375, 938
@@ -650,7 +693,7 @@ def main():
         del wav3
 
     cpu_baseline, parity = None, None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "C2":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload == "C2":
         from oracle import f5e_oracle as O   # the checker: parity of the timed workload + the reported CPU baseline
         ocfg = O.DiTConfig()
         torch.set_num_threads(host_threads())

@@ -433,7 +433,7 @@ def test_bench_gpus_flag_launches_that_many_ranks():
     (reference: `accelerate launch`, eval/eval_infer_batch.sh:4-6) and relays exactly one JSON line whose n_gpus /
     world_size / per-rank records show two ranks; the fixed-total C4 leg splits every utterance onto exactly one rank.
     --stub: gloo and a sleep instead of RCCL and the GPU pass (the launch / partition / reduction code is the same)."""
-    pr = _run_bench(["--gpus", "2", "--stub", "--steps", "4", "--warmup", "1", "--c4-total", "21"])
+    pr = _run_bench(["--gpus", "2", "--stub", "--full", "--steps", "4", "--warmup", "1", "--c4-total", "21"])
     assert pr.returncode == 0, pr.stderr[-2000:]
     lines = [ln for ln in pr.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, pr.stdout
@@ -601,3 +601,29 @@ def test_profile_summaries_are_read_back_only_on_matching_kernel_sources(tmp_pat
     assert ops2 is None and "mismatch" in note2
     ops3, note3 = bench.stamped_ops("ops_trace_c9")
     assert ops3 is None and "no profiles/" in note3
+
+
+def test_bench_dump_outputs_are_float32_and_a_fixed_sample_past_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float32, whole while the total fits 64 MB; past the budget
+    each array is cut to the same fraction by a fixed seed, so two runs write the same elements."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(3)
+    arrays = {"mel": torch.randn(2, 50, 100, generator=g), "wave": torch.randn(2, 4000, generator=g).to(torch.bfloat16)}
+    shapes = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    for k, v in arrays.items():
+        a = np.load(str(tmp_path / "a" / f"{k}.npy"))
+        assert a.dtype == np.float32 and shapes[k] == [list(v.shape), list(v.shape)]
+        assert np.array_equal(a, v.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 8000)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    bench.dump_outputs(str(tmp_path / "c"), arrays)
+    total = 0
+    for k, v in arrays.items():
+        b, c = np.load(str(tmp_path / "b" / f"{k}.npy")), np.load(str(tmp_path / "c" / f"{k}.npy"))
+        assert b.dtype == np.float32 and b.ndim == 1 and 0 < b.size < v.numel() and np.array_equal(b, c)
+        assert np.isin(b, v.float().numpy().reshape(-1)).all()
+        total += b.nbytes
+    assert total <= 8000

@@ -3,8 +3,8 @@
 # Runs bench.py --no-cpu-baseline once per arm (same box, back to back), JSON lines to gpurun_out/<tag>_<i>.json,
 # and prints one summary line per arm.  An empty string is a valid arm (defaults).
 tag=$1; shift
-bargs=""
-if [ "$1" = "--args" ]; then bargs=$2; shift 2; fi
+bargs="--full"   # the summary below reads the roofline / concurrent / roofline_c3 legs
+if [ "$1" = "--args" ]; then bargs="$bargs $2"; shift 2; fi
 i=0
 for e in "$@"; do
   env $e timeout -k 10 400 python bench.py --no-cpu-baseline $bargs > gpurun_out/${tag}_${i}.json 2> gpurun_out/${tag}_${i}.err || { echo "arm $i failed"; tail -5 gpurun_out/${tag}_${i}.err; exit 1; }

@@ -70,10 +70,14 @@ __global__ __launch_bounds__(256) void stft_logmel_kernel(const float* wav, int 
 // order, exactly the partial sums the dense loop produces, whose other terms are +0 -- and the ~1000 non-zero weights
 // (compact, <= 2048 floats) are staged in LDS once per workgroup instead of 513 dependent L2 round trips per filter
 // (the dense kernel spends 70 of its 73 us at C2 in that loop).
+// EX (f5e_stft_logmel_banded_ex, the BigVGAN front-end): frames start pad_left samples before f * hop and the magnitude
+// takes mag_eps under the root; EX = false is the original kernel, instruction for instruction.
 constexpr int FB_MAX_NNZ = 2048;
+template <bool EX>
 __global__ __launch_bounds__(256) void stft_logmel_banded_kernel(const float* wav, int nw, int ldw, const float* window,
                                                                   const float2* tw, const float* fbc, const int* band,
-                                                                  int nnz, float* out, int T, int hop, int n_mels) {
+                                                                  int nnz, float* out, int T, int hop, int n_mels,
+                                                                  int pad_left, float mag_eps) {
   __shared__ float2 x[NFFT];
   __shared__ float mag[NBIN + 3];
   __shared__ float wts[FB_MAX_NNZ];
@@ -81,7 +85,7 @@ __global__ __launch_bounds__(256) void stft_logmel_banded_kernel(const float* wa
   const int f = blockIdx.x, b = blockIdx.y;
   const float* w = wav + (size_t)b * ldw;
   for (int j = tid; j < NFFT; j += 256) {
-    int i = f * hop + j - NFFT / 2;
+    int i = f * hop + j - (EX ? pad_left : NFFT / 2);
     if (i < 0) i = -i;                    // reflect padding (no edge repeat)
     if (i >= nw) i = 2 * (nw - 1) - i;
     x[bitrev10(j)] = make_float2(w[i] * window[j], 0.f);
@@ -90,7 +94,8 @@ __global__ __launch_bounds__(256) void stft_logmel_banded_kernel(const float* wa
   int lo = 0, cnt = 0, off = 0;
   if (tid < n_mels) { lo = band[tid * 3]; cnt = band[tid * 3 + 1]; off = band[tid * 3 + 2]; }
   fft1024<false>(x, tw, tid);
-  for (int k = tid; k < NBIN; k += 256) mag[k] = sqrtf(x[k].x * x[k].x + x[k].y * x[k].y);
+  for (int k = tid; k < NBIN; k += 256)
+    mag[k] = EX ? sqrtf(x[k].x * x[k].x + x[k].y * x[k].y + mag_eps) : sqrtf(x[k].x * x[k].x + x[k].y * x[k].y);
   __syncthreads();
   if (tid < n_mels) {
     float acc = 0.f;
@@ -166,9 +171,27 @@ int f5e_stft_logmel_banded(hipStream_t st, const float* wav, int nw, int ldw, co
               "stft_logmel_banded: bad shape (n_mels <= 256, 0 < nnz=%d <= %d)", nnz, FB_MAX_NNZ);
   F5E_REQUIRE(nw > NFFT / 2, "stft_logmel_banded: reflect padding needs nw > %d samples (got %d)", NFFT / 2, nw);
   const int T = 1 + nw / hop;
-  hipLaunchKernelGGL(stft_logmel_banded_kernel, dim3(T, B), dim3(256), 0, st, wav, nw, ldw, window,
-                     (const float2*)twiddle, fb_compact, fb_band, nnz, out, T, hop, n_mels);
+  hipLaunchKernelGGL(stft_logmel_banded_kernel<false>, dim3(T, B), dim3(256), 0, st, wav, nw, ldw, window,
+                     (const float2*)twiddle, fb_compact, fb_band, nnz, out, T, hop, n_mels, 0, 0.f);
   F5E_LAUNCH_CHECK("stft_logmel_banded");
+  return F5E_OK;
+}
+
+int f5e_stft_logmel_banded_ex(hipStream_t st, const float* wav, int nw, int ldw, const float* window,
+                              const float* twiddle, const float* fb_compact, const int* fb_band, int nnz, float* out, int B,
+                              int n_fft, int hop, int n_mels, int pad_left, int T, float mag_eps) {
+  F5E_REQUIRE(wav && window && twiddle && fb_compact && fb_band && out, "stft_logmel_banded_ex: null operand");
+  F5E_REQUIRE(n_fft == NFFT, "stft_logmel_banded_ex: only n_fft = win_length = 1024 is built (got %d)", n_fft);
+  F5E_REQUIRE(B > 0 && hop > 0 && T > 0 && n_mels > 0 && n_mels <= 256 && nnz > 0 && nnz <= FB_MAX_NNZ,
+              "stft_logmel_banded_ex: bad shape (T=%d, n_mels <= 256, 0 < nnz=%d <= %d)", T, nnz, FB_MAX_NNZ);
+  F5E_REQUIRE(pad_left >= 0 && pad_left < nw, "stft_logmel_banded_ex: reflect padding needs 0 <= pad_left=%d < nw=%d",
+              pad_left, nw);
+  // the last frame's right edge must reflect at most once: (T - 1) hop - pad_left + 1023 <= 2 (nw - 1)
+  F5E_REQUIRE((long long)(T - 1) * hop - pad_left + NFFT - 1 <= 2LL * (nw - 1),
+              "stft_logmel_banded_ex: T=%d frames run past the reflected signal (nw=%d)", T, nw);
+  hipLaunchKernelGGL(stft_logmel_banded_kernel<true>, dim3(T, B), dim3(256), 0, st, wav, nw, ldw, window,
+                     (const float2*)twiddle, fb_compact, fb_band, nnz, out, T, hop, n_mels, pad_left, mag_eps);
+  F5E_LAUNCH_CHECK("stft_logmel_banded_ex");
   return F5E_OK;
 }
 

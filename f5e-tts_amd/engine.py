@@ -79,6 +79,30 @@ def mel_filterbank(n_freqs: int, n_mels: int, sr: int) -> Tensor:
     return torch.clamp(torch.min(-slopes[:, :-2] / f_diff[:-1], slopes[:, 2:] / f_diff[1:]), min=0.0).contiguous()
 
 
+def slaney_mel_filterbank(n_fft: int, n_mels: int, sr: int, fmin: float = 0.0, fmax: Optional[float] = None) -> Tensor:
+    """librosa.filters.mel(sr, n_fft, n_mels, fmin, fmax) with its defaults htk=False, norm="slaney" (the BigVGAN
+    front-end, reference model/modules.py:44), restated from the published formula in float64 -> [n_fft // 2 + 1, n_mels]
+    float32.  "parity unpinned" for the filter values: librosa is not a dependency."""
+    fmax = sr / 2.0 if fmax is None else float(fmax)
+    f_sp, min_log_hz = 200.0 / 3, 1000.0
+    min_log_mel = min_log_hz / f_sp
+    logstep = math.log(6.4) / 27.0
+
+    def hz_to_mel(f):
+        return f / f_sp if f < min_log_hz else min_log_mel + math.log(f / min_log_hz) / logstep
+
+    mels = torch.linspace(hz_to_mel(float(fmin)), hz_to_mel(fmax), n_mels + 2, dtype=torch.float64)
+    hz = torch.where(mels >= min_log_mel, min_log_hz * torch.exp(logstep * (mels - min_log_mel)), f_sp * mels)
+    fft_freqs = torch.linspace(0.0, sr / 2.0, n_fft // 2 + 1, dtype=torch.float64)
+    fdiff = hz[1:] - hz[:-1]
+    ramps = hz.unsqueeze(1) - fft_freqs.unsqueeze(0)                     # [n_mels + 2, n_freqs]
+    lower = -ramps[:-2] / fdiff[:-1].unsqueeze(1)
+    upper = ramps[2:] / fdiff[1:].unsqueeze(1)
+    w = torch.clamp(torch.minimum(lower, upper), min=0.0)               # [n_mels, n_freqs]
+    enorm = 2.0 / (hz[2:n_mels + 2] - hz[:n_mels])
+    return (w * enorm.unsqueeze(1)).t().to(torch.float32).contiguous()
+
+
 def text_pos_table(dim: int, end: int = 4096, theta: float = 10000.0) -> Tensor:
     """precompute_freqs_cis (model/modules.py:196-207): constant [end, dim] = cos || sin table."""
     freqs = 1.0 / (theta ** (torch.arange(0, dim, 2)[: dim // 2].float() / dim))

@@ -247,6 +247,14 @@ def run_sharded(work: Sequence[Tuple[str, int, int]], process_one, rank: int, wo
     return dict(red, utts=done)
 
 
+def yaml_mel_spec_type(mc: dict) -> str:
+    """model.mel_spec.mel_spec_type of a parsed model yaml (reference eval_infer_batch.py:77), "vocos" if absent."""
+    t = (mc.get("mel_spec") or {}).get("mel_spec_type", "vocos")
+    if t not in ("vocos", "bigvgan"):
+        raise ValueError(f"unknown mel_spec_type {t!r} in the model yaml")
+    return t
+
+
 def main(argv=None):
     p = argparse.ArgumentParser(description="batch inference")
     p.add_argument("-s", "--seed", default=None, type=int)
@@ -258,7 +266,8 @@ def main(argv=None):
     p.add_argument("-t", "--testset", required=True, help="a .lst: ref_utt \\t ref_dur \\t ref_txt \\t gen_utt \\t gen_dur \\t gen_txt")
     p.add_argument("--ckpt", default="", help="checkpoint file (default ckpts/<expname>/model_<ckptstep>.pt)")
     p.add_argument("--audio_root", default="", help="directory with <ref_utt>.wav prompt audio (24 kHz)")
-    p.add_argument("--vocoder_path", default="pretrained_models/vocos-mel-24khz")
+    p.add_argument("--vocoder_path", default="", help="local vocoder directory (default pretrained_models/"
+                                                     "vocos-mel-24khz or bigvgan_v2_24khz_100band_256x, by the model yaml)")
     p.add_argument("--output_dir", default="")
     p.add_argument("--partition", default="lpt", choices=["lpt", "contiguous"])
     p.add_argument("--workers", default=4, type=int,
@@ -302,18 +311,21 @@ def main(argv=None):
         mc = parse_model_yaml(yaml.safe_load(f))
     if args.mode == "vc" and not mc["transformer_ppg_config"]["use_ppg"]:
         raise SystemExit("--mode vc needs a model with use_ppg: True")
+    mel_spec_type = yaml_mel_spec_type(mc)
     vocab_char_map, vocab_size = get_tokenizer(U._DEFAULT_VOCAB)
     model = CFM(transformer=DiT(**mc["arch"], text_num_embeds=vocab_size, mel_dim=U.n_mel_channels,
                                 ppg_config=mc["transformer_ppg_config"], cb_config=mc["transformer_codebook_config"]),
                 mel_spec_kwargs=dict(n_fft=U.n_fft, hop_length=U.hop_length, win_length=U.win_length,
                                      n_mel_channels=U.n_mel_channels, target_sample_rate=U.target_sample_rate,
-                                     mel_spec_type="vocos"),
+                                     mel_spec_type=mel_spec_type),
                 odeint_kwargs=dict(method=args.odemethod), vocab_char_map=vocab_char_map,
                 ppg_config=mc["cfm_ppg_config"], cb_config=mc["cfm_codebook_config"]).to(device)
     model = U.load_checkpoint(model, ckpt, device, use_ema=True)
-    vocoder = U.load_vocoder("vocos", is_local=True, local_path=args.vocoder_path, device=device)
+    vocoder_path = args.vocoder_path or {"vocos": "pretrained_models/vocos-mel-24khz",
+                                         "bigvgan": "pretrained_models/bigvgan_v2_24khz_100band_256x"}[mel_spec_type]
+    vocoder = U.load_vocoder(mel_spec_type, is_local=True, local_path=vocoder_path, device=device)
     out_dir = args.output_dir or (f"results/{args.expname}_{args.ckptstep}/{os.path.basename(args.testset)}/"
-                                  f"seed{args.seed}_{args.odemethod}_nfe{args.nfestep}_vocos_ss{args.swaysampling}"
+                                  f"seed{args.seed}_{args.odemethod}_nfe{args.nfestep}_{mel_spec_type}_ss{args.swaysampling}"
                                   + {"cfg": "_cfg2.0_speed1.0",
                                      "tts": f"_alpha_spk{args.alpha_spk}_txt{args.alpha_txt}_speed1.0",
                                      "vc": f"_alpha_spk{args.alpha_spk}_ppg{args.alpha_ppg}_speed1.0"}[args.mode])
@@ -392,7 +404,8 @@ def main(argv=None):
                     ppg = torch.from_numpy(np.load(os.path.join(args.ppg_dir, utt + ".npy")).astype("float32"))[None]
                 gen, _ = model.sample_vc(cond=ref_mel, ppg=ppg.to(device), alpha_spk=args.alpha_spk,
                                          alpha_ppg=args.alpha_ppg, **kw)
-            wav = vocoder.decode(gen[:, ref_len:tot].permute(0, 2, 1).float())
+            mel_out = gen[:, ref_len:tot].permute(0, 2, 1).float()
+            wav = vocoder.decode(mel_out) if mel_spec_type == "vocos" else vocoder(mel_out).squeeze(1)
         if rms < U.target_rms:
             wav = wav * rms / U.target_rms
         U.save_wav(os.path.join(out_dir, f"{utt}.wav"), wav[0].cpu().numpy(), U.target_sample_rate)

@@ -45,6 +45,11 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+# local vocoder directories when the config names none (reference infer_cli.py:264-267; no download here)
+DEFAULT_VOCODER_PATH = {"vocos": "pretrained_models/vocos-mel-24khz",
+                        "bigvgan": "pretrained_models/bigvgan_v2_24khz_100band_256x"}
+
+
 def resolve_settings(args: argparse.Namespace, config: dict) -> dict:
     """flag > toml > default, with the reference's falsy-``or`` semantics (only ref_text uses ``is not None``)."""
     g = config.get
@@ -110,7 +115,7 @@ def main(argv=None):
             s["gen_text"] = f.read()
     from ..model import DiT
     vocoder = U.load_vocoder(s["vocoder_name"], is_local=True,
-                             local_path=config.get("vocoder_local_path", "pretrained_models/vocos-mel-24khz"),
+                             local_path=config.get("vocoder_local_path", DEFAULT_VOCODER_PATH[s["vocoder_name"]]),
                              device=s["device"])
     model = U.load_model(DiT, load_arch(s["model"], s["model_cfg"]), s["ckpt_file"], mel_spec_type=s["vocoder_name"],
                          vocab_file=s["vocab_file"], device=s["device"])

@@ -5,7 +5,7 @@ here is host glue (text chunking, wav I/O, numpy cross-fade) exactly as in the r
 
 Resampling and the pydub-style silence clipping live in ``infer/audio.py``.  Not rebuilt (out of scope,
 SURVEY section 8): the Whisper ASR fallback of ``preprocess_ref_audio_text`` (an empty ``ref_text`` is an error here),
-the bigvgan vocoder, HF-hub downloads (no network).  Chinese g2p needs the optional ``jieba`` + ``pypinyin`` packages;
+HF-hub downloads (no network).  Chinese g2p needs the optional ``jieba`` + ``pypinyin`` packages;
 the ASCII path is self-contained.
 """
 from __future__ import annotations
@@ -24,6 +24,7 @@ import torch
 from ..model import CFM
 from ..model.utils import get_tokenizer
 from ..vocoder import Vocos, load_vocos
+from ..vocoder_bigvgan import load_bigvgan
 from . import audio as A
 
 # ----------------------------------------- defaults (reference infer/utils_infer.py:49-62)
@@ -121,10 +122,12 @@ def convert_char_to_pinyin(text_list: List[str], polyphone: bool = True) -> List
 # ----------------------------------------- loading (reference utils_infer.py:101-271)
 
 def load_vocoder(vocoder_name="vocos", is_local=False, local_path="", device=device, hf_cache_dir=None):
-    if vocoder_name != "vocos":
-        raise NotImplementedError("only the vocos vocoder is built for MI355X")
+    if vocoder_name not in ("vocos", "bigvgan"):
+        raise NotImplementedError(f"unknown vocoder {vocoder_name!r} (vocos / bigvgan)")
     if not is_local:
-        raise RuntimeError("no network access: pass is_local=True and local_path=<vocos-mel-24khz directory>")
+        raise RuntimeError(f"no network access: pass is_local=True and local_path=<{vocoder_name} checkpoint directory>")
+    if vocoder_name == "bigvgan":   # config.json + bigvgan_generator.pt (reference utils_infer.py:125-138)
+        return load_bigvgan(local_path, device)
     return load_vocos(local_path, device)
 
 
@@ -297,7 +300,8 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
                                                 seed=seed)
             del _traj
             generated = generated.to(torch.float32)[:, ref_audio_len:, :].permute(0, 2, 1)
-            wave_ = vocoder.decode(generated)
+            # reference utils_infer.py:488-491: Vocos.decode -> [b, n], BigVGAN's forward -> [b, 1, n]
+            wave_ = vocoder.decode(generated) if mel_spec_type == "vocos" else vocoder(generated)
             if rms < target_rms:
                 wave_ = wave_ * rms / target_rms
             return wave_, generated

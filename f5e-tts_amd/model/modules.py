@@ -10,7 +10,7 @@ import torch
 from torch import nn
 
 from .. import _C, ops
-from ..engine import fft_tables, mel_filterbank
+from ..engine import fft_tables, mel_filterbank, slaney_mel_filterbank
 
 BF, F32, I32 = torch.bfloat16, torch.float32, torch.int32
 
@@ -22,8 +22,6 @@ class MelSpec(nn.Module):
                  mel_spec_type="vocos"):
         super().__init__()
         assert mel_spec_type in ["vocos", "bigvgan"], "We only support two extract mel backend: vocos or bigvgan"
-        if mel_spec_type != "vocos":
-            raise _C.F5EError("only the vocos mel front-end is built for MI355X (bigvgan needs librosa's slaney filters)")
         if n_fft != 1024 or win_length != 1024:
             raise _C.F5EError("the STFT kernel is built for n_fft = win_length = 1024")
         self.n_fft, self.hop_length, self.win_length = n_fft, hop_length, win_length
@@ -35,12 +33,16 @@ class MelSpec(nn.Module):
     def _get_tables(self, device):
         if self._tables is None or self._tables[0].device != device:
             win, tw = fft_tables(device)
-            fb = mel_filterbank(self.n_fft // 2 + 1, self.n_mel_channels, self.target_sample_rate).to(device)
+            if self.mel_spec_type == "bigvgan":
+                fb = slaney_mel_filterbank(self.n_fft, self.n_mel_channels, self.target_sample_rate).to(device)
+            else:
+                fb = mel_filterbank(self.n_fft // 2 + 1, self.n_mel_channels, self.target_sample_rate).to(device)
             self._tables = (win, tw, fb, ops.band_filterbank(fb))
         return self._tables
 
     def forward(self, wav: torch.Tensor) -> torch.Tensor:
-        """wav [b, nw] (or [b, 1, nw]) on the GPU -> log-mel [b, n_mels, 1 + nw // hop]."""
+        """wav [b, nw] (or [b, 1, nw]) on the GPU -> log-mel [b, n_mels, 1 + nw // hop] (vocos) or [b, n_mels, nw // hop]
+        (bigvgan: reflect-pad (n_fft - hop) / 2, center=False, sqrt(|X|^2 + 1e-9), slaney filters; modules.py:30-72)."""
         if wav.ndim == 3:
             wav = wav.squeeze(1)
         assert wav.ndim == 2
@@ -48,6 +50,14 @@ class MelSpec(nn.Module):
             self.to(wav.device)
         win, tw, fb, banded = self._get_tables(wav.device)
         wav = wav.to(F32).contiguous()
+        if self.mel_spec_type == "bigvgan":
+            if banded is None:
+                raise _C.F5EError("the slaney filterbank does not fit the banded STFT kernel (nnz > 2048)")
+            pad = (self.n_fft - self.hop_length) // 2
+            frames = (wav.shape[1] + 2 * pad - self.n_fft) // self.hop_length + 1
+            out = torch.empty(wav.shape[0], frames, self.n_mel_channels, device=wav.device)
+            ops.stft_logmel_banded_ex(wav, win, tw, banded[0], banded[1], out, self.n_fft, self.hop_length, pad, 1e-9)
+            return out.permute(0, 2, 1)
         frames = 1 + wav.shape[1] // self.hop_length
         out = torch.empty(wav.shape[0], frames, self.n_mel_channels, device=wav.device)
         if banded is not None:   # same result bit for bit; the filters' non-zero runs from LDS instead of 513 dense rows

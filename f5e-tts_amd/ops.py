@@ -382,12 +382,74 @@ def stft_logmel_banded(wav: Tensor, window: Tensor, twiddle: Tensor, fb_compact:
     return out
 
 
+def stft_logmel_banded_ex(wav: Tensor, window: Tensor, twiddle: Tensor, fb_compact: Tensor, fb_band: Tensor, out: Tensor,
+                          n_fft: int, hop: int, pad_left: int, mag_eps: float):
+    """out f32 [B, T, n_mels]: frames start pad_left samples before f * hop (reflect-padded); T = out.shape[1]."""
+    require_device()
+    B, nw = wav.shape
+    T = out.shape[1]
+    if out.shape != (B, T, fb_band.shape[0]):
+        raise _C.F5EError(f"out must be [B, T, n_mels] = [{B}, T, {fb_band.shape[0]}] (got {tuple(out.shape)})")
+    check(lib().f5e_stft_logmel_banded_ex(_stream(), _p(wav, F32, "wav"), nw, wav.stride(0), _p(window, F32, "window"),
+                                          _p(twiddle, F32, "twiddle"), _p(fb_compact, F32, "fb_compact"),
+                                          _p(fb_band, I32, "fb_band"), fb_compact.numel(), _p(out, F32, "out"), B, n_fft,
+                                          hop, fb_band.shape[0], pad_left, T, mag_eps), "f5e_stft_logmel_banded_ex")
+    return out
+
+
 def istft_head(z: Tensor, window: Tensor, twiddle: Tensor, frames_ws: Tensor, out: Tensor, B: int, T: int, n_fft: int,
                hop: int):
     require_device()
     check(lib().f5e_istft_head(_stream(), _p(z, F32, "z"), z.stride(0), _p(window, F32, "window"),
                                _p(twiddle, F32, "twiddle"), _p(frames_ws, F32, "frames_ws"), _p(out, F32, "out"), B, T,
                                n_fft, hop), "f5e_istft_head")
+    return out
+
+
+def bigvgan_act(x: Tensor, out: Tensor, alpha: Tensor, inv_beta: Tensor, f_up: Tensor, f_dn: Tensor):
+    """Activation1d: x f32 [B, L, C] -> out [B, L, C] (bf16 conv operand, or f32)."""
+    require_device()
+    B, L, C = x.shape
+    if out.shape != x.shape or out.dtype not in (BF, F32):
+        raise _C.F5EError("bigvgan_act: out must be bf16 or f32 of x's shape")
+    if alpha.numel() != C or inv_beta.numel() != C or f_up.numel() != 12 or f_dn.numel() != 12:
+        raise _C.F5EError("bigvgan_act: alpha / inv_beta [C], filters [12]")
+    check(lib().f5e_bigvgan_act(_stream(), _p(x, F32, "x"), _p(out, None, "out"), 1 if out.dtype == F32 else 0,
+                                _p(alpha, F32, "alpha"), _p(inv_beta, F32, "inv_beta"), _p(f_up, F32, "f_up"),
+                                _p(f_dn, F32, "f_dn"), B, L, C), "f5e_bigvgan_act")
+    return out
+
+
+def bigvgan_conv(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], N: int, ksz: int, dil: int, pad: int, *,
+                 out: Optional[Tensor] = None, resid: Optional[Tensor] = None, sum_: Optional[Tensor] = None,
+                 sum_scale: float = 1.0, sum_init: bool = False):
+    """Conv1d on bf16 operands, x bf16 [B, L, Cin] -> f32 [B, L, N] (see f5e_bigvgan_conv); w_packed bf16
+    [roundup(N, 64), ksz * Cin_pad] from vocoder_bigvgan.pack_conv_weight."""
+    require_device()
+    B, L, Cin = x.shape
+    cin_pad = w_packed.shape[1] // ksz
+    if w_packed.dtype != BF or w_packed.shape != ((N + 63) // 64 * 64, ksz * cin_pad) or cin_pad < Cin:
+        raise _C.F5EError(f"bigvgan_conv: w_packed must be bf16 [{(N + 63) // 64 * 64}, {ksz} * Cin_pad] "
+                          f"(got {w_packed.dtype} {tuple(w_packed.shape)})")
+    for name, t in (("out", out), ("resid", resid), ("sum", sum_)):
+        if t is not None and t.shape != (B, L, N):
+            raise _C.F5EError(f"bigvgan_conv: {name} must be [{B}, {L}, {N}] (got {tuple(t.shape)})")
+    if bias is not None and bias.numel() != N:
+        raise _C.F5EError("bigvgan_conv: bias must have N elements")
+    check(lib().f5e_bigvgan_conv(_stream(), _p(x, BF, "x"), _p(w_packed, BF, "w_packed"), _p(bias, F32, "bias"),
+                                 _p(resid, F32, "resid"), _p(out, F32, "out"), _p(sum_, F32, "sum"), sum_scale,
+                                 1 if sum_init else 0, B, L, Cin, cin_pad, N, ksz, dil, pad), "f5e_bigvgan_conv")
+    return out if out is not None else sum_
+
+
+def bigvgan_post(a: Tensor, w: Tensor, bias: Optional[Tensor], out: Tensor, use_tanh: bool):
+    """conv_post: a f32 [B, L, C], w f32 [ksz, C] -> out f32 [B, L] = clamp(conv + bias, -1, 1) (or tanh)."""
+    require_device()
+    B, L, C = a.shape
+    if w.shape[1] != C or out.shape != (B, L):
+        raise _C.F5EError("bigvgan_post: w [ksz, C], out [B, L]")
+    check(lib().f5e_bigvgan_post(_stream(), _p(a, F32, "a"), _p(w, F32, "w"), _p(bias, F32, "bias"), _p(out, F32, "out"),
+                                 B, L, C, w.shape[0], 1 if use_tanh else 0), "f5e_bigvgan_post")
     return out
 
 

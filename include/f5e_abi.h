@@ -220,10 +220,37 @@ F5E_API int f5e_stft_logmel(f5e_stream st, const float* wav, int nw, int ldw, co
 F5E_API int f5e_stft_logmel_banded(f5e_stream st, const float* wav, int nw, int ldw, const float* window, const float* twiddle,
                            const float* fb_compact, const int* fb_band, int nnz, float* out, int B, int n_fft, int hop,
                            int n_mels);
+/* The banded form generalised for the BigVGAN front-end (reference model/modules.py:30-72): frame f covers samples
+ * [f hop - pad_left, f hop - pad_left + 1024) of wav, reflect-padded (no edge repeat; pad_left < nw), T frames
+ * (caller-chosen), magnitude sqrt(re^2 + im^2 + mag_eps).  pad_left = 512, T = 1 + nw / hop, mag_eps = 0 is
+ * f5e_stft_logmel_banded; BigVGAN uses pad_left = (1024 - hop) / 2, T = nw / hop, mag_eps = 1e-9. */
+F5E_API int f5e_stft_logmel_banded_ex(f5e_stream st, const float* wav, int nw, int ldw, const float* window,
+                              const float* twiddle, const float* fb_compact, const int* fb_band, int nnz, float* out, int B,
+                              int n_fft, int hop, int n_mels, int pad_left, int T, float mag_eps);
 /* Vocos ISTFTHead tail: z f32 [B*T][ldz] (513 log-magnitudes | 513 phases) -> out f32 [B][hop * (T - 1)];
  * frames_ws f32 [B*T][1024] scratch. */
 F5E_API int f5e_istft_head(f5e_stream st, const float* z, int ldz, const float* window, const float* twiddle, float* frames_ws,
                    float* out, int B, int T, int n_fft, int hop);
+
+/* ---------------------------------------------------------------- BigVGAN-v2 generator (vocoder_bigvgan.py) --- */
+
+/* Activation1d (anti-aliased SnakeBeta, channels-last): x f32 [B][L][C] -> y [B][L][C], bf16 (out_f32 = 0) or f32.
+ * 2x upsample (replicate-pad 5, 2 * conv_transpose1d stride 2 with f_up[12], crop 15 / 15), s = u + inv_beta[c] *
+ * sin^2(alpha[c] u), 2x downsample (replicate-pad 5 / 6, stride-2 conv1d with f_dn[12]).  alpha / inv_beta f32 [C] are
+ * the final per-channel factors (exp() of a log-scale parameter and 1 / (beta + 1e-9) applied by the caller). */
+F5E_API int f5e_bigvgan_act(f5e_stream st, const float* x, void* y, int out_f32, const float* alpha, const float* inv_beta,
+                    const float* f_up, const float* f_dn, int B, int L, int C);
+/* Conv1d(Cin -> N, ksz taps, dilation dil, zero padding pad, output length L) on bf16 operands, fp32 accumulation:
+ * x bf16 [B][L][Cin] (Cin % 4 == 0), w_packed bf16 [roundup(N, 64)][ksz][Cin_pad] (Cin_pad % 32 == 0, zero-padded),
+ * bias f32 [N] (optional).  v = acc + bias + resid (resid f32 [B][L][N], optional); out f32 [B][L][N] = v (optional);
+ * sum f32 [B][L][N] = (sum_init ? 0 : sum) + sum_scale * v (optional).  ksz <= 11, (ksz - 1) dil <= 64. */
+F5E_API int f5e_bigvgan_conv(f5e_stream st, const void* x, const void* w_packed, const float* bias, const float* resid,
+                     float* out, float* sum, float sum_scale, int sum_init, int B, int L, int Cin, int Cin_pad, int N,
+                     int ksz, int dil, int pad);
+/* conv_post: out f32 [B][L] = clamp(conv1d(a, w) + bias, -1, 1) (or tanh), a f32 [B][L][C], w f32 [ksz][C] (odd ksz,
+ * pad (ksz - 1) / 2), bias f32 [1] optional. */
+F5E_API int f5e_bigvgan_post(f5e_stream st, const float* a, const float* w, const float* bias, float* out, int B, int L, int C,
+                     int ksz, int use_tanh);
 
 /* ---------------------------------------------------------------- PPG extractor front ------------ */
 

@@ -166,3 +166,69 @@ def synthetic_text_ids(n_total: int, batch: int = 1, seed: int = 7, vocab: int =
     g = torch.Generator().manual_seed(seed)
     nt = max(1, round(n_total / 8))
     return torch.randint(1, vocab, (batch, nt), generator=g)
+
+
+def bigvgan_config(initial_channel: int = 1536, **kw) -> Dict:
+    """BigVGAN-v2 24 kHz / 100-band / 256x config.json fields (smaller ``initial_channel`` for quick tests)."""
+    cfg = dict(num_mels=100, upsample_initial_channel=initial_channel, upsample_rates=[4, 4, 2, 2, 2, 2],
+               upsample_kernel_sizes=[8, 8, 4, 4, 4, 4], resblock="1", resblock_kernel_sizes=[3, 7, 11],
+               resblock_dilation_sizes=[[1, 3, 5], [1, 3, 5], [1, 3, 5]], activation="snakebeta", snake_logscale=True,
+               use_tanh_at_final=False, use_bias_at_final=False, sampling_rate=24000, hop_size=256, n_fft=1024,
+               win_size=1024, fmin=0, fmax=None)
+    cfg.update(kw)
+    return cfg
+
+
+def init_bigvgan_state(cfg: Dict, seed: int = 777, weight_norm_form: str = "weight_g",
+                       post_gain: float = 0.09) -> State:
+    """Seeded BigVGAN generator state dict with the package's key names (weight-norm form ``weight_g`` -> weight_g /
+    weight_v, ``parametrizations`` -> parametrizations.weight.original0 / 1).  Activations stay O(1) through all stages:
+    every conv has std ~ 0.5 / sqrt(C_in k) (weight_v random, weight_g rescales it), the SnakeBeta log-parameters are
+    N(0, 0.1), and conv_post has std post_gain / sqrt(C k), which keeps the waveform RMS near 0.2 without clipping (the
+    package's normal(0, 0.01) init decays the signal toward zero and would make parity checks vacuous)."""
+    g = torch.Generator().manual_seed(seed)
+    sd: State = {}
+
+    def conv(prefix, cout, cin, k, std, bias=True, transposed=False):
+        shape = (cin, cout, k) if transposed else (cout, cin, k)
+        v = torch.randn(shape, generator=g)
+        gn = v.flatten(1).norm(dim=1).view(-1, 1, 1) * std   # folded weight g v / ||v|| = std * v
+        if weight_norm_form == "weight_g":
+            sd[f"{prefix}.weight_g"], sd[f"{prefix}.weight_v"] = gn, v
+        else:
+            sd[f"{prefix}.parametrizations.weight.original0"] = gn
+            sd[f"{prefix}.parametrizations.weight.original1"] = v
+        if bias:
+            sd[f"{prefix}.bias"] = 0.02 * torch.randn(cout, generator=g)
+
+    def act(prefix, c):
+        sd[f"{prefix}.act.alpha"] = 0.1 * torch.randn(c, generator=g)
+        if cfg["activation"] == "snakebeta":
+            sd[f"{prefix}.act.beta"] = 0.1 * torch.randn(c, generator=g)
+
+    c = cfg["upsample_initial_channel"]
+    conv("conv_pre", c, cfg["num_mels"], 7, 0.5 / math.sqrt(cfg["num_mels"] * 7))
+    nk = len(cfg["resblock_kernel_sizes"])
+    for i, (u, k) in enumerate(zip(cfg["upsample_rates"], cfg["upsample_kernel_sizes"])):
+        # a transposed conv sums k / u taps per output: scale for that fan-in
+        conv(f"ups.{i}.0", c // 2, c, k, 1.0 / math.sqrt(c * k / u), transposed=True)
+        c //= 2
+        for j, (kr, dils) in enumerate(zip(cfg["resblock_kernel_sizes"], cfg["resblock_dilation_sizes"])):
+            r = i * nk + j
+            for m in range(len(dils)):
+                conv(f"resblocks.{r}.convs1.{m}", c, c, kr, 0.5 / math.sqrt(c * kr))
+                conv(f"resblocks.{r}.convs2.{m}", c, c, kr, 0.5 / math.sqrt(c * kr))
+            for n in range(2 * len(dils)):
+                act(f"resblocks.{r}.activations.{n}", c)
+    act("activation_post", c)
+    conv("conv_post", 1, c, 7, post_gain / math.sqrt(c * 7), bias=bool(cfg["use_bias_at_final"]))
+    return sd
+
+
+def synthetic_mel(n_frames: int, batch: int = 1, seed: int = 99, n_mels: int = 100) -> Tensor:
+    """Log-mel-like input [batch, n_mels, n_frames]: a smooth spectral envelope around -4 plus noise."""
+    g = torch.Generator().manual_seed(seed)
+    env = torch.linspace(-2.0, -7.0, n_mels).view(1, n_mels, 1)
+    slow = F.interpolate(torch.randn(batch, n_mels, max(2, n_frames // 8), generator=g), size=n_frames, mode="linear",
+                         align_corners=True)
+    return (env + 1.5 * slow + 0.5 * torch.randn(batch, n_mels, n_frames, generator=g)).float()

@@ -27,6 +27,7 @@ SIGNATURES = {
     "f5e_gemm_bf16_qkv_rope_ln": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _P],
     "f5e_adaln_pre": [_P, _P, _I, _P, _I, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _I],
     "f5e_flash_attn": [_P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I],
+    "f5e_joint_attn": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I],
     "f5e_layernorm": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _F],
     "f5e_grn": [_P, _P, _P, _P, _P, _P, _I, _I, _I],
     "f5e_l2norm": [_P, _P, _I, _P, _I, _I, _P, _I, _I],

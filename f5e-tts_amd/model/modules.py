@@ -156,14 +156,20 @@ class AttnProcessor:
         self.pe_attn_head = pe_attn_head
 
 
+class JointAttnProcessor:
+    """reference modules.py:647-718 (stateless); the computation is f5e_joint_attn inside MMDiT.forward."""
+
+    def __init__(self):
+        pass
+
+
 class Attention(nn.Module):
-    """reference modules.py:360-416, self-attention members only (keys to_q/to_k/to_v/to_out.0[/q_norm/k_norm])."""
+    """reference modules.py:360-416 (keys to_q/to_k/to_v/to_out.0[/q_norm/k_norm]; with ``context_dim`` also the joint
+    members to_q_c/to_k_c/to_v_c[/c_q_norm/c_k_norm][/to_out_c] of MMDiT, in the reference's registration order)."""
 
     def __init__(self, processor, dim: int, heads: int = 8, dim_head: int = 64, dropout: float = 0.0,
                  context_dim: Optional[int] = None, context_pre_only: bool = False, qk_norm: Optional[str] = None):
         super().__init__()
-        if context_dim is not None:
-            raise _C.F5EError("joint (MMDiT) attention is not on the sampled path (SURVEY F4) and is not built")
         self.processor = processor
         self.dim, self.heads, self.inner_dim, self.dropout = dim, heads, dim_head * heads, dropout
         self.to_q = nn.Linear(dim, self.inner_dim)
@@ -177,7 +183,20 @@ class Attention(nn.Module):
             self.k_norm = RMSNorm(dim_head, eps=1e-6)
         else:
             raise ValueError(f"Unimplemented qk_norm: {qk_norm}")
+        if context_dim is not None:
+            self.context_dim, self.context_pre_only = context_dim, context_pre_only
+            self.to_q_c = nn.Linear(context_dim, self.inner_dim)
+            self.to_k_c = nn.Linear(context_dim, self.inner_dim)
+            self.to_v_c = nn.Linear(context_dim, self.inner_dim)
+            if qk_norm is None:
+                self.c_q_norm = None
+                self.c_k_norm = None
+            else:
+                self.c_q_norm = RMSNorm(dim_head, eps=1e-6)
+                self.c_k_norm = RMSNorm(dim_head, eps=1e-6)
         self.to_out = nn.ModuleList([nn.Linear(self.inner_dim, dim), nn.Dropout(dropout)])
+        if context_dim is not None and not context_pre_only:
+            self.to_out_c = nn.Linear(self.inner_dim, context_dim)
 
 
 # ---------------------------------------------------------------- DiT block (reference modules.py:610-641)
@@ -250,6 +269,33 @@ class DiTBlock(nn.Module):
         ops.gemm_bf16_bias(hn, w["w_ff1"], w["b_ff1"], ff, act=ops.ACT_GELU_TANH)
         ops.gemm_bf16_gate_residual(ff, w["w_ff2"], w["b_ff2"], xs, emb[:, 5 * D:6 * D], N)
         return xs.view(B, N, D)
+
+
+# ---------------------------------------------------------------- MMDiT block (reference modules.py:510-604)
+
+class MMDiTBlock(nn.Module):
+    """Parameter container (keys attn_norm_c / attn_norm_x / attn / [ff_norm_c / ff_c] / ff_norm_x / ff_x); the block runs
+    inside MMDiT.forward (backbones/mmdit.py).  The last block (``context_pre_only``) modulates the text stream with an
+    AdaLayerNorm_Final and has no text feed-forward."""
+
+    def __init__(self, dim, heads, dim_head, ff_mult=4, dropout=0.1, context_dim=None, context_pre_only=False,
+                 qk_norm=None):
+        super().__init__()
+        if context_dim is None:
+            context_dim = dim
+        self.context_pre_only = context_pre_only
+        self.attn_norm_c = AdaLayerNorm_Final(context_dim) if context_pre_only else AdaLayerNorm(context_dim)
+        self.attn_norm_x = AdaLayerNorm(dim)
+        self.attn = Attention(processor=JointAttnProcessor(), dim=dim, heads=heads, dim_head=dim_head, dropout=dropout,
+                              context_dim=context_dim, context_pre_only=context_pre_only, qk_norm=qk_norm)
+        if not context_pre_only:
+            self.ff_norm_c = nn.LayerNorm(context_dim, elementwise_affine=False, eps=1e-6)
+            self.ff_c = FeedForward(dim=context_dim, mult=ff_mult, dropout=dropout, approximate="tanh")
+        else:
+            self.ff_norm_c = None
+            self.ff_c = None
+        self.ff_norm_x = nn.LayerNorm(dim, elementwise_affine=False, eps=1e-6)
+        self.ff_x = FeedForward(dim=dim, mult=ff_mult, dropout=dropout, approximate="tanh")
 
 
 # ---------------------------------------------------------------- codebook (reference modules.py:744-950, eval only)

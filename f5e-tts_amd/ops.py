@@ -157,6 +157,29 @@ def flash_attn(q: Tensor, k: Tensor, vt: Tensor, out: Tensor, rows_per_seq: int,
     return out
 
 
+def joint_attn(qx: Tensor, kx: Tensor, vtx: Tensor, qc: Optional[Tensor], kc: Tensor, vtc: Tensor, out_x: Tensor,
+               out_c: Optional[Tensor], N: int, Nt: int, kv_len: Optional[Tensor] = None, waves: int = 0):
+    """MMDiT joint attention (f5e_joint_attn): keys = audio keys < kv_len[s] (all N if None) ++ all Nt text keys.
+    qx, kx, vtx: [S, H, n_pad_x, 64]-sized and qc, kc, vtc: [S, H, n_pad_c, 64]-sized bf16 fragment-major buffers;
+    out_x bf16 [S*N, >= H*64], out_c bf16 [S*Nt, >= H*64] or None (text queries skipped); ``waves`` = KV splits."""
+    require_device()
+    S, H, n_pad_x, _ = qx.shape
+    n_pad_c = kc.shape[2]
+    if kx.shape != qx.shape or vtx.numel() != qx.numel() or kc.shape[:2] != (S, H) or vtc.numel() != kc.numel():
+        raise _C.F5EError("joint_attn: audio buffers [S, H, n_pad_x, 64], text buffers [S, H, n_pad_c, 64]")
+    if out_c is not None and (qc is None or qc.shape != kc.shape):
+        raise _C.F5EError("joint_attn: out_c needs qc of kc's shape")
+    if out_x.shape[0] != S * N or (out_c is not None and out_c.shape[0] != S * Nt):
+        raise _C.F5EError(f"joint_attn: out_x must have S*N = {S * N} rows and out_c S*Nt = {S * Nt}")
+    if kv_len is not None and kv_len.numel() < S:
+        raise _C.F5EError(f"joint_attn: kv_len needs one entry per sequence ({S})")
+    check(lib().f5e_joint_attn(_stream(), _p(qx, BF, "qx"), _p(kx, BF, "kx"), _p(vtx, BF, "vtx"), _p(qc, BF, "qc"),
+                               _p(kc, BF, "kc"), _p(vtc, BF, "vtc"), _p(out_x, BF, "out_x"), out_x.stride(0),
+                               _p(out_c, BF, "out_c"), out_c.stride(0) if out_c is not None else 0,
+                               _p(kv_len, I32, "kv_len"), S, H, N, n_pad_x, Nt, n_pad_c, waves), "f5e_joint_attn")
+    return out_x, out_c
+
+
 def layernorm(x: Tensor, out: Tensor, gamma: Optional[Tensor] = None, beta: Optional[Tensor] = None,
               scale: Optional[Tensor] = None, shift: Optional[Tensor] = None, rows_per_seq: int = 1,
               eval_ptr: Optional[Tensor] = None, eval_stride: int = 0, eps: float = 1e-6):

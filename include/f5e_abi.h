@@ -122,6 +122,19 @@ F5E_API int f5e_gemm_bf16_qkv_rope_ln(f5e_stream st, const void* A, int lda, con
 F5E_API int f5e_flash_attn(f5e_stream st, const void* q, const void* k, const void* vt, void* o, int ldo, const int* kv_len,
                    int S, int H, int rows_per_seq, int n_pad, int splits);
 
+/* MMDiT joint attention: per (sequence s, head h) the keys / values are the audio keys 0 .. kv_len[s]-1 followed by the
+ * text keys 0 .. Nt-1 (kv_len NULL = all N audio keys; text keys are never masked), and
+ *   o_x[s*N  + i][h*64 + d] (ldo_x) = softmax(qx k^T / 8) v   for the audio queries i < N,
+ *   o_c[s*Nt + j][h*64 + d] (ldo_c) = softmax(qc k^T / 8) v   for the text queries j < Nt  (o_c NULL: skipped, qc unused).
+ * qx / kx / vx and qc / kc / vc are two sets of f5e_gemm_bf16_qkv_rope outputs (fragment-major, q pre-scaled by log2(e) / 8):
+ * audio [S][H][n_pad_x][64] written with rows_per_seq = N, text [S][H][n_pad_c][64] written with rows_per_seq = Nt and
+ * its own RoPE table from position 0.  splits: KV splits per 32-query tile (0 = auto, 1, 2 or 4).
+ * Replaces: the concatenation of the two streams, the padded key mask and F.scaled_dot_product_attention + the split of
+ * its output (modules.py:688-710). */
+F5E_API int f5e_joint_attn(f5e_stream st, const void* qx, const void* kx, const void* vx, const void* qc, const void* kc,
+                   const void* vc, void* o_x, int ldo_x, void* o_c, int ldo_c, const int* kv_len, int S, int H, int N,
+                   int n_pad_x, int Nt, int n_pad_c, int splits);
+
 /* ---------------------------------------------------------------- normalisation ------------------------------ */
 
 /* y = LN(x; eps)  [* gamma + beta]  [* (1 + scale[r]) + shift[r]],  r = (row / rows_per_seq) % mod_rows.

@@ -57,6 +57,8 @@ SIGNATURES = {
     "f5e_glu": [_P, _P, _I, _P, _I, _LL, _I],
     "f5e_dwconv": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
     "f5e_softmax_rows": [_P, _P, _I, _P, _I, _P, _LL, _I, _I, _F],
+    "f5e_dwconv_stream": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],
+    "f5e_relpos_attn": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F],
     "f5e_dit_forward": [_P, _P],
     "f5e_sample_loop": [_P, _P],
     "f5e_workspace_bytes": [_P, _P],

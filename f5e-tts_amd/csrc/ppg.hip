@@ -7,6 +7,8 @@
 //   f5e_glu            nn.functional.glu over the channel axis (ppg/wenet/transformer/convolution.py:119), channels-last.
 //   f5e_dwconv         depthwise Conv1d(C, C, k, padding (k - 1) / 2, groups C), channels-last fp32, any odd k <= 31
 //                      (ConvolutionModule.depthwise_conv, k = 15; eval-mode BatchNorm folded into weight / bias on the host).
+//   f5e_dwconv_stream  the same convolution restricted to the frame's chunk, or causal with a constant left fill (the two
+//                      forms the chunk-by-chunk streaming mode needs, encoder.py:210-355 + convolution.py:103-116).
 //   f5e_softmax_rows   softmax(scale * x[row, :len]) with the keys >= len of the row's sequence set to 0
 //                      (MultiHeadedAttention.forward_attention, attention.py:75-87: masked_fill(-inf), softmax, masked_fill(0)).
 #include "f5e_common.h"
@@ -107,6 +109,38 @@ __global__ __launch_bounds__(256) void dwconv_kernel(const float* x, const float
   }
 }
 
+// the two convolutions of the chunk-trained (streaming) conformer (convolution.py:81-134), y may not alias x:
+//   causal == 0: symmetric taps t + j - (K - 1) / 2 that stay inside t's chunk [c chunk, (c + 1) chunk) and the sequence:
+//                what the chunk-by-chunk loop computes when every chunk is convolved on its own with zero padding
+//   causal != 0: taps t - (K - 1) .. t; positions before the sequence read fill[c] (GLU(pointwise_conv1.bias): the
+//                reference pads zeros BEFORE pointwise_conv1), or 0 without fill
+__global__ __launch_bounds__(256) void dwconv_stream_kernel(const float* x, const float* wT, const float* bias,
+                                                             const float* fill, float* y, int B, int T, int C, int K,
+                                                             int causal, int chunk) {
+  const int c4n = C / 4, pad = causal ? K - 1 : (K - 1) / 2;
+  const size_t total = (size_t)B * T * c4n;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % c4n) * 4;
+    const size_t bt = i / c4n;
+    const int t = (int)(bt % T);
+    const size_t b = bt / T;
+    int lo = 0, hi = T;
+    if (!causal && chunk > 0) {
+      lo = t / chunk * chunk;
+      hi = min(lo + chunk, T);
+    }
+    f32x4 acc = *(const f32x4*)(bias + c);
+    for (int j = 0; j < K; ++j) {
+      const int tj = t + j - pad;
+      if (tj >= lo && tj < hi)
+        acc += *(const f32x4*)(wT + (size_t)j * C + c) * *(const f32x4*)(x + (b * T + tj) * C + c);
+      else if (causal && fill && tj < 0)
+        acc += *(const f32x4*)(wT + (size_t)j * C + c) * *(const f32x4*)(fill + c);
+    }
+    *(f32x4*)(y + (b * T + t) * C + c) = acc;
+  }
+}
+
 // one wave per row; row r belongs to sequence r / rows_per_seq whose valid key count is kv_len[seq] (or L)
 __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* x, int ldx, float* y, int ldy, const int* kv_len,
                                                             size_t rows, int rows_per_seq, int L, float scale) {
@@ -163,6 +197,17 @@ int f5e_dwconv(hipStream_t st, const float* x, const float* w_t, const float* bi
   hipLaunchKernelGGL(dwconv_kernel, dim3(grid_for((size_t)B * T * C / 4)), dim3(256), 0, st, x, w_t, bias, keep, y, B, T,
                      C, K);
   F5E_LAUNCH_CHECK("dwconv");
+  return F5E_OK;
+}
+
+int f5e_dwconv_stream(hipStream_t st, const float* x, const float* w_t, const float* bias, const float* fill, float* y,
+                      int B, int T, int C, int K, int causal, int chunk) {
+  F5E_REQUIRE(x && w_t && bias && y && x != y, "dwconv_stream: null operand or y aliases x");
+  F5E_REQUIRE(B > 0 && T > 0 && C > 0 && C % 4 == 0 && K > 0 && K <= 31 && (causal || (K & 1)),
+              "dwconv_stream: C %% 4 == 0, K <= 31, and odd K unless causal");
+  hipLaunchKernelGGL(dwconv_stream_kernel, dim3(grid_for((size_t)B * T * C / 4)), dim3(256), 0, st, x, w_t, bias, fill, y,
+                     B, T, C, K, causal, chunk);
+  F5E_LAUNCH_CHECK("dwconv_stream");
   return F5E_OK;
 }
 

@@ -286,6 +286,9 @@ def main(argv=None):
                                                      "utterances whose content is converted (default: --audio_root)")
     p.add_argument("--ppg_model", default="", help="PPG checkpoint (default: ppg_config.model_path of the model yaml)")
     p.add_argument("--ppg_config", default="", help="PPG train.yaml (default: ppg_config.config of the model yaml)")
+    p.add_argument("--ppg_stream", action="store_true",
+                   help="vc mode without --ppg_dir: extract the PPGs chunk by chunk (extract(stream=True): 16-frame chunks, "
+                        "17 left chunks), for conversion models trained on streaming PPGs; needs a chunk-trained PPG model")
     args = p.parse_args(argv)
 
     import torch.distributed as dist
@@ -364,7 +367,7 @@ def main(argv=None):
                                    output_type=fc["output_type"], ppg_frame_length=fc["frame_length"],
                                    mel_f_shift=fc["mel_frame_shift"], map_mix_ratio=fc["map_mix_ratio"],
                                    global_phn_center_path=fc["global_phn_center_path"],
-                                   para_softmax_path=fc["para_softmax_path"])
+                                   para_softmax_path=fc["para_softmax_path"], stream=args.ppg_stream)
 
     def extract_ppg(utt, ref_path):
         from ..infer import audio as A

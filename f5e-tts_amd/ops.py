@@ -514,6 +514,42 @@ def softmax_rows(x: Tensor, out: Tensor, L: int, scale: float, kv_len: Optional[
     return out
 
 
+def dwconv_stream(x: Tensor, w_t: Tensor, bias: Tensor, out: Tensor, causal: bool = False, chunk: int = 0,
+                  fill: Optional[Tensor] = None):
+    """Depthwise conv over time of the streaming conformer, channels-last f32 [B, T, C]; w_t [K, C].  causal False: taps
+    that stay inside the frame's chunk (chunk <= 0: the whole sequence); causal True: taps t-(K-1)..t, positions before
+    the sequence read the per-channel constant ``fill`` [C] (None: 0)."""
+    require_device()
+    B, T, Cc = x.shape
+    check(lib().f5e_dwconv_stream(_stream(), _p(x, F32, "x"), _p(w_t, F32, "w_t"), _p(bias, F32, "bias"),
+                                  _p(fill, F32, "fill"), _p(out, F32, "out"), B, T, Cc, w_t.shape[0], int(bool(causal)),
+                                  int(chunk)), "f5e_dwconv_stream")
+    return out
+
+
+def relpos_attn(qu: Tensor, k: Tensor, pos: Tensor, v: Tensor, out: Tensor, heads: int, scale: float, B: int = 1,
+                kv_len: Optional[Tensor] = None, chunk: int = 0, left_chunks: int = -1, q_begin: int = 0):
+    """Fused relative-position attention with an optional chunk band (f5e_abi.h): qu f32 [B*T, 2D] (q+u | q+v), k / v / out
+    f32 [B*T, D], pos f32 [>= T, D] indexed by the key; chunk <= 0: full context, left_chunks < 0: all left chunks."""
+    require_device()
+    M, D = out.shape
+    T = M // B
+    if M != B * T or qu.shape != (M, 2 * D) or k.shape != (M, D) or v.shape != (M, D) or pos.shape[0] < T or \
+            pos.shape[1] != D or D % heads:
+        raise _C.F5EError(f"relpos_attn: inconsistent shapes qu {tuple(qu.shape)} k {tuple(k.shape)} pos {tuple(pos.shape)} "
+                          f"v {tuple(v.shape)} out {tuple(out.shape)} B={B} heads={heads}")
+    for n_, t_ in (("qu", qu), ("k", k), ("pos", pos), ("v", v), ("out", out)):
+        if t_.stride(1) != 1:
+            raise _C.F5EError(f"relpos_attn: {n_} must have unit column stride")
+    if kv_len is not None and kv_len.numel() != B:
+        raise _C.F5EError("relpos_attn: kv_len needs one entry per sequence")
+    check(lib().f5e_relpos_attn(_stream(), _p(qu, F32, "qu"), qu.stride(0), _p(k, F32, "k"), k.stride(0),
+                                _p(pos, F32, "pos"), pos.stride(0), _p(v, F32, "v"), v.stride(0), _p(out, F32, "out"),
+                                out.stride(0), _p(kv_len, I32, "kv_len"), B, T, heads, D // heads, int(q_begin), int(chunk),
+                                int(left_chunks), float(scale)), "f5e_relpos_attn")
+    return out
+
+
 def dit_forward(plan: "_C.DitPlan"):
     require_device()
     check(lib().f5e_dit_forward(_stream(), C.byref(plan)), "f5e_dit_forward")

@@ -10,14 +10,18 @@ global CMVN are folded into the adjacent convolution weights, ``pos_bias_u / v``
 
 What is built is the configuration the reference ships (``encoder: conformer``, ``input_layer: conv2d`` = 1/2
 subsampling for 20 ms PPG frames, ``rel_pos``, macaron feed-forward, convolution module with batch norm, swish, pre-norm,
-no chunking: ``extract(stream=False)`` decodes with the full context).  Other encoder variants raise F5EError.
+``causal`` either way).  ``extract(stream=False)`` decodes with the full context; ``extract(stream=True)`` reproduces the
+reference's chunk-by-chunk loop (``BaseEncoder.forward_chunk_by_chunk(speech, 16, 17)``, encoder.py:293-355) as ONE pass
+with a banded attention kernel (``f5e_relpos_attn``) and a chunk-isolated or causal depthwise convolution
+(``f5e_dwconv_stream``); ``forward_encoder_chunk`` is the incremental form with explicit caches.  Other encoder variants
+raise F5EError.
 """
 from __future__ import annotations
 
 import json
 import math
 import os
-from typing import Dict, Optional, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -127,13 +131,17 @@ class ConformerPPG(nn.Module):
 
     def __init__(self, input_dim: int = 80, vocab_size: int = 218, output_size: int = 256, attention_heads: int = 4,
                  linear_units: int = 2048, num_blocks: int = 6, cnn_module_kernel: int = 15,
-                 global_cmvn: Optional[Tuple[Tensor, Tensor]] = None):
+                 global_cmvn: Optional[Tuple[Tensor, Tensor]] = None, causal: bool = False,
+                 use_dynamic_chunk: bool = False, static_chunk_size: int = 0):
         super().__init__()
         cm = _GlobalCMVN(global_cmvn[0].float(), global_cmvn[1].float()) if global_cmvn is not None else None
         self.encoder = _Encoder(input_dim, output_size, attention_heads, linear_units, num_blocks, cnn_module_kernel, cm)
         self.linear = nn.Linear(output_size, output_size)
         self.ce = _CE(output_size, vocab_size + 1)
         self.input_dim, self.heads, self.dim = input_dim, attention_heads, output_size
+        # causal: the depthwise convolution looks back only (convolution.py:45-52); the chunk settings say whether the
+        # model was trained with chunk masks, which the streaming mode requires (encoder.py:327)
+        self.causal, self.use_dynamic_chunk, self.static_chunk_size = bool(causal), bool(use_dynamic_chunk), int(static_chunk_size)
         self._engine = None
 
     @classmethod
@@ -143,7 +151,7 @@ class ConformerPPG(nn.Module):
         if configs.get("encoder", "conformer") != "conformer":
             raise _C.F5EError("PPG extractor: only `encoder: conformer` is built for MI355X")
         bad = {k: enc[k] for k, want in dict(input_layer="conv2d", pos_enc_layer_type="rel_pos", normalize_before=True,
-                                             concat_after=False, macaron_style=True, use_cnn_module=True, causal=False,
+                                             concat_after=False, macaron_style=True, use_cnn_module=True,
                                              cnn_module_norm="batch_norm", activation_type="swish", use_emb=False,
                                              positionwise_conv_kernel_size=1).items() if k in enc and enc[k] != want}
         if bad:
@@ -153,7 +161,9 @@ class ConformerPPG(nn.Module):
             mean, istd = load_cmvn(configs["cmvn_file"], configs["is_json_cmvn"])
             cmvn = (torch.from_numpy(mean).float(), torch.from_numpy(istd).float())
         return cls(configs["input_dim"], configs["output_dim"], enc.get("output_size", 256), enc.get("attention_heads", 4),
-                   enc.get("linear_units", 2048), enc.get("num_blocks", 6), enc.get("cnn_module_kernel", 15), cmvn)
+                   enc.get("linear_units", 2048), enc.get("num_blocks", 6), enc.get("cnn_module_kernel", 15), cmvn,
+                   causal=enc.get("causal", False), use_dynamic_chunk=enc.get("use_dynamic_chunk", False),
+                   static_chunk_size=enc.get("static_chunk_size", 0))
 
     def _apply(self, fn, *a, **kw):
         self._engine = None
@@ -168,26 +178,49 @@ class ConformerPPG(nn.Module):
         if self._engine is None or self._engine.device != dev:
             if dev.type != "cuda":
                 raise _C.F5EError(f"PPG model lives on {dev}: move it to the GPU (there is no CPU path)")
-            self._engine = ConformerEngine(self.state_dict(), self.heads, dev, self.input_dim)
+            self._engine = ConformerEngine(self.state_dict(), self.heads, dev, self.input_dim, causal=self.causal)
         return self._engine
 
     @torch.no_grad()
     def extract(self, speech: Tensor, speech_lengths: Tensor, stream: bool = False) -> Tuple[Tensor, Tensor]:
         """reference asr_model.py:221-244 -> (ppg [B, T', D], logits [B*T', vocab + 1])."""
-        if stream:
-            raise _C.F5EError("PPG extractor: the chunk-by-chunk streaming mode is not built (extract(stream=False))")
         assert speech.shape[0] == speech_lengths.shape[0]
+        if stream:
+            # forward_chunk_by_chunk(speech, 16, 17): chunk of 16 encoder frames, 17 left chunks; speech_lengths is not
+            # used and the batch must be 1 (encoder.py:243), the model chunk-trained (encoder.py:327)
+            self._require_stream(speech)
+            eng = self.engine()
+            return eng.head(eng.forward_chunk_by_chunk(speech, 16, 17))
         return self.engine().forward(speech, speech_lengths)
+
+    def _require_stream(self, xs: Tensor) -> None:
+        if not (self.static_chunk_size > 0 or self.use_dynamic_chunk):
+            raise _C.F5EError("PPG extractor: streaming needs a chunk-trained model (static_chunk_size > 0 or "
+                              "use_dynamic_chunk in encoder_conf)")
+        if xs.shape[0] != 1:
+            raise _C.F5EError(f"PPG extractor: streaming runs one utterance at a time (batch {xs.shape[0]})")
+
+    @torch.no_grad()
+    def forward_encoder_chunk(self, xs: Tensor, offset: int, required_cache_size: int,
+                              subsampling_cache: Optional[Tensor] = None,
+                              elayers_output_cache: Optional[List[Tensor]] = None,
+                              conformer_cnn_cache: Optional[List[Tensor]] = None):
+        """reference asr_model.py:705-737 -> BaseEncoder.forward_chunk (encoder.py:210-291): one window of features
+        ``xs`` [1, n, idim] whose first output frame is encoder frame ``offset`` -> (encoder output of the new frames
+        [1, n', D], subsampling cache, per-layer output caches, per-layer convolution caches)."""
+        self._require_stream(xs)
+        return self.engine().forward_chunk(xs, offset, required_cache_size, subsampling_cache, elayers_output_cache,
+                                           conformer_cnn_cache)
 
 
 class ConformerEngine:
     """Repacked fp32 weights + the launch sequence of ``BaseEncoder.forward`` (wenet/transformer/encoder.py:141-209)."""
 
-    def __init__(self, sd: Dict[str, Tensor], heads: int, device, idim: int):
+    def __init__(self, sd: Dict[str, Tensor], heads: int, device, idim: int, causal: bool = False):
         ops.require_device()
         self.device = dv = torch.device(device)
         f = lambda k: sd[k].detach().to(dv, F32).contiguous()   # noqa: E731
-        self.heads = heads
+        self.heads, self.causal = heads, bool(causal)
         cw, cb = f("encoder.embed.conv.0.weight"), f("encoder.embed.conv.0.bias")        # [C, 1, 3, 3]
         C = cw.shape[0]
         ow = f("encoder.embed.out.0.weight")                                             # [D, C * F2]
@@ -225,6 +258,9 @@ class ConformerEngine:
             cm = p + "conv_module."
             dw, db = f(cm + "depthwise_conv.weight")[:, 0, :], f(cm + "depthwise_conv.bias")       # [D, k]
             s = f(cm + "norm.weight") / torch.sqrt(f(cm + "norm.running_var") + 1e-5)             # eval-mode BatchNorm1d
+            if not self.causal and dw.shape[1] % 2 == 0:
+                raise _C.F5EError(f"PPG extractor: cnn_module_kernel {dw.shape[1]} must be odd unless causal")
+            pb1 = f(cm + "pointwise_conv1.bias")
             self.layers.append(dict(
                 ln={n_: (f(p + n_ + ".weight"), f(p + n_ + ".bias"))
                     for n_ in ("norm_ff", "norm_mha", "norm_ff_macaron", "norm_conv", "norm_final")},
@@ -239,6 +275,9 @@ class ConformerEngine:
                 pw1=f(cm + "pointwise_conv1.weight")[:, :, 0].contiguous(), pb1=f(cm + "pointwise_conv1.bias"),
                 dw=(dw * s[:, None]).t().contiguous(),
                 db=((db - f(cm + "norm.running_mean")) * s + f(cm + "norm.bias")).contiguous(),
+                # causal: what the depthwise conv sees left of an utterance is GLU(pointwise_conv1(0)) (the reference pads
+                # zeros BEFORE pointwise_conv1, convolution.py:103-119)
+                fill=(pb1[:D] * torch.sigmoid(pb1[D:])).contiguous(),
                 pw2=f(cm + "pointwise_conv2.weight")[:, :, 0].contiguous(), pb2=f(cm + "pointwise_conv2.bias")))
             i += 1
         self.after = (f("encoder.after_norm.weight"), f("encoder.after_norm.bias"))
@@ -248,16 +287,23 @@ class ConformerEngine:
         self.dk = dk
         self._pe: Dict[int, Tensor] = {}
 
-    def pos_table(self, t: int) -> Tensor:
-        """PositionalEncoding.pe[:, :t] (embedding.py:34-46), a constant table built in fp32 like the reference."""
-        if t not in self._pe:
-            d = self.dim
-            pe = torch.zeros(t, d)
-            pos = torch.arange(0, t, dtype=F32).unsqueeze(1)
-            div = torch.exp(torch.arange(0, d, 2, dtype=F32) * -(math.log(10000.0) / d))
-            pe[:, 0::2], pe[:, 1::2] = torch.sin(pos * div), torch.cos(pos * div)
-            self._pe = {t: pe.to(self.device).contiguous()}
-        return self._pe[t]
+    def pos_table(self, t: int, offset: int = 0) -> Tensor:
+        """PositionalEncoding.pe[:, offset:offset + t] (embedding.py:34-46, 65-82), a constant table built in fp32 like the
+        reference.  One table is cached; threads may race to replace it, so the entry is built into a local, published
+        as a whole new dict and returned from the local: a caller never indexes a dict another thread has swapped."""
+        n = offset + t
+        for have, pe in self._pe.items():       # a snapshot of the dict object; rows do not depend on the table's length
+            if have >= n:
+                return pe[offset:n]
+        d = self.dim
+        rows = n if offset == 0 else (n + 511) // 512 * 512       # incremental callers come back with growing offsets
+        pe = torch.zeros(rows, d)
+        pos = torch.arange(0, rows, dtype=F32).unsqueeze(1)
+        div = torch.exp(torch.arange(0, d, 2, dtype=F32) * -(math.log(10000.0) / d))
+        pe[:, 0::2], pe[:, 1::2] = torch.sin(pos * div), torch.cos(pos * div)
+        pe = pe.to(self.device).contiguous()
+        self._pe = {rows: pe}
+        return pe[offset:n]
 
     def forward(self, feats: Tensor, lens: Tensor) -> Tuple[Tensor, Tensor]:
         dv, D, H, dk = self.device, self.dim, self.heads, self.dk
@@ -340,7 +386,10 @@ class ConformerEngine:
             else:
                 ops.gemm_f32(hn, L["pw1"], L["pb1"], out=pw)
             ops.glu(pw, gl.view(M, D))
-            ops.dwconv(gl, L["dw"], L["db"], dwo)
+            if self.causal:
+                ops.dwconv_stream(gl, L["dw"], L["db"], dwo, causal=True, fill=L["fill"])
+            else:
+                ops.dwconv(gl, L["dw"], L["db"], dwo)
             ops.gemm_f32(dwo.view(M, D), L["pw2"], L["pb2"], out=hn, a_act=ops.ACT_SILU, row_scale=keep_flat)
             ops.axpby(xs, hn, xs, 1.0, 1.0)
             # feed-forward + final norm
@@ -359,6 +408,154 @@ class ConformerEngine:
         if getattr(self, "_eye_t", None) is None or self._eye_t.shape[0] != d:
             self._eye_t = torch.eye(d, device=self.device)
         return self._eye_t
+
+    # ---- chunk-by-chunk (streaming) mode: BaseEncoder.forward_chunk / forward_chunk_by_chunk (encoder.py:210-355)
+    #
+    # The reference feeds overlapping windows of 2 chunk + 1 feature frames at stride 2 chunk through forward_chunk, which
+    # keeps the last chunk * left_chunks rows of every layer's output as keys / values for the next window and convolves
+    # each chunk on its own.  Everything in a layer is row-wise except (a) the attention, where a query of chunk
+    # c = t // chunk therefore sees keys [max(0, (c - left) chunk), (c + 1) chunk), the position term indexed by the key's
+    # absolute position, and (b) the depthwise convolution: causal with kernel - 1 frames of carried left context, or, not
+    # causal, zero-padded inside each chunk.  forward_chunk_by_chunk is that as ONE pass (one attention launch per layer
+    # whatever the number of chunks); forward_chunk runs the same kernels on [cached rows ; new rows].
+
+    def _subsample(self, x: Tensor) -> Tensor:
+        """Conv2dSubsampling2 + xscale of one utterance [1, T, idim] -> [T', D] (as in ``forward``)."""
+        _, T, idim = x.shape
+        if idim != self.idim:
+            raise _C.F5EError(f"PPG extractor: features have {idim} bins, the model expects {self.idim}")
+        if T < 3:
+            raise _C.F5EError("PPG extractor: needs at least 3 feature frames")
+        dv, T2 = self.device, (T - 3) // 2 + 1
+        col = torch.empty(1, T, self.sub_k, device=dv)
+        ops.im2col(x, col, 3, 0)
+        h = torch.empty(T2, self.sub_w.shape[0], device=dv)
+        ops.gemm_f32(col.view(T, self.sub_k)[0:T:2], self.sub_w, self.sub_b, out=h, M=T2, act=ops.ACT_RELU)
+        xs = torch.empty(T2, self.dim, device=dv)
+        ops.gemm_f32(h, self.out_w, self.out_b, out=xs)
+        ops.axpby(xs, None, xs, self.xscale, 0.0, 0.0)
+        return xs
+
+    def _stream_layer(self, L: dict, x: Tensor, q0: int, pos: Tensor, chunk: int, left: int,
+                      cnn_cache: Optional[Tensor], one_pass: bool) -> Tuple[Tensor, Optional[Tensor]]:
+        """One conformer layer over x [R, D] (updated in place): rows < q0 are cached rows that only serve as keys / values
+        (encoder_layer.py:220-231), rows >= q0 are computed.  one_pass: q0 = 0, the band (chunk, left) and the conv's chunk
+        isolation / left fill apply.  Otherwise every cached key is visible and the conv runs on the new rows behind
+        ``cnn_cache`` [1, D, K - 1] (causal) or on their own.  -> (the new rows' output, a view of x; new conv cache)."""
+        dv, D, H = self.device, self.dim, self.heads
+        R, n = x.shape[0], x.shape[0] - q0
+        ln = L["ln"]
+        hn = torch.empty(R, D, device=dv)
+        mid = torch.empty(R, L["ffm"][0].shape[0], device=dv)
+        ops.layernorm(x, hn, gamma=ln["norm_ff_macaron"][0], beta=ln["norm_ff_macaron"][1], eps=1e-5)
+        ops.gemm_f32(hn, L["ffm"][0], L["ffm"][1], out=mid, act=ops.ACT_SILU)
+        ops.gemm_f32(mid, L["ffm"][2], L["ffm"][3], out=x, ch_scale=self.half[:D], addend=x)
+        ops.layernorm(x, hn, gamma=ln["norm_mha"][0], beta=ln["norm_mha"][1], eps=1e-5)
+        qu, kb, vb = torch.empty(R, 2 * D, device=dv), torch.empty(R, D, device=dv), torch.empty(R, D, device=dv)
+        pb, ctx = torch.empty(R, D, device=dv), torch.empty(R, D, device=dv)
+        ops.gemm_f32(hn, L["wq2"], L["bq2"], out=qu)
+        ops.gemm_f32(hn, L["wk"], L["bk"], out=kb)
+        ops.gemm_f32(hn, L["wv"], L["bv"], out=vb)
+        ops.gemm_f32(pos, L["wp"], None, out=pb)
+        ops.relpos_attn(qu, kb, pb, vb, ctx, H, 1.0 / math.sqrt(self.dk), chunk=chunk if one_pass else 0,
+                        left_chunks=left, q_begin=q0)
+        xq = x[q0:]
+        ops.gemm_f32(ctx[q0:], L["wo"], L["bo"], out=xq, addend=xq)
+        # convolution module (convolution.py:81-134) on the new rows
+        hq = torch.empty(n, D, device=dv)
+        ops.layernorm(xq, hq, gamma=ln["norm_conv"][0], beta=ln["norm_conv"][1], eps=1e-5)
+        K = L["dw"].shape[0]
+        causal = self.causal and K > 1
+        src, skip, new_cache = hq, 0, None
+        if causal and not one_pass:
+            prev = cnn_cache[0].t().to(dv, F32) if cnn_cache is not None else torch.zeros(K - 1, D, device=dv)
+            src, skip = torch.cat((prev, hq), 0), K - 1
+            new_cache = src[-(K - 1):].t().unsqueeze(0).contiguous()
+        elif not one_pass:
+            new_cache = torch.zeros(1, device=dv)                # the reference's dummy (convolution.py:113-116)
+        rows = src.shape[0]
+        pw = torch.empty(rows, 2 * D, device=dv)
+        gl, dwo = torch.empty(1, rows, D, device=dv), torch.empty(1, rows, D, device=dv)
+        ops.gemm_f32(src, L["pw1"], L["pb1"], out=pw)
+        ops.glu(pw, gl.view(rows, D))
+        if causal:
+            ops.dwconv_stream(gl, L["dw"], L["db"], dwo, causal=True, fill=L["fill"] if one_pass else None)
+        else:
+            ops.dwconv_stream(gl, L["dw"], L["db"], dwo, causal=False, chunk=chunk if one_pass else 0)
+        ops.gemm_f32(dwo.view(rows, D)[skip:], L["pw2"], L["pb2"], out=hq, a_act=ops.ACT_SILU)
+        ops.axpby(xq, hq, xq, 1.0, 1.0)
+        ops.layernorm(xq, hq, gamma=ln["norm_ff"][0], beta=ln["norm_ff"][1], eps=1e-5)
+        ops.gemm_f32(hq, L["ff"][0], L["ff"][1], out=mid[:n], act=ops.ACT_SILU)
+        ops.gemm_f32(mid[:n], L["ff"][2], L["ff"][3], out=xq, ch_scale=self.half[:D], addend=xq)
+        ops.layernorm(xq, xq, gamma=ln["norm_final"][0], beta=ln["norm_final"][1], eps=1e-5)
+        return xq, new_cache
+
+    @staticmethod
+    def stream_frames(num_frames: int, chunk: int) -> int:
+        """Encoder frames the reference's loop yields (encoder.py:328-343): windows of 2 (chunk - 1) + 3 feature frames at
+        stride 2 chunk, starting while ``cur < num_frames - 3 + 1``; each window of n frames gives (n - 3) // 2 + 1."""
+        window, total = 2 * (chunk - 1) + 3, 0
+        for cur in range(0, num_frames - 3 + 1, 2 * chunk):
+            total += (min(cur + window, num_frames) - cur - 3) // 2 + 1
+        return total
+
+    def forward_chunk_by_chunk(self, feats: Tensor, decoding_chunk_size: int, num_decoding_left_chunks: int = -1) -> Tensor:
+        """BaseEncoder.forward_chunk_by_chunk (encoder.py:293-355) in one pass -> encoder output [1, T', D]."""
+        if decoding_chunk_size <= 0:
+            raise _C.F5EError("PPG extractor: decoding_chunk_size must be positive")
+        if feats.shape[0] != 1:
+            raise _C.F5EError(f"PPG extractor: streaming runs one utterance at a time (batch {feats.shape[0]})")
+        xs = self._subsample(feats.to(self.device, F32).contiguous())
+        n = self.stream_frames(feats.shape[1], decoding_chunk_size)
+        if n > xs.shape[0]:
+            raise _C.F5EError(f"PPG extractor: the streaming loop yields {n} frames, the subsampling {xs.shape[0]}")
+        xs = xs[:n]
+        pos = self.pos_table(n)
+        for L in self.layers:
+            self._stream_layer(L, xs, 0, pos, decoding_chunk_size, num_decoding_left_chunks, None, True)
+        out = torch.empty(n, self.dim, device=self.device)
+        ops.layernorm(xs, out, gamma=self.after[0], beta=self.after[1], eps=1e-5)
+        return out.unsqueeze(0)
+
+    def forward_chunk(self, xs: Tensor, offset: int, required_cache_size: int, subsampling_cache: Optional[Tensor] = None,
+                      elayers_output_cache: Optional[List[Tensor]] = None,
+                      conformer_cnn_cache: Optional[List[Tensor]] = None):
+        """BaseEncoder.forward_chunk (encoder.py:210-291): caches in the reference's shapes (subsampling / layer outputs
+        [1, rows, D], convolution [1, D, K - 1] or the dummy [1])."""
+        if xs.shape[0] != 1:
+            raise _C.F5EError(f"PPG extractor: streaming runs one utterance at a time (batch {xs.shape[0]})")
+        dv, D = self.device, self.dim
+        new = self._subsample(xs.to(dv, F32).contiguous())
+        cs = 0 if subsampling_cache is None else subsampling_cache.shape[1]
+        if offset < cs:
+            raise _C.F5EError(f"PPG extractor: offset {offset} is smaller than the cache ({cs} frames)")
+        x = torch.cat((subsampling_cache[0].to(dv, F32), new), 0) if cs else new
+        R = x.shape[0]
+        pos = self.pos_table(R, offset - cs)
+        start = 0 if required_cache_size < 0 else (R if required_cache_size == 0 else max(R - required_cache_size, 0))
+        r_sub, r_att, r_cnn = x[start:].unsqueeze(0).clone(), [], []
+        for i, L in enumerate(self.layers):
+            cache = None if elayers_output_cache is None else elayers_output_cache[i][0].to(dv, F32)
+            q0 = 0 if cache is None else cache.shape[0]
+            if not q0 < R:
+                raise _C.F5EError("PPG extractor: the layer output cache must be shorter than cache + chunk")
+            xq, cnn = self._stream_layer(L, x, q0, pos, 0, -1, None if conformer_cnn_cache is None else conformer_cnn_cache[i],
+                                         False)
+            x = torch.cat((cache, xq), 0) if q0 else xq
+            r_att.append(x[start:].unsqueeze(0).clone())
+            r_cnn.append(cnn)
+        out = torch.empty(R, D, device=dv)
+        ops.layernorm(x, out, gamma=self.after[0], beta=self.after[1], eps=1e-5)
+        return out[cs:].unsqueeze(0), r_sub, r_att, r_cnn
+
+    def head(self, enc: Tensor) -> Tuple[Tensor, Tensor]:
+        """``linear`` (the PPG) and ``ce.fc`` logits of an encoder output [B, T', D] (asr_model.py:241-244)."""
+        B, T2, D = enc.shape
+        ppg = torch.empty(B * T2, D, device=self.device)
+        ops.gemm_f32(enc.reshape(B * T2, D), self.lin_w, self.lin_b, out=ppg)
+        logits = torch.empty(B * T2, self.ce_w.shape[0], device=self.device)
+        ops.gemm_f32(ppg, self.ce_w, self.ce_b, out=logits)
+        return ppg.view(B, T2, D), logits
 
 
 # ------------------------------------------------------------------ features + wrapper (reference ppg/ppg_model.py)
@@ -434,12 +631,13 @@ class PPGModelWapper(object):
     """reference ppg/ppg_model.py:58-168 (name as spelled there)."""
 
     def __init__(self, ppg_model_path, ppg_config, device, output_type="ppg", map_mix_ratio=1.0, ppg_frame_length=20,
-                 mel_f_shift=10, global_phn_center_path=None, para_softmax_path=None):
+                 mel_f_shift=10, global_phn_center_path=None, para_softmax_path=None, stream: bool = False):
         print(f"loading ppg model from {ppg_model_path}")
         print(f"output_type : {output_type}")
         self.ppg_model = build_ppg_model(ppg_model_path, ppg_config, device)
         self.device, self.output_type, self.map_mix_ratio = device, output_type, map_mix_ratio
         self.ppg_frame_length, self.mel_f_shift = ppg_frame_length, mel_f_shift
+        self.stream = bool(stream)       # extract(stream=True): chunk-by-chunk PPGs for models trained on streaming PPGs
         self.featCal = kaldiFbank().eval()
         if self.output_type == "map":
             import pickle
@@ -486,7 +684,7 @@ class PPGModelWapper(object):
 
     @torch.no_grad()
     def mel_to_ppg(self, mel, mel_lens):
-        ppg, _logits = self.ppg_model.extract(mel, mel_lens, stream=False)
+        ppg, _logits = self.ppg_model.extract(mel, mel_lens, stream=getattr(self, "stream", False))
         true_len = (mel_lens.to("cpu") / (self.ppg_frame_length / self.mel_f_shift)).long().clamp(max=ppg.shape[1])
         return self.ppg_to_target(ppg, true_len), true_len.to(ppg.device)
 

@@ -284,6 +284,26 @@ F5E_API int f5e_dwconv(f5e_stream st, const float* x, const float* w_t, const fl
  * (ppg/wenet/transformer/attention.py:75-87). */
 F5E_API int f5e_softmax_rows(f5e_stream st, const float* x, int ldx, float* y, int ldy, const int* kv_len, long long rows,
                      int rows_per_seq, int L, float scale);
+/* The depthwise convolutions of a chunk-trained (streaming) conformer (convolution.py:81-134); layouts as f5e_dwconv, y must
+ * not alias x.  causal == 0: taps t + j - (K-1)/2 that lie in t's chunk [c*chunk, (c+1)*chunk) and in [0, T) (chunk <= 0:
+ * the whole sequence), odd K <= 31.  causal != 0: taps t-(K-1) .. t, any K <= 31; positions before the sequence read
+ * fill[c] (optional f32 [C], GLU(pointwise_conv1.bias); null: 0); chunk is ignored. */
+F5E_API int f5e_dwconv_stream(f5e_stream st, const float* x, const float* w_t, const float* bias, const float* fill, float* y,
+                      int B, int T, int C, int K, int causal, int chunk);
+/* Fused relative-position attention (attention.py:172-222, no rel_shift), exact fp32, one launch for all sequences, heads
+ * and 16-query tiles:  out[b*T + t][h*dk + d] = sum_k softmax_k(scale * (qu[.][h*dk + :] . k[b*T + k][h*dk + :] +
+ * qu[.][H*dk + h*dk + :] . pos[k][h*dk + :])) * v[b*T + k][h*dk + d]  over the keys k of the query's band.
+ *   qu  [B*T][>= 2*H*dk]  (q + pos_bias_u | q + pos_bias_v);  k, v, out [B*T][>= H*dk];  pos [>= T][>= H*dk] (row = key index)
+ *   kv_len (optional int32 [B]): keys >= kv_len[b] are not attended; query rows >= kv_len[b] produce zeros
+ *   chunk > 0: a query in chunk c = t / chunk attends keys [max(0, (c - left_chunks) * chunk), min((c + 1) * chunk, len))
+ *              (wenet/utils/mask.py subsequent_chunk_mask); chunk <= 0: full context; left_chunks < 0: all left chunks.
+ *              Key tiles outside a query tile's band are skipped, so the work is linear in T for a bounded band.
+ *   q_begin:   only query rows t >= q_begin of each sequence are computed and written (a chunk appended to cached rows)
+ * Head dims dk = 16, 32, 64, 128; row strides multiples of 4 floats, qu / k / pos / out 16-byte aligned.  No allocation,
+ * no synchronisation. */
+F5E_API int f5e_relpos_attn(f5e_stream st, const float* qu, int ldq, const float* k, int ldk, const float* pos, int ldp,
+                    const float* v, int ldv, float* out, int ldo, const int* kv_len, int B, int T, int H, int dk,
+                    int q_begin, int chunk, int left_chunks, float scale);
 
 /* ---------------------------------------------------------------- fused DiT evaluation ----------------------- */
 

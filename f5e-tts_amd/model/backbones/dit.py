@@ -1,15 +1,18 @@
-"""DiT backbone mirror (reference model/backbones/dit.py:37-283,417-472): same constructor signature, attributes
-(``.dim``, ``.depth``), ``state_dict`` keys and ``sample`` / ``clear_cache`` methods.  The members are parameter
-containers; the computation is ``engine.DiTEngine`` on libf5e_hip.so.  Training (``forward``) is out of scope."""
+"""DiT backbone mirror (reference model/backbones/dit.py:37-283,309-360,417-472): same constructor signature, attributes
+(``.dim``, ``.depth``), ``state_dict`` keys and ``sample`` / ``clear_cache`` / ``align_text_ppg`` / ``calc_align_loss``
+methods.  The members are parameter containers; the computation is ``engine.DiTEngine`` on libf5e_hip.so.  Training
+(``forward``) is out of scope."""
 from __future__ import annotations
 
-from typing import Optional
+import math
+from typing import Optional, Tuple
 
 import torch
 from torch import nn
 
-from ... import _C
+from ... import _C, ops
 from ...engine import DiTConfig, DiTEngine
+from ..monotonic_align import dense_path, maximum_path_index
 from ..modules import (AdaLayerNorm_Final, ConvNeXtV2Block, ConvPositionEmbedding, DiTBlock, GumbelVectorQuantizer,
                        TimestepEmbedding)
 
@@ -102,6 +105,9 @@ class DiT(nn.Module):
                 groups=cb_config["groups"], combine_groups=cb_config["combine_groups"], vq_dim=text_dim,
                 time_first=True, weight_proj_depth=cb_config["weight_proj_depth"],
                 weight_proj_factor=cb_config["weight_proj_factor"])
+        # text-PPG alignment (reference dit.py:255-258): forward-only here, see align_text_ppg / calc_align_loss
+        self.use_align_loss = bool(self.use_codebook and cb_config.get("use_align_loss", False))
+        self.align_loss_weight = (cb_config.get("align_loss_config") or {}).get("align_loss_weight", 1.0)
         self.input_embed = InputEmbedding(mel_dim, text_dim, dim, self.use_ppg)
         self.rotary_embed = RotaryEmbedding(dim_head)
         self.dim, self.depth = dim, depth
@@ -192,6 +198,79 @@ class DiT(nn.Module):
         y = x.to(dv, F32).contiguous()
         plan = eng.make_plan(B, B, N, y, in_const, mod, None, eng.rope_table(N), seq_len)
         return eng.forward(plan).view(B, N, -1).clone()
+
+    # ------------------------------------------------------------------ text-PPG alignment (reference dit.py:309-360)
+
+    @staticmethod
+    def _block_len(lens, n: int) -> int:
+        """Rows / columns of the likelihood block: the longest sequence when the lengths are on the host, else all n
+        (a device maximum would cost a sync)."""
+        if isinstance(lens, torch.Tensor) and lens.device.type != "cpu":
+            return n
+        return max(1, min(n, int(torch.as_tensor(lens).max())))
+
+    @torch.no_grad()
+    def align_logp(self, text_embed, ppg_embed, Ty: int, Tx: int) -> torch.Tensor:
+        """Gaussian log-likelihood of every PPG-frame embedding under every text-token embedding (unit variance; reference
+        dit.py:320-325) -> f32 [b, Ty, Tx]:  -d/2 log(2 pi) - |p|^2 / 2 + p . t - |t|^2 / 2.  ONE f5e_gemm_f32 per item: the
+        two squared-norm terms and the constant ride in two extra K columns (p | -|p|^2/2 | 1) . (t | 1 | c - |t|^2/2)."""
+        B, _, d = text_embed.shape
+        dv = text_embed.device
+        if dv.type != "cuda" or ppg_embed.device != dv:
+            raise _C.F5EError(f"align_text_ppg: the embeddings must live on the GPU (got {dv}); there is no CPU path")
+        p, t = ppg_embed[:, :Ty].to(F32), text_embed[:, :Tx].to(F32)
+        K = (d + 2 + 3) // 4 * 4
+        a, w = torch.zeros(B, Ty, K, device=dv), torch.zeros(B, Tx, K, device=dv)
+        a[..., :d], a[..., d], a[..., d + 1] = p, -0.5 * (p * p).sum(-1), 1.0
+        w[..., :d], w[..., d], w[..., d + 1] = t, 1.0, -0.5 * (t * t).sum(-1) + d * (-0.5 * math.log(2 * math.pi))
+        out = torch.empty(B, Ty, Tx, device=dv)
+        for b in range(B):
+            ops.gemm_f32(a[b], w[b], out=out[b])
+        return out
+
+    @torch.no_grad()
+    def align_index(self, text_embed, text_len, ppg_embed, ppg_len) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Compact form of align_text_ppg: (token_of_frame i32 [b, Ty], -1 past ppg_len;  durations i32 [b, Tx], 0 past
+        text_len), Ty / Tx = the longest PPG / text of the batch (host lengths) or n (device lengths)."""
+        n = text_embed.shape[1]
+        Ty, Tx = self._block_len(ppg_len, n), self._block_len(text_len, n)
+        return maximum_path_index(self.align_logp(text_embed, ppg_embed, Ty, Tx), ppg_len, text_len)
+
+    @torch.no_grad()
+    def align_text_ppg(self, text_embed, text_len, ppg_embed, ppg_len):
+        """Monotonic alignment of PPG frames to text tokens (reference dit.py:309-331).  text_embed, ppg_embed [b, n, d]
+        (both padded to the mel length); text_len, ppg_len [b] -> attn [b, n, n] of 0 / 1, attn[b, token, frame].  Only the
+        max(ppg_len) x max(text_len) block is computed and searched (csrc/mas.hip); nothing goes through the host."""
+        B, n, _ = text_embed.shape
+        tok, _ = self.align_index(text_embed, text_len, ppg_embed, ppg_len)
+        Ty, Tx = tok.shape[1], self._block_len(text_len, n)
+        attn = torch.zeros(B, n, n, dtype=text_embed.dtype, device=text_embed.device)
+        attn[:, :Tx, :Ty] = dense_path(tok, Tx, text_embed.dtype).transpose(1, 2)
+        return attn
+
+    @torch.no_grad()
+    def calc_align_loss(self, attn, text_embed, text_len, ppg_embed):
+        """Eval-mode value of the alignment loss (reference dit.py:333-360): mean squared distance between every quantised
+        text token and the mean of the quantised PPG frames aligned to it, times align_loss_weight.  The straight-through
+        terms of the reference equal the quantised values in the forward direction."""
+        if not self.use_codebook:
+            raise _C.F5EError("calc_align_loss needs a codebook model (cb_config.use_codebook)")
+        text_q = self.quantizer(text_embed)["x"]      # raises in training mode, like the quantizer itself
+        ppg_q = self.quantizer(ppg_embed)["x"]
+        B, n, d = text_q.shape
+        dv = text_q.device
+        K = (n + 3) // 4 * 4
+        a = torch.zeros(B, n, K, device=dv)
+        a[..., :n] = attn.to(dv, F32)
+        w = torch.zeros(B, d, K, device=dv)
+        w[..., :n] = ppg_q.transpose(1, 2)
+        summed = torch.empty(B, n, d, device=dv)      # sum of the PPG embeddings aligned to every token
+        for b in range(B):
+            ops.gemm_f32(a[b], w[b], out=summed[b])
+        counts = attn.to(dv, F32).sum(dim=2).clamp(min=1e-8)
+        per_token = ((text_q - summed / counts.unsqueeze(-1)) ** 2).mean(dim=2)
+        mask = torch.arange(n, device=dv)[None, :] < torch.as_tensor(text_len).to(dv)[:, None]
+        return (per_token * mask).sum() / (mask.sum() + 1e-8) * self.align_loss_weight
 
     def forward(self, *args, **kwargs):
         raise NotImplementedError("training forward (reference backbones/dit.py:474-549) is out of scope of the "

@@ -9,7 +9,7 @@ Documented deviations from the reference-on-GPU (both are identical to the refer
 """
 from __future__ import annotations
 
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 import torch.nn.functional as F
@@ -21,6 +21,15 @@ from .modules import MelSpec
 from .utils import default, exists, intersperse, lens_to_mask, list_str_to_idx, list_str_to_tensor
 
 F32, I32 = torch.float32, torch.int32
+
+
+class Alignment(NamedTuple):
+    """CFM.align: token_of_frame i32 [b, max ppg_len] (-1 past ppg_len), durations i32 [b, max text_len] (frames per
+    token, 0 past text_len), and the lengths i32 [b] they refer to; all on the device."""
+    token_of_frame: torch.Tensor
+    durations: torch.Tensor
+    text_len: torch.Tensor
+    ppg_len: torch.Tensor
 
 
 class CFM(nn.Module):
@@ -202,6 +211,38 @@ class CFM(nn.Module):
                              duplicate_test, t_inter, edit_mask, use_text=False)
         branches = [(True, True, True), (True, True, False), (False, True, False)]  # null, ppg, spk_ppg
         return self._integrate(prep, ppg, branches, 2, float(alpha_spk), float(alpha_ppg), vocoder)
+
+    @torch.no_grad()
+    def align(self, text, ppg, ppg_lens=None, seq_len: Optional[int] = None) -> Alignment:
+        """Forced alignment of text to audio through the PPGs: the monotonic path of DiT.align_text_ppg for `text` (list of
+        str / list of token lists, or int ids [b, nt] padded with -1) and ppg [b, n_ppg, ppg_dim]; ppg_lens [b] (default: all
+        n_ppg frames).  The embeddings are taken at seq_len frames (default n_ppg; the text ConvNeXt's GRN statistics
+        depend on it).  Works for any PPG model; the codebook is only needed for DiT.calc_align_loss."""
+        if self.training:
+            self.eval()
+        dv = self.device
+        if dv.type != "cuda":
+            raise _C.F5EError(f"CFM lives on {dv}: move it to the GPU (there is no CPU path)")
+        if not getattr(self.transformer, "use_ppg", False) or not hasattr(self.transformer, "align_index"):
+            raise _C.F5EError("CFM.align needs a DiT backbone with a PPG embedding (ppg_config.use_ppg)")
+        if isinstance(text, list):   # exactly sample_tts's preparation
+            if exists(self.vocab_char_map):
+                if self.use_align_loss or self.use_cross_mask:
+                    text = intersperse(text)
+                text = list_str_to_idx(text, self.vocab_char_map)
+            else:
+                text = list_str_to_tensor(text)
+        batch, n_ppg = ppg.shape[:2]
+        if text.shape[0] != batch:
+            raise _C.F5EError(f"CFM.align: {text.shape[0]} texts for {batch} PPG sequences")
+        N = int(default(seq_len, n_ppg))
+        ppg_len = torch.full((batch,), n_ppg, dtype=torch.long) if ppg_lens is None else torch.as_tensor(ppg_lens)
+        text_len = (text[:, :N] != -1).sum(dim=-1)   # host ids: host lengths, validated there; device ids: stay there
+        eng = self.transformer.engine()
+        text_embed = eng.text_embed(text, batch, N, False)
+        ppg_embed = eng.ppg_embed(ppg, batch, N, False)
+        tok, dur = self.transformer.align_index(text_embed, text_len, ppg_embed, ppg_len)
+        return Alignment(tok, dur, text_len.to(dv, I32), ppg_len.to(dv, I32))
 
     def forward(self, *args, **kwargs):
         raise NotImplementedError("flow-matching training loss (reference model/cfm.py:484-590) is out of scope of "

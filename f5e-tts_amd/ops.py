@@ -365,6 +365,37 @@ def vq_eval(logits: Tensor, vars_: Tensor, combine_groups: bool, out: Tensor, ta
     return out
 
 
+def mas_workspace_bytes(B: int, Ty: int, Tx: int) -> int:
+    """Scratch bytes of ``mas_path`` for a [B, Ty, Tx] problem (host call)."""
+    n = C.c_ulonglong()
+    check(lib().f5e_mas_workspace_bytes(B, Ty, Tx, C.byref(n)), "f5e_mas_workspace_bytes")
+    return int(n.value)
+
+
+def mas_path(logp: Tensor, t_y: Tensor, t_x: Tensor, token_of_frame: Tensor, durations: Optional[Tensor] = None,
+             workspace: Optional[Tensor] = None):
+    """Monotonic alignment search (f5e_mas_path): logp f32 [B, Ty, Tx] (frame x token; batch / row strides free, unit
+    column stride), t_y / t_x i32 [B] on the device -> token_of_frame i32 [B, Ty] (-1 past t_y), durations i32 [B, Tx]
+    (optional).  workspace: a device tensor of at least ``mas_workspace_bytes`` bytes (allocated here when None)."""
+    require_device()
+    if logp.ndim != 3 or not logp.is_cuda or logp.dtype != F32 or logp.stride(2) != 1:
+        raise _C.F5EError("mas_path: logp must be an f32 GPU tensor [B, Ty, Tx] with unit column stride; there is no "
+                          "CPU path")
+    B, Ty, Tx = logp.shape
+    if t_y.numel() != B or t_x.numel() != B or token_of_frame.shape != (B, Ty) or \
+            (durations is not None and durations.shape != (B, Tx)):
+        raise _C.F5EError(f"mas_path: lengths [{B}], token_of_frame [{B}, {Ty}], durations [{B}, {Tx}]")
+    need = mas_workspace_bytes(B, Ty, Tx)
+    if workspace is None:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=logp.device)
+    nbytes = workspace.numel() * workspace.element_size()
+    check(lib().f5e_mas_path(_stream(), C.c_void_p(logp.data_ptr()), logp.stride(0), logp.stride(1), _p(t_y, I32, "t_y"),
+                             _p(t_x, I32, "t_x"), _p(token_of_frame, I32, "token_of_frame"),
+                             _p(durations, I32, "durations"), _p(workspace, None, "workspace"), nbytes, B, Ty, Tx),
+          "f5e_mas_path")
+    return token_of_frame, durations
+
+
 def stft_logmel(wav: Tensor, window: Tensor, twiddle: Tensor, fb: Tensor, out: Tensor, n_fft: int, hop: int):
     require_device()
     B, nw = wav.shape

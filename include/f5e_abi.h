@@ -221,6 +221,21 @@ F5E_API int f5e_axpby(f5e_stream st, const float* x, const float* y, float* out,
 F5E_API int f5e_vq_eval(f5e_stream st, const float* logits, int ld, const float* vars, int combine_groups, float* out,
                 int* targets, float* stats, int rows, int groups, int num_vars, int var_dim);
 
+/* Monotonic alignment search (durpred/monotonic_align/core.py maximum_path_jit, called through DiT.align_text_ppg,
+ * model/backbones/dit.py:309-331): the best monotonic path through logp f32 [B][Ty][ld] (row = frame y, column = token x;
+ * sequence b at logp + b * batch_stride, elements), for the device lengths t_y[b] frames and t_x[b] tokens.
+ *   Q[0][0] = L[0][0];  Q[y][x] = L[y][x] + max(x < y ? Q[y-1][x] : -1e9, x > 0 ? Q[y-1][x-1] : -1e9)   (fp32, one add per
+ *   cell) over the band max(0, t_x - (t_y - y)) <= x <= min(t_x - 1, y); backtrack from (t_y - 1, t_x - 1): frame y takes
+ *   token i, then i -= 1 iff i > 0 and (i == y or Q[y-1][i] < Q[y-1][i-1]) -- a tie stays on the token.
+ * token_of_frame i32 [B][Ty]: the token of every frame, -1 for y >= t_y[b]; durations (optional) i32 [B][Tx]: frames per
+ * token, 0 for x >= t_x[b].  A sequence without a monotonic path (t_x < 1, t_y < t_x, or a length beyond Ty / Tx) gets
+ * all -1 / all 0.  logp is not modified (the reference accumulates in place).  workspace: f5e_mas_workspace_bytes(B, Ty, Tx)
+ * bytes of caller-owned scratch, 8-byte aligned, contents irrelevant.  Tx <= 4096.  No allocation, no synchronisation. */
+F5E_API int f5e_mas_workspace_bytes(int B, int Ty, int Tx, unsigned long long* bytes_out_host);
+F5E_API int f5e_mas_path(f5e_stream st, const float* logp, long long batch_stride, int ld, const int* t_y, const int* t_x,
+                 int* token_of_frame, int* durations, void* workspace, unsigned long long workspace_bytes, int B, int Ty,
+                 int Tx);
+
 /* ---------------------------------------------------------------- mel / vocoder ------------------------------ */
 
 /* out[B][T][n_mels] = log(clamp(|STFT(wav)| . fb, 1e-5)), T = 1 + nw / hop, reflect-padded, centred (modules.py:75-101).

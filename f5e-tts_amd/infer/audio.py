@@ -7,7 +7,8 @@ The reference delegates these to third-party packages that are absent here and N
     infer/utils_infer.py:273-334 (preprocess_ref_audio_text, remove_silence_edges) and :567-575.
 Both are restated from their published algorithms; PARITY UNPINNED (no reference fixture exists for either — SURVEY
 8c).  Everything here is once-per-reference-clip CPU work on 16-bit PCM, as it is in the reference (the audio is
-still on the host at those call sites); nothing here is on the measured path.
+still on the host at those call sites); nothing here is on the measured path.  The exception is ``resample_device``: the
+voice-conversion path (``utils_infer.infer_vc_process``) needs every clip at two rates and converts on the GPU.
 """
 from __future__ import annotations
 
@@ -21,12 +22,21 @@ import torch.nn.functional as F
 # ----------------------------------------------------------------------------- resampling
 
 
-def sinc_resample_kernel(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
-    """Polyphase windowed-sinc bank [new, 1, 2*width + orig] (hann window), torchaudio's default resampling method."""
+def resample_plan(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """(orig, new, width, taps) of a conversion: the ratio in lowest terms, the filter's half width in input samples and
+    the taps of one phase, 2 * width + orig.  Shared by the host route (``resample``) and the device route
+    (``resample_device`` -> ``ops.resample``, csrc/resample.hip)."""
     g = math.gcd(int(orig_freq), int(new_freq))
     orig, new = int(orig_freq) // g, int(new_freq) // g
     base_freq = min(orig, new) * rolloff
     width = math.ceil(lowpass_filter_width * orig / base_freq)
+    return orig, new, width, 2 * width + orig
+
+
+def sinc_resample_kernel(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
+    """Polyphase windowed-sinc bank [new, 1, 2*width + orig] (hann window), torchaudio's default resampling method."""
+    orig, new, width, _taps = resample_plan(orig_freq, new_freq, lowpass_filter_width, rolloff)
+    base_freq = min(orig, new) * rolloff
     idx = torch.arange(-width, width + orig, dtype=torch.float64)[None, None] / orig
     t = torch.arange(0, -new, -1, dtype=torch.float64)[:, None, None] / new + idx
     t = (t * base_freq).clamp_(-lowpass_filter_width, lowpass_filter_width)
@@ -50,6 +60,17 @@ def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Ten
     y = y.transpose(1, 2).reshape(x.shape[0], -1)
     target = int(math.ceil(new * length / orig))
     return y[..., :target].reshape(shape[:-1] + (target,))
+
+
+def resample_device(waveform: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:
+    """``resample`` for audio that already lives on the GPU: [..., n] -> [..., ceil(n * new / orig)], one launch of
+    f5e_resample with the same filter bank, no host detour.  Differs from the host route in summation order only."""
+    from .. import ops
+    if int(orig_freq) == int(new_freq):
+        return waveform
+    shape = waveform.shape
+    y = ops.resample(waveform.reshape(-1, shape[-1]).to(torch.float32), orig_freq, new_freq)
+    return y.reshape(shape[:-1] + (y.shape[-1],))
 
 
 # ----------------------------------------------------------------------------- 16-bit segments with millisecond slicing

@@ -1,6 +1,10 @@
 """Command-line entry with the argument surface of reference infer/infer_cli.py:34-171 and its three-layer setting
 resolution (flag > TOML > module default, including the ``x or default`` quirk that lets falsy flag values such as
-``--cfg_strength 0`` fall through, reference :181-211).  Model/vocoder weights are local files only (no network)."""
+``--cfg_strength 0`` fall through, reference :181-211).  Model/vocoder weights are local files only (no network).
+
+Beyond the reference: ``--mode tts|vc`` reach the PPG / codebook model family (``sample_tts`` through the same text
+chunking; ``--source_audio`` converted to the prompt's voice through ``utils_infer.infer_vc_process``), which the
+reference only drives from its eval scripts.  Without the new flags ``main`` does what it always did."""
 from __future__ import annotations
 
 import argparse
@@ -42,6 +46,18 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--speed", type=float, help="The speed of the generated audio")
     p.add_argument("--fix_duration", type=float, help="Fix the total duration (ref and gen audios) in seconds")
     p.add_argument("--device", type=str, help="Specify the device to run on")
+    p.add_argument("--mode", type=str, choices=["cfg", "tts", "vc"],
+                   help="cfg: sample with --cfg_strength (default); tts: sample_tts of a PPG model with --alpha_spk / "
+                        "--alpha_txt; vc: convert --source_audio to the voice of --ref_audio (default when "
+                        "--source_audio is given)")
+    p.add_argument("--source_audio", type=str, help="vc mode: the audio file whose content is converted")
+    p.add_argument("--alpha_spk", type=float, help="tts / vc: speaker guidance strength")
+    p.add_argument("--alpha_txt", type=float, help="tts: text guidance strength")
+    p.add_argument("--alpha_ppg", type=float, help="vc: PPG guidance strength")
+    p.add_argument("--ppg_model", type=str, help="vc: PPG checkpoint (default: ppg_config.model_path of the model yaml)")
+    p.add_argument("--ppg_config", type=str, help="vc: PPG train.yaml (default: ppg_config.config of the model yaml)")
+    p.add_argument("--ppg_stream", action="store_true",
+                   help="vc: extract the PPGs chunk by chunk (for conversion models trained on streaming PPGs)")
     return p
 
 
@@ -77,7 +93,18 @@ def resolve_settings(args: argparse.Namespace, config: dict) -> dict:
         speed=args.speed or g("speed", U.speed),
         fix_duration=args.fix_duration or g("fix_duration", U.fix_duration),
         device=args.device or g("device", U.device),
+        source_audio=args.source_audio or g("source_audio", ""),
+        alpha_spk=args.alpha_spk or g("alpha_spk", 2.5),
+        alpha_txt=args.alpha_txt or g("alpha_txt", 3.0),
+        alpha_ppg=args.alpha_ppg or g("alpha_ppg", 3.0),
+        ppg_model=args.ppg_model or g("ppg_model", ""),
+        ppg_config=args.ppg_config or g("ppg_config", ""),
+        ppg_stream=args.ppg_stream or g("ppg_stream", False),
     )
+    # --source_audio without a mode means voice conversion
+    s["mode"] = args.mode or g("mode", "") or ("vc" if s["source_audio"] else "cfg")
+    if s["mode"] not in ("cfg", "tts", "vc"):
+        raise SystemExit(f"unknown mode {s['mode']!r} in the config (cfg / tts / vc)")
     return s
 
 
@@ -89,6 +116,23 @@ def load_arch(model: str, model_cfg: str) -> dict:
     arch = dict(cfg["model"]["arch"])
     arch.pop("checkpoint_activations", None)
     return arch
+
+
+def load_model_config(model: str, model_cfg: str) -> dict:
+    """The ``train.parse_cfg.parse_model_yaml`` split of the model yaml: ``arch`` (what ``load_arch`` returns), the backbone
+    / CFM dicts of the PPG and codebook blocks (``transformer_ppg_config``, ``cfm_ppg_config``,
+    ``transformer_codebook_config``, ``cfm_codebook_config``) and ``frontend_ppg_config`` for the PPG extractor."""
+    import yaml
+
+    from ..train.parse_cfg import parse_model_yaml
+    path = model_cfg or os.path.join(_PKG, "configs", f"{model}.yaml")
+    with open(path, "r") as f:
+        return parse_model_yaml(yaml.safe_load(f))
+
+
+def require_ppg_model(mode: str, mc: dict) -> None:
+    if mode in ("tts", "vc") and not mc["transformer_ppg_config"]["use_ppg"]:
+        raise SystemExit(f"--mode {mode} needs a model with use_ppg: True in its yaml (a PPG-conditioned model)")
 
 
 def split_voices(gen_text: str):
@@ -114,11 +158,24 @@ def main(argv=None):
         with open(s["gen_file"], "r", encoding="utf-8") as f:
             s["gen_text"] = f.read()
     from ..model import DiT
+    mc = None
+    if s["mode"] != "cfg":      # refuse a model without PPG conditioning before anything is loaded
+        mc = load_model_config(s["model"], s["model_cfg"])
+        require_ppg_model(s["mode"], mc)
+        if s["mode"] == "vc" and not s["source_audio"]:
+            raise SystemExit("--mode vc needs --source_audio")
     vocoder = U.load_vocoder(s["vocoder_name"], is_local=True,
                              local_path=config.get("vocoder_local_path", DEFAULT_VOCODER_PATH[s["vocoder_name"]]),
                              device=s["device"])
+    mc = mc or load_model_config(s["model"], s["model_cfg"])
+    family = {}
+    if mc["transformer_ppg_config"]["use_ppg"]:     # a PPG / codebook yaml: the plain load_model call cannot build it
+        family = dict(ppg_config=(mc["transformer_ppg_config"], mc["cfm_ppg_config"]),
+                      cb_config=(mc["transformer_codebook_config"], mc["cfm_codebook_config"]))
     model = U.load_model(DiT, load_arch(s["model"], s["model_cfg"]), s["ckpt_file"], mel_spec_type=s["vocoder_name"],
-                         vocab_file=s["vocab_file"], device=s["device"])
+                         vocab_file=s["vocab_file"], device=s["device"], **family)
+    if s["mode"] == "vc":
+        return main_vc(s, mc, model, vocoder)
     voices = dict(config.get("voices", {}))
     voices["main"] = {"ref_audio": s["ref_audio"], "ref_text": s["ref_text"]}
     for v in voices.values():   # reference infer_cli.py:297-303
@@ -130,7 +187,8 @@ def main(argv=None):
                                      mel_spec_type=s["vocoder_name"], target_rms=s["target_rms"],
                                      cross_fade_duration=s["cross_fade_duration"], nfe_step=s["nfe_step"],
                                      cfg_strength=s["cfg_strength"], sway_sampling_coef=s["sway_sampling_coef"],
-                                     speed=s["speed"], fix_duration=s["fix_duration"], device=s["device"])
+                                     speed=s["speed"], fix_duration=s["fix_duration"], device=s["device"],
+                                     mode=s["mode"], alpha_spk=s["alpha_spk"], alpha_txt=s["alpha_txt"])
         segments.append(seg)
         if s["save_chunk"]:
             os.makedirs(os.path.join(s["output_dir"], "chunks"), exist_ok=True)
@@ -142,6 +200,30 @@ def main(argv=None):
         if s["remove_silence"]:
             U.remove_silence_for_generated_wav(path)
         print(path)
+
+
+def main_vc(s: dict, mc: dict, model, vocoder):
+    """--mode vc: the content of --source_audio in the voice of --ref_audio, one wav out."""
+    from ..ppg import PPGModelWapper
+    fc = mc["frontend_ppg_config"]
+    ppg_front = PPGModelWapper(s["ppg_model"] or fc["model_path"], s["ppg_config"] or fc["config"], s["device"],
+                               output_type=fc["output_type"], ppg_frame_length=fc["frame_length"],
+                               mel_f_shift=fc["mel_frame_shift"], map_mix_ratio=fc["map_mix_ratio"],
+                               global_phn_center_path=fc["global_phn_center_path"],
+                               para_softmax_path=fc["para_softmax_path"], stream=s["ppg_stream"])
+    wave, sr, _ = U.infer_vc_process(s["ref_audio"], s["source_audio"], model, vocoder, ppg_front,
+                                     mel_spec_type=s["vocoder_name"], target_rms=s["target_rms"],
+                                     cross_fade_duration=s["cross_fade_duration"], nfe_step=s["nfe_step"],
+                                     alpha_spk=s["alpha_spk"], alpha_ppg=s["alpha_ppg"],
+                                     sway_sampling_coef=s["sway_sampling_coef"], speed=s["speed"], device=s["device"])
+    if wave is None:
+        raise SystemExit("--mode vc: the source audio is too short to convert")
+    os.makedirs(s["output_dir"], exist_ok=True)
+    path = os.path.join(s["output_dir"], s["output_file"])
+    U.save_wav(path, wave, sr)
+    if s["remove_silence"]:
+        U.remove_silence_for_generated_wav(path)
+    print(path)
 
 
 if __name__ == "__main__":

@@ -1,7 +1,8 @@
 """Callers of the hot path (mirror of reference infer/utils_infer.py): checkpoint/model/vocoder loading and
 ``infer_process`` / ``infer_batch_process`` with the reference's argument names, defaults and duration / RMS /
 cross-fade rules.  Everything between ``model_obj.sample`` and ``vocoder.decode`` runs on libf5e_hip.so; what is left
-here is host glue (text chunking, wav I/O, numpy cross-fade) exactly as in the reference.
+here is host glue (text chunking, wav I/O, numpy cross-fade) exactly as in the reference.  ``infer_vc_process`` is the
+voice-conversion counterpart (PPG models, ``sample_vc``), which the reference only offers as an eval driver.
 
 Resampling and the pydub-style silence clipping live in ``infer/audio.py``.  Not rebuilt (out of scope,
 SURVEY section 8): the Whisper ASR fallback of ``preprocess_ref_audio_text`` (an empty ``ref_text`` is an error here),
@@ -157,16 +158,23 @@ def load_checkpoint(model, ckpt_path: str, device: str, dtype=None, use_ema=True
 
 
 def load_model(model_cls, model_cfg, ckpt_path, mel_spec_type=mel_spec_type, vocab_file="", ode_method=ode_method,
-               use_ema=True, device=device):
+               use_ema=True, device=device, ppg_config=None, cb_config=None):
+    """``ppg_config`` / ``cb_config``: (backbone dict, CFM dict) pairs of a PPG / codebook model, as
+    ``train.parse_cfg.parse_model_yaml`` splits them (``infer_cli.load_model_config``); the reference's load_model has no
+    way to build such a model.  None = the plain model, exactly as before."""
     if vocab_file == "":
         vocab_file = _DEFAULT_VOCAB
     vocab_char_map, vocab_size = get_tokenizer(vocab_file)
+    dit_kw, cfm_kw = {}, {}
+    for name, pair in (("ppg_config", ppg_config), ("cb_config", cb_config)):
+        if pair is not None:
+            dit_kw[name], cfm_kw[name] = pair
     model = CFM(
-        transformer=model_cls(**model_cfg, text_num_embeds=vocab_size, mel_dim=n_mel_channels),
+        transformer=model_cls(**model_cfg, text_num_embeds=vocab_size, mel_dim=n_mel_channels, **dit_kw),
         mel_spec_kwargs=dict(n_fft=n_fft, hop_length=hop_length, win_length=win_length,
                              n_mel_channels=n_mel_channels, target_sample_rate=target_sample_rate,
                              mel_spec_type=mel_spec_type),
-        odeint_kwargs=dict(method=ode_method), vocab_char_map=vocab_char_map).to(device)
+        odeint_kwargs=dict(method=ode_method), vocab_char_map=vocab_char_map, **cfm_kw).to(device)
     if ckpt_path:
         model = load_checkpoint(model, ckpt_path, device, use_ema=use_ema)
     return model
@@ -273,9 +281,12 @@ def plan_batch(ref_audio_len: int, ref_text: str, gen_text: str, speed_: float, 
 def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type="vocos", progress=None,
                         target_rms=0.1, cross_fade_duration=0.15, nfe_step=32, cfg_strength=2.0,
                         sway_sampling_coef=-1, speed=1, fix_duration=None, device=None, streaming=False,
-                        chunk_size=2048):
+                        chunk_size=2048, mode="cfg", alpha_spk=2.5, alpha_txt=3.0):
     """Generator like the reference's: yields (final_wave, sample_rate, combined_spectrogram) or, when streaming,
-    (chunk, sample_rate) pieces."""
+    (chunk, sample_rate) pieces.  mode "tts" (PPG / codebook models): ``sample_tts`` with alpha_spk / alpha_txt in place
+    of ``sample`` with cfg_strength (reference eval_infer_batch_tts.py:203-214)."""
+    if mode not in ("cfg", "tts"):
+        raise ValueError(f"infer_batch_process: mode {mode!r} (cfg / tts; voice conversion is infer_vc_process)")
     audio, sr = ref_audio
     if audio.shape[0] > 1:
         audio = torch.mean(audio, dim=0, keepdim=True)
@@ -295,9 +306,14 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
         ref_audio_len = audio.shape[-1] // hop_length
         duration, _ = plan_batch(ref_audio_len, ref_text, gen_text, speed, fix_duration)
         with torch.inference_mode():
-            generated, _traj = model_obj.sample(cond=audio, text=text_list, duration=duration, steps=nfe_step,
-                                                cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
-                                                seed=seed)
+            if mode == "tts":
+                generated, _traj = model_obj.sample_tts(cond=audio, text=text_list, duration=duration, steps=nfe_step,
+                                                        alpha_spk=alpha_spk, alpha_txt=alpha_txt,
+                                                        sway_sampling_coef=sway_sampling_coef, seed=seed)
+            else:
+                generated, _traj = model_obj.sample(cond=audio, text=text_list, duration=duration, steps=nfe_step,
+                                                    cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef,
+                                                    seed=seed)
             del _traj
             generated = generated.to(torch.float32)[:, ref_audio_len:, :].permute(0, 2, 1)
             # reference utils_infer.py:488-491: Vocos.decode -> [b, n], BigVGAN's forward -> [b, 1, n]
@@ -354,7 +370,7 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print,
                   progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
                   cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed,
-                  fix_duration=fix_duration, device=device):
+                  fix_duration=fix_duration, device=device, mode="cfg", alpha_spk=2.5, alpha_txt=3.0):
     audio, sr = load_wav(ref_audio)
     secs = audio.shape[-1] / sr
     max_chars = int(len(ref_text.encode("utf-8")) / secs * (22 - secs))
@@ -364,4 +380,125 @@ def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_ty
                                     mel_spec_type=mel_spec_type, progress=progress, target_rms=target_rms,
                                     cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
                                     cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed,
-                                    fix_duration=fix_duration, device=device))
+                                    fix_duration=fix_duration, device=device, mode=mode, alpha_spk=alpha_spk,
+                                    alpha_txt=alpha_txt))
+
+
+# ----------------------------------------- voice conversion (reference eval_infer_batch_vc.py:214-238, utils_eval.py:284-336)
+
+max_total_secs = 22.0      # prompt + converted piece per sample_vc call: the budget infer_process gives a text chunk
+
+
+def plan_vc_chunks(n_samples: int, sr: int, ref_secs: float, silences=(), max_total_secs: float = max_total_secs
+                   ) -> List[Tuple[int, int]]:
+    """Split a source of ``n_samples`` at ``sr`` into consecutive [start, end) pieces of at most
+    ``max_total_secs - ref_secs`` seconds (the reference clamps prompt + source at 4096 frames and silently truncates).
+    A piece that has to end before the source does is cut at the midpoint of the longest silence inside the last third of
+    its window (``silences``: [start_ms, end_ms] pairs of ``audio.detect_silence``; the part of a silence inside that third
+    is what counts), and at the window's end when there is none.  Pure host arithmetic."""
+    budget = float(max_total_secs) - float(ref_secs)
+    if budget < 1.0:
+        raise ValueError(f"voice conversion: a {ref_secs:.2f} s prompt leaves {budget:.2f} s of the {max_total_secs:.1f} s "
+                         "budget for the source; at least 1 s is needed (use a shorter prompt)")
+    max_len = int(budget * sr)
+    spans = [(int(a * sr / 1000.0), int(b * sr / 1000.0)) for a, b in silences]
+    pieces, start = [], 0
+    while n_samples - start > max_len:
+        lo, hi = start + max_len - max_len // 3, start + max_len
+        best = None
+        for a, b in spans:
+            a, b = max(a, lo), min(b, hi)
+            if b > a and (best is None or b - a > best[1] - best[0]):
+                best = (a, b)
+        cut = (best[0] + best[1]) // 2 if best is not None else hi
+        pieces.append((start, cut))
+        start = cut
+    if n_samples > start or not pieces:
+        pieces.append((start, n_samples))
+    return pieces
+
+
+def _mono(audio: torch.Tensor) -> torch.Tensor:
+    if audio.ndim == 1:
+        audio = audio.unsqueeze(0)
+    return torch.mean(audio, dim=0, keepdim=True) if audio.shape[0] > 1 else audio
+
+
+def infer_vc_batch_process(ref_audio, source_audio, pieces, model_obj, vocoder, ppg_front, mel_spec_type="vocos",
+                           target_rms=0.1, cross_fade_duration=0.15, nfe_step=32, alpha_spk=2.5, alpha_ppg=3.0,
+                           sway_sampling_coef=-1, speed=1.0, seed=None, device=None):
+    """Generator (one item, like ``infer_batch_process``): converts the ``pieces`` ([start, end) sample ranges) of
+    ``source_audio`` = (wave [channels, n], rate) to the voice of ``ref_audio`` = (wave, rate), in order and with the same
+    prompt, and yields (joined wave, 24000, joined mel [100, frames]).
+
+    Per piece, what eval_infer_batch.py --mode vc does per utterance: prompt mel at 24 kHz (RMS-raised to ``target_rms``
+    when quieter, undone after the vocoder), the PPG of [prompt ; piece] at 16 kHz (both from their own rates, unscaled),
+    total = ref_len + int(n24_piece / hop / speed), ``sample_vc``, the frames after the prompt through the vocoder.  The
+    audio goes to the device once; every rate conversion is ``audio.resample_device``."""
+    audio, sr = ref_audio
+    source, src_sr = source_audio
+    audio, source = _mono(audio), _mono(source)
+    rms = torch.sqrt(torch.mean(torch.square(audio)))
+    quiet = bool(rms < target_rms)
+    audio, source = audio.to(device, torch.float32), source.to(device, torch.float32)
+    rms = rms.to(device)
+    with torch.inference_mode():
+        scaled = audio * target_rms / rms if quiet else audio
+        audio24 = A.resample_device(scaled, sr, target_sample_rate)
+        ref_len = audio24.shape[-1] // hop_length
+        ref_mel = model_obj.mel_spec(audio24).permute(0, 2, 1)[:, :ref_len]
+        prompt16 = A.resample_device(audio, sr, 16000)
+
+    def process_piece(start, end):
+        with torch.inference_mode():
+            piece = source[:, start:end]
+            full16 = torch.cat([prompt16, A.resample_device(piece, src_sr, 16000)], dim=1)
+            ppg, _len = ppg_front.audio_to_ppg(full16, 16000)
+            orig, new, _w, _t = A.resample_plan(src_sr, target_sample_rate)
+            n24 = -(-new * (end - start) // orig)        # the resampler's output length for this piece
+            total = ref_len + int(n24 / hop_length / speed)
+            if total - ref_len < 2:                      # under two frames (a 20 ms tail after a cut): nothing to vocode
+                return None
+            generated, _traj = model_obj.sample_vc(cond=ref_mel, ppg=ppg.to(device), duration=torch.tensor([total]),
+                                                   steps=nfe_step, alpha_spk=alpha_spk, alpha_ppg=alpha_ppg,
+                                                   sway_sampling_coef=sway_sampling_coef, seed=seed)
+            del _traj
+            generated = generated.to(torch.float32)[:, ref_len:total, :].permute(0, 2, 1)
+            wave_ = vocoder.decode(generated) if mel_spec_type == "vocos" else vocoder(generated)
+            if quiet:
+                wave_ = wave_ * rms / target_rms
+            return wave_, generated
+
+    # queued piece after piece on the caller's stream; the host copies come after the last piece is queued
+    results = [r for r in (process_piece(a, b) for a, b in pieces) if r is not None]
+    results = [(w.squeeze().cpu().numpy(), g[0].cpu().numpy()) for w, g in results]
+    if results:
+        yield (cross_fade_concat([r[0] for r in results], cross_fade_duration), target_sample_rate,
+               np.concatenate([r[1] for r in results], axis=1))
+    else:
+        yield None, target_sample_rate, None
+
+
+def infer_vc_process(ref_audio, source_audio, model_obj, vocoder, ppg_front, mel_spec_type=mel_spec_type,
+                     show_info=print, target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
+                     alpha_spk=2.5, alpha_ppg=3.0, sway_sampling_coef=sway_sampling_coef, speed=speed, seed=None,
+                     max_total_secs=max_total_secs, device=device):
+    """Voice conversion: the content of ``source_audio`` in the voice of ``ref_audio`` (wav paths, or (wave [channels, n],
+    rate) pairs) -> (wave, 24000, mel), as ``infer_process`` returns them.  ``ppg_front``: any object with
+    ``audio_to_ppg(audio [1, n] on the device, 16000) -> (ppg, len)`` (``ppg.PPGModelWapper``).  A source longer than
+    ``max_total_secs`` minus the prompt is converted in pieces cut at silences (``plan_vc_chunks``) and cross-faded."""
+    audio, sr = load_wav(ref_audio) if isinstance(ref_audio, str) else ref_audio
+    source, src_sr = load_wav(source_audio) if isinstance(source_audio, str) else source_audio
+    n = source.shape[-1]
+    ref_secs = audio.shape[-1] / sr
+    silences = []
+    if n > int((max_total_secs - ref_secs) * src_sr) >= src_sr:      # only a source that needs cutting is searched
+        seg = A.Segment.from_float(_mono(source).cpu().numpy(), src_sr)
+        silences = A.detect_silence(seg, min_silence_len=100, silence_thresh=-40, seek_step=10)
+    pieces = plan_vc_chunks(n, src_sr, ref_secs, silences, max_total_secs)
+    show_info(f"Converting audio in {len(pieces)} pieces...")
+    return next(infer_vc_batch_process((audio, sr), (source, src_sr), pieces, model_obj, vocoder, ppg_front,
+                                       mel_spec_type=mel_spec_type, target_rms=target_rms,
+                                       cross_fade_duration=cross_fade_duration, nfe_step=nfe_step, alpha_spk=alpha_spk,
+                                       alpha_ppg=alpha_ppg, sway_sampling_coef=sway_sampling_coef, speed=speed, seed=seed,
+                                       device=device))

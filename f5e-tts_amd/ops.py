@@ -396,6 +396,54 @@ def mas_path(logp: Tensor, t_y: Tensor, t_x: Tensor, token_of_frame: Tensor, dur
     return token_of_frame, durations
 
 
+_resample_banks = {}
+_resample_lock = threading.Lock()
+
+
+def resample_bank(orig_freq: int, new_freq: int, device) -> Tensor:
+    """The filter bank f32 [new, taps] of a conversion on ``device``: computed once per (orig, new) on the host
+    (``infer.audio.sinc_resample_kernel``) and kept per device.  The first use uploads, so it must happen outside a graph
+    capture."""
+    from .infer import audio as A
+    orig, new, _w, taps = A.resample_plan(orig_freq, new_freq)
+    device = torch.device(device)
+    key = (orig, new, device.type, device.index if device.index is not None else torch.cuda.current_device())
+    bank = _resample_banks.get(key)
+    if bank is None:
+        bank = A.sinc_resample_kernel(orig, new)[0].reshape(new, taps).to(device).contiguous()
+        with _resample_lock:
+            bank = _resample_banks.setdefault(key, bank)
+    return bank
+
+
+def resample(x: Tensor, orig_freq: int, new_freq: int, out: Optional[Tensor] = None) -> Tensor:
+    """Sample-rate conversion on the device (f5e_resample): x f32 [n] or [B, n] (row stride free, unit sample stride) at
+    ``orig_freq`` -> [.., ceil(n * new / orig)] at ``new_freq``; ``out`` (optional) f32 [B, n_out] view with unit sample
+    stride.  The same rate returns ``x`` itself."""
+    if int(orig_freq) == int(new_freq):
+        return x
+    require_device()
+    if not x.is_cuda or x.dtype != F32 or x.ndim not in (1, 2) or x.stride(-1) != 1 and x.shape[-1] > 1:
+        raise _C.F5EError("resample: x must be an f32 GPU tensor [n] or [B, n] with unit sample stride; there is no CPU path")
+    from .infer import audio as A
+    orig, new, width, _taps = A.resample_plan(orig_freq, new_freq)
+    x2 = x if x.ndim == 2 else x.unsqueeze(0)
+    B, n = x2.shape
+    n_out = -(-new * n // orig)
+    if out is None:
+        out = torch.empty(B, n_out, dtype=F32, device=x.device)
+    o2 = out if out.ndim == 2 else out.unsqueeze(0)
+    if not o2.is_cuda or o2.dtype != F32 or o2.ndim != 2 or o2.shape[0] != B or (o2.stride(1) != 1 and o2.shape[1] > 1):
+        raise _C.F5EError(f"resample: out must be an f32 GPU tensor [{B}, n_out] with unit sample stride")
+    ld_x = x2.stride(0) if B > 1 else max(n, 1)
+    ld_y = o2.stride(0) if B > 1 else max(o2.shape[1], 1)
+    bank = resample_bank(orig, new, x.device)
+    # the library checks n >= 1 and n_out == ceil(new n / orig) (a mis-sized ``out`` is its BAD_SHAPE)
+    check(lib().f5e_resample(_stream(), C.c_void_p(x2.data_ptr()), ld_x, _p(bank, F32, "bank"), orig, new, width,
+                             C.c_void_p(o2.data_ptr()), ld_y, B, n, o2.shape[1]), "f5e_resample")
+    return out if x.ndim == 2 else o2[0]
+
+
 def stft_logmel(wav: Tensor, window: Tensor, twiddle: Tensor, fb: Tensor, out: Tensor, n_fft: int, hop: int):
     require_device()
     B, nw = wav.shape

@@ -236,6 +236,16 @@ F5E_API int f5e_mas_path(f5e_stream st, const float* logp, long long batch_strid
                  int* token_of_frame, int* durations, void* workspace, unsigned long long workspace_bytes, int B, int Ty,
                  int Tx);
 
+/* Polyphase windowed-sinc sample-rate conversion (torchaudio.transforms.Resample, sinc_interp_hann, as restated by
+ * infer/audio.py::resample; reference infer/utils_infer.py:445-447, ppg/ppg_model.py:156-158) for the reduced ratio
+ * orig : new:   y[b][f * new + p] = sum_{k < taps} bank[p][k] * x[b][f * orig + k - width],   taps = 2 * width + orig,
+ * x read as 0 outside [0, n).  x f32 [B][ld_x] (n used), bank f32 [new][taps] (the caller's filter bank, computed once per
+ * ratio), y f32 [B][ld_y] (n_out = ceil(new * n / orig) written per row; the gap ld_y - n_out is not touched).  fp32 FMA,
+ * eight interleaved partial sums per output.  F5E_ERR_BAD_SHAPE for orig, new, n < 1, n_out != ceil(new * n / orig) or
+ * ld < length; F5E_ERR_UNSUPPORTED beyond 4096 taps.  No allocation, no synchronisation. */
+F5E_API int f5e_resample(f5e_stream st, const float* x, long long ld_x, const float* bank, int orig, int new_, int width,
+                 float* y, long long ld_y, int B, int n, int n_out);
+
 /* ---------------------------------------------------------------- mel / vocoder ------------------------------ */
 
 /* out[B][T][n_mels] = log(clamp(|STFT(wav)| . fb, 1e-5)), T = 1 + nw / hop, reflect-padded, centred (modules.py:75-101).

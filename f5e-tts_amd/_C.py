@@ -49,6 +49,9 @@ SIGNATURES = {
     "f5e_mas_workspace_bytes": [_I, _I, _I, C.POINTER(C.c_ulonglong)],
     "f5e_mas_path": [_P, _P, _LL, _I, _P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I],
     "f5e_resample": [_P, _P, _LL, _P, _I, _I, _I, _P, _LL, _I, _I, _I],
+    "f5e_ctc_align_workspace_bytes": [_I, _I, _I, C.POINTER(C.c_ulonglong)],
+    "f5e_ctc_align": [_P, _P, _LL, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _I],
+    "f5e_ctc_greedy": [_P, _P, _LL, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I],
     "f5e_stft_logmel": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I],
     "f5e_stft_logmel_banded": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I],
     "f5e_stft_logmel_banded_ex": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F],

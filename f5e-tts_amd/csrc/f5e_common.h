@@ -172,6 +172,8 @@ template <int CTRL>
 __device__ __forceinline__ float dpp_f32(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
 }
+// lane i <- lane i - 1, lane 0 <- lane 63 (DPP wave_ror:1): the neighbour state of mas.hip / ctc.hip
+__device__ __forceinline__ float wave_ror1(float v) { return dpp_f32<0x13C>(v); }
 __device__ __forceinline__ float add_xor1(float v) { return v + dpp_f32<0xB1>(v); }    // quad_perm [1,0,3,2]
 __device__ __forceinline__ float add_xor2(float v) { return v + dpp_f32<0x4E>(v); }    // quad_perm [2,3,0,1]
 // v_permlane16/32_swap exchange halves between two registers (gfx950): lanes 16-31 / 48-63 (resp. 32-63) of vdst swap

@@ -30,9 +30,6 @@ constexpr float MAS_NEG = -1e9f;   // the reference's max_neg_val
 constexpr int MAS_R = 8;           // rows of logp in flight per thread (x CPT registers, twice)
 constexpr int MAS_MAX_TX = 4096;   // 16 waves x 4 slots x 64 columns
 
-// lane i <- lane i - 1, lane 0 <- lane 63 (DPP wave_ror:1)
-__device__ __forceinline__ float wave_ror1(float v) { return dpp_f32<0x13C>(v); }
-
 template <int CPT, bool MULTI>
 __global__ __launch_bounds__(MULTI ? 1024 : 64) void mas_kernel(const float* __restrict__ logp, long long batch_stride,
                                                                   int ld, const int* __restrict__ t_y_p,

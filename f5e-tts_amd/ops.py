@@ -396,6 +396,80 @@ def mas_path(logp: Tensor, t_y: Tensor, t_x: Tensor, token_of_frame: Tensor, dur
     return token_of_frame, durations
 
 
+def ctc_align_workspace_bytes(B: int, T: int, L: int) -> int:
+    """Scratch bytes of ``ctc_align`` for B sequences of up to T frames and L labels (host call)."""
+    n = C.c_ulonglong()
+    check(lib().f5e_ctc_align_workspace_bytes(B, T, L, C.byref(n)), "f5e_ctc_align_workspace_bytes")
+    return int(n.value)
+
+
+def _ctc_scores(scores: Tensor, name: str):
+    if scores.ndim != 3 or not scores.is_cuda or scores.dtype != F32 or scores.stride(2) != 1:
+        raise _C.F5EError(f"{name}: scores must be an f32 GPU tensor [B, T, V] with unit class stride; there is no CPU path")
+    return scores.shape
+
+
+def ctc_align(scores: Tensor, labels: Tensor, t_len: Tensor, l_len: Tensor, blank: int = 0, *,
+              align: Optional[Tensor] = None, tok_start: Optional[Tensor] = None, tok_end: Optional[Tensor] = None,
+              score: Optional[Tensor] = None, spans: bool = True, workspace: Optional[Tensor] = None):
+    """CTC forced alignment (f5e_ctc_align): scores f32 [B, T, V] (log-probabilities or raw logits; batch / row strides free,
+    unit class stride, only read), labels i32 [B, L], t_len / l_len i32 [B] on the device -> (align i32 [B, T]: the class of
+    every frame's state, -1 past t_len; tok_start, tok_end i32 [B, L]; score f32 [B]).  Outputs are allocated here when not
+    given; ``spans=False`` skips the three optional ones that were not passed.  workspace: a device tensor of at least
+    ``ctc_align_workspace_bytes`` bytes (allocated here when None)."""
+    B, T, V = _ctc_scores(scores, "ctc_align")
+    if labels.ndim != 2 or labels.shape[0] != B or labels.stride(1) != 1 or labels.dtype != I32 or not labels.is_cuda:
+        raise _C.F5EError(f"ctc_align: labels must be an i32 GPU tensor [{B}, L] with unit label stride")
+    require_device()
+    L = labels.shape[1]
+    dev = scores.device
+    if align is None:
+        align = torch.empty(B, T, dtype=I32, device=dev)
+    if spans:
+        tok_start = torch.empty(B, L, dtype=I32, device=dev) if tok_start is None else tok_start
+        tok_end = torch.empty(B, L, dtype=I32, device=dev) if tok_end is None else tok_end
+        score = torch.empty(B, dtype=F32, device=dev) if score is None else score
+    if t_len.numel() != B or l_len.numel() != B or align.shape != (B, T) or \
+            any(o is not None and o.shape != (B, L) for o in (tok_start, tok_end)) or \
+            (score is not None and score.shape != (B,)):
+        raise _C.F5EError(f"ctc_align: lengths [{B}], align [{B}, {T}], tok_start / tok_end [{B}, {L}], score [{B}]")
+    need = ctc_align_workspace_bytes(B, T, L)
+    if workspace is None:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    nbytes = workspace.numel() * workspace.element_size()
+    # the stride of a size-1 dimension is arbitrary (0 for a NumPy new axis) and never used
+    ld, ld_labels = (scores.stride(1) if T > 1 else max(V, scores.stride(1))), (labels.stride(0) if B > 1 else L)
+    check(lib().f5e_ctc_align(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0), ld,
+                              C.c_void_p(labels.data_ptr()), ld_labels, _p(t_len, I32, "t_len"),
+                              _p(l_len, I32, "l_len"), int(blank), _p(align, I32, "align"), _p(tok_start, I32, "tok_start"),
+                              _p(tok_end, I32, "tok_end"), _p(score, F32, "score"), _p(workspace, None, "workspace"),
+                              nbytes, B, T, L, V), "f5e_ctc_align")
+    return align, tok_start, tok_end, score
+
+
+def ctc_greedy(scores: Tensor, t_len: Tensor, blank: int = 0, pad_id: int = -1, *, hyp: Optional[Tensor] = None,
+               hyp_len: Optional[Tensor] = None, frame_logp: Optional[Tensor] = None, want_logp: bool = False):
+    """CTC best-path decoding (f5e_ctc_greedy): scores f32 [B, T, V] as in ``ctc_align``, t_len i32 [B] on the device ->
+    (hyp i32 [B, T] padded with -1, hyp_len i32 [B], frame_logp f32 [B, T] or None).  Frames past t_len take ``pad_id`` when
+    it is >= 0 (the reference's eos fill) and are skipped when it is -1.  frame_logp (max - logsumexp of every row) is
+    computed when a tensor is passed or ``want_logp`` is set."""
+    B, T, V = _ctc_scores(scores, "ctc_greedy")
+    require_device()
+    dev = scores.device
+    hyp = torch.empty(B, T, dtype=I32, device=dev) if hyp is None else hyp
+    hyp_len = torch.empty(B, dtype=I32, device=dev) if hyp_len is None else hyp_len
+    if frame_logp is None and want_logp:
+        frame_logp = torch.empty(B, T, dtype=F32, device=dev)
+    if t_len.numel() != B or hyp.shape != (B, T) or hyp_len.shape != (B,) or \
+            (frame_logp is not None and frame_logp.shape != (B, T)):
+        raise _C.F5EError(f"ctc_greedy: t_len / hyp_len [{B}], hyp / frame_logp [{B}, {T}]")
+    check(lib().f5e_ctc_greedy(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0),
+                               scores.stride(1) if T > 1 else max(V, scores.stride(1)),
+                               _p(t_len, I32, "t_len"), int(blank), int(pad_id), _p(hyp, I32, "hyp"),
+                               _p(hyp_len, I32, "hyp_len"), _p(frame_logp, F32, "frame_logp"), B, T, V), "f5e_ctc_greedy")
+    return hyp, hyp_len, frame_logp
+
+
 _resample_banks = {}
 _resample_lock = threading.Lock()
 

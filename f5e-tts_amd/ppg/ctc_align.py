@@ -1,0 +1,180 @@
+"""Text in, timestamps out: the CTC half of the ASR model (``ConformerPPG(ctc=True)``) as a forced aligner and a greedy
+transcriber.  The reference tells the user of ``infer/speech_edit.py`` to install an outside CTC forced aligner and to type
+the ``parts_to_edit`` by hand, although its own ASR model carries a CTC head, ``wenet/utils/ctc_util.py::forced_align`` and
+``wenet/bin/alignment.py``; this module is those three behind one class, with the search on the device (csrc/ctc.hip).
+
+Host code here: the symbol table, the tokeniser and the frame -> second arithmetic.  ``frames_timestamp`` restates
+``get_frames_timestamp`` of wenet/bin/alignment.py (that script cannot be imported -- it pulls in ``textgrid`` and dataset
+modules at the top -- so its parity is not pinned by a fixture; tests/test_ctc_cpu.py checks its properties)."""
+from __future__ import annotations
+
+from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import torch
+
+from .. import _C
+
+FRAME_SHIFT_S = 0.01      # kaldi fbank: 10 ms
+SUBSAMPLING = 2           # Conv2dSubsampling2, the `conv2d` front-end built here
+
+
+class WordSpan(NamedTuple):
+    word: str
+    start_s: float
+    end_s: float
+
+
+def read_symbol_table(path: str) -> Dict[str, int]:
+    """``token id`` lines (wenet/utils/file_utils.py::read_symbol_table)."""
+    table = {}
+    with open(path, "r", encoding="utf8") as fin:
+        for line in fin:
+            arr = line.strip().split()
+            if not arr:
+                continue
+            if len(arr) != 2:
+                raise ValueError(f"{path}: expected `token id`, got {line!r}")
+            table[arr[0]] = int(arr[1])
+    return table
+
+
+def _is_cjk(ch: str) -> bool:
+    o = ord(ch)
+    return (0x4E00 <= o <= 0x9FFF or 0x3400 <= o <= 0x4DBF or 0xF900 <= o <= 0xFAFF or 0x3040 <= o <= 0x30FF
+            or 0xAC00 <= o <= 0xD7AF or 0x20000 <= o <= 0x2FA1F)
+
+
+def split_words(text: str) -> List[str]:
+    """Whitespace splits words; every CJK character is its own word."""
+    words, cur = [], ""
+    for ch in text:
+        if ch.isspace() or _is_cjk(ch):
+            if cur:
+                words.append(cur)
+                cur = ""
+            if not ch.isspace():
+                words.append(ch)
+        else:
+            cur += ch
+    if cur:
+        words.append(cur)
+    return words
+
+
+def default_tokenize(text: str, table: Dict[str, int]) -> Tuple[List[str], List[List[int]]]:
+    """-> (words, ids per word).  A word becomes its characters, looked up as-is, then lower-cased, then upper-cased, then
+    ``<unk>`` if the table has it; characters without an entry are dropped (a word may be left with no ids)."""
+    words = split_words(text)
+    ids = []
+    for w in words:
+        row = []
+        for ch in w:
+            for cand in (ch, ch.lower(), ch.upper(), "<unk>"):
+                if cand in table:
+                    row.append(table[cand])
+                    break
+        ids.append(row)
+    return words, ids
+
+
+def frames_timestamp(alignment: Sequence[int], blank: int = 0) -> List[List[int]]:
+    """``get_frames_timestamp`` (wenet/bin/alignment.py:55-73): the frame classes cut into one segment per token -- leading
+    blanks belong to the following token, the token's own frames follow, trailing blanks join the last segment."""
+    alignment = list(alignment)
+    out, start, end = [], 0, 0
+    while end < len(alignment):
+        while end < len(alignment) and alignment[end] == blank:
+            end += 1
+        if end == len(alignment):
+            if not out:
+                raise ValueError("frames_timestamp: the alignment holds no token")
+            out[-1] += alignment[start:]
+            break
+        end += 1
+        while end < len(alignment) and alignment[end - 1] == alignment[end]:
+            end += 1
+        out.append(alignment[start:end])
+        start = end
+    return out
+
+
+def word_spans(words: Sequence[str], ids: Sequence[Sequence[int]], tok_end: Sequence[int], n_frames: int,
+               frame_s: float = FRAME_SHIFT_S * SUBSAMPLING, total_s: Optional[float] = None) -> List[WordSpan]:
+    """Token segments in ``frames_timestamp``'s sense from the kernel's ``tok_end`` (segment i = [tok_end[i-1], tok_end[i]),
+    the first from frame 0, the last to ``n_frames``) -> one span per word, from the start of its first token's segment to the
+    end of its last.  A word with no tokens gets an empty span at its neighbour's edge.  ``total_s`` caps the times (the
+    last encoder frame may reach past the audio by part of a window)."""
+    n_tok = sum(len(r) for r in ids)
+    if n_tok == 0:
+        raise ValueError("no character of the text is in the symbol table")
+    edges = [0] + [int(e) for e in tok_end[:n_tok]]
+    edges[-1] = int(n_frames)
+    cap = (lambda t: min(t, total_s)) if total_s is not None else (lambda t: t)
+    spans, k, last = [], 0, None
+    for w, row in zip(words, ids):
+        if row:
+            last = (cap(edges[k] * frame_s), cap(edges[k + len(row)] * frame_s))
+            spans.append(WordSpan(w, *last))
+            k += len(row)
+        else:
+            spans.append(None)
+    # empty words: the end of the word before, or the start of the first word that has tokens
+    first = next(s for s in spans if s is not None)
+    edge = first.start_s
+    for i, (w, s) in enumerate(zip(words, spans)):
+        if s is None:
+            spans[i] = WordSpan(w, edge, edge)
+        else:
+            edge = s.end_s
+    return spans
+
+
+class CTCAligner:
+    """``align(audio, sr, text)`` -> word-level timestamps; ``transcribe(audio, sr)`` -> text.  ``tokenize``: optional
+    ``text -> (words, ids per word)`` in place of ``default_tokenize`` (BPE models bring their own).  ``model`` /
+    ``symbol_table``: an already built ``ConformerPPG(ctc=True)`` and table instead of the three paths."""
+
+    def __init__(self, ppg_model_path: Optional[str] = None, ppg_config: Optional[str] = None,
+                 dict_path: Optional[str] = None, device="cuda", tokenize: Optional[Callable] = None, *, model=None,
+                 symbol_table: Optional[Dict[str, int]] = None):
+        from .ppg_model import build_ppg_model, kaldiFbank
+        self.device = device
+        self.model = model if model is not None else build_ppg_model(ppg_model_path, ppg_config, device, ctc=True)
+        if not getattr(self.model, "has_ctc", False):
+            raise _C.F5EError("CTCAligner: the model was built without its CTC head (ctc=True)")
+        self.table = dict(symbol_table) if symbol_table is not None else read_symbol_table(dict_path)
+        self.inverse = {v: k for k, v in self.table.items()}
+        self.tokenize = tokenize or (lambda text: default_tokenize(text, self.table))
+        self.featCal = kaldiFbank().eval()
+
+    def _feats(self, audio, sr):
+        from ..infer import audio as A
+        from ..infer.utils_infer import load_wav
+        if isinstance(audio, str):
+            audio, sr = load_wav(audio)
+        if audio.ndim == 1:
+            audio = audio.unsqueeze(0)
+        if audio.shape[0] > 1:
+            audio = audio.mean(0, keepdim=True)
+        secs = audio.shape[-1] / float(sr)
+        audio = A.resample_device(audio.to(self.device, torch.float32), sr, 16000)
+        feats, feats_len = self.featCal(audio)
+        return feats, feats_len.to(self.device), secs
+
+    @torch.no_grad()
+    def transcribe(self, audio, sr: Optional[int] = None) -> str:
+        feats, lens, _ = self._feats(audio, sr)
+        hyps, _ = self.model.ctc_greedy_search(feats, lens, pad_id=-1)
+        return "".join(self.inverse.get(i, "") for i in hyps[0]).replace("▁", " ").strip()
+
+    @torch.no_grad()
+    def align(self, audio, sr: Optional[int], text: str) -> List[WordSpan]:
+        words, ids = self.tokenize(text)
+        labels = [i for row in ids for i in row]
+        if not labels:
+            raise ValueError("CTCAligner.align: no character of the text is in the symbol table")
+        feats, lens, secs = self._feats(audio, sr)
+        al = self.model.ctc_forced_align(feats, lens, [labels])       # host ids and lengths: validated there (F5EError)
+        if int(al.align[0, 0]) < 0:                                   # the kernel's "no path" row: never build spans from it
+            raise _C.F5EError("CTCAligner.align: the text has no CTC path through this recording")
+        return word_spans(words, ids, al.tok_end[0].cpu().tolist(), int(al.frame_lens[0]), total_s=secs)

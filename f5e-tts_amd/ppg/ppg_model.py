@@ -21,7 +21,7 @@ from __future__ import annotations
 import json
 import math
 import os
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
@@ -124,20 +124,60 @@ class _CE(nn.Module):
         self.fc = nn.Linear(d, n)
 
 
+class _CTC(nn.Module):
+    """reference ppg/wenet/transformer/ctc.py: only the projection (the loss is a training feature)."""
+
+    def __init__(self, odim, d):
+        super().__init__()
+        self.ctc_lo = nn.Linear(d, odim)
+
+
+class CTCAlignment(NamedTuple):
+    """``ConformerPPG.ctc_forced_align``: align i32 [B, T'] (class of every encoder frame: blank or a label, -1 past the
+    utterance), tok_start / tok_end i32 [B, L] (first / one-past-last frame of every label), score f32 [B] (the path's
+    sum of CTC LOGITS, not log-probabilities), frame_lens i32 [B] (valid encoder frames); all on the device."""
+    align: Tensor
+    tok_start: Tensor
+    tok_end: Tensor
+    score: Tensor
+    frame_lens: Tensor
+
+
+def check_ctc_lengths(labels, label_lengths, frame_lens, L: int, vocab: Optional[int] = None) -> None:
+    """Host-side lengths of a forced alignment are caller bugs when they admit no CTC path (device lengths get -1 / 0 /
+    -inf rows from the kernel): 1 <= l <= L and frames >= l + adjacent equal labels.  ``labels``: the ids as nested lists
+    when they are known on the host (then the repeats and, with ``vocab``, the id range are checked too), else None."""
+    for b, (l, t) in enumerate(zip(label_lengths, frame_lens)):
+        l, t = int(l), int(t)
+        row = [int(v) for v in labels[b][:max(l, 0)]] if labels is not None else []
+        if vocab is not None and any(not 0 <= v < vocab for v in row):
+            raise _C.F5EError(f"ctc_forced_align: sequence {b} has no CTC path: label ids must lie in [0, {vocab})")
+        rep = sum(1 for i in range(1, len(row)) if row[i] == row[i - 1])
+        if not (1 <= l <= L and t >= l + rep):
+            raise _C.F5EError(f"ctc_forced_align: sequence {b} has no CTC path: need 1 <= labels ({l}) <= {L} and "
+                              f"labels + adjacent repeats ({l} + {rep}) <= encoder frames ({t})")
+
+
 class ConformerPPG(nn.Module):
     """The part of the reference ``ASRModel`` that ``extract`` touches (asr_model.py:221-244), same state_dict names:
-    ``encoder.*``, ``linear.*``, ``ce.fc.*``.  Decoder / CTC keys of a checkpoint are not on this path and are skipped
-    by ``build_ppg_model`` exactly as the reference's key filter does."""
+    ``encoder.*``, ``linear.*``, ``ce.fc.*``.  Decoder keys of a checkpoint are not on this path and are skipped by
+    ``build_ppg_model`` exactly as the reference's key filter does.  ``ctc=True`` adds the CTC half of the ASR model
+    (``ctc.ctc_lo.*``, the reference's key names): ``ctc_greedy_search`` and ``ctc_forced_align``.  The default stays False so
+    that ``state_dict()`` is what it was."""
 
     def __init__(self, input_dim: int = 80, vocab_size: int = 218, output_size: int = 256, attention_heads: int = 4,
                  linear_units: int = 2048, num_blocks: int = 6, cnn_module_kernel: int = 15,
                  global_cmvn: Optional[Tuple[Tensor, Tensor]] = None, causal: bool = False,
-                 use_dynamic_chunk: bool = False, static_chunk_size: int = 0):
+                 use_dynamic_chunk: bool = False, static_chunk_size: int = 0, ctc: bool = False):
         super().__init__()
         cm = _GlobalCMVN(global_cmvn[0].float(), global_cmvn[1].float()) if global_cmvn is not None else None
         self.encoder = _Encoder(input_dim, output_size, attention_heads, linear_units, num_blocks, cnn_module_kernel, cm)
         self.linear = nn.Linear(output_size, output_size)
         self.ce = _CE(output_size, vocab_size + 1)
+        if ctc:
+            self.ctc = _CTC(vocab_size, output_size)
+        self.has_ctc, self.vocab_size = bool(ctc), vocab_size
+        self.sos = self.eos = vocab_size - 1                 # asr_model.py: sos = eos = vocab_size - 1
         self.input_dim, self.heads, self.dim = input_dim, attention_heads, output_size
         # causal: the depthwise convolution looks back only (convolution.py:45-52); the chunk settings say whether the
         # model was trained with chunk masks, which the streaming mode requires (encoder.py:327)
@@ -145,7 +185,7 @@ class ConformerPPG(nn.Module):
         self._engine = None
 
     @classmethod
-    def from_config(cls, configs: dict) -> "ConformerPPG":
+    def from_config(cls, configs: dict, ctc: bool = False) -> "ConformerPPG":
         """``init_asr_model`` (asr_model.py:814-859) for the supported encoder family."""
         enc = dict(configs.get("encoder_conf") or {})
         if configs.get("encoder", "conformer") != "conformer":
@@ -163,7 +203,7 @@ class ConformerPPG(nn.Module):
         return cls(configs["input_dim"], configs["output_dim"], enc.get("output_size", 256), enc.get("attention_heads", 4),
                    enc.get("linear_units", 2048), enc.get("num_blocks", 6), enc.get("cnn_module_kernel", 15), cmvn,
                    causal=enc.get("causal", False), use_dynamic_chunk=enc.get("use_dynamic_chunk", False),
-                   static_chunk_size=enc.get("static_chunk_size", 0))
+                   static_chunk_size=enc.get("static_chunk_size", 0), ctc=ctc)
 
     def _apply(self, fn, *a, **kw):
         self._engine = None
@@ -192,6 +232,68 @@ class ConformerPPG(nn.Module):
             eng = self.engine()
             return eng.head(eng.forward_chunk_by_chunk(speech, 16, 17))
         return self.engine().forward(speech, speech_lengths)
+
+    def _require_ctc(self) -> "ConformerEngine":
+        if not self.has_ctc:
+            raise _C.F5EError("PPG extractor: built without the CTC head (ConformerPPG(ctc=True) / build_ppg_model(ctc=True))")
+        return self.engine()
+
+    def _ctc_scores(self, speech: Tensor, speech_lengths: Tensor, use_linear: bool) -> Tuple[Tensor, Tensor, Tensor]:
+        """-> (CTC logits [B, T', V], valid frames i32 [B] on the device, the same on the host)."""
+        eng = self._require_ctc()
+        enc, lens_host = eng._encode(speech, speech_lengths)
+        if use_linear:
+            enc = eng.head(enc)[0]
+        return eng.ctc_logits(enc), lens_host.to(enc.device), lens_host
+
+    @torch.no_grad()
+    def ctc_greedy_search(self, speech: Tensor, speech_lengths: Tensor, use_linear: bool = False,
+                          pad_id: Optional[int] = None) -> Tuple[List[List[int]], Tensor]:
+        """reference asr_model.py:416-459 (full context; the streaming modes are not built) -> (hyps, scores [B, 1]).
+        Argmax, collapse and the frame log-probabilities run on the device (f5e_ctc_greedy) straight from the logits.
+
+        The reference DECODES from the encoder output, although its training forward feeds ``linear(encoder_out)`` to the
+        CTC loss (asr_model.py:159-170 against :444-451).  ``use_linear=False`` is what the reference decodes with;
+        ``use_linear=True`` is what a checkpoint's CTC head was trained on.
+
+        Frames past an utterance take ``pad_id`` = eos before the collapse, as the reference's masked_fill does: a shorter
+        utterance of a batch ends in a trailing eos.  ``scores`` equals ``.values`` of the reference's ``topk_prob.max(1)``
+        (the best frame's top-1 log-probability, padded frames included)."""
+        assert speech.shape[0] == speech_lengths.shape[0]
+        logits, frame_lens, _ = self._ctc_scores(speech, speech_lengths, use_linear)
+        hyp, hyp_len, logp = ops.ctc_greedy(logits, frame_lens, blank=0, pad_id=self.eos if pad_id is None else pad_id,
+                                            want_logp=True)
+        hyp_h, len_h = hyp.cpu(), hyp_len.cpu().tolist()
+        return [hyp_h[b, :n].tolist() for b, n in enumerate(len_h)], logp.max(1, keepdim=True).values
+
+    @torch.no_grad()
+    def ctc_forced_align(self, speech: Tensor, speech_lengths: Tensor, labels, label_lengths=None,
+                         use_linear: bool = False) -> CTCAlignment:
+        """Forced alignment of ``labels`` (ids, [B, L] tensor or a list of lists) to the encoder frames
+        (wenet/utils/ctc_util.py::forced_align per utterance, here one launch for the batch, fed with the LOGITS: per-frame
+        constants cancel in the search).  Lengths that start on the host are validated there (F5EError); device lengths
+        that admit no path give -1 / 0 / -inf rows."""
+        assert speech.shape[0] == speech_lengths.shape[0]
+        logits, frame_lens, lens_host = self._ctc_scores(speech, speech_lengths, use_linear)
+        dev = logits.device
+        if not torch.is_tensor(labels):
+            rows = [list(r) for r in labels]
+            label_lengths = [len(r) for r in rows] if label_lengths is None else label_lengths
+            L = max(1, max(len(r) for r in rows))
+            labels = torch.tensor([r + [0] * (L - len(r)) for r in rows], dtype=I32)
+        if label_lengths is None:
+            label_lengths = [labels.shape[1]] * labels.shape[0]
+        if labels.ndim != 2 or labels.shape[0] != logits.shape[0] or len(label_lengths) != logits.shape[0]:
+            raise _C.F5EError(f"ctc_forced_align: labels [B, L] and label_lengths [B] for a batch of {logits.shape[0]}")
+        if not (torch.is_tensor(label_lengths) and label_lengths.is_cuda):
+            # every length that starts on the host is validated there, whether or not the ids are (the encoder's frame counts
+            # are host values); ids on the host add the repeat count and the id range
+            check_ctc_lengths(None if labels.is_cuda else labels.tolist(),
+                              label_lengths.tolist() if torch.is_tensor(label_lengths) else label_lengths,
+                              lens_host.tolist(), labels.shape[1], self.vocab_size)
+        l_len = torch.as_tensor(label_lengths, dtype=I32).to(dev)
+        out = ops.ctc_align(logits, labels.to(dev, I32).contiguous(), frame_lens, l_len, blank=0)
+        return CTCAlignment(*out, frame_lens)
 
     def _require_stream(self, xs: Tensor) -> None:
         if not (self.static_chunk_size > 0 or self.use_dynamic_chunk):
@@ -283,6 +385,9 @@ class ConformerEngine:
         self.after = (f("encoder.after_norm.weight"), f("encoder.after_norm.bias"))
         self.lin_w, self.lin_b = f("linear.weight"), f("linear.bias")
         self.ce_w, self.ce_b = f("ce.fc.weight"), f("ce.fc.bias")
+        self.ctc_w = self.ctc_b = None
+        if "ctc.ctc_lo.weight" in sd:
+            self.ctc_w, self.ctc_b = f("ctc.ctc_lo.weight"), f("ctc.ctc_lo.bias")
         self.half = torch.full((max(D, 1),), 0.5, device=dv)
         self.dk = dk
         self._pe: Dict[int, Tensor] = {}
@@ -306,6 +411,26 @@ class ConformerEngine:
         return pe[offset:n]
 
     def forward(self, feats: Tensor, lens: Tensor) -> Tuple[Tensor, Tensor]:
+        return self.head(self._encode(feats, lens)[0])
+
+    def ctc_logits(self, enc: Tensor) -> Tensor:
+        """``ctc.ctc_lo`` of an encoder output [B, T', D] -> logits f32 [B, T', vocab] (ctc.py: log_softmax without the
+        softmax, which the decoding kernels do not need)."""
+        if self.ctc_w is None:
+            raise _C.F5EError("PPG extractor: the state_dict has no ctc.ctc_lo.* tensors")
+        B, T2, D = enc.shape
+        logits = torch.empty(B * T2, self.ctc_w.shape[0], device=self.device)
+        ops.gemm_f32(enc.reshape(B * T2, D), self.ctc_w, self.ctc_b, out=logits)
+        return logits.view(B, T2, -1)
+
+    def encode(self, feats: Tensor, lens: Tensor) -> Tuple[Tensor, Tensor]:
+        """BaseEncoder.forward: features -> (encoder output after ``after_norm`` [B, T', D], valid frames i32 [B] on the
+        device = the reference's ``encoder_mask.squeeze(1).sum(1)``)."""
+        enc, len2 = self._encode(feats, lens)
+        return enc, len2.to(self.device)
+
+    def _encode(self, feats: Tensor, lens: Tensor) -> Tuple[Tensor, Tensor]:
+        """``encode`` with the frame counts left on the host, where they are computed (``forward`` does not need them)."""
         dv, D, H, dk = self.device, self.dim, self.heads, self.dk
         B, T, idim = feats.shape
         if idim != self.idim:
@@ -398,11 +523,7 @@ class ConformerEngine:
             ops.gemm_f32(mid, L["ff"][2], L["ff"][3], out=xs, ch_scale=self.half[:D], addend=xs)
             ops.layernorm(xs, xs, gamma=ln["norm_final"][0], beta=ln["norm_final"][1], eps=1e-5)
         ops.layernorm(xs, hn, gamma=self.after[0], beta=self.after[1], eps=1e-5)
-        ppg = torch.empty(M, D, device=dv)
-        ops.gemm_f32(hn, self.lin_w, self.lin_b, out=ppg)
-        logits = torch.empty(M, self.ce_w.shape[0], device=dv)
-        ops.gemm_f32(ppg, self.ce_w, self.ce_b, out=logits)
-        return ppg.view(B, T2, D), logits
+        return hn.view(B, T2, D), len2
 
     def _eye(self, d: int) -> Tensor:
         if getattr(self, "_eye_t", None) is None or self._eye_t.shape[0] != d:
@@ -603,9 +724,9 @@ class kaldiFbank(nn.Module):
         return out, torch.tensor([T])
 
 
-def build_ppg_model(ppg_model_path, ppg_config, device="cpu"):
+def build_ppg_model(ppg_model_path, ppg_config, device="cpu", ctc: bool = False):
     """reference ppg/ppg_model.py:11-29: yaml -> model (cmvn path fallback next to the checkpoint) -> checkpoint keys that
-    exist in the model are loaded, the rest (decoder, CTC) ignored."""
+    exist in the model are loaded, the rest (decoder; the CTC head too unless ``ctc=True``) ignored."""
     import yaml
     with open(ppg_config, "r") as fin:
         ppg_configs = yaml.safe_load(fin)
@@ -613,7 +734,7 @@ def build_ppg_model(ppg_model_path, ppg_config, device="cpu"):
         old = ppg_configs["cmvn_file"]
         ppg_configs["cmvn_file"] = os.path.join(os.path.dirname(ppg_model_path), "global_cmvn")
         print(f"{old} not exist, use {ppg_configs['cmvn_file']}")
-    model = ConformerPPG.from_config(ppg_configs)
+    model = ConformerPPG.from_config(ppg_configs, ctc=ctc)
     checkpoint = torch.load(ppg_model_path, map_location="cpu", weights_only=True)
     model_dict = model.state_dict()
     model_dict.update({k: v for k, v in checkpoint.items() if k in model_dict})

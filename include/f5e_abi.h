@@ -246,6 +246,33 @@ F5E_API int f5e_mas_path(f5e_stream st, const float* logp, long long batch_strid
 F5E_API int f5e_resample(f5e_stream st, const float* x, long long ld_x, const float* bank, int orig, int new_, int width,
                  float* y, long long ld_y, int B, int n, int n_out);
 
+/* CTC forced alignment (csrc/ctc.hip; reference ppg/wenet/utils/ctc_util.py::forced_align, batched, on the device).
+ * scores f32 [B][T][V]: log-probabilities OR raw logits of the CTC head (per-frame constants cancel), batch stride
+ * `batch_stride`, row stride `ld` >= V, unit class stride, only read.  labels i32 [B][ld_labels] (L used).  t_len / l_len:
+ * DEVICE int [B].  Viterbi over the blank-interleaved sequence (S = 2 l + 1 states; stay, s-1, and s-2 where the label
+ * differs from the one before it), fp32, one max and one add per cell, the first maximum winning; the path ends in the last
+ * blank unless the last label scores strictly higher.  State 0 can only stay (the reference's negative index there wraps to
+ * the last state).  align i32 [B][T]: the class of every frame's state (blank or a label), -1 for t >= t_len.
+ * Optional tok_start / tok_end i32 [B][L]: first / one-past-last frame of every label's own state (0 / 0 for a label the
+ * path never visits, which needs -inf in the scores); score f32 [B]: alpha of
+ * the chosen end state.  A sequence without a path (l_len < 1, t_len < l_len + adjacent equal labels, a label outside
+ * [0, V), lengths beyond T / L) gets -1 / 0 / -inf rows; the other sequences are untouched.  workspace:
+ * f5e_ctc_align_workspace_bytes(B, T, L) bytes of caller-owned scratch, 8-byte aligned, contents irrelevant.
+ * T <= 16384, L <= 2047.  No allocation, no synchronisation. */
+F5E_API int f5e_ctc_align_workspace_bytes(int B, int T, int L, unsigned long long* bytes_out_host);
+F5E_API int f5e_ctc_align(f5e_stream st, const float* scores, long long batch_stride, int ld, const int* labels, int ld_labels,
+                  const int* t_len, const int* l_len, int blank, int* align, int* tok_start, int* tok_end, float* score,
+                  void* workspace, unsigned long long workspace_bytes, int B, int T, int L, int V);
+
+/* CTC best-path decoding (reference ppg/asr_model.py:450-458): per frame the argmax over V of scores (layout as above; the
+ * lowest index among equal maxima), per sequence the collapse "keep frame t iff its id is not blank and differs from frame
+ * t-1's", compacted into hyp i32 [B][T] (padded with -1) and hyp_len i32 [B].  Frames t >= t_len[b] (DEVICE int [B]) take the
+ * id pad_id when pad_id >= 0 (the reference fills them with eos BEFORE collapsing) and are skipped when pad_id = -1.
+ * Optional frame_logp f32 [B][T]: max - logsumexp of EVERY row of the buffer (padded frames included, as the reference's
+ * topk_prob).  T <= 16384.  No allocation, no synchronisation. */
+F5E_API int f5e_ctc_greedy(f5e_stream st, const float* scores, long long batch_stride, int ld, const int* t_len, int blank,
+                   int pad_id, int* hyp, int* hyp_len, float* frame_logp, int B, int T, int V);
+
 /* ---------------------------------------------------------------- mel / vocoder ------------------------------ */
 
 /* out[B][T][n_mels] = log(clamp(|STFT(wav)| . fb, 1e-5)), T = 1 + nw / hop, reflect-padded, centred (modules.py:75-101).

@@ -145,13 +145,13 @@ __global__ __launch_bounds__(256) void vq_lookup_kernel(const float* logits, int
 }
 
 // code / prob perplexity of the same forward: hard_probs = mean one-hot, avg_probs = mean softmax, each
-// exp(-sum p log(p + 1e-7)) summed over groups.  One block, deterministic (no atomics).
+// exp(-sum p log(p + 1e-7)) summed over groups.  One block, deterministic (no atomics, fixed summation order).
 __global__ __launch_bounds__(256) void vq_stats_kernel(const float* logits, int ld, const int* targets, float* stats,
                                                         int rows, int G, int V) {
   extern __shared__ float sm[];  // [4 waves][V] softmax sums, then [V] counts
   float* accw = sm;
   float* cnt = sm + 4 * V;
-  __shared__ float red[2];
+  __shared__ float red[2][4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   float code_ppl = 0.f, prob_ppl = 0.f;
   for (int g = 0; g < G; ++g) {
@@ -181,12 +181,10 @@ __global__ __launch_bounds__(256) void vq_stats_kernel(const float* logits, int 
     }
     hc = wave_sum(hc);
     hp = wave_sum(hp);
-    if (tid == 0) { red[0] = 0.f; red[1] = 0.f; }
+    if (lane == 0) { red[0][wave] = hc; red[1][wave] = hp; }   // one slot per wave, added in a fixed order below
     __syncthreads();
-    if (lane == 0) { atomicAdd(&red[0], hc); atomicAdd(&red[1], hp); }  // 4 LDS adds per group
-    __syncthreads();
-    code_ppl += expf(-red[0]);
-    prob_ppl += expf(-red[1]);
+    code_ppl += expf(-((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])));
+    prob_ppl += expf(-((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])));
     __syncthreads();
   }
   if (tid == 0) { stats[0] = code_ppl; stats[1] = prob_ppl; }
@@ -260,12 +258,13 @@ int f5e_vq_eval(hipStream_t st, const float* logits, int ld, const float* vars, 
                 int* targets, float* stats, int rows, int groups, int num_vars, int var_dim) {
   F5E_REQUIRE(logits && vars && out && targets, "vq_eval: null operand");
   F5E_REQUIRE(rows > 0 && groups > 0 && num_vars > 0 && var_dim > 0 && ld >= groups * num_vars, "vq_eval: bad shape");
+  // refused before the lookup is launched: a refusal leaves out / targets untouched
+  F5E_REQUIRE(!stats || num_vars <= 2048, "vq_eval: statistics kernel supports num_vars <= 2048");
   const long long items = (long long)rows * groups;
   hipLaunchKernelGGL(vq_lookup_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), 0, st, logits, ld, vars,
                      combine_groups, out, targets, rows, groups, num_vars, var_dim);
   F5E_LAUNCH_CHECK("vq_lookup");
   if (stats) {
-    F5E_REQUIRE(num_vars <= 2048, "vq_eval: statistics kernel supports num_vars <= 2048");
     hipLaunchKernelGGL(vq_stats_kernel, dim3(1), dim3(256), 5 * num_vars * sizeof(float), st, logits, ld, targets, stats,
                        rows, groups, num_vars);
     F5E_LAUNCH_CHECK("vq_stats");

@@ -45,6 +45,31 @@ def _p(t: Optional[Tensor], dtype=None, name="tensor"):
 BF, F32, I32, U8 = torch.bfloat16, torch.float32, torch.int32, torch.uint8
 
 
+def _rows(t: Tensor, dtypes, name: str, cols: int, vec: int = 4, whole_rows: bool = False):
+    """(pointer, row stride) of a 2-D row-strided view: unit column stride, any row stride >= cols.  ``vec`` = elements per
+    vector access of the kernel (4: 16-byte fp32 / 8-byte bf16 accesses -> the base address must be aligned to them and the
+    row stride a multiple of 4; 1: scalar accesses).  ``whole_rows``: the kernel touches all of the last row's stride, not
+    only its first ``cols`` elements.  Everything is refused here, before any launch."""
+    if not t.is_cuda:
+        raise _C.F5EError(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+    if t.dtype not in dtypes:
+        raise _C.F5EError(f"{name} must be {' or '.join(str(d) for d in dtypes)} (got {t.dtype})")
+    if t.ndim != 2 or t.shape[0] < 1 or t.shape[1] < cols or (t.stride(1) != 1 and t.shape[1] > 1):
+        raise _C.F5EError(f"{name} must be a [rows, >= {cols}] view with unit column stride (got shape {tuple(t.shape)}, "
+                          f"strides {tuple(t.stride())})")
+    rows = t.shape[0]
+    ld = t.stride(0) if rows > 1 else max(t.stride(0), t.shape[1])     # the stride of a size-1 dimension is arbitrary
+    if ld < cols or ld % vec:
+        raise _C.F5EError(f"{name}: row stride {ld} must be >= {cols}" + (f" and a multiple of {vec}" if vec > 1 else ""))
+    if t.data_ptr() % (vec * t.element_size()):
+        raise _C.F5EError(f"{name}: base address must be {vec * t.element_size()}-byte aligned")
+    have = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+    need = rows * ld if whole_rows else (rows - 1) * ld + cols
+    if have < need:
+        raise _C.F5EError(f"{name}: {rows} rows of stride {ld} need {need} elements, the storage holds {have}")
+    return C.c_void_p(t.data_ptr()), ld
+
+
 def ln_consumer(stats: Tensor, c: Tensor, d: Tensor, rows_per_seq: int, row_mean: Tensor, eval_ptr: Optional[Tensor] = None,
                 cd_eval_stride: int = 0, eps: float = 1e-6) -> "_C.LnFuse":
     """Consumer side of the fused AdaLN (see f5e_ln_fuse): stats f32 [M, parts, 2] (tile means relative to row_mean);
@@ -183,16 +208,30 @@ def joint_attn(qx: Tensor, kx: Tensor, vtx: Tensor, qc: Optional[Tensor], kc: Te
 def layernorm(x: Tensor, out: Tensor, gamma: Optional[Tensor] = None, beta: Optional[Tensor] = None,
               scale: Optional[Tensor] = None, shift: Optional[Tensor] = None, rows_per_seq: int = 1,
               eval_ptr: Optional[Tensor] = None, eval_stride: int = 0, eps: float = 1e-6):
-    """x f32 [rows, D]; scale/shift: f32 [mod_rows, D] views (row stride free)."""
+    """x f32 [rows, D], out f32 or bf16 [rows, D] (may be x itself); scale/shift: f32 [mod_rows, D].  x, out, scale and shift
+    may be views with unit column stride and any row stride that is a multiple of 4, on a 16-byte aligned base (8-byte for a
+    bf16 out): the kernels use vector accesses."""
     require_device()
+    if x.ndim != 2 or out.shape != x.shape:
+        raise _C.F5EError(f"layernorm: x and out must be [rows, D] of one shape (got {tuple(x.shape)}, {tuple(out.shape)})")
     rows, D = x.shape
-    mod_rows = scale.shape[0] if scale is not None else 0
-    mod_stride = scale.stride(0) if scale is not None else 0
-    if scale is not None and shift.stride(0) != mod_stride:
-        raise _C.F5EError("scale and shift must share a row stride")
-    sp = C.c_void_p(scale.data_ptr()) if scale is not None else None
-    hp = C.c_void_p(shift.data_ptr()) if shift is not None else None
-    check(lib().f5e_layernorm(_stream(), _p(x, F32, "x"), x.stride(0), _p(out, None, "out"), out.stride(0),
+    for t, nm in ((gamma, "gamma"), (beta, "beta")):
+        if t is not None and t.numel() != D:
+            raise _C.F5EError(f"layernorm: {nm} must have D = {D} elements")
+    if (scale is None) != (shift is None):
+        raise _C.F5EError("layernorm: scale and shift go together")
+    xp, ldx = _rows(x, (F32,), "x", D)
+    op, ldo = _rows(out, (F32, BF), "out", D)
+    sp = hp = None
+    mod_rows = mod_stride = 0
+    if scale is not None:
+        if shift.shape != scale.shape or scale.shape[1:] != (D,):
+            raise _C.F5EError(f"layernorm: scale and shift must be [mod_rows, {D}]")
+        mod_rows = scale.shape[0]
+        (sp, mod_stride), (hp, shift_stride) = _rows(scale, (F32,), "scale", D), _rows(shift, (F32,), "shift", D)
+        if shift_stride != mod_stride:
+            raise _C.F5EError("scale and shift must share a row stride")
+    check(lib().f5e_layernorm(_stream(), xp, ldx, op, ldo,
                               1 if out.dtype == BF else 0, _p(gamma, F32, "gamma"), _p(beta, F32, "beta"), sp, hp,
                               mod_stride, mod_rows, rows_per_seq, _p(eval_ptr, I32, "eval_ptr"), eval_stride, rows, D,
                               eps), "f5e_layernorm")
@@ -200,10 +239,14 @@ def layernorm(x: Tensor, out: Tensor, gamma: Optional[Tensor] = None, beta: Opti
 
 
 def l2norm(x: Tensor, out: Tensor, g: Tensor):
-    """out = x / ||x|| * sqrt(D) * g (x_transformers.RMSNorm); x f32 [rows, D], out bf16 or f32."""
+    """out = x / ||x|| * sqrt(D) * g (x_transformers.RMSNorm); x f32 [rows, D], out bf16 or f32, g f32 [D].  x and out may be
+    views with unit column stride and any row stride that is a multiple of 4, on a 16-byte (bf16 out: 8-byte) aligned base."""
     require_device()
+    if x.ndim != 2 or out.shape != x.shape or g.numel() != x.shape[1]:
+        raise _C.F5EError(f"l2norm: x and out [rows, D], g [D] (got {tuple(x.shape)}, {tuple(out.shape)}, {tuple(g.shape)})")
     rows, D = x.shape
-    check(lib().f5e_l2norm(_stream(), _p(x, F32, "x"), x.stride(0), _p(out, None, "out"), out.stride(0),
+    (xp, ldx), (op, ldo) = _rows(x, (F32,), "x", D), _rows(out, (F32, BF), "out", D)
+    check(lib().f5e_l2norm(_stream(), xp, ldx, op, ldo,
                            1 if out.dtype == BF else 0, _p(g, F32, "g"), rows, D), "f5e_l2norm")
     return out
 
@@ -640,11 +683,14 @@ def kaldi_fbank(wav: Tensor, window: Tensor, twiddle: Tensor, fb: Tensor, out: T
 
 
 def glu(x: Tensor, out: Tensor):
-    """out[r, c] = x[r, c] * sigmoid(x[r, C + c]); x f32 [rows, 2C], out f32 [rows, C] (row strides free)."""
+    """out[r, c] = x[r, c] * sigmoid(x[r, C + c]); x f32 [rows, 2C], out f32 [rows, C]: views with unit column stride and any
+    row stride that is a multiple of 4, on a 16-byte aligned base (16-byte accesses)."""
     require_device()
-    rows, C = out.shape
-    check(lib().f5e_glu(_stream(), _p(x, F32, "x"), x.stride(0), _p(out, F32, "out"),
-                        out.stride(0), rows, C), "f5e_glu")
+    if out.ndim != 2 or x.shape != (out.shape[0], 2 * out.shape[1]):
+        raise _C.F5EError(f"glu: x [rows, 2C], out [rows, C] (got {tuple(x.shape)}, {tuple(out.shape)})")
+    rows, Cc = out.shape
+    (xp, ldx), (op, ldo) = _rows(x, (F32,), "x", 2 * Cc), _rows(out, (F32,), "out", Cc)
+    check(lib().f5e_glu(_stream(), xp, ldx, op, ldo, rows, Cc), "f5e_glu")
     return out
 
 
@@ -658,10 +704,18 @@ def dwconv(x: Tensor, w_t: Tensor, bias: Tensor, out: Tensor, keep: Optional[Ten
 
 
 def softmax_rows(x: Tensor, out: Tensor, L: int, scale: float, kv_len: Optional[Tensor] = None, rows_per_seq: int = 1):
-    """Row softmax of scale * x[:, :len] (zeros beyond); x, out f32 [rows, >= L]."""
+    """Row softmax of scale * x[:, :len], len = min(kv_len[row // rows_per_seq], L) (L without kv_len); x, out f32
+    [rows, >= L] views with unit column stride and any row stride (scalar accesses: no alignment beyond the element's).
+    Every column of ``out`` from len up to its ROW STRIDE is set to zero (the pad columns a following GEMM reads), so
+    ``out`` must own whole rows of its stride.  out may be x."""
     require_device()
+    if x.ndim != 2 or out.ndim != 2 or out.shape[0] != x.shape[0] or L < 1:
+        raise _C.F5EError(f"softmax_rows: x, out [rows, >= L] (got {tuple(x.shape)}, {tuple(out.shape)}, L={L})")
     rows = x.shape[0]
-    check(lib().f5e_softmax_rows(_stream(), _p(x, F32, "x"), x.stride(0), _p(out, F32, "out"), out.stride(0),
+    if kv_len is not None and (rows_per_seq < 1 or kv_len.numel() < -(-rows // rows_per_seq)):
+        raise _C.F5EError(f"softmax_rows: kv_len needs one entry per sequence of {rows_per_seq} rows")
+    (xp, ldx), (op, ldo) = _rows(x, (F32,), "x", L, vec=1), _rows(out, (F32,), "out", L, vec=1, whole_rows=True)
+    check(lib().f5e_softmax_rows(_stream(), xp, ldx, op, ldo,
                                  _p(kv_len, I32, "kv_len"), rows, rows_per_seq if kv_len is not None else max(rows, 1), L,
                                  scale), "f5e_softmax_rows")
     return out

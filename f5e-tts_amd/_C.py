@@ -52,6 +52,10 @@ SIGNATURES = {
     "f5e_ctc_align_workspace_bytes": [_I, _I, _I, C.POINTER(C.c_ulonglong)],
     "f5e_ctc_align": [_P, _P, _LL, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _I],
     "f5e_ctc_greedy": [_P, _P, _LL, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I],
+    "f5e_ctc_beam_workspace_bytes": [_I, _I, _I, C.POINTER(C.c_ulonglong)],
+    "f5e_ctc_beam": [_P, _P, _LL, _I, _P, _I, _I, _P, _I, _P, _P, _P, C.c_ulonglong, _I, _I, _I],
+    "f5e_token_logp": [_P, _P, _LL, _P, _P, _LL, _I],
+    "f5e_log_softmax_rows": [_P, _P, _LL, _P, _LL, _LL, _I],
     "f5e_stft_logmel": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I],
     "f5e_stft_logmel_banded": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I],
     "f5e_stft_logmel_banded_ex": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F],
@@ -65,6 +69,7 @@ SIGNATURES = {
     "f5e_softmax_rows": [_P, _P, _I, _P, _I, _P, _LL, _I, _I, _F],
     "f5e_dwconv_stream": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],
     "f5e_relpos_attn": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F],
+    "f5e_mha_f32": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F],
     "f5e_dit_forward": [_P, _P],
     "f5e_sample_loop": [_P, _P],
     "f5e_workspace_bytes": [_P, _P],

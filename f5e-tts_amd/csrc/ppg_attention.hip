@@ -113,6 +113,94 @@ __global__ __launch_bounds__(64) void relpos_attn_kernel(RelposArgs a) {
   }
 }
 
+// ---- f5e_mha_f32: plain masked attention with its own query and key counts (the attention decoder's self- and source
+// attention, ppg/wenet/transformer/attention.py:79-111).  The wave tile of relpos_attn_kernel without the position term; the
+// band of query i is [0, min(i + 1, len)) when causal and [0, len) otherwise, so a query below the key length is NOT
+// required: every query row is computed, and one with no visible key yields zeros (the reference's masked_fill after the
+// softmax).
+struct MhaArgs {
+  const float *q, *k, *v;
+  float* out;
+  const int* kv_len;
+  int ldq, ldk, ldv, ldo;
+  int Tq, Tk, causal;
+  float scale;
+};
+
+template <int DK>
+__global__ __launch_bounds__(64) void mha_f32_kernel(MhaArgs a) {
+  constexpr int NB = DK / 16;
+  const int lane = threadIdx.x, c16 = lane & 15, g = lane >> 4;
+  const int q0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
+  const int len = a.kv_len ? min(max(a.kv_len[b], 0), a.Tk) : a.Tk;
+  const size_t rowq = (size_t)b * a.Tq, rowk = (size_t)b * a.Tk;
+  const int hc = hd * DK;
+  const int q_last = min(q0 + 15, a.Tq - 1);
+  const int qr = min(q0 + c16, a.Tq - 1);                 // this lane's query row (clamped: loads stay in bounds)
+  const bool q_ok = q0 + c16 < a.Tq;
+  const int hi_q = q_ok ? (a.causal ? min(qr + 1, len) : len) : 0;
+  const int t_hi = a.causal ? min(q_last + 1, len) : len;
+
+  f32x4 qa[NB];
+  {
+    const float* qp = a.q + (rowq + qr) * a.ldq + hc + 4 * g;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) qa[j] = *(const f32x4*)(qp + 16 * j);
+  }
+  f32x4 acc[NB];
+#pragma unroll
+  for (int j = 0; j < NB; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  float m_run = -INFINITY, l_run = 0.f;
+
+  for (int kt = 0; kt < t_hi; kt += 16) {
+    const int kr = min(kt + c16, len - 1);               // key row of the score product's A operand (len > 0 here)
+    const float* kp = a.k + (rowk + kr) * a.ldk + hc + 4 * g;
+    f32x4 s0 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const f32x4 kf = *(const f32x4*)(kp + 16 * j);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[r], qa[j][r], s0, 0, 0, 0);
+    }
+    float p[4], mx = -INFINITY;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p[r] = kt + 4 * g + r < hi_q ? s0[r] * a.scale : -INFINITY;
+      mx = fmaxf(mx, p[r]);
+    }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float m_new = fmaxf(m_run, mx);
+    const float m_use = m_new == -INFINITY ? 0.f : m_new;     // a row with nothing visible yet: exp(-inf - 0) = 0
+    const float alpha = __expf(m_run - m_use);
+    float sum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      p[r] = __expf(p[r] - m_use);
+      sum += p[r];
+    }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    l_run = l_run * alpha + sum;
+    m_run = m_new;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) acc[j] *= alpha;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int vr = min(kt + 4 * g + r, len - 1);
+      const float* vp = a.v + (rowk + vr) * a.ldv + hc + c16;
+#pragma unroll
+      for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[16 * j], p[r], acc[j], 0, 0, 0);
+    }
+  }
+  if (q_ok) {
+    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;   // no visible key: zeros
+    float* op = a.out + (rowq + q0 + c16) * a.ldo + hc + 4 * g;
+#pragma unroll
+    for (int j = 0; j < NB; ++j) *(f32x4*)(op + 16 * j) = acc[j] * inv;
+  }
+}
+
 }  // namespace
 
 extern "C" int f5e_relpos_attn(hipStream_t st, const float* qu, int ldq, const float* k, int ldk, const float* pos, int ldp,
@@ -138,5 +226,28 @@ extern "C" int f5e_relpos_attn(hipStream_t st, const float* qu, int ldq, const f
     default: hipLaunchKernelGGL(relpos_attn_kernel<128>, grid, dim3(64), 0, st, a); break;
   }
   F5E_LAUNCH_CHECK("relpos_attn");
+  return F5E_OK;
+}
+
+extern "C" int f5e_mha_f32(hipStream_t st, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out,
+                           int ldo, const int* kv_len, int B, int Tq, int Tk, int H, int dk, int causal, float scale) {
+  F5E_REQUIRE(q && k && v && out, "mha_f32: null operand");
+  F5E_REQUIRE(dk == 16 || dk == 32 || dk == 64 || dk == 128, "mha_f32: head dim %d is not built (16, 32, 64 and 128 are)", dk);
+  const long long D = (long long)H * dk;
+  F5E_REQUIRE(B > 0 && B <= 65535 && Tq > 0 && Tk > 0 && H > 0 && H <= 65535, "mha_f32: bad shape (B=%d Tq=%d Tk=%d H=%d)", B,
+              Tq, Tk, H);
+  F5E_REQUIRE(!causal || Tq == Tk, "mha_f32: causal needs Tq == Tk (got %d and %d)", Tq, Tk);
+  F5E_REQUIRE(ldq >= D && ldk >= D && ldv >= D && ldo >= D && ldq % 4 == 0 && ldk % 4 == 0 && ldo % 4 == 0,
+              "mha_f32: row strides must cover the heads (H dk) and those of q, k and out be multiples of 4 floats");
+  F5E_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)out) & 15) == 0, "mha_f32: q, k and out must be 16-byte aligned");
+  MhaArgs a{q, k, v, out, kv_len, ldq, ldk, ldv, ldo, Tq, Tk, causal ? 1 : 0, scale};
+  const dim3 grid((unsigned)((Tq + 15) / 16), (unsigned)H, (unsigned)B);
+  switch (dk) {
+    case 16: hipLaunchKernelGGL(mha_f32_kernel<16>, grid, dim3(64), 0, st, a); break;
+    case 32: hipLaunchKernelGGL(mha_f32_kernel<32>, grid, dim3(64), 0, st, a); break;
+    case 64: hipLaunchKernelGGL(mha_f32_kernel<64>, grid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL(mha_f32_kernel<128>, grid, dim3(64), 0, st, a); break;
+  }
+  F5E_LAUNCH_CHECK("mha_f32");
   return F5E_OK;
 }

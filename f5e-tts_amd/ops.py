@@ -513,6 +513,86 @@ def ctc_greedy(scores: Tensor, t_len: Tensor, blank: int = 0, pad_id: int = -1, 
     return hyp, hyp_len, frame_logp
 
 
+def ctc_beam_workspace_bytes(B: int, T: int, beam: int) -> int:
+    """Scratch bytes of ``ctc_beam_search`` for B sequences of up to T frames at beam size ``beam`` (host call)."""
+    n = C.c_ulonglong()
+    check(lib().f5e_ctc_beam_workspace_bytes(B, T, beam, C.byref(n)), "f5e_ctc_beam_workspace_bytes")
+    return int(n.value)
+
+
+def ctc_beam_search(scores: Tensor, t_len: Tensor, beam: int, blank: int = 0, *, ld_hyp: Optional[int] = None,
+                    hyp: Optional[Tensor] = None, hyp_len: Optional[Tensor] = None, score: Optional[Tensor] = None,
+                    workspace: Optional[Tensor] = None):
+    """CTC prefix beam search (f5e_ctc_beam): scores f32 [B, T, V] as in ``ctc_align`` (raw logits or log-probabilities, the
+    kernel normalises every frame), t_len i32 [B] on the device -> (hyp i32 [B, beam, ld_hyp] padded with -1, best first;
+    hyp_len i32 [B, beam], the true lengths; score f32 [B, beam]).  ld_hyp defaults to T, which no prefix exceeds.
+    workspace: a device tensor of at least ``ctc_beam_workspace_bytes`` bytes (allocated here when None)."""
+    B, T, V = _ctc_scores(scores, "ctc_beam_search")
+    if t_len.dtype != I32 or not t_len.is_cuda or t_len.numel() != B:
+        raise _C.F5EError(f"ctc_beam_search: t_len must be an i32 GPU tensor [{B}]")
+    beam = int(beam)
+    if not 1 <= beam <= min(16, V):
+        raise _C.F5EError(f"ctc_beam_search: beam must lie in 1..min(16, V = {V}), got {beam}")
+    require_device()
+    dev = scores.device
+    if hyp is not None:
+        if hyp.ndim != 3 or not hyp.is_contiguous():
+            raise _C.F5EError(f"ctc_beam_search: hyp must be a contiguous i32 tensor [{B}, {beam}, ld_hyp]")
+        ld_hyp = hyp.shape[2]
+    ld_hyp = T if ld_hyp is None else int(ld_hyp)
+    hyp = torch.empty(B, beam, ld_hyp, dtype=I32, device=dev) if hyp is None else hyp
+    hyp_len = torch.empty(B, beam, dtype=I32, device=dev) if hyp_len is None else hyp_len
+    score = torch.empty(B, beam, dtype=F32, device=dev) if score is None else score
+    if ld_hyp < 1 or hyp.shape != (B, beam, ld_hyp) or hyp_len.shape != (B, beam) or score.shape != (B, beam) or \
+            not (hyp_len.is_contiguous() and score.is_contiguous()):
+        raise _C.F5EError(f"ctc_beam_search: hyp [{B}, {beam}, ld_hyp >= 1], hyp_len / score [{B}, {beam}], contiguous")
+    need = ctc_beam_workspace_bytes(B, T, beam)
+    if workspace is None:
+        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+    nbytes = workspace.numel() * workspace.element_size()
+    check(lib().f5e_ctc_beam(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0),
+                             scores.stride(1) if T > 1 else max(V, scores.stride(1)), _p(t_len, I32, "t_len"), int(blank),
+                             beam, _p(hyp, I32, "hyp"), ld_hyp, _p(hyp_len, I32, "hyp_len"), _p(score, F32, "score"),
+                             _p(workspace, None, "workspace"), nbytes, B, T, V), "f5e_ctc_beam")
+    return hyp, hyp_len, score
+
+
+def token_logp(logits: Tensor, target: Tensor, out: Optional[Tensor] = None):
+    """out[r] = logits[r, target[r]] - logsumexp(logits[r]) (f5e_token_logp): logits f32 [rows, V] on the device (row stride
+    free, unit class stride), target i32 [rows]; a negative target gives 0."""
+    if logits.ndim != 2 or not logits.is_cuda or logits.dtype != F32 or logits.stride(1) != 1:
+        raise _C.F5EError("token_logp: logits must be an f32 GPU tensor [rows, V] with unit class stride; there is no CPU "
+                          "path")
+    rows, V = logits.shape
+    if target.dtype != I32 or not target.is_cuda or target.shape != (rows,) or not target.is_contiguous():
+        raise _C.F5EError(f"token_logp: target must be a contiguous i32 GPU tensor [{rows}]")
+    require_device()
+    out = torch.empty(rows, dtype=F32, device=logits.device) if out is None else out
+    if out.shape != (rows,) or not out.is_contiguous():
+        raise _C.F5EError(f"token_logp: out must be a contiguous f32 tensor [{rows}]")
+    check(lib().f5e_token_logp(_stream(), C.c_void_p(logits.data_ptr()), logits.stride(0) if rows > 1 else max(V, logits.stride(0)),
+                               _p(target, I32, "target"), _p(out, F32, "out"), rows, V), "f5e_token_logp")
+    return out
+
+
+def log_softmax_rows(x: Tensor, out: Optional[Tensor] = None):
+    """out[r] = x[r] - logsumexp(x[r]) (f5e_log_softmax_rows): x f32 [rows, V] on the device (row stride free, unit column
+    stride); out likewise (allocated here when None; may be x)."""
+    for n_, t_ in (("x", x), ("out", out)):
+        if t_ is not None and (t_.ndim != 2 or not t_.is_cuda or t_.dtype != F32 or t_.stride(1) != 1):
+            raise _C.F5EError(f"log_softmax_rows: {n_} must be an f32 GPU tensor [rows, V] with unit column stride; there is "
+                              "no CPU path")
+    rows, V = x.shape
+    require_device()
+    out = torch.empty(rows, V, dtype=F32, device=x.device) if out is None else out
+    if out.shape != (rows, V):
+        raise _C.F5EError(f"log_softmax_rows: out must be [{rows}, {V}]")
+    ld = [t_.stride(0) if rows > 1 else max(V, t_.stride(0)) for t_ in (x, out)]
+    check(lib().f5e_log_softmax_rows(_stream(), C.c_void_p(x.data_ptr()), ld[0], C.c_void_p(out.data_ptr()), ld[1], rows, V),
+          "f5e_log_softmax_rows")
+    return out
+
+
 _resample_banks = {}
 _resample_lock = threading.Lock()
 
@@ -754,6 +834,34 @@ def relpos_attn(qu: Tensor, k: Tensor, pos: Tensor, v: Tensor, out: Tensor, head
                                 _p(pos, F32, "pos"), pos.stride(0), _p(v, F32, "v"), v.stride(0), _p(out, F32, "out"),
                                 out.stride(0), _p(kv_len, I32, "kv_len"), B, T, heads, D // heads, int(q_begin), int(chunk),
                                 int(left_chunks), float(scale)), "f5e_relpos_attn")
+    return out
+
+
+def mha_f32(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float, B: int = 1, kv_len: Optional[Tensor] = None,
+            causal: bool = False, out: Optional[Tensor] = None):
+    """Plain masked fp32 attention (f5e_mha_f32): q f32 [B*Tq, D], k / v f32 [B*Tk, D] on the device (row strides free, unit
+    column stride) -> out f32 [B*Tq, D].  Key j is visible to query i iff j < kv_len[b] (i32 [B] on the device, optional) and,
+    when ``causal`` (Tq == Tk), j <= i; a query with no visible key yields zeros."""
+    if q.ndim != 2 or k.ndim != 2:
+        raise _C.F5EError("mha_f32: q and k must be f32 GPU matrices; there is no CPU path")
+    Mq, D = q.shape
+    Mk = k.shape[0]
+    if B < 1 or Mq % B or Mk % B or Mq == 0 or Mk == 0 or k.shape != (Mk, D) or v.shape != (Mk, D) or D % heads or \
+            (out is not None and out.shape != (Mq, D)):
+        raise _C.F5EError(f"mha_f32: inconsistent shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} B={B} "
+                          f"heads={heads}")
+    Tq, Tk = Mq // B, Mk // B
+    if causal and Tq != Tk:
+        raise _C.F5EError(f"mha_f32: causal needs Tq == Tk (got {Tq} and {Tk})")
+    if kv_len is not None and (kv_len.numel() != B or kv_len.dtype != I32 or not kv_len.is_cuda):
+        raise _C.F5EError(f"mha_f32: kv_len must be an i32 GPU tensor [{B}]")
+    (qp, ldq), (kp, ldk), (vp, ldv) = _rows(q, (F32,), "mha_f32: q", D), _rows(k, (F32,), "mha_f32: k", D), \
+        _rows(v, (F32,), "mha_f32: v", D, vec=1)
+    require_device()
+    out = torch.empty(Mq, D, dtype=F32, device=q.device) if out is None else out
+    op, ldo = _rows(out, (F32,), "mha_f32: out", D)
+    check(lib().f5e_mha_f32(_stream(), qp, ldq, kp, ldk, vp, ldv, op, ldo, _p(kv_len, I32, "kv_len"), B, Tq, Tk, heads,
+                            D // heads, 1 if causal else 0, float(scale)), "f5e_mha_f32")
     return out
 
 

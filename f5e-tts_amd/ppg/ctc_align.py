@@ -129,17 +129,22 @@ def word_spans(words: Sequence[str], ids: Sequence[Sequence[int]], tok_end: Sequ
     return spans
 
 
+DECODE_MODES = ("ctc_greedy_search", "ctc_prefix_beam_search", "attention_rescoring")     # the reference's mode names
+
+
 class CTCAligner:
-    """``align(audio, sr, text)`` -> word-level timestamps; ``transcribe(audio, sr)`` -> text.  ``tokenize``: optional
+    """``align(audio, sr, text)`` -> word-level timestamps; ``transcribe(audio, sr, mode=...)`` -> text (greedy by default;
+    ``attention_rescoring`` needs ``decoder=True`` or a model built with its attention decoder).  ``tokenize``: optional
     ``text -> (words, ids per word)`` in place of ``default_tokenize`` (BPE models bring their own).  ``model`` /
     ``symbol_table``: an already built ``ConformerPPG(ctc=True)`` and table instead of the three paths."""
 
     def __init__(self, ppg_model_path: Optional[str] = None, ppg_config: Optional[str] = None,
                  dict_path: Optional[str] = None, device="cuda", tokenize: Optional[Callable] = None, *, model=None,
-                 symbol_table: Optional[Dict[str, int]] = None):
+                 symbol_table: Optional[Dict[str, int]] = None, decoder: bool = False):
         from .ppg_model import build_ppg_model, kaldiFbank
         self.device = device
-        self.model = model if model is not None else build_ppg_model(ppg_model_path, ppg_config, device, ctc=True)
+        self.model = model if model is not None else build_ppg_model(ppg_model_path, ppg_config, device, ctc=True,
+                                                                           decoder=decoder)
         if not getattr(self.model, "has_ctc", False):
             raise _C.F5EError("CTCAligner: the model was built without its CTC head (ctc=True)")
         self.table = dict(symbol_table) if symbol_table is not None else read_symbol_table(dict_path)
@@ -162,10 +167,24 @@ class CTCAligner:
         return feats, feats_len.to(self.device), secs
 
     @torch.no_grad()
-    def transcribe(self, audio, sr: Optional[int] = None) -> str:
+    def transcribe(self, audio, sr: Optional[int] = None, mode: str = "ctc_greedy_search", beam_size: int = 10,
+                   ctc_weight: float = 0.5, reverse_weight: float = 0.0) -> str:
+        """``mode``: one of the reference's ``ctc_greedy_search`` (the default), ``ctc_prefix_beam_search`` (the best of the
+        n-best at ``beam_size``) and ``attention_rescoring`` (that list re-ranked by the attention decoder)."""
+        if mode not in DECODE_MODES:
+            raise _C.F5EError(f"CTCAligner.transcribe: unknown mode {mode!r} (one of {', '.join(DECODE_MODES)})")
+        if mode == "attention_rescoring" and getattr(self.model, "decoder_type", None) is None:
+            raise _C.F5EError("CTCAligner.transcribe: attention_rescoring needs a model built with its attention decoder "
+                              "(CTCAligner(decoder=True) / build_ppg_model(decoder=True))")
         feats, lens, _ = self._feats(audio, sr)
-        hyps, _ = self.model.ctc_greedy_search(feats, lens, pad_id=-1)
-        return "".join(self.inverse.get(i, "") for i in hyps[0]).replace("▁", " ").strip()
+        if mode == "ctc_greedy_search":
+            ids = self.model.ctc_greedy_search(feats, lens, pad_id=-1)[0][0]
+        elif mode == "ctc_prefix_beam_search":
+            ids = self.model.ctc_prefix_beam_search(feats, lens, beam_size)[0][0][0]
+        else:
+            ids = self.model.attention_rescoring(feats, lens, beam_size, ctc_weight=ctc_weight,
+                                                 reverse_weight=reverse_weight)[0][0]
+        return "".join(self.inverse.get(i, "") for i in ids).replace("▁", " ").strip()
 
     @torch.no_grad()
     def align(self, audio, sr: Optional[int], text: str) -> List[WordSpan]:

@@ -132,6 +132,97 @@ class _CTC(nn.Module):
         self.ctc_lo = nn.Linear(d, odim)
 
 
+class _MHA(nn.Module):
+    def __init__(self, d):
+        super().__init__()
+        self.linear_q, self.linear_k, self.linear_v = nn.Linear(d, d), nn.Linear(d, d), nn.Linear(d, d)
+        self.linear_out = nn.Linear(d, d)
+
+
+class _DecoderLayer(nn.Module):
+    def __init__(self, d, units):
+        super().__init__()
+        self.self_attn, self.src_attn = _MHA(d), _MHA(d)
+        self.feed_forward = _FFN(d, units)
+        self.norm1, self.norm2, self.norm3 = (nn.LayerNorm(d, eps=1e-5) for _ in range(3))
+        # checkpoint keys of the reference layer; unused (concat_after False)
+        self.concat_linear1, self.concat_linear2 = nn.Linear(2 * d, d), nn.Linear(2 * d, d)
+
+
+class _TransformerDecoder(nn.Module):
+    """reference ppg/wenet/transformer/decoder.py:17-84 (``embed.1`` is the parameter-free positional encoding)."""
+
+    def __init__(self, vocab, d, units, blocks):
+        super().__init__()
+        self.embed = nn.Sequential(nn.Embedding(vocab, d))
+        self.after_norm = nn.LayerNorm(d, eps=1e-5)
+        self.output_layer = nn.Linear(d, vocab)
+        self.decoders = nn.ModuleList([_DecoderLayer(d, units) for _ in range(blocks)])
+
+
+class _BiTransformerDecoder(nn.Module):
+    def __init__(self, vocab, d, units, blocks, r_blocks):
+        super().__init__()
+        self.left_decoder = _TransformerDecoder(vocab, d, units, blocks)
+        self.right_decoder = _TransformerDecoder(vocab, d, units, r_blocks)
+
+
+DECODER_DEFAULTS = dict(attention_heads=4, linear_units=2048, num_blocks=6, r_num_blocks=0)
+DECODER_FIXED = dict(input_layer="embed", use_output_layer=True, normalize_before=True, concat_after=False)
+DECODER_IGNORED = ("dropout_rate", "positional_dropout_rate", "self_attention_dropout_rate", "src_attention_dropout_rate")
+
+
+def check_decoder_conf(decoder: Optional[str], conf: Optional[dict]) -> dict:
+    """The decoder settings that are built (decoder.py:37-52, 205-221): F5EError names every entry that is not."""
+    if decoder not in ("transformer", "bitransformer"):
+        raise _C.F5EError(f"PPG extractor: unsupported decoder {decoder!r} (transformer and bitransformer are built)")
+    conf = dict(conf or {})
+    bad = {k: v for k, v in conf.items() if (k in DECODER_FIXED and v != DECODER_FIXED[k]) or
+           (k not in DECODER_FIXED and k not in DECODER_DEFAULTS and k not in DECODER_IGNORED)}
+    if decoder == "transformer" and conf.get("r_num_blocks", 0):
+        bad["r_num_blocks"] = conf["r_num_blocks"]
+    if decoder == "bitransformer" and conf.get("r_num_blocks", 0) < 1:
+        bad["r_num_blocks"] = conf.get("r_num_blocks", 0)           # init_asr_model asserts r_num_blocks > 0
+    if bad:
+        raise _C.F5EError(f"PPG extractor: unsupported decoder_conf entries {bad}")
+    return {k: int(conf.get(k, v)) for k, v in DECODER_DEFAULTS.items()}
+
+
+def check_beam(beam_size: int, vocab: int) -> int:
+    if not 1 <= int(beam_size) <= min(16, vocab):
+        raise _C.F5EError(f"ctc_prefix_beam_search: beam_size must lie in 1..{min(16, vocab)} (got {beam_size})")
+    return int(beam_size)
+
+
+def check_hyps(hyps_lens, U1: int, vocab: int, hyps=None) -> None:
+    """Host-side hypothesis lengths (sos included) and ids of ``forward_attention_decoder``: caller bugs raise here."""
+    for i, n in enumerate(hyps_lens):
+        if not 1 <= int(n) <= U1:
+            raise _C.F5EError(f"forward_attention_decoder: hypothesis {i} has length {int(n)}, need 1 <= length <= {U1}")
+        if hyps is not None and any(not 0 <= int(v) < vocab for v in hyps[i][:int(n)]):
+            raise _C.F5EError(f"forward_attention_decoder: hypothesis {i} holds ids outside [0, {vocab})")
+
+
+def rescoring_inputs(hyps: List[Tuple[int, ...]], sos: int, eos: int, rows: Optional[int] = None):
+    """The decoder inputs and targets of ``attention_rescoring`` (asr_model.py:628-647, 660-670) for one utterance's n-best:
+    ys_in = sos + hyp, eos-padded; r_ys_in = sos + reversed hyp, eos-padded; lens = len + 1; the targets whose log-
+    probabilities the score sums (hyp then eos at position len, -1 after it; the right-to-left ones reversed).  All i32
+    [rows, U + 1] / [rows]; rows past the list (``rows`` > len(hyps)) hold sos alone and no target."""
+    rows = len(hyps) if rows is None else rows
+    U1 = max([len(h) for h in hyps] + [0]) + 1
+    ys, r_ys = np.full((rows, U1), eos, np.int32), np.full((rows, U1), eos, np.int32)
+    tg, r_tg = np.full((rows, U1), -1, np.int32), np.full((rows, U1), -1, np.int32)
+    lens = np.ones(rows, np.int32)
+    ys[:, 0] = r_ys[:, 0] = sos
+    for i, h in enumerate(hyps):
+        n = len(h)
+        ys[i, 1:n + 1], r_ys[i, 1:n + 1] = h, h[::-1]
+        tg[i, :n], r_tg[i, :n] = h, h[::-1]
+        tg[i, n] = r_tg[i, n] = eos
+        lens[i] = n + 1
+    return ys, r_ys, lens, tg, r_tg
+
+
 class CTCAlignment(NamedTuple):
     """``ConformerPPG.ctc_forced_align``: align i32 [B, T'] (class of every encoder frame: blank or a label, -1 past the
     utterance), tok_start / tok_end i32 [B, L] (first / one-past-last frame of every label), score f32 [B] (the path's
@@ -168,7 +259,8 @@ class ConformerPPG(nn.Module):
     def __init__(self, input_dim: int = 80, vocab_size: int = 218, output_size: int = 256, attention_heads: int = 4,
                  linear_units: int = 2048, num_blocks: int = 6, cnn_module_kernel: int = 15,
                  global_cmvn: Optional[Tuple[Tensor, Tensor]] = None, causal: bool = False,
-                 use_dynamic_chunk: bool = False, static_chunk_size: int = 0, ctc: bool = False):
+                 use_dynamic_chunk: bool = False, static_chunk_size: int = 0, ctc: bool = False,
+                 decoder: Optional[str] = None, decoder_conf: Optional[dict] = None):
         super().__init__()
         cm = _GlobalCMVN(global_cmvn[0].float(), global_cmvn[1].float()) if global_cmvn is not None else None
         self.encoder = _Encoder(input_dim, output_size, attention_heads, linear_units, num_blocks, cnn_module_kernel, cm)
@@ -177,6 +269,16 @@ class ConformerPPG(nn.Module):
         if ctc:
             self.ctc = _CTC(vocab_size, output_size)
         self.has_ctc, self.vocab_size = bool(ctc), vocab_size
+        self.decoder_type, self.decoder_heads = decoder, 0
+        if decoder is not None:
+            dc = check_decoder_conf(decoder, decoder_conf)
+            if output_size % dc["attention_heads"]:
+                raise _C.F5EError(f"PPG extractor: decoder_conf attention_heads {dc['attention_heads']} does not divide "
+                                  f"output_size {output_size}")
+            self.decoder_heads = dc["attention_heads"]
+            self.decoder = _TransformerDecoder(vocab_size, output_size, dc["linear_units"], dc["num_blocks"]) \
+                if decoder == "transformer" else \
+                _BiTransformerDecoder(vocab_size, output_size, dc["linear_units"], dc["num_blocks"], dc["r_num_blocks"])
         self.sos = self.eos = vocab_size - 1                 # asr_model.py: sos = eos = vocab_size - 1
         self.input_dim, self.heads, self.dim = input_dim, attention_heads, output_size
         # causal: the depthwise convolution looks back only (convolution.py:45-52); the chunk settings say whether the
@@ -185,8 +287,9 @@ class ConformerPPG(nn.Module):
         self._engine = None
 
     @classmethod
-    def from_config(cls, configs: dict, ctc: bool = False) -> "ConformerPPG":
-        """``init_asr_model`` (asr_model.py:814-859) for the supported encoder family."""
+    def from_config(cls, configs: dict, ctc: bool = False, decoder: bool = False) -> "ConformerPPG":
+        """``init_asr_model`` (asr_model.py:814-859) for the supported encoder family; ``decoder=True`` also builds the
+        attention decoder the config names (``decoder`` -- bitransformer when absent, as there -- and ``decoder_conf``)."""
         enc = dict(configs.get("encoder_conf") or {})
         if configs.get("encoder", "conformer") != "conformer":
             raise _C.F5EError("PPG extractor: only `encoder: conformer` is built for MI355X")
@@ -203,7 +306,9 @@ class ConformerPPG(nn.Module):
         return cls(configs["input_dim"], configs["output_dim"], enc.get("output_size", 256), enc.get("attention_heads", 4),
                    enc.get("linear_units", 2048), enc.get("num_blocks", 6), enc.get("cnn_module_kernel", 15), cmvn,
                    causal=enc.get("causal", False), use_dynamic_chunk=enc.get("use_dynamic_chunk", False),
-                   static_chunk_size=enc.get("static_chunk_size", 0), ctc=ctc)
+                   static_chunk_size=enc.get("static_chunk_size", 0), ctc=ctc,
+                   decoder=configs.get("decoder", "bitransformer") if decoder else None,
+                   decoder_conf=configs.get("decoder_conf") if decoder else None)
 
     def _apply(self, fn, *a, **kw):
         self._engine = None
@@ -218,7 +323,8 @@ class ConformerPPG(nn.Module):
         if self._engine is None or self._engine.device != dev:
             if dev.type != "cuda":
                 raise _C.F5EError(f"PPG model lives on {dev}: move it to the GPU (there is no CPU path)")
-            self._engine = ConformerEngine(self.state_dict(), self.heads, dev, self.input_dim, causal=self.causal)
+            self._engine = ConformerEngine(self.state_dict(), self.heads, dev, self.input_dim, causal=self.causal,
+                                           decoder_heads=self.decoder_heads)
         return self._engine
 
     @torch.no_grad()
@@ -295,6 +401,104 @@ class ConformerPPG(nn.Module):
         out = ops.ctc_align(logits, labels.to(dev, I32).contiguous(), frame_lens, l_len, blank=0)
         return CTCAlignment(*out, frame_lens)
 
+    def _require_decoder(self, reverse_weight: float = 0.0) -> "ConformerEngine":
+        if self.decoder_type is None:
+            raise _C.F5EError("PPG extractor: built without the attention decoder (ConformerPPG(decoder=...) / "
+                              "build_ppg_model(decoder=True))")
+        if reverse_weight > 0.0 and self.decoder_type != "bitransformer":
+            raise _C.F5EError("PPG extractor: reverse_weight > 0 needs the bitransformer decoder (its right-to-left half)")
+        return self.engine()
+
+    def _nbest(self, logits: Tensor, frame_lens: Tensor, beam_size: int):
+        """f5e_ctc_beam on CTC logits -> per utterance the list of (ids tuple, score), best first (one D2H of the lists)."""
+        K = check_beam(beam_size, self.vocab_size)
+        hyp, n, sc = ops.ctc_beam_search(logits, frame_lens, K, blank=0)
+        hyp_h, n_h, sc_h = hyp.cpu().numpy(), n.cpu().tolist(), sc.cpu().tolist()
+        return [[(tuple(int(v) for v in hyp_h[b, k, :n_h[b][k]]), float(sc_h[b][k])) for k in range(K) if n_h[b][k] >= 0]
+                for b in range(len(n_h))]
+
+    @torch.no_grad()
+    def ctc_prefix_beam_search(self, speech: Tensor, speech_lengths: Tensor, beam_size: int,
+                               use_linear: bool = False) -> List[List[Tuple[Tuple[int, ...], float]]]:
+        """reference asr_model.py:461-578 (full context) for a batch of ANY size -> per utterance the n-best list of
+        (ids, score = logaddexp(pb, pnb)), best first; at batch 1, ``[0]`` is the reference's ``_ctc_prefix_beam_search``
+        list.  The search runs on the device (f5e_ctc_beam) straight from the logits, frames past an utterance skipped.
+        ``use_linear`` as in ``ctc_greedy_search``."""
+        assert speech.shape[0] == speech_lengths.shape[0]
+        check_beam(beam_size, self.vocab_size)
+        logits, frame_lens, _ = self._ctc_scores(speech, speech_lengths, use_linear)
+        return self._nbest(logits, frame_lens, beam_size)
+
+    @torch.no_grad()
+    def attention_rescoring(self, speech: Tensor, speech_lengths: Tensor, beam_size: int, ctc_weight: float = 0.0,
+                            reverse_weight: float = 0.0, use_linear: bool = False) -> List[Tuple[Tuple[int, ...], float]]:
+        """reference asr_model.py:580-677 for a batch of any size -> per utterance (ids, score) of the n-best entry the
+        attention decoder likes best:  sum_j logp[j][w_j] + logp[len][eos], with reverse_weight > 0 mixed as
+        score (1 - rw) + r_score rw with the right-to-left decoder's sum (taken at len - j - 1), plus ctc_weight x the CTC
+        score; the first maximum wins.  The decoder runs ONCE per batch on the device: the memory's key / value projections
+        once per utterance (the reference repeats the encoder output beam_size times), every hypothesis' queries in one
+        launch; f5e_token_logp leaves one float per target, summed here in double precision as the reference does."""
+        assert speech.shape[0] == speech_lengths.shape[0]
+        eng = self._require_decoder(reverse_weight)
+        self._require_ctc()
+        K = check_beam(beam_size, self.vocab_size)
+        enc, lens_host = eng._encode(speech, speech_lengths)
+        frame_lens = lens_host.to(enc.device)
+        nbest = self._nbest(eng.ctc_logits(eng.head(enc)[0] if use_linear else enc), frame_lens, K)
+        B, dev = len(nbest), enc.device
+        U1 = max(len(h) for hyps in nbest for h, _ in hyps) + 1 if any(nbest) else 1
+        packs = [rescoring_inputs([h for h, _ in hyps], self.sos, self.eos, rows=K) for hyps in nbest]
+        pad = lambda a: np.pad(a, ((0, 0), (0, U1 - a.shape[1])), constant_values=self.eos)          # noqa: E731
+        pad_t = lambda a: np.pad(a, ((0, 0), (0, U1 - a.shape[1])), constant_values=-1)               # noqa: E731
+        ys = torch.from_numpy(np.concatenate([pad(p[0]) for p in packs])).to(dev)
+        r_ys = torch.from_numpy(np.concatenate([pad(p[1]) for p in packs])).to(dev)
+        lens = torch.from_numpy(np.concatenate([p[2] for p in packs])).to(dev)
+        tg = torch.from_numpy(np.concatenate([pad_t(p[3]) for p in packs])).to(dev)
+        r_tg = torch.from_numpy(np.concatenate([pad_t(p[4]) for p in packs])).to(dev)
+        ragged = bool(int(lens_host.min()) < enc.shape[1])
+        mem_len = frame_lens if ragged else None
+        lp = ops.token_logp(eng.decode("left", enc, mem_len, ys, lens, K), tg.view(-1)).view(B, K, U1).cpu().double()
+        total = lp.sum(-1)
+        if reverse_weight > 0.0:
+            r_lp = ops.token_logp(eng.decode("right", enc, mem_len, r_ys, lens, K), r_tg.view(-1)).view(B, K, U1)
+            total = total * (1 - reverse_weight) + r_lp.cpu().double().sum(-1) * reverse_weight
+        out = []
+        for b, hyps in enumerate(nbest):
+            best, best_i = -float("inf"), 0
+            for i, (_, ctc_score) in enumerate(hyps):
+                score = float(total[b, i]) + ctc_score * ctc_weight
+                if score > best:
+                    best, best_i = score, i
+            out.append((hyps[best_i][0] if hyps else tuple(), best))
+        return out
+
+    @torch.no_grad()
+    def forward_attention_decoder(self, hyps: Tensor, hyps_lens: Tensor, encoder_out: Tensor,
+                                  reverse_weight: float = 0) -> Tuple[Tensor, Tensor]:
+        """reference asr_model.py:763-811: ``hyps`` [N, U + 1] ids with the leading sos, eos-padded, ``hyps_lens`` [N] counting
+        the sos, ``encoder_out`` [1, T', D] -> (log_softmax of the decoder output [N, U + 1, V], the same of the
+        right-to-left decoder fed the reversed hypotheses, or tensor(0.0) when reverse_weight is 0)."""
+        eng = self._require_decoder(reverse_weight)
+        if encoder_out.ndim != 3 or encoder_out.shape[0] != 1 or hyps.ndim != 2 or hyps_lens.shape[0] != hyps.shape[0]:
+            raise _C.F5EError("forward_attention_decoder: hyps [N, U + 1], hyps_lens [N] and encoder_out [1, T', D]")
+        N, U1 = hyps.shape
+        h, n = hyps.detach().cpu().numpy().astype(np.int64), hyps_lens.detach().cpu().numpy().astype(np.int64)
+        check_hyps(n, U1, self.vocab_size, h)
+        dev = eng.device
+        enc = encoder_out.to(dev, F32).contiguous()
+        ys = torch.from_numpy(h.astype(np.int32)).to(dev)
+        lens = torch.from_numpy(n.astype(np.int32)).to(dev)
+        V = self.vocab_size
+        out = ops.log_softmax_rows(eng.decode("left", enc, None, ys, lens, N)).view(N, U1, V)
+        if not reverse_weight > 0:
+            return out, torch.tensor(0.0)
+        r = np.full((N, U1), self.eos, np.int32)
+        r[:, 0] = self.sos
+        for i in range(N):
+            r[i, 1:n[i]] = h[i, 1:n[i]][::-1]
+        r_out = ops.log_softmax_rows(eng.decode("right", enc, None, torch.from_numpy(r).to(dev), lens, N)).view(N, U1, V)
+        return out, r_out
+
     def _require_stream(self, xs: Tensor) -> None:
         if not (self.static_chunk_size > 0 or self.use_dynamic_chunk):
             raise _C.F5EError("PPG extractor: streaming needs a chunk-trained model (static_chunk_size > 0 or "
@@ -318,7 +522,7 @@ class ConformerPPG(nn.Module):
 class ConformerEngine:
     """Repacked fp32 weights + the launch sequence of ``BaseEncoder.forward`` (wenet/transformer/encoder.py:141-209)."""
 
-    def __init__(self, sd: Dict[str, Tensor], heads: int, device, idim: int, causal: bool = False):
+    def __init__(self, sd: Dict[str, Tensor], heads: int, device, idim: int, causal: bool = False, decoder_heads: int = 0):
         ops.require_device()
         self.device = dv = torch.device(device)
         f = lambda k: sd[k].detach().to(dv, F32).contiguous()   # noqa: E731
@@ -390,7 +594,70 @@ class ConformerEngine:
             self.ctc_w, self.ctc_b = f("ctc.ctc_lo.weight"), f("ctc.ctc_lo.bias")
         self.half = torch.full((max(D, 1),), 0.5, device=dv)
         self.dk = dk
+        # attention decoder(s): decoder.* (transformer) or decoder.left_decoder.* / right_decoder.* (bitransformer)
+        self.dec, self.dec_heads = {}, int(decoder_heads)
+        for name, pre in (("left", "decoder."), ("left", "decoder.left_decoder."), ("right", "decoder.right_decoder.")):
+            if pre + "embed.0.weight" in sd:
+                self.dec[name] = self._decoder_weights(f, sd, pre)
         self._pe: Dict[int, Tensor] = {}
+
+    def _decoder_weights(self, f, sd, pre: str) -> dict:
+        """One TransformerDecoder's weights, repacked once: the embedding pre-scaled by sqrt(D) (embedding.py:62), q | k | v
+        of the self-attention and k | v of the source attention stacked into one GEMM each."""
+        att = lambda p, names: (torch.cat([f(p + f"linear_{n}.weight") for n in names], 0).contiguous(),   # noqa: E731
+                                torch.cat([f(p + f"linear_{n}.bias") for n in names], 0).contiguous())
+        layers, i = [], 0
+        while f"{pre}decoders.{i}.norm1.weight" in sd:
+            p = f"{pre}decoders.{i}."
+            layers.append(dict(
+                ln=[(f(p + f"norm{k}.weight"), f(p + f"norm{k}.bias")) for k in (1, 2, 3)],
+                self_qkv=att(p + "self_attn.", "qkv"), self_out=att(p + "self_attn.", ["out"]),
+                src_q=att(p + "src_attn.", "q"), src_kv=att(p + "src_attn.", "kv"), src_out=att(p + "src_attn.", ["out"]),
+                ff=tuple(f(p + "feed_forward." + n_) for n_ in ("w_1.weight", "w_1.bias", "w_2.weight", "w_2.bias"))))
+            i += 1
+        return dict(embed=(f(pre + "embed.0.weight") * math.sqrt(self.dim)).contiguous(), layers=layers,
+                    after=(f(pre + "after_norm.weight"), f(pre + "after_norm.bias")),
+                    out=(f(pre + "output_layer.weight"), f(pre + "output_layer.bias")))
+
+    def decode(self, which: str, memory: Tensor, mem_len: Optional[Tensor], ys_in: Tensor, ys_len: Tensor, n_hyp: int) -> Tensor:
+        """TransformerDecoder.forward (decoder.py:86-135, pre-norm) for ``n_hyp`` hypotheses per utterance: memory f32
+        [B, T', D], mem_len i32 [B] on the device or None (every frame valid), ys_in i32 [B * n_hyp, U1] (sos + ids, padded),
+        ys_len i32 [B * n_hyp] -> logits f32 [B * n_hyp * U1, V].  Per layer: the self-attention is one causal f5e_mha_f32
+        over B * n_hyp items of U1 rows (keys < ys_len); the source attention projects the memory's keys and values ONCE per
+        utterance and runs one f5e_mha_f32 over B items of n_hyp * U1 queries against T' keys."""
+        if which not in self.dec:
+            raise _C.F5EError(f"PPG extractor: the state_dict has no {which} attention decoder")
+        W, dv, D, H = self.dec[which], self.device, self.dim, self.dec_heads
+        B, T2, _ = memory.shape
+        NB, U1 = ys_in.shape
+        if NB != B * n_hyp or ys_len.shape != (NB,) or H < 1 or D % H:
+            raise _C.F5EError(f"decode: ys_in [{B} * {n_hyp}, U1], ys_len [{B * n_hyp}], heads {H} dividing {D}")
+        R, scale = NB * U1, 1.0 / math.sqrt(D // H)
+        mem = memory.reshape(B * T2, D)
+        x = torch.empty(NB, U1, D, device=dv)
+        ops.text_gather(ys_in.contiguous(), W["embed"], self.pos_table(U1).contiguous(), None, x)
+        x = x.view(R, D)
+        hn, ctx, q = torch.empty(R, D, device=dv), torch.empty(R, D, device=dv), torch.empty(R, D, device=dv)
+        qkv, kv = torch.empty(R, 3 * D, device=dv), torch.empty(B * T2, 2 * D, device=dv)
+        units = W["layers"][0]["ff"][0].shape[0] if W["layers"] else D
+        mid = torch.empty(R, units, device=dv)
+        for L in W["layers"]:
+            ops.layernorm(x, hn, gamma=L["ln"][0][0], beta=L["ln"][0][1], eps=1e-5)
+            ops.gemm_f32(hn, *L["self_qkv"], out=qkv)
+            ops.mha_f32(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], H, scale, B=NB, kv_len=ys_len, causal=True, out=ctx)
+            ops.gemm_f32(ctx, *L["self_out"], out=x, addend=x)
+            ops.layernorm(x, hn, gamma=L["ln"][1][0], beta=L["ln"][1][1], eps=1e-5)
+            ops.gemm_f32(hn, *L["src_q"], out=q)
+            ops.gemm_f32(mem, *L["src_kv"], out=kv)
+            ops.mha_f32(q, kv[:, :D], kv[:, D:], H, scale, B=B, kv_len=mem_len, causal=False, out=ctx)
+            ops.gemm_f32(ctx, *L["src_out"], out=x, addend=x)
+            ops.layernorm(x, hn, gamma=L["ln"][2][0], beta=L["ln"][2][1], eps=1e-5)
+            ops.gemm_f32(hn, L["ff"][0], L["ff"][1], out=mid, act=ops.ACT_RELU)
+            ops.gemm_f32(mid, L["ff"][2], L["ff"][3], out=x, addend=x)
+        ops.layernorm(x, hn, gamma=W["after"][0], beta=W["after"][1], eps=1e-5)
+        logits = torch.empty(R, W["out"][0].shape[0], device=dv)
+        ops.gemm_f32(hn, *W["out"], out=logits)
+        return logits
 
     def pos_table(self, t: int, offset: int = 0) -> Tensor:
         """PositionalEncoding.pe[:, offset:offset + t] (embedding.py:34-46, 65-82), a constant table built in fp32 like the
@@ -724,9 +991,10 @@ class kaldiFbank(nn.Module):
         return out, torch.tensor([T])
 
 
-def build_ppg_model(ppg_model_path, ppg_config, device="cpu", ctc: bool = False):
+def build_ppg_model(ppg_model_path, ppg_config, device="cpu", ctc: bool = False, decoder: bool = False):
     """reference ppg/ppg_model.py:11-29: yaml -> model (cmvn path fallback next to the checkpoint) -> checkpoint keys that
-    exist in the model are loaded, the rest (decoder; the CTC head too unless ``ctc=True``) ignored."""
+    exist in the model are loaded, the rest (the attention decoder unless ``decoder=True``; the CTC head unless ``ctc=True``)
+    ignored."""
     import yaml
     with open(ppg_config, "r") as fin:
         ppg_configs = yaml.safe_load(fin)
@@ -734,7 +1002,7 @@ def build_ppg_model(ppg_model_path, ppg_config, device="cpu", ctc: bool = False)
         old = ppg_configs["cmvn_file"]
         ppg_configs["cmvn_file"] = os.path.join(os.path.dirname(ppg_model_path), "global_cmvn")
         print(f"{old} not exist, use {ppg_configs['cmvn_file']}")
-    model = ConformerPPG.from_config(ppg_configs, ctc=ctc)
+    model = ConformerPPG.from_config(ppg_configs, ctc=ctc, decoder=decoder)
     checkpoint = torch.load(ppg_model_path, map_location="cpu", weights_only=True)
     model_dict = model.state_dict()
     model_dict.update({k: v for k, v in checkpoint.items() if k in model_dict})

@@ -273,6 +273,42 @@ F5E_API int f5e_ctc_align(f5e_stream st, const float* scores, long long batch_st
 F5E_API int f5e_ctc_greedy(f5e_stream st, const float* scores, long long batch_stride, int ld, const int* t_len, int blank,
                    int pad_id, int* hyp, int* hyp_len, float* frame_logp, int B, int T, int V);
 
+/* CTC prefix beam search (csrc/ctc_beam.hip; reference ppg/asr_model.py:461-546, batched, on the device).  scores f32
+ * [B][T][V] in the layout of f5e_ctc_align, raw logits OR log-probabilities: every frame is normalised here as
+ * (x - max) - log1p(sum over the other classes of exp(x - max)), so both give the same lists and scores.  t_len: DEVICE
+ * int [B].  Per frame t < t_len: the first prune keeps the `beam` best classes of the frame; for every kept class s with
+ * log-probability ps and every beam prefix (pb, pnb):
+ *   s = blank:               prefix      pb  <- logaddexp(pb + ps, pnb + ps);
+ *   s = the prefix's last:   prefix      pnb <- pnb + ps,   and   prefix + (s)   pnb <- pb + ps;
+ *   otherwise:               prefix + (s)   pnb <- logaddexp(pb + ps, pnb + ps),
+ * contributions to one prefix being combined with logaddexp (fp32, log1p(exp(-|d|)) form); a prefix nothing contributed to
+ * is dropped.  The second prune keeps the `beam` best prefixes by logaddexp(pb, pnb).  The start is the empty prefix with
+ * (0, -inf).  Ties: among equal scores of a frame the lower class index comes first; among equal prefix totals the
+ * candidates are ordered "beam entries that keep their prefix, in beam order (best first), then the new prefixes by (rank of
+ * the parent entry, rank of the class in the frame's first prune)" -- a fixed order of this kernel; the reference's is its
+ * dict's insertion order.
+ * hyp i32 [B][beam][ld_hyp]: the prefixes, best first, padded with -1; a prefix longer than ld_hyp leaves its first ld_hyp
+ * tokens.  hyp_len i32 [B][beam]: the true lengths.  score f32 [B][beam] = logaddexp(pb, pnb).  t_len = 0 gives the empty
+ * prefix (length 0, score 0) in row 0; rows the search did not fill (those, and every row of a sequence with t_len outside
+ * [0, T]) are -1 / length -1 / -inf; the other sequences are untouched.  workspace: f5e_ctc_beam_workspace_bytes(B, T, beam)
+ * bytes (16 per sequence, frame and beam slot) of caller-owned scratch, 8-byte aligned, contents irrelevant.
+ * 1 <= beam <= 16, beam <= V, T <= 16384, B <= 65535.  No allocation, no synchronisation. */
+F5E_API int f5e_ctc_beam_workspace_bytes(int B, int T, int beam, unsigned long long* bytes_out_host);
+F5E_API int f5e_ctc_beam(f5e_stream st, const float* scores, long long batch_stride, int ld, const int* t_len, int blank,
+                 int beam, int* hyp, int ld_hyp, int* hyp_len, float* score, void* workspace,
+                 unsigned long long workspace_bytes, int B, int T, int V);
+
+/* out[r] = logits[r][target[r]] - logsumexp(logits[r][0..V)) for `rows` rows of row stride ld (fp32, max-subtracted), one wave
+ * per row: the terms of the reference's rescoring sum (ppg/asr_model.py:660-670) without the copy of [N, U, V]
+ * log-probabilities to the host.  target[r] < 0 gives 0 (a padded position), target[r] >= V gives NaN.  No allocation, no
+ * synchronisation. */
+F5E_API int f5e_token_logp(f5e_stream st, const float* logits, long long ld, const int* target, float* out, long long rows,
+                   int V);
+/* out[r][v] = x[r][v] - logsumexp(x[r][0..V)) (torch.log_softmax over the last axis; fp32, max-subtracted), one wave per row;
+ * row strides ldx, ldo >= V; out may be x.  No allocation, no synchronisation. */
+F5E_API int f5e_log_softmax_rows(f5e_stream st, const float* x, long long ldx, float* out, long long ldo, long long rows,
+                         int V);
+
 /* ---------------------------------------------------------------- mel / vocoder ------------------------------ */
 
 /* out[B][T][n_mels] = log(clamp(|STFT(wav)| . fb, 1e-5)), T = 1 + nw / hop, reflect-padded, centred (modules.py:75-101).
@@ -356,6 +392,17 @@ F5E_API int f5e_dwconv_stream(f5e_stream st, const float* x, const float* w_t, c
 F5E_API int f5e_relpos_attn(f5e_stream st, const float* qu, int ldq, const float* k, int ldk, const float* pos, int ldp,
                     const float* v, int ldv, float* out, int ldo, const int* kv_len, int B, int T, int H, int dk,
                     int q_begin, int chunk, int left_chunks, float scale);
+/* Plain masked attention with separate query and key counts (attention.py:79-111: the attention decoder's self- and source
+ * attention), exact fp32, one launch for all sequences, heads and 16-query tiles (the wave tile of f5e_relpos_attn):
+ *   out[b*Tq + i][h*dk + d] = sum_j softmax_j(scale * q[b*Tq + i][h*dk + :] . k[b*Tk + j][h*dk + :]) * v[b*Tk + j][h*dk + d]
+ * over the visible keys j of query i:  j < kv_len[b] (optional DEVICE int32 [B], clamped to [0, Tk]; null: Tk), and j <= i
+ * when causal != 0 (which needs Tq == Tk).  EVERY query row i < Tq is computed -- kv_len limits keys, not queries -- and a
+ * query with no visible key yields zeros (the reference's masked_fill(mask, 0.0) after its softmax).
+ *   q, out [B*Tq][>= H*dk];  k, v [B*Tk][>= H*dk];  each operand has its own row stride.
+ * Head dims dk = 16, 32, 64, 128; row strides of q, k and out multiples of 4 floats, q / k / out 16-byte aligned.  No
+ * allocation, no synchronisation. */
+F5E_API int f5e_mha_f32(f5e_stream st, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out,
+                int ldo, const int* kv_len, int B, int Tq, int Tk, int H, int dk, int causal, float scale);
 
 /* ---------------------------------------------------------------- fused DiT evaluation ----------------------- */
 

@@ -89,34 +89,16 @@ __global__ void glu_kernel(const float* x, int ldx, float* y, int ldy, size_t ro
   }
 }
 
-__global__ __launch_bounds__(256) void dwconv_kernel(const float* x, const float* wT, const float* bias, const float* keep,
-                                                      float* y, int B, int T, int C, int K) {
-  const int c4n = C / 4, pad = (K - 1) / 2;
-  const size_t total = (size_t)B * T * c4n;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
-    const int c = (int)(i % c4n) * 4;
-    const size_t bt = i / c4n;
-    const int t = (int)(bt % T);
-    const size_t b = bt / T;
-    f32x4 acc = *(const f32x4*)(bias + c);
-    for (int j = 0; j < K; ++j) {
-      const int tj = t + j - pad;
-      // keep (optional, [B][T] 0/1): the reference zeroes padded frames BEFORE the conv (convolution.py:100-101)
-      if (tj >= 0 && tj < T && (!keep || keep[b * T + tj] != 0.f))
-        acc += *(const f32x4*)(wT + (size_t)j * C + c) * *(const f32x4*)(x + (b * T + tj) * C + c);
-    }
-    *(f32x4*)(y + (b * T + t) * C + c) = acc;
-  }
-}
-
-// the two convolutions of the chunk-trained (streaming) conformer (convolution.py:81-134), y may not alias x:
-//   causal == 0: symmetric taps t + j - (K - 1) / 2 that stay inside t's chunk [c chunk, (c + 1) chunk) and the sequence:
-//                what the chunk-by-chunk loop computes when every chunk is convolved on its own with zero padding
+// the depthwise convolutions of the conformer (convolution.py:81-134), one loop over the taps j = 0 .. K - 1:
+//   causal == 0: symmetric taps t + j - (K - 1) / 2 that stay inside the sequence and, with chunk > 0, inside t's chunk
+//                [c chunk, (c + 1) chunk): what the chunk-by-chunk loop computes when every chunk is convolved on its own
+//                with zero padding.  keep (optional, [B][T] 0/1) drops the taps on padded frames: the reference zeroes
+//                them BEFORE the conv (convolution.py:100-101)
 //   causal != 0: taps t - (K - 1) .. t; positions before the sequence read fill[c] (GLU(pointwise_conv1.bias): the
 //                reference pads zeros BEFORE pointwise_conv1), or 0 without fill
-__global__ __launch_bounds__(256) void dwconv_stream_kernel(const float* x, const float* wT, const float* bias,
-                                                             const float* fill, float* y, int B, int T, int C, int K,
-                                                             int causal, int chunk) {
+__global__ __launch_bounds__(256) void dwconv_kernel(const float* x, const float* wT, const float* bias, const float* keep,
+                                                      const float* fill, float* y, int B, int T, int C, int K, int causal,
+                                                      int chunk) {
   const int c4n = C / 4, pad = causal ? K - 1 : (K - 1) / 2;
   const size_t total = (size_t)B * T * c4n;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
@@ -132,10 +114,12 @@ __global__ __launch_bounds__(256) void dwconv_stream_kernel(const float* x, cons
     f32x4 acc = *(const f32x4*)(bias + c);
     for (int j = 0; j < K; ++j) {
       const int tj = t + j - pad;
-      if (tj >= lo && tj < hi)
-        acc += *(const f32x4*)(wT + (size_t)j * C + c) * *(const f32x4*)(x + (b * T + tj) * C + c);
-      else if (causal && fill && tj < 0)
+      if (tj >= lo && tj < hi) {
+        if (!keep || keep[b * T + tj] != 0.f)
+          acc += *(const f32x4*)(wT + (size_t)j * C + c) * *(const f32x4*)(x + (b * T + tj) * C + c);
+      } else if (causal && fill && tj < 0) {
         acc += *(const f32x4*)(wT + (size_t)j * C + c) * *(const f32x4*)(fill + c);
+      }
     }
     *(f32x4*)(y + (b * T + t) * C + c) = acc;
   }
@@ -194,8 +178,8 @@ int f5e_dwconv(hipStream_t st, const float* x, const float* w_t, const float* bi
                int T, int C, int K) {
   F5E_REQUIRE(x && w_t && bias && y, "dwconv: null operand");
   F5E_REQUIRE(B > 0 && T > 0 && C > 0 && C % 4 == 0 && K > 0 && K <= 31 && (K & 1), "dwconv: C %% 4 == 0 and odd K <= 31");
-  hipLaunchKernelGGL(dwconv_kernel, dim3(grid_for((size_t)B * T * C / 4)), dim3(256), 0, st, x, w_t, bias, keep, y, B, T,
-                     C, K);
+  hipLaunchKernelGGL(dwconv_kernel, dim3(grid_for((size_t)B * T * C / 4)), dim3(256), 0, st, x, w_t, bias, keep,
+                     nullptr, y, B, T, C, K, 0, 0);
   F5E_LAUNCH_CHECK("dwconv");
   return F5E_OK;
 }
@@ -205,8 +189,8 @@ int f5e_dwconv_stream(hipStream_t st, const float* x, const float* w_t, const fl
   F5E_REQUIRE(x && w_t && bias && y && x != y, "dwconv_stream: null operand or y aliases x");
   F5E_REQUIRE(B > 0 && T > 0 && C > 0 && C % 4 == 0 && K > 0 && K <= 31 && (causal || (K & 1)),
               "dwconv_stream: C %% 4 == 0, K <= 31, and odd K unless causal");
-  hipLaunchKernelGGL(dwconv_stream_kernel, dim3(grid_for((size_t)B * T * C / 4)), dim3(256), 0, st, x, w_t, bias, fill, y,
-                     B, T, C, K, causal, chunk);
+  hipLaunchKernelGGL(dwconv_kernel, dim3(grid_for((size_t)B * T * C / 4)), dim3(256), 0, st, x, w_t, bias, nullptr, fill,
+                     y, B, T, C, K, causal, chunk);
   F5E_LAUNCH_CHECK("dwconv_stream");
   return F5E_OK;
 }

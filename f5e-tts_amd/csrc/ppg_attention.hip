@@ -19,39 +19,55 @@
 
 namespace {
 
-struct RelposArgs {
-  const float *qu, *k, *pos, *v;
+// One argument block for both entry points.  f5e_relpos_attn: Tq == Tk == T, pos and D (= H dk, the offset of the q + v half
+// of a qu row) set, causal unused.  f5e_mha_f32: pos / D / chunk / left unused, q_begin 0.
+struct AttnArgs {
+  const float *q, *k, *pos, *v;
   float* out;
   const int* kv_len;
   int ldq, ldk, ldp, ldv, ldo;
-  int T, D, q_begin, chunk, left;
+  int Tq, Tk, D, q_begin, chunk, left, causal;
   float scale;
 };
 
-template <int DK>
-__global__ __launch_bounds__(64) void relpos_attn_kernel(RelposArgs a) {
+// The wave tile.  RELPOS: the second score product (q + v) . p, the chunk band, and a query at or beyond the key length
+// yields zeros.  Otherwise (f5e_mha_f32, the attention decoder's self- and source attention, attention.py:79-111): the band
+// of query i is [0, min(i + 1, len)) when causal and [0, len) otherwise, so a query below the key length is NOT required:
+// every query row is computed, and one with no visible key yields zeros (the reference's masked_fill after the softmax).
+template <int DK, bool RELPOS>
+__global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
   constexpr int NB = DK / 16;
   const int lane = threadIdx.x, c16 = lane & 15, g = lane >> 4;
   const int q0 = a.q_begin + blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
-  const int len = a.kv_len ? min(max(a.kv_len[b], 0), a.T) : a.T;
-  const size_t row0 = (size_t)b * a.T;
+  const int len = a.kv_len ? min(max(a.kv_len[b], 0), a.Tk) : a.Tk;
+  const size_t rowq = (size_t)b * a.Tq, rowk = (size_t)b * a.Tk;
   const int hc = hd * DK;
-  // band of local row r: [lo(r), hi(r)); both are monotonic in r, so the tile's union is [lo(first row), hi(last row))
-  auto band_lo = [&](int r) { return (a.chunk <= 0 || a.left < 0) ? 0 : max(0, (r / a.chunk - a.left) * a.chunk); };
-  auto band_hi = [&](int r) { return a.chunk <= 0 ? len : min((r / a.chunk + 1) * a.chunk, len); };
-  const int q_last = min(q0 + 15, a.T - 1);
-  const int qr = min(q0 + c16, a.T - 1);                 // this lane's query row (clamped: loads stay in bounds)
-  const bool q_ok = q0 + c16 < a.T && q0 + c16 < len;
-  const int lo_q = band_lo(qr), hi_q = q_ok ? band_hi(qr) : 0;
-  const int t_lo = band_lo(q0) & ~15, t_hi = q0 < len ? band_hi(q_last) : 0;
+  const int q_last = min(q0 + 15, a.Tq - 1);
+  const int qr = min(q0 + c16, a.Tq - 1);                 // this lane's query row (clamped: loads stay in bounds)
+  const bool q_in = q0 + c16 < a.Tq;
+  // band of this lane's row: keys [lo_q, hi_q); of the tile (the union of its rows' bands, 16-aligned): [t_lo, t_hi)
+  bool q_ok;
+  int lo_q, hi_q, t_lo, t_hi;
+  if constexpr (RELPOS) {
+    // band of local row r: [lo(r), hi(r)); both are monotonic in r, so the tile's union is [lo(first row), hi(last row))
+    auto band_lo = [&](int r) { return (a.chunk <= 0 || a.left < 0) ? 0 : max(0, (r / a.chunk - a.left) * a.chunk); };
+    auto band_hi = [&](int r) { return a.chunk <= 0 ? len : min((r / a.chunk + 1) * a.chunk, len); };
+    q_ok = q_in && q0 + c16 < len;
+    lo_q = band_lo(qr), hi_q = q_ok ? band_hi(qr) : 0;
+    t_lo = band_lo(q0) & ~15, t_hi = q0 < len ? band_hi(q_last) : 0;
+  } else {
+    q_ok = q_in;
+    lo_q = 0, hi_q = q_ok ? (a.causal ? min(qr + 1, len) : len) : 0;
+    t_lo = 0, t_hi = a.causal ? min(q_last + 1, len) : len;
+  }
 
-  f32x4 qa[NB], qb[NB];
+  f32x4 qa[NB], qb[RELPOS ? NB : 1];
   {
-    const float* qp = a.qu + (row0 + qr) * a.ldq + hc + 4 * g;
+    const float* qp = a.q + (rowq + qr) * a.ldq + hc + 4 * g;
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
       qa[j] = *(const f32x4*)(qp + 16 * j);
-      qb[j] = *(const f32x4*)(qp + a.D + 16 * j);
+      if constexpr (RELPOS) qb[j] = *(const f32x4*)(qp + a.D + 16 * j);
     }
   }
   f32x4 acc[NB];
@@ -61,111 +77,27 @@ __global__ __launch_bounds__(64) void relpos_attn_kernel(RelposArgs a) {
 
   for (int kt = t_lo; kt < t_hi; kt += 16) {
     const int kr = min(kt + c16, len - 1);               // key row of the score product's A operand (len > 0 here)
-    const float* kp = a.k + (row0 + kr) * a.ldk + hc + 4 * g;
-    const float* pp = a.pos + (size_t)kr * a.ldp + hc + 4 * g;
+    const float* kp = a.k + (rowk + kr) * a.ldk + hc + 4 * g;
+    const float* pp = RELPOS ? a.pos + (size_t)kr * a.ldp + hc + 4 * g : nullptr;
     f32x4 s0 = {0.f, 0.f, 0.f, 0.f}, s1 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-      const f32x4 kf = *(const f32x4*)(kp + 16 * j), pf = *(const f32x4*)(pp + 16 * j);
+      const f32x4 kf = *(const f32x4*)(kp + 16 * j);
+      f32x4 pf = {0.f, 0.f, 0.f, 0.f};
+      if constexpr (RELPOS) pf = *(const f32x4*)(pp + 16 * j);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[r], qa[j][r], s0, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(pf[r], qb[j][r], s1, 0, 0, 0);
+        if constexpr (RELPOS) s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(pf[r], qb[j][r], s1, 0, 0, 0);
       }
     }
     float p[4], mx = -INFINITY;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int key = kt + 4 * g + r;
-      p[r] = (key >= lo_q && key < hi_q) ? (s0[r] + s1[r]) * a.scale : -INFINITY;
-      mx = fmaxf(mx, p[r]);
-    }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    const float m_new = fmaxf(m_run, mx);
-    const float m_use = m_new == -INFINITY ? 0.f : m_new;     // a row with nothing visible yet: exp(-inf - 0) = 0
-    const float alpha = __expf(m_run - m_use);
-    float sum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p[r] = __expf(p[r] - m_use);
-      sum += p[r];
-    }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
-    l_run = l_run * alpha + sum;
-    m_run = m_new;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) acc[j] *= alpha;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int vr = min(kt + 4 * g + r, len - 1);
-      const float* vp = a.v + (row0 + vr) * a.ldv + hc + c16;
-#pragma unroll
-      for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[16 * j], p[r], acc[j], 0, 0, 0);
-    }
-  }
-  if (q0 + c16 < a.T) {
-    const float inv = (q_ok && l_run > 0.f) ? 1.0f / l_run : 0.f;   // rows at or beyond the key length: zeros
-    float* op = a.out + (row0 + q0 + c16) * a.ldo + hc + 4 * g;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) *(f32x4*)(op + 16 * j) = acc[j] * inv;
-  }
-}
-
-// ---- f5e_mha_f32: plain masked attention with its own query and key counts (the attention decoder's self- and source
-// attention, ppg/wenet/transformer/attention.py:79-111).  The wave tile of relpos_attn_kernel without the position term; the
-// band of query i is [0, min(i + 1, len)) when causal and [0, len) otherwise, so a query below the key length is NOT
-// required: every query row is computed, and one with no visible key yields zeros (the reference's masked_fill after the
-// softmax).
-struct MhaArgs {
-  const float *q, *k, *v;
-  float* out;
-  const int* kv_len;
-  int ldq, ldk, ldv, ldo;
-  int Tq, Tk, causal;
-  float scale;
-};
-
-template <int DK>
-__global__ __launch_bounds__(64) void mha_f32_kernel(MhaArgs a) {
-  constexpr int NB = DK / 16;
-  const int lane = threadIdx.x, c16 = lane & 15, g = lane >> 4;
-  const int q0 = blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
-  const int len = a.kv_len ? min(max(a.kv_len[b], 0), a.Tk) : a.Tk;
-  const size_t rowq = (size_t)b * a.Tq, rowk = (size_t)b * a.Tk;
-  const int hc = hd * DK;
-  const int q_last = min(q0 + 15, a.Tq - 1);
-  const int qr = min(q0 + c16, a.Tq - 1);                 // this lane's query row (clamped: loads stay in bounds)
-  const bool q_ok = q0 + c16 < a.Tq;
-  const int hi_q = q_ok ? (a.causal ? min(qr + 1, len) : len) : 0;
-  const int t_hi = a.causal ? min(q_last + 1, len) : len;
-
-  f32x4 qa[NB];
-  {
-    const float* qp = a.q + (rowq + qr) * a.ldq + hc + 4 * g;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) qa[j] = *(const f32x4*)(qp + 16 * j);
-  }
-  f32x4 acc[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float m_run = -INFINITY, l_run = 0.f;
-
-  for (int kt = 0; kt < t_hi; kt += 16) {
-    const int kr = min(kt + c16, len - 1);               // key row of the score product's A operand (len > 0 here)
-    const float* kp = a.k + (rowk + kr) * a.ldk + hc + 4 * g;
-    f32x4 s0 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      const f32x4 kf = *(const f32x4*)(kp + 16 * j);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf[r], qa[j][r], s0, 0, 0, 0);
-    }
-    float p[4], mx = -INFINITY;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      p[r] = kt + 4 * g + r < hi_q ? s0[r] * a.scale : -INFINITY;
+      const bool seen = key >= lo_q && key < hi_q;
+      if constexpr (RELPOS) p[r] = seen ? (s0[r] + s1[r]) * a.scale : -INFINITY;
+      else p[r] = seen ? s0[r] * a.scale : -INFINITY;
       mx = fmaxf(mx, p[r]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -193,11 +125,22 @@ __global__ __launch_bounds__(64) void mha_f32_kernel(MhaArgs a) {
       for (int j = 0; j < NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vp[16 * j], p[r], acc[j], 0, 0, 0);
     }
   }
-  if (q_ok) {
-    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;   // no visible key: zeros
+  if (q_in) {
+    const float inv = (q_ok && l_run > 0.f) ? 1.0f / l_run : 0.f;   // no visible key (RELPOS: or a row beyond the keys): zeros
     float* op = a.out + (rowq + q0 + c16) * a.ldo + hc + 4 * g;
 #pragma unroll
     for (int j = 0; j < NB; ++j) *(f32x4*)(op + 16 * j) = acc[j] * inv;
+  }
+}
+
+template <bool RELPOS>
+void launch_attn(hipStream_t st, const AttnArgs& a, int H, int B, int dk) {
+  const dim3 grid((unsigned)((a.Tq - a.q_begin + 15) / 16), (unsigned)H, (unsigned)B);
+  switch (dk) {
+    case 16: hipLaunchKernelGGL((attn_f32_kernel<16, RELPOS>), grid, dim3(64), 0, st, a); break;
+    case 32: hipLaunchKernelGGL((attn_f32_kernel<32, RELPOS>), grid, dim3(64), 0, st, a); break;
+    case 64: hipLaunchKernelGGL((attn_f32_kernel<64, RELPOS>), grid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL((attn_f32_kernel<128, RELPOS>), grid, dim3(64), 0, st, a); break;
   }
 }
 
@@ -217,14 +160,8 @@ extern "C" int f5e_relpos_attn(hipStream_t st, const float* qu, int ldq, const f
               "relpos_attn: row strides must cover the heads (qu: 2 H dk) and be multiples of 4 floats");
   F5E_REQUIRE((((uintptr_t)qu | (uintptr_t)k | (uintptr_t)pos | (uintptr_t)out) & 15) == 0,
               "relpos_attn: qu, k, pos and out must be 16-byte aligned");
-  RelposArgs a{qu, k, pos, v, out, kv_len, ldq, ldk, ldp, ldv, ldo, T, (int)D, q_begin, chunk, left_chunks, scale};
-  const dim3 grid((unsigned)((T - q_begin + 15) / 16), (unsigned)H, (unsigned)B);
-  switch (dk) {
-    case 16: hipLaunchKernelGGL(relpos_attn_kernel<16>, grid, dim3(64), 0, st, a); break;
-    case 32: hipLaunchKernelGGL(relpos_attn_kernel<32>, grid, dim3(64), 0, st, a); break;
-    case 64: hipLaunchKernelGGL(relpos_attn_kernel<64>, grid, dim3(64), 0, st, a); break;
-    default: hipLaunchKernelGGL(relpos_attn_kernel<128>, grid, dim3(64), 0, st, a); break;
-  }
+  const AttnArgs a{qu, k, pos, v, out, kv_len, ldq, ldk, ldp, ldv, ldo, T, T, (int)D, q_begin, chunk, left_chunks, 0, scale};
+  launch_attn<true>(st, a, H, B, dk);
   F5E_LAUNCH_CHECK("relpos_attn");
   return F5E_OK;
 }
@@ -240,14 +177,8 @@ extern "C" int f5e_mha_f32(hipStream_t st, const float* q, int ldq, const float*
   F5E_REQUIRE(ldq >= D && ldk >= D && ldv >= D && ldo >= D && ldq % 4 == 0 && ldk % 4 == 0 && ldo % 4 == 0,
               "mha_f32: row strides must cover the heads (H dk) and those of q, k and out be multiples of 4 floats");
   F5E_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)out) & 15) == 0, "mha_f32: q, k and out must be 16-byte aligned");
-  MhaArgs a{q, k, v, out, kv_len, ldq, ldk, ldv, ldo, Tq, Tk, causal ? 1 : 0, scale};
-  const dim3 grid((unsigned)((Tq + 15) / 16), (unsigned)H, (unsigned)B);
-  switch (dk) {
-    case 16: hipLaunchKernelGGL(mha_f32_kernel<16>, grid, dim3(64), 0, st, a); break;
-    case 32: hipLaunchKernelGGL(mha_f32_kernel<32>, grid, dim3(64), 0, st, a); break;
-    case 64: hipLaunchKernelGGL(mha_f32_kernel<64>, grid, dim3(64), 0, st, a); break;
-    default: hipLaunchKernelGGL(mha_f32_kernel<128>, grid, dim3(64), 0, st, a); break;
-  }
+  const AttnArgs a{q, k, nullptr, v, out, kv_len, ldq, ldk, 0, ldv, ldo, Tq, Tk, 0, 0, 0, -1, causal ? 1 : 0, scale};
+  launch_attn<false>(st, a, H, B, dk);
   F5E_LAUNCH_CHECK("mha_f32");
   return F5E_OK;
 }

@@ -21,6 +21,8 @@ from __future__ import annotations
 import json
 import math
 import os
+from functools import partial
+from types import SimpleNamespace
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 import numpy as np
@@ -519,6 +521,18 @@ class ConformerPPG(nn.Module):
                                            conformer_cnn_cache)
 
 
+def _ln(x: Tensor, out: Tensor, pair: Tuple[Tensor, Tensor]) -> Tensor:
+    """nn.LayerNorm(eps=1e-5) with ``pair`` = (weight, bias); out may be x."""
+    return ops.layernorm(x, out, gamma=pair[0], beta=pair[1], eps=1e-5)
+
+
+def mask_rows(x: Tensor, keep: Tensor, out: Tensor, eye: Optional[Tensor] = None) -> Tensor:
+    """out = x [rows, d] with the rows whose ``keep`` [rows] is 0 zeroed.  row_scale acts on a GEMM's output side, hence the
+    identity GEMM; ``eye``: the [d, d] identity when the caller keeps one."""
+    eye = torch.eye(x.shape[1], device=x.device) if eye is None else eye
+    return ops.gemm_f32(x, eye, None, out=out, row_scale=keep)
+
+
 class ConformerEngine:
     """Repacked fp32 weights + the launch sequence of ``BaseEncoder.forward`` (wenet/transformer/encoder.py:141-209)."""
 
@@ -593,6 +607,7 @@ class ConformerEngine:
         if "ctc.ctc_lo.weight" in sd:
             self.ctc_w, self.ctc_b = f("ctc.ctc_lo.weight"), f("ctc.ctc_lo.bias")
         self.half = torch.full((max(D, 1),), 0.5, device=dv)
+        self.eye = torch.eye(D, device=dv)                  # mask_rows of a ragged batch
         self.dk = dk
         # attention decoder(s): decoder.* (transformer) or decoder.left_decoder.* / right_decoder.* (bitransformer)
         self.dec, self.dec_heads = {}, int(decoder_heads)
@@ -642,19 +657,19 @@ class ConformerEngine:
         units = W["layers"][0]["ff"][0].shape[0] if W["layers"] else D
         mid = torch.empty(R, units, device=dv)
         for L in W["layers"]:
-            ops.layernorm(x, hn, gamma=L["ln"][0][0], beta=L["ln"][0][1], eps=1e-5)
+            _ln(x, hn, L["ln"][0])
             ops.gemm_f32(hn, *L["self_qkv"], out=qkv)
             ops.mha_f32(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], H, scale, B=NB, kv_len=ys_len, causal=True, out=ctx)
             ops.gemm_f32(ctx, *L["self_out"], out=x, addend=x)
-            ops.layernorm(x, hn, gamma=L["ln"][1][0], beta=L["ln"][1][1], eps=1e-5)
+            _ln(x, hn, L["ln"][1])
             ops.gemm_f32(hn, *L["src_q"], out=q)
             ops.gemm_f32(mem, *L["src_kv"], out=kv)
             ops.mha_f32(q, kv[:, :D], kv[:, D:], H, scale, B=B, kv_len=mem_len, causal=False, out=ctx)
             ops.gemm_f32(ctx, *L["src_out"], out=x, addend=x)
-            ops.layernorm(x, hn, gamma=L["ln"][2][0], beta=L["ln"][2][1], eps=1e-5)
+            _ln(x, hn, L["ln"][2])
             ops.gemm_f32(hn, L["ff"][0], L["ff"][1], out=mid, act=ops.ACT_RELU)
             ops.gemm_f32(mid, L["ff"][2], L["ff"][3], out=x, addend=x)
-        ops.layernorm(x, hn, gamma=W["after"][0], beta=W["after"][1], eps=1e-5)
+        _ln(x, hn, W["after"])
         logits = torch.empty(R, W["out"][0].shape[0], device=dv)
         ops.gemm_f32(hn, *W["out"], out=logits)
         return logits
@@ -698,185 +713,162 @@ class ConformerEngine:
 
     def _encode(self, feats: Tensor, lens: Tensor) -> Tuple[Tensor, Tensor]:
         """``encode`` with the frame counts left on the host, where they are computed (``forward`` does not need them)."""
-        dv, D, H, dk = self.device, self.dim, self.heads, self.dk
-        B, T, idim = feats.shape
-        if idim != self.idim:
-            raise _C.F5EError(f"PPG extractor: features have {idim} bins, the model expects {self.idim}")
-        if T < 3:
-            raise _C.F5EError("PPG extractor: needs at least 3 feature frames")
-        x = feats.to(dv, F32).contiguous()
-        T2 = (T - 3) // 2 + 1
+        dv, D = self.device, self.dim
+        B, T, _ = feats.shape
+        xs = self._subsample(feats.to(dv, F32).contiguous())
+        T2 = xs.shape[0] // B
         lens_h = lens.detach().to("cpu", torch.long)
         len2 = torch.tensor([int(((torch.arange(0, T - 2, 2)) < int(n)).sum()) for n in lens_h], dtype=I32)  # mask[:, :, :-2:2]
-        M = B * T2
-        # --- Conv2dSubsampling2 (+ folded CMVN): patches of 3 frames at stride 2 -> ReLU(Toeplitz GEMM) -> Linear
-        col = torch.empty(B, T, self.sub_k, device=dv)
-        ops.im2col(x, col, 3, 0)
-        patches = col.view(B * T, self.sub_k)
-        h = torch.empty(M, self.sub_w.shape[0], device=dv)
-        for b in range(B):
-            ops.gemm_f32(patches[b * T:(b + 1) * T:2], self.sub_w, self.sub_b, out=h[b * T2:(b + 1) * T2], M=T2,
-                         act=ops.ACT_RELU)
-        xs = torch.empty(M, D, device=dv)
-        ops.gemm_f32(h, self.out_w, self.out_b, out=xs)
-        ops.axpby(xs, None, xs, self.xscale, 0.0, 0.0)                         # RelPositionalEncoding: x * sqrt(d)
         pos = self.pos_table(T2)
         # masks whenever ANY item is shorter than the padded length (reference BaseEncoder always builds them from xs_lens,
         # ppg/wenet/transformer/encoder.py: also for a single padded utterance); all-full batches need none
-        ragged = bool(int(len2.min()) < T2)
-        kv_len = len2.to(dv) if ragged else None
-        keep = None
-        if ragged:
-            keep = (torch.arange(T2)[None, :] < len2[:, None].long()).to(F32).to(dv).contiguous()      # mask_pad
-        keep_flat = keep.view(-1) if keep is not None else None
-        Tp = (T2 + 3) // 4 * 4
-        hn = torch.empty(M, D, device=dv)
-        hm = torch.empty(M, D, device=dv) if ragged else None
-        units = self.layers[0]["ffm"][0].shape[0] if self.layers else D
-        mid = torch.empty(M, units, device=dv)
-        qu = torch.empty(M, 2 * D, device=dv)
-        kb = torch.empty(M, D, device=dv)
-        pb = torch.empty(T2, D, device=dv)
-        vt = torch.zeros(D, Tp, device=dv)
-        sc = torch.empty(T2, Tp, device=dv)
-        pr = torch.empty(T2, Tp, device=dv)
-        ctx = torch.empty(M, D, device=dv)
-        pw = torch.empty(M, 2 * D, device=dv)
-        gl = torch.empty(B, T2, D, device=dv)
-        dwo = torch.empty(B, T2, D, device=dv)
-        scale = 1.0 / math.sqrt(dk)
+        kv_len = keep = None
+        if int(len2.min()) < T2:
+            kv_len = len2.to(dv)
+            keep = (torch.arange(T2)[None, :] < len2[:, None].long()).to(F32).to(dv).reshape(-1).contiguous()      # mask_pad
+        S = self._scratch(B, B * T2, pos, masked=keep is not None)
+        attn = partial(self._full_attn, B=B, T=T2, kv_len=kv_len, ws=self._full_attn_scratch(T2))
+        conv = partial(self._conv_one_pass, chunk=0)
         for L in self.layers:
-            ln = L["ln"]
-            # macaron feed-forward: x += 0.5 * W2 swish(W1 LN(x))
-            ops.layernorm(xs, hn, gamma=ln["norm_ff_macaron"][0], beta=ln["norm_ff_macaron"][1], eps=1e-5)
-            ops.gemm_f32(hn, L["ffm"][0], L["ffm"][1], out=mid, act=ops.ACT_SILU)
-            ops.gemm_f32(mid, L["ffm"][2], L["ffm"][3], out=xs, ch_scale=self.half[:D], addend=xs)
-            # relative-position self-attention (attention.py:172-222), one sequence and head at a time on the fp32 GEMM
-            ops.layernorm(xs, hn, gamma=ln["norm_mha"][0], beta=ln["norm_mha"][1], eps=1e-5)
-            ops.gemm_f32(hn, L["wq2"], L["bq2"], out=qu)
-            ops.gemm_f32(hn, L["wk"], L["bk"], out=kb)
-            ops.gemm_f32(pos, L["wp"], None, out=pb)
-            for b in range(B):
-                r0, r1 = b * T2, (b + 1) * T2
-                # V^T [D, T2] = Wv . LN(x)^T (bias added after P.V: softmax rows sum to one)
-                ops.gemm_f32(L["wv"], hn[r0:r1], None, out=vt[:, :T2])
-                for hd in range(H):
-                    c0, c1 = hd * dk, (hd + 1) * dk
-                    ops.gemm_f32(qu[r0:r1, c0:c1], kb[r0:r1, c0:c1], None, out=sc[:, :T2])               # (q + u) k^T
-                    ops.gemm_f32(qu[r0:r1, D + c0:D + c1], pb[:, c0:c1], None, out=sc[:, :T2], addend=sc[:, :T2])  # + (q + v) p^T
-                    ops.softmax_rows(sc, pr, T2, scale, kv_len=kv_len[b:b + 1] if kv_len is not None else None,
-                                     rows_per_seq=T2)
-                    ops.gemm_f32(pr, vt[c0:c1], L["bv"][c0:c1], out=ctx[r0:r1, c0:c1], K=Tp)
-            ops.gemm_f32(ctx, L["wo"], L["bo"], out=xs, addend=xs)
-            # convolution module (convolution.py:84-133): mask, pointwise -> GLU -> depthwise (+BN) -> swish -> pointwise, mask
-            ops.layernorm(xs, hn, gamma=ln["norm_conv"][0], beta=ln["norm_conv"][1], eps=1e-5)
-            if keep_flat is not None:
-                # the reference zeroes padded frames BEFORE pointwise_conv1 (whose bias then makes them non-zero again for the
-                # depthwise conv's neighbours): mask LN(x) first (row_scale acts on the output side, hence the identity GEMM)
-                ops.gemm_f32(hn, self._eye(D), None, out=hm, row_scale=keep_flat)
-                ops.gemm_f32(hm, L["pw1"], L["pb1"], out=pw)
-            else:
-                ops.gemm_f32(hn, L["pw1"], L["pb1"], out=pw)
-            ops.glu(pw, gl.view(M, D))
-            if self.causal:
-                ops.dwconv_stream(gl, L["dw"], L["db"], dwo, causal=True, fill=L["fill"])
-            else:
-                ops.dwconv(gl, L["dw"], L["db"], dwo)
-            ops.gemm_f32(dwo.view(M, D), L["pw2"], L["pb2"], out=hn, a_act=ops.ACT_SILU, row_scale=keep_flat)
-            ops.axpby(xs, hn, xs, 1.0, 1.0)
-            # feed-forward + final norm
-            ops.layernorm(xs, hn, gamma=ln["norm_ff"][0], beta=ln["norm_ff"][1], eps=1e-5)
-            ops.gemm_f32(hn, L["ff"][0], L["ff"][1], out=mid, act=ops.ACT_SILU)
-            ops.gemm_f32(mid, L["ff"][2], L["ff"][3], out=xs, ch_scale=self.half[:D], addend=xs)
-            ops.layernorm(xs, xs, gamma=ln["norm_final"][0], beta=ln["norm_final"][1], eps=1e-5)
-        ops.layernorm(xs, hn, gamma=self.after[0], beta=self.after[1], eps=1e-5)
-        return hn.view(B, T2, D), len2
+            self._layer(L, xs, S, attn=attn, conv=conv, keep=keep)
+        return _ln(xs, S.hn, self.after).view(B, T2, D), len2
 
-    def _eye(self, d: int) -> Tensor:
-        if getattr(self, "_eye_t", None) is None or self._eye_t.shape[0] != d:
-            self._eye_t = torch.eye(d, device=self.device)
-        return self._eye_t
-
-    # ---- chunk-by-chunk (streaming) mode: BaseEncoder.forward_chunk / forward_chunk_by_chunk (encoder.py:210-355)
+    # ---- the conformer layer (encoder_layer.py:199-268), written once.  Full context (BaseEncoder.forward) and the chunk-by-
+    # chunk modes (BaseEncoder.forward_chunk / forward_chunk_by_chunk, encoder.py:210-355) differ in three steps, which the
+    # caller picks: the context product, what the depthwise convolution sees left of the rows, and the pad mask.
     #
-    # The reference feeds overlapping windows of 2 chunk + 1 feature frames at stride 2 chunk through forward_chunk, which
-    # keeps the last chunk * left_chunks rows of every layer's output as keys / values for the next window and convolves
-    # each chunk on its own.  Everything in a layer is row-wise except (a) the attention, where a query of chunk
+    # The reference's streaming loop feeds overlapping windows of 2 chunk + 1 feature frames at stride 2 chunk through
+    # forward_chunk, which keeps the last chunk * left_chunks rows of every layer's output as keys / values for the next window
+    # and convolves each chunk on its own.  Everything in a layer is row-wise except (a) the attention, where a query of chunk
     # c = t // chunk therefore sees keys [max(0, (c - left) chunk), (c + 1) chunk), the position term indexed by the key's
     # absolute position, and (b) the depthwise convolution: causal with kernel - 1 frames of carried left context, or, not
     # causal, zero-padded inside each chunk.  forward_chunk_by_chunk is that as ONE pass (one attention launch per layer
     # whatever the number of chunks); forward_chunk runs the same kernels on [cached rows ; new rows].
 
     def _subsample(self, x: Tensor) -> Tensor:
-        """Conv2dSubsampling2 + xscale of one utterance [1, T, idim] -> [T', D] (as in ``forward``)."""
-        _, T, idim = x.shape
+        """Conv2dSubsampling2 (+ folded CMVN) + xscale of [B, T, idim] -> [B * T', D]: patches of 3 frames at stride 2 ->
+        ReLU(Toeplitz GEMM), one strided GEMM per item -> Linear -> x * sqrt(d) (RelPositionalEncoding)."""
+        B, T, idim = x.shape
         if idim != self.idim:
             raise _C.F5EError(f"PPG extractor: features have {idim} bins, the model expects {self.idim}")
         if T < 3:
             raise _C.F5EError("PPG extractor: needs at least 3 feature frames")
         dv, T2 = self.device, (T - 3) // 2 + 1
-        col = torch.empty(1, T, self.sub_k, device=dv)
+        col = torch.empty(B, T, self.sub_k, device=dv)
         ops.im2col(x, col, 3, 0)
-        h = torch.empty(T2, self.sub_w.shape[0], device=dv)
-        ops.gemm_f32(col.view(T, self.sub_k)[0:T:2], self.sub_w, self.sub_b, out=h, M=T2, act=ops.ACT_RELU)
-        xs = torch.empty(T2, self.dim, device=dv)
+        patches = col.view(B * T, self.sub_k)
+        h = torch.empty(B * T2, self.sub_w.shape[0], device=dv)
+        for b in range(B):
+            ops.gemm_f32(patches[b * T:(b + 1) * T:2], self.sub_w, self.sub_b, out=h[b * T2:(b + 1) * T2], M=T2,
+                         act=ops.ACT_RELU)
+        xs = torch.empty(B * T2, self.dim, device=dv)
         ops.gemm_f32(h, self.out_w, self.out_b, out=xs)
         ops.axpby(xs, None, xs, self.xscale, 0.0, 0.0)
         return xs
 
-    def _stream_layer(self, L: dict, x: Tensor, q0: int, pos: Tensor, chunk: int, left: int,
-                      cnn_cache: Optional[Tensor], one_pass: bool) -> Tuple[Tensor, Optional[Tensor]]:
-        """One conformer layer over x [R, D] (updated in place): rows < q0 are cached rows that only serve as keys / values
-        (encoder_layer.py:220-231), rows >= q0 are computed.  one_pass: q0 = 0, the band (chunk, left) and the conv's chunk
-        isolation / left fill apply.  Otherwise every cached key is visible and the conv runs on the new rows behind
-        ``cnn_cache`` [1, D, K - 1] (causal) or on their own.  -> (the new rows' output, a view of x; new conv cache)."""
-        dv, D, H = self.device, self.dim, self.heads
-        R, n = x.shape[0], x.shape[0] - q0
-        ln = L["ln"]
-        hn = torch.empty(R, D, device=dv)
-        mid = torch.empty(R, L["ffm"][0].shape[0], device=dv)
-        ops.layernorm(x, hn, gamma=ln["norm_ff_macaron"][0], beta=ln["norm_ff_macaron"][1], eps=1e-5)
+    def _scratch(self, B: int, R: int, pos: Tensor, q0: int = 0, left: int = 0, masked: bool = False) -> SimpleNamespace:
+        """The buffers of ``_layer`` for x of R rows (B sequences) whose rows from q0 on are computed: allocated and cut
+        into the views the layer uses ONCE per call.  pos: the position table of the call; left: rows of carried context in
+        front of the computed rows in the conv module; masked: a pad mask will be applied."""
+        D, n = self.dim, R - q0
+        c = n + left
+        units = self.layers[0]["ffm"][0].shape[0] if self.layers else D
+        e = lambda r, w: torch.empty(r, w, device=self.device)   # noqa: E731
+        hn, mid, ctx, gl, dwo = e(R, D), e(R, units), e(R, D), e(c, D), e(c, D)
+        return SimpleNamespace(B=B, R=R, q0=q0, pos=pos, hn=hn, hq=hn[q0:], hm=e(n, D) if masked else None, mid=mid,
+                               midq=mid[:n], qu=e(R, 2 * D), kb=e(R, D), vb=e(R, D), pb=e(pos.shape[0], D), ctx=ctx,
+                               ctxq=ctx[q0:], pw=e(c, 2 * D), gl=gl, gl3=gl.view(B, c // B, D),
+                               dwo3=dwo.view(B, c // B, D), dwoq=dwo[left:])
+
+    def _layer(self, L: dict, x: Tensor, S: SimpleNamespace, *, attn, conv,
+               keep: Optional[Tensor] = None) -> Tuple[Tensor, Optional[Tensor]]:
+        """One conformer layer over x [S.R, D] (updated in place): rows < S.q0 are cached rows that only serve as keys /
+        values (encoder_layer.py:220-231), rows >= S.q0 are computed.
+          attn(L, qu, k, pb, hn, ctx)         the context product into ctx's rows >= q0: ``_full_attn`` or ``_band_attn``
+          conv(L, h) -> (src, dw, new_cache)  the rows pointwise_conv1 -> GLU -> depthwise conv run on (h behind S's ``left``
+                                              rows of context), f5e_dwconv_stream's mode, and the conv cache to hand back:
+                                              ``_conv_one_pass`` or ``_conv_cached``
+          keep                                f32 [R] 0 / 1 or None: the pad mask of a ragged batch
+        -> (the computed rows' output, a view of x; new conv cache)."""
+        ln, hn, hq, mid = L["ln"], S.hn, S.hq, S.mid
+        # macaron feed-forward: x += 0.5 * W2 swish(W1 LN(x))
+        _ln(x, hn, ln["norm_ff_macaron"])
         ops.gemm_f32(hn, L["ffm"][0], L["ffm"][1], out=mid, act=ops.ACT_SILU)
-        ops.gemm_f32(mid, L["ffm"][2], L["ffm"][3], out=x, ch_scale=self.half[:D], addend=x)
-        ops.layernorm(x, hn, gamma=ln["norm_mha"][0], beta=ln["norm_mha"][1], eps=1e-5)
-        qu, kb, vb = torch.empty(R, 2 * D, device=dv), torch.empty(R, D, device=dv), torch.empty(R, D, device=dv)
-        pb, ctx = torch.empty(R, D, device=dv), torch.empty(R, D, device=dv)
-        ops.gemm_f32(hn, L["wq2"], L["bq2"], out=qu)
-        ops.gemm_f32(hn, L["wk"], L["bk"], out=kb)
-        ops.gemm_f32(hn, L["wv"], L["bv"], out=vb)
-        ops.gemm_f32(pos, L["wp"], None, out=pb)
-        ops.relpos_attn(qu, kb, pb, vb, ctx, H, 1.0 / math.sqrt(self.dk), chunk=chunk if one_pass else 0,
-                        left_chunks=left, q_begin=q0)
-        xq = x[q0:]
-        ops.gemm_f32(ctx[q0:], L["wo"], L["bo"], out=xq, addend=xq)
-        # convolution module (convolution.py:81-134) on the new rows
-        hq = torch.empty(n, D, device=dv)
-        ops.layernorm(xq, hq, gamma=ln["norm_conv"][0], beta=ln["norm_conv"][1], eps=1e-5)
-        K = L["dw"].shape[0]
-        causal = self.causal and K > 1
-        src, skip, new_cache = hq, 0, None
-        if causal and not one_pass:
-            prev = cnn_cache[0].t().to(dv, F32) if cnn_cache is not None else torch.zeros(K - 1, D, device=dv)
-            src, skip = torch.cat((prev, hq), 0), K - 1
-            new_cache = src[-(K - 1):].t().unsqueeze(0).contiguous()
-        elif not one_pass:
-            new_cache = torch.zeros(1, device=dv)                # the reference's dummy (convolution.py:113-116)
-        rows = src.shape[0]
-        pw = torch.empty(rows, 2 * D, device=dv)
-        gl, dwo = torch.empty(1, rows, D, device=dv), torch.empty(1, rows, D, device=dv)
-        ops.gemm_f32(src, L["pw1"], L["pb1"], out=pw)
-        ops.glu(pw, gl.view(rows, D))
-        if causal:
-            ops.dwconv_stream(gl, L["dw"], L["db"], dwo, causal=True, fill=L["fill"] if one_pass else None)
-        else:
-            ops.dwconv_stream(gl, L["dw"], L["db"], dwo, causal=False, chunk=chunk if one_pass else 0)
-        ops.gemm_f32(dwo.view(rows, D)[skip:], L["pw2"], L["pb2"], out=hq, a_act=ops.ACT_SILU)
+        ops.gemm_f32(mid, L["ffm"][2], L["ffm"][3], out=x, ch_scale=self.half, addend=x)
+        # relative-position self-attention (attention.py:172-222)
+        _ln(x, hn, ln["norm_mha"])
+        ops.gemm_f32(hn, L["wq2"], L["bq2"], out=S.qu)
+        ops.gemm_f32(hn, L["wk"], L["bk"], out=S.kb)
+        ops.gemm_f32(S.pos, L["wp"], None, out=S.pb)
+        attn(L, S.qu, S.kb, S.pb, hn, S.ctx)
+        xq = x[S.q0:] if S.q0 else x
+        ops.gemm_f32(S.ctxq, L["wo"], L["bo"], out=xq, addend=xq)
+        # convolution module (convolution.py:81-134): mask, pointwise -> GLU -> depthwise (+BN) -> swish -> pointwise, mask
+        _ln(xq, hq, ln["norm_conv"])
+        # the reference zeroes padded frames BEFORE pointwise_conv1 (whose bias then makes them non-zero again for the
+        # depthwise conv's neighbours): mask LN(x) first
+        src, dw, new_cache = conv(L, hq if keep is None else mask_rows(hq, keep, S.hm, self.eye))
+        ops.gemm_f32(src, L["pw1"], L["pb1"], out=S.pw)
+        ops.glu(S.pw, S.gl)
+        ops.dwconv_stream(S.gl3, L["dw"], L["db"], S.dwo3, **dw)
+        ops.gemm_f32(S.dwoq, L["pw2"], L["pb2"], out=hq, a_act=ops.ACT_SILU, row_scale=keep)
         ops.axpby(xq, hq, xq, 1.0, 1.0)
-        ops.layernorm(xq, hq, gamma=ln["norm_ff"][0], beta=ln["norm_ff"][1], eps=1e-5)
-        ops.gemm_f32(hq, L["ff"][0], L["ff"][1], out=mid[:n], act=ops.ACT_SILU)
-        ops.gemm_f32(mid[:n], L["ff"][2], L["ff"][3], out=xq, ch_scale=self.half[:D], addend=xq)
-        ops.layernorm(xq, xq, gamma=ln["norm_final"][0], beta=ln["norm_final"][1], eps=1e-5)
+        # feed-forward + final norm
+        _ln(xq, hq, ln["norm_ff"])
+        ops.gemm_f32(hq, L["ff"][0], L["ff"][1], out=S.midq, act=ops.ACT_SILU)
+        ops.gemm_f32(S.midq, L["ff"][2], L["ff"][3], out=xq, ch_scale=self.half, addend=xq)
+        _ln(xq, xq, ln["norm_final"])
         return xq, new_cache
+
+    def _full_attn_scratch(self, T: int) -> Tuple[Tensor, Tensor, Tensor]:
+        """(V^T [D, Tp] with zeroed pad columns, scores [T, Tp], probabilities [T, Tp]) of ``_full_attn``, Tp = T up to 4."""
+        Tp = (T + 3) // 4 * 4
+        return (torch.zeros(self.dim, Tp, device=self.device), torch.empty(T, Tp, device=self.device),
+                torch.empty(T, Tp, device=self.device))
+
+    def _full_attn(self, L: dict, qu: Tensor, k: Tensor, pb: Tensor, vsrc: Tensor, ctx: Tensor, *, B: int, T: int,
+                   kv_len: Optional[Tensor], ws: Tuple[Tensor, Tensor, Tensor]) -> Tensor:
+        """Full-context attention of B sequences of T rows, one sequence and head at a time on the fp32 GEMM: qu [B * T, 2 D]
+        (q + u | q + v), k [B * T, D], pb [T, D] projected positions, vsrc [B * T, D] the rows ``L["wv"]`` projects to the
+        values, kv_len i32 [B] on the device or None -> ctx [B * T, D]."""
+        D, dk, scale = self.dim, self.dk, 1.0 / math.sqrt(self.dk)
+        vt, sc, pr = ws
+        for b in range(B):
+            r0, r1 = b * T, (b + 1) * T
+            # V^T [D, T] = Wv . LN(x)^T (bias added after P.V: softmax rows sum to one)
+            ops.gemm_f32(L["wv"], vsrc[r0:r1], None, out=vt[:, :T])
+            for hd in range(self.heads):
+                c0, c1 = hd * dk, (hd + 1) * dk
+                ops.gemm_f32(qu[r0:r1, c0:c1], k[r0:r1, c0:c1], None, out=sc[:, :T])               # (q + u) k^T
+                ops.gemm_f32(qu[r0:r1, D + c0:D + c1], pb[:, c0:c1], None, out=sc[:, :T], addend=sc[:, :T])  # + (q + v) p^T
+                ops.softmax_rows(sc, pr, T, scale, kv_len=kv_len[b:b + 1] if kv_len is not None else None, rows_per_seq=T)
+                ops.gemm_f32(pr, vt[c0:c1], L["bv"][c0:c1], out=ctx[r0:r1, c0:c1], K=vt.shape[1])
+        return ctx
+
+    def _band_attn(self, L: dict, qu: Tensor, k: Tensor, pb: Tensor, vsrc: Tensor, ctx: Tensor, *, vb: Tensor, q0: int,
+                   chunk: int, left: int) -> Tensor:
+        """Streaming attention of one sequence in ONE launch (f5e_relpos_attn): the queries from row q0 on against the keys
+        of the band (chunk, left), chunk 0: every key.  vb [rows, D]: scratch for the projected values."""
+        ops.gemm_f32(vsrc, L["wv"], L["bv"], out=vb)
+        return ops.relpos_attn(qu, k, pb, vb, ctx, self.heads, 1.0 / math.sqrt(self.dk), chunk=chunk, left_chunks=left,
+                               q_begin=q0)
+
+    def _conv_one_pass(self, L: dict, h: Tensor, *, chunk: int):
+        """The conv of whole utterances.  Causal: left of them it sees GLU(pointwise_conv1(0)), ``L["fill"]``.  Otherwise
+        symmetric, every chunk of ``chunk`` rows on its own with zero padding (0: the whole sequence)."""
+        if self.causal and L["dw"].shape[0] > 1:
+            return h, dict(causal=True, fill=L["fill"]), None
+        return h, dict(causal=False, chunk=chunk), None
+
+    def _conv_cached(self, L: dict, h: Tensor, *, left: int, cnn_cache: Optional[Tensor]):
+        """forward_chunk's conv.  Causal (left = K - 1 > 0): behind the carried ``cnn_cache`` [1, D, left] (None: zeros),
+        handing back the last ``left`` rows; otherwise on the rows alone, handing back the reference's dummy
+        (convolution.py:113-116)."""
+        if not left:
+            return h, dict(causal=False, chunk=0), torch.zeros(1, device=self.device)
+        prev = cnn_cache[0].t().to(self.device, F32) if cnn_cache is not None else torch.zeros(left, self.dim, device=self.device)
+        src = torch.cat((prev, h), 0)
+        return src, dict(causal=True), src[-left:].t().unsqueeze(0).contiguous()
 
     @staticmethod
     def stream_frames(num_frames: int, chunk: int) -> int:
@@ -899,11 +891,12 @@ class ConformerEngine:
             raise _C.F5EError(f"PPG extractor: the streaming loop yields {n} frames, the subsampling {xs.shape[0]}")
         xs = xs[:n]
         pos = self.pos_table(n)
+        S = self._scratch(1, n, pos)
+        attn = partial(self._band_attn, vb=S.vb, q0=0, chunk=decoding_chunk_size, left=num_decoding_left_chunks)
+        conv = partial(self._conv_one_pass, chunk=decoding_chunk_size)
         for L in self.layers:
-            self._stream_layer(L, xs, 0, pos, decoding_chunk_size, num_decoding_left_chunks, None, True)
-        out = torch.empty(n, self.dim, device=self.device)
-        ops.layernorm(xs, out, gamma=self.after[0], beta=self.after[1], eps=1e-5)
-        return out.unsqueeze(0)
+            self._layer(L, xs, S, attn=attn, conv=conv)
+        return _ln(xs, S.hn, self.after).unsqueeze(0)
 
     def forward_chunk(self, xs: Tensor, offset: int, required_cache_size: int, subsampling_cache: Optional[Tensor] = None,
                       elayers_output_cache: Optional[List[Tensor]] = None,
@@ -922,19 +915,23 @@ class ConformerEngine:
         pos = self.pos_table(R, offset - cs)
         start = 0 if required_cache_size < 0 else (R if required_cache_size == 0 else max(R - required_cache_size, 0))
         r_sub, r_att, r_cnn = x[start:].unsqueeze(0).clone(), [], []
+        K = self.layers[0]["dw"].shape[0] if self.layers else 1
+        left = K - 1 if self.causal else 0                  # rows of the carried conv cache
+        S = None
         for i, L in enumerate(self.layers):
             cache = None if elayers_output_cache is None else elayers_output_cache[i][0].to(dv, F32)
             q0 = 0 if cache is None else cache.shape[0]
             if not q0 < R:
                 raise _C.F5EError("PPG extractor: the layer output cache must be shorter than cache + chunk")
-            xq, cnn = self._stream_layer(L, x, q0, pos, 0, -1, None if conformer_cnn_cache is None else conformer_cnn_cache[i],
-                                         False)
+            if S is None or (S.R, S.q0) != (x.shape[0], q0):      # once per call: the caches of a call have one length
+                S = self._scratch(1, x.shape[0], pos, q0, left)
+            xq, cnn = self._layer(L, x, S, attn=partial(self._band_attn, vb=S.vb, q0=q0, chunk=0, left=-1),
+                                  conv=partial(self._conv_cached, left=left,
+                                               cnn_cache=None if conformer_cnn_cache is None else conformer_cnn_cache[i]))
             x = torch.cat((cache, xq), 0) if q0 else xq
             r_att.append(x[start:].unsqueeze(0).clone())
             r_cnn.append(cnn)
-        out = torch.empty(R, D, device=dv)
-        ops.layernorm(x, out, gamma=self.after[0], beta=self.after[1], eps=1e-5)
-        return out[cs:].unsqueeze(0), r_sub, r_att, r_cnn
+        return _ln(x, torch.empty(R, D, device=dv), self.after)[cs:].unsqueeze(0), r_sub, r_att, r_cnn
 
     def head(self, enc: Tensor) -> Tuple[Tensor, Tensor]:
         """``linear`` (the PPG) and ``ce.fc`` logits of an encoder output [B, T', D] (asr_model.py:241-244)."""
@@ -1062,14 +1059,7 @@ class PPGModelWapper(object):
             src = ppg.reshape(B * T, D).contiguous()
         else:
             raise _C.F5EError(f"unknown output_type {self.output_type!r}")
-        out = torch.empty(B * T, src.shape[1], device=ppg.device)
-        ops.gemm_f32(src, self._eye(src.shape[1], ppg.device), None, out=out, row_scale=keep)
-        return out.view(B, T, -1)
-
-    def _eye(self, d, dv):
-        if getattr(self, "_eye_t", None) is None or self._eye_t.shape[0] != d:
-            self._eye_t = torch.eye(d, device=dv)
-        return self._eye_t
+        return mask_rows(src, keep, torch.empty(B * T, src.shape[1], device=ppg.device)).view(B, T, -1)
 
     @torch.no_grad()
     def mel_to_ppg(self, mel, mel_lens):

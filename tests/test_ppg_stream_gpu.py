@@ -96,6 +96,26 @@ def test_default_size_stream_vs_restatement(T, causal, monkeypatch):
         assert d > 1e-3
 
 
+@pytest.mark.parametrize("causal", [False, True])
+def test_one_chunk_stream_equals_full_context(causal):
+    """With ONE chunk covering the utterance (101 feature frames -> 50 encoder frames, chunk 64, all left chunks) the
+    streaming pass and the full-context pass are the same function up to the attention's summation order (f5e_relpos_attn
+    against the per-head GEMM + softmax_rows sequence): nothing mode-specific hides in the shared conformer layer.  Gate
+    2e-4 relative L2, the gate each mode has against the reference fixture at this encoder size (two results within 2e-4
+    of one reference are within 4e-4 of each other: the tighter of the two).  Measured on one MI355X: 1.21e-07 (not
+    causal), 1.25e-07 (causal)."""
+    from f5e_tts_amd.ppg.ppg_model import ConformerEngine
+    m, _, g = fixture_model(causal)
+    feats = g["feats_long"][:, :101].cuda()
+    eng = m.engine()
+    assert ConformerEngine.stream_frames(101, 64) == 50
+    stream = eng.forward_chunk_by_chunk(feats, 64, -1)
+    full = eng.encode(feats, torch.tensor([101]))[0]
+    e = rel_l2(stream, full)
+    print("causal=%d: one-chunk stream vs full context rel L2 %.2e" % (causal, e))
+    assert stream.shape == full.shape == (1, 50, 64) and e < 2e-4
+
+
 # ------------------------------------------------------------------ the kernels on their own
 
 def attn_operands(B, T, H, dk, seed):
@@ -130,24 +150,17 @@ def dense_attention(qu, k, pos, v, B, T, H, dk, lens, chunk, left):
 
 
 def existing_sequence(qu, k, pos, v, B, T, H, dk, lens):
-    """The launch sequence of ConformerEngine.forward on the same operands: per sequence and head (q+u) k^T, + (q+v) p^T,
-    softmax_rows, P.V on the fp32 GEMM."""
-    from f5e_tts_amd import ops
-    D, Tp = H * dk, (T + 3) // 4 * 4
-    dv = qu.device
-    vt, sc, pr = torch.zeros(D, Tp, device=dv), torch.empty(T, Tp, device=dv), torch.empty(T, Tp, device=dv)
-    ctx = torch.empty(B * T, D, device=dv)
+    """The full-context launch sequence of ConformerEngine.forward on the same operands, by the engine's own method
+    (ConformerEngine._full_attn: per sequence and head (q+u) k^T, + (q+v) p^T, softmax_rows, P.V on the fp32 GEMM).  The
+    method projects its value rows with the layer's weight and adds the bias after P.V: an identity and zeros hand it v."""
+    from f5e_tts_amd.ppg.ppg_model import ConformerEngine
+    D, dv = H * dk, qu.device
+    eng = object.__new__(ConformerEngine)
+    eng.device, eng.dim, eng.heads, eng.dk = dv, D, H, dk
+    layer = dict(wv=torch.eye(D, device=dv), bv=torch.zeros(D, device=dv))
     kv = None if lens is None else torch.tensor(lens, dtype=torch.int32, device=dv)
-    for b in range(B):
-        r0, r1 = b * T, (b + 1) * T
-        vt[:, :T] = v[r0:r1].t()
-        for h in range(H):
-            c0, c1 = h * dk, (h + 1) * dk
-            ops.gemm_f32(qu[r0:r1, c0:c1], k[r0:r1, c0:c1], None, out=sc[:, :T])
-            ops.gemm_f32(qu[r0:r1, D + c0:D + c1], pos[:T, c0:c1], None, out=sc[:, :T], addend=sc[:, :T])
-            ops.softmax_rows(sc, pr, T, 1.0 / math.sqrt(dk), kv_len=kv[b:b + 1] if kv is not None else None, rows_per_seq=T)
-            ops.gemm_f32(pr, vt[c0:c1], None, out=ctx[r0:r1, c0:c1], K=Tp)
-    return ctx
+    return eng._full_attn(layer, qu, k, pos[:T], v, torch.empty(B * T, D, device=dv), B=B, T=T, kv_len=kv,
+                          ws=eng._full_attn_scratch(T))
 
 
 @pytest.mark.parametrize("dk", [16, 64])

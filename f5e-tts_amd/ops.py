@@ -593,6 +593,76 @@ def log_softmax_rows(x: Tensor, out: Optional[Tensor] = None):
     return out
 
 
+def attn_decode_f32(qkv: Tensor, kc: Tensor, vc: Tensor, p: int, heads: int, scale: float, anc: Optional[Tensor] = None,
+                    out: Optional[Tensor] = None):
+    """Cached single-query self-attention of decode step ``p`` (f5e_attn_decode_f32): qkv f32 [R, >= 3 D] (q | k | v of the
+    step), kc / vc f32 [R, Umax, D] views of the layer's caches (row and position strides free, unit channel stride, the same
+    strides for both), anc i32 [R, >= p] or None -> out f32 [R, D].  Slot [r, p] of both caches receives the step's k / v;
+    position j < p is read from cache row ``anc[r, j]`` (row r when None)."""
+    if qkv.ndim != 2 or kc.ndim != 3 or kc.shape != vc.shape or kc.stride() != vc.stride():
+        raise _C.F5EError("attn_decode_f32: qkv [R, >= 3 D] and kc, vc [R, Umax, D] with equal strides; there is no CPU path")
+    R, Umax, D = kc.shape
+    for t, nm in ((kc, "kc"), (vc, "vc")):
+        if not t.is_cuda or t.dtype != F32 or t.stride(2) != 1:
+            raise _C.F5EError(f"attn_decode_f32: {nm} must be an f32 GPU tensor with unit channel stride")
+    if qkv.shape[0] != R or D % heads or not 0 <= int(p) < Umax:
+        raise _C.F5EError(f"attn_decode_f32: qkv rows {qkv.shape[0]} != {R}, heads {heads} must divide {D}, 0 <= p < {Umax}")
+    pos_stride = kc.stride(1) if Umax > 1 else max(D, kc.stride(1))
+    row_stride = kc.stride(0) if R > 1 else max(kc.stride(0), (Umax - 1) * pos_stride + D)
+    have = kc.untyped_storage().nbytes() // 4 - kc.storage_offset()
+    if pos_stride < D or row_stride < (Umax - 1) * pos_stride + D or have < (R - 1) * row_stride + (Umax - 1) * pos_stride + D \
+            or pos_stride % 4 or row_stride % 4 or kc.data_ptr() % 16:
+        raise _C.F5EError(f"attn_decode_f32: cache strides ({row_stride}, {pos_stride}) must be multiples of 4 spanning "
+                          f"[{R}, {Umax}, {D}] inside the storage, kc 16-byte aligned")
+    qp, ldq = _rows(qkv, (F32,), "attn_decode_f32: qkv", 3 * D)
+    ap, ld_anc = None, 0
+    if anc is not None:
+        if anc.ndim != 2 or anc.shape[0] != R:
+            raise _C.F5EError(f"attn_decode_f32: anc must be an i32 GPU tensor [{R}, >= p]")
+        ap, ld_anc = _rows(anc, (I32,), "attn_decode_f32: anc", max(int(p), 1), vec=1)
+    require_device()
+    out = torch.empty(R, D, dtype=F32, device=qkv.device) if out is None else out
+    if out.shape != (R, D):
+        raise _C.F5EError(f"attn_decode_f32: out must be [{R}, {D}]")
+    op, ldo = _rows(out, (F32,), "attn_decode_f32: out", D, vec=1)
+    check(lib().f5e_attn_decode_f32(_stream(), qp, ldq, C.c_void_p(kc.data_ptr()), C.c_void_p(vc.data_ptr()), row_stride,
+                                    pos_stride, ap, ld_anc, op, ldo, R, Umax, heads, D // heads, int(p), float(scale)),
+          "f5e_attn_decode_f32")
+    return out
+
+
+def beam_step(logits: Tensor, score: Tensor, hyp_in: Tensor, anc_in: Tensor, hyp_out: Tensor, anc_out: Tensor, last: Tensor,
+              alive: Tensor, done_at: Tensor, p: int, beam: int, eos: int):
+    """One step of the attention decoder's beam search (f5e_beam_step): logits f32 [B * beam, V] (raw; row stride free),
+    score f32 [B * beam] (in / out), the hyp / anc table pairs i32 [B * beam, ld] (contiguous, in != out), last i32
+    [B * beam], alive / done_at i32 [B]; all on the device.  See include/f5e_abi.h for the semantics."""
+    if logits.ndim != 2 or not logits.is_cuda or logits.dtype != F32 or logits.stride(1) != 1:
+        raise _C.F5EError("beam_step: logits must be an f32 GPU tensor [rows, V] with unit class stride; there is no CPU path")
+    R, V = logits.shape
+    beam, p = int(beam), int(p)
+    if not 1 <= beam <= min(16, V) or R % beam:
+        raise _C.F5EError(f"beam_step: beam must lie in 1..min(16, V = {V}) and divide the {R} rows, got {beam}")
+    B = R // beam
+    ld = hyp_in.shape[1] if hyp_in.ndim == 2 else 0
+    for t, nm in ((hyp_in, "hyp_in"), (anc_in, "anc_in"), (hyp_out, "hyp_out"), (anc_out, "anc_out")):
+        if t.shape != (R, ld) or not t.is_contiguous():
+            raise _C.F5EError(f"beam_step: {nm} must be a contiguous i32 tensor [{R}, {ld}]")
+    if not 0 <= p <= ld - 2:
+        raise _C.F5EError(f"beam_step: step {p} needs tables of at least {p + 2} columns (got {ld})")
+    if hyp_in.data_ptr() == hyp_out.data_ptr() or anc_in.data_ptr() == anc_out.data_ptr():
+        raise _C.F5EError("beam_step: the tables are double-buffered: in and out must differ")
+    if score.shape != (R,) or last.shape != (R,) or alive.shape != (B,) or done_at.shape != (B,):
+        raise _C.F5EError(f"beam_step: score / last [{R}], alive / done_at [{B}]")
+    if not 0 <= int(eos) < V:
+        raise _C.F5EError(f"beam_step: eos must lie in [0, {V})")
+    require_device()
+    check(lib().f5e_beam_step(_stream(), C.c_void_p(logits.data_ptr()), logits.stride(0) if R > 1 else max(V, logits.stride(0)),
+                              _p(score, F32, "score"), _p(hyp_in, I32, "hyp_in"), _p(anc_in, I32, "anc_in"),
+                              _p(hyp_out, I32, "hyp_out"), _p(anc_out, I32, "anc_out"), ld, _p(last, I32, "last"),
+                              _p(alive, I32, "alive"), _p(done_at, I32, "done_at"), B, V, beam, p, int(eos)), "f5e_beam_step")
+    return hyp_out, anc_out
+
+
 _resample_banks = {}
 _resample_lock = threading.Lock()
 

@@ -187,6 +187,19 @@ class CTCAligner:
         return "".join(self.inverse.get(i, "") for i in ids).replace("▁", " ").strip()
 
     @torch.no_grad()
+    def recognize(self, audio, sr: Optional[int] = None, beam_size: int = 10, reorder_cache: bool = False) -> str:
+        """The reference's decoding mode ``attention`` (wenet/bin/recognize.py -> ASRModel.recognize): beam search over the
+        attention decoder; the ids up to the first eos, detokenised as ``transcribe`` does.  It is a method of its own and
+        not a ``transcribe`` mode.  Needs a model built with its attention decoder."""
+        if getattr(self.model, "decoder_type", None) is None:
+            raise _C.F5EError("CTCAligner.recognize needs a model built with its attention decoder "
+                              "(CTCAligner(decoder=True) / build_ppg_model(decoder=True))")
+        feats, lens, _ = self._feats(audio, sr)
+        row = self.model.recognize(feats, lens, beam_size, reorder_cache=reorder_cache)[0][0].cpu().tolist()
+        ids = row[:row.index(self.model.eos)] if self.model.eos in row else row
+        return "".join(self.inverse.get(i, "") for i in ids).replace("▁", " ").strip()
+
+    @torch.no_grad()
     def align(self, audio, sr: Optional[int], text: str) -> List[WordSpan]:
         words, ids = self.tokenize(text)
         labels = [i for row in ids for i in row]

@@ -475,6 +475,37 @@ class ConformerPPG(nn.Module):
         return out
 
     @torch.no_grad()
+    def recognize(self, speech: Tensor, speech_lengths: Tensor, beam_size: int = 10, *, reorder_cache: bool = False,
+                  nbest: bool = False, sync_every: int = 4) -> Tuple[Tensor, Tensor]:
+        """reference asr_model.py:309-414 (full context): beam search over the attention decoder (the left one of a
+        bitransformer, decoder.py:294) -> (best_hyps i64 [B, L], best_scores f32 [B]) on the device: ``hyps[:, 1:]`` of each
+        utterance's max-score row, eos-padded, L as the reference's early stop leaves it.  ``nbest=True`` returns the whole
+        beam instead, (hyps [B, beam, L], scores [B, beam]) in beam order (best first).
+
+        The search keeps per-layer key / value caches on the device and never moves a cache row (f5e_attn_decode_f32 follows
+        an ancestry table instead).  The reference does not reorder its per-layer cache when the second prune reshuffles the
+        beam, so with two or more decoder blocks the layers above the first attend to what their ROW computed earlier, not
+        to what the hypothesis' ancestor did; the default reproduces that.  ``reorder_cache=True`` is the corrected search,
+        every layer following the ancestry, equal to recomputing the decoder on the whole prefix at every step.
+        ``sync_every``: the host asks the device whether every row has finished once per that many steps; the result does
+        not depend on it."""
+        assert speech.shape[0] == speech_lengths.shape[0]
+        # caller bugs first: they are the same on any device
+        K = check_beam(beam_size, self.vocab_size) if self.decoder_type is not None else 0
+        if int(sync_every) < 1:
+            raise _C.F5EError(f"recognize: sync_every must be >= 1 (got {sync_every})")
+        eng = self._require_decoder()
+        enc, lens_host = eng._encode(speech, speech_lengths)
+        mem_len = lens_host.to(enc.device) if int(lens_host.min()) < enc.shape[1] else None
+        hyps, scores = eng.attention_beam_search("left", enc, mem_len, K, self.sos, self.eos, bool(reorder_cache),
+                                                 int(sync_every))
+        hyps = hyps.long()
+        if nbest:
+            return hyps, scores
+        best_scores, best = scores.max(dim=-1)
+        return hyps[torch.arange(hyps.shape[0], device=hyps.device), best], best_scores
+
+    @torch.no_grad()
     def forward_attention_decoder(self, hyps: Tensor, hyps_lens: Tensor, encoder_out: Tensor,
                                   reverse_weight: float = 0) -> Tuple[Tensor, Tensor]:
         """reference asr_model.py:763-811: ``hyps`` [N, U + 1] ids with the leading sos, eos-padded, ``hyps_lens`` [N] counting
@@ -531,6 +562,24 @@ def mask_rows(x: Tensor, keep: Tensor, out: Tensor, eye: Optional[Tensor] = None
     identity GEMM; ``eye``: the [d, d] identity when the caller keeps one."""
     eye = torch.eye(x.shape[1], device=x.device) if eye is None else eye
     return ops.gemm_f32(x, eye, None, out=out, row_scale=keep)
+
+
+def beam_loop(S: SimpleNamespace, step, sync_every: int) -> Tuple[Tensor, Tensor]:
+    """The loop control of ``ConformerEngine.attention_beam_search`` around ``step(S)`` (one decode step that ends in
+    f5e_beam_step and advances ``S.p``): up to ``S.umax`` steps, ``S.done_at`` read every ``sync_every`` steps -> (hyps i32
+    [B, beam, L] without the sos, scores f32 [B, beam]).  L = max_b done_at[b] + 1, the width the reference's per-step check
+    leaves, whatever the number of steps run beyond it (they append eos to eos-filled columns); ``S.umax`` when a row never
+    finishes."""
+    done = None
+    while S.p < S.umax:
+        step(S)
+        if S.p % sync_every == 0 or S.p == S.umax:
+            done = S.done_at.cpu()
+            if bool((done >= 0).all()):
+                break
+    width = int(done.max()) + 1 if bool((done >= 0).all()) else S.umax
+    hyps = S.hyp[S.p & 1][:, 1:width + 1].reshape(S.B, S.beam, width)
+    return hyps, S.score.view(S.B, S.beam)
 
 
 class ConformerEngine:
@@ -673,6 +722,86 @@ class ConformerEngine:
         logits = torch.empty(R, W["out"][0].shape[0], device=dv)
         ops.gemm_f32(hn, *W["out"], out=logits)
         return logits
+
+    def decode_state(self, which: str, memory: Tensor, mem_len: Optional[Tensor], beam: int, sos: int, eos: int,
+                     umax: Optional[int] = None) -> SimpleNamespace:
+        """Everything ``decode_step`` reads and writes for a search over ``memory`` f32 [B, T', D] with ``beam`` rows per
+        utterance: the per-layer key / value caches [layers, R, Umax, D] (Umax = the reference's loop bound, the padded T'),
+        the memory's k | v projection of every layer (done ONCE, here), the two hypothesis / ancestry table pairs
+        [R, Umax + 1] (hypotheses eos-filled behind column 0 = sos) and the reference's start scores 0, -inf, ..."""
+        if which not in self.dec:
+            raise _C.F5EError(f"PPG extractor: the state_dict has no {which} attention decoder")
+        W, dv, D, H = self.dec[which], self.device, self.dim, self.dec_heads
+        B, T2, _ = memory.shape
+        if H < 1 or D % H:
+            raise _C.F5EError(f"decode_state: heads {H} must divide {D}")
+        umax = T2 if umax is None else int(umax)
+        if not 1 <= umax <= 4096:
+            raise _C.F5EError(f"decode_state: the search runs at most 4096 steps (got {umax})")
+        R, nl = B * beam, len(W["layers"])
+        units = W["layers"][0]["ff"][0].shape[0] if nl else D
+        V = W["out"][0].shape[0]
+        S = SimpleNamespace(W=W, B=B, beam=beam, R=R, umax=umax, eos=eos, mem_len=mem_len, p=0,
+                            scale=1.0 / math.sqrt(D // H),
+                            kc=torch.empty(nl, R, umax, D, device=dv), vc=torch.empty(nl, R, umax, D, device=dv), kv=[],
+                            hyp=[torch.full((R, umax + 1), eos, dtype=I32, device=dv) for _ in range(2)],
+                            anc=[torch.zeros(R, umax + 1, dtype=I32, device=dv) for _ in range(2)],
+                            score=torch.tensor([0.0] + [-float("inf")] * (beam - 1)).repeat(B).to(dv),
+                            last=torch.full((R,), sos, dtype=I32, device=dv),
+                            alive=torch.full((B,), beam, dtype=I32, device=dv), done_at=torch.full((B,), -1, dtype=I32, device=dv),
+                            x=torch.empty(R, 1, D, device=dv), hn=torch.empty(R, D, device=dv), ctx=torch.empty(R, D, device=dv),
+                            q=torch.empty(R, D, device=dv), qkv=torch.empty(R, 3 * D, device=dv),
+                            mid=torch.empty(R, units, device=dv), logits=torch.empty(R, V, device=dv))
+        for h in S.hyp:
+            h[:, 0] = sos
+        mem = memory.reshape(B * T2, D)
+        for L in W["layers"]:
+            S.kv.append(ops.gemm_f32(mem, *L["src_kv"], out=torch.empty(B * T2, 2 * D, device=dv)))
+        return S
+
+    def decode_step(self, S: SimpleNamespace, reorder_cache: bool = False, prune: bool = True) -> Tensor:
+        """TransformerDecoder.forward_one_step (decoder.py:137-181) for position ``S.p`` of all R rows plus, with ``prune``,
+        the beam update of asr_model.py:374-403 -> the step's raw logits [R, V] (a buffer of ``S``).  11 launches per layer
+        + 4: embedding of the last tokens at position p; per layer LayerNorm, q | k | v, f5e_attn_decode_f32 on the layer's
+        cache, out-projection, LayerNorm, q, f5e_mha_f32 of B items x beam queries against the memory, out-projection,
+        LayerNorm, two feed-forward GEMMs; after_norm, output layer, f5e_beam_step.  The ancestry table goes to layer 0 alone
+        (the reference: its caches of the layers above stay with the row index) or, ``reorder_cache``, to every layer."""
+        W, D, H, p = S.W, self.dim, self.dec_heads, S.p
+        if p >= S.umax:
+            raise _C.F5EError(f"decode_step: the caches hold {S.umax} positions")
+        cur, nxt = p & 1, (p & 1) ^ 1
+        ops.text_gather(S.last.view(S.R, 1), W["embed"], self.pos_table(1, offset=p), None, S.x)
+        x = S.x.view(S.R, D)
+        for i, L in enumerate(W["layers"]):
+            _ln(x, S.hn, L["ln"][0])
+            ops.gemm_f32(S.hn, *L["self_qkv"], out=S.qkv)
+            ops.attn_decode_f32(S.qkv, S.kc[i], S.vc[i], p, H, S.scale, anc=S.anc[cur] if (i == 0 or reorder_cache) else None,
+                                out=S.ctx)
+            ops.gemm_f32(S.ctx, *L["self_out"], out=x, addend=x)
+            _ln(x, S.hn, L["ln"][1])
+            ops.gemm_f32(S.hn, *L["src_q"], out=S.q)
+            ops.mha_f32(S.q, S.kv[i][:, :D], S.kv[i][:, D:], H, S.scale, B=S.B, kv_len=S.mem_len, causal=False, out=S.ctx)
+            ops.gemm_f32(S.ctx, *L["src_out"], out=x, addend=x)
+            _ln(x, S.hn, L["ln"][2])
+            ops.gemm_f32(S.hn, L["ff"][0], L["ff"][1], out=S.mid, act=ops.ACT_RELU)
+            ops.gemm_f32(S.mid, L["ff"][2], L["ff"][3], out=x, addend=x)
+        _ln(x, S.hn, W["after"])
+        ops.gemm_f32(S.hn, *W["out"], out=S.logits)
+        if prune:
+            ops.beam_step(S.logits, S.score, S.hyp[cur], S.anc[cur], S.hyp[nxt], S.anc[nxt], S.last, S.alive, S.done_at, p,
+                          S.beam, S.eos)
+            S.p = p + 1
+        return S.logits
+
+    def attention_beam_search(self, which: str, memory: Tensor, mem_len: Optional[Tensor], beam: int, sos: int, eos: int,
+                              reorder_cache: bool = False, sync_every: int = 4) -> Tuple[Tensor, Tensor]:
+        """The loop of ASRModel.recognize (asr_model.py:364-403) -> (hyps i32 [B, beam, L] without the sos, eos-padded, in
+        beam order; scores f32 [B, beam]).  The reference asks the device every step whether all rows have finished; here
+        the host reads ``done_at`` every ``sync_every`` steps.  A step run after an utterance is complete appends eos at score
+        + 0 and keeps the row order (what the reference does at B > 1 for utterances that finish early), so the result is
+        the same for any ``sync_every``: L = max_b done_at[b] + 1, or the loop bound when some row never finishes."""
+        S = self.decode_state(which, memory, mem_len, beam, sos, eos)
+        return beam_loop(S, lambda st: self.decode_step(st, reorder_cache), sync_every)
 
     def pos_table(self, t: int, offset: int = 0) -> Tensor:
         """PositionalEncoding.pe[:, offset:offset + t] (embedding.py:34-46, 65-82), a constant table built in fp32 like the

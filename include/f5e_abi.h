@@ -404,6 +404,47 @@ F5E_API int f5e_relpos_attn(f5e_stream st, const float* qu, int ldq, const float
 F5E_API int f5e_mha_f32(f5e_stream st, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, float* out,
                 int ldo, const int* kv_len, int B, int Tq, int Tk, int H, int dk, int causal, float scale);
 
+/* ---- attention-decoder beam search (reference ASRModel.recognize, ppg/asr_model.py:309-414), one decode step at a time.
+ *
+ * Cached single-query self-attention of decode step p (0-based position of the token being fed) for R = B * beam rows:
+ *   kc, vc  f32 [R][Umax][>= H*dk], caller-owned per decoder layer: element (r, j, c) at r*row_stride + j*pos_stride + c
+ *   qkv     f32 [R][ld_qkv >= 3*H*dk]: the step's fused projection q | k | v of every row
+ *   anc     i32 [R][ld_anc >= p] or NULL: anc[r][j] = the row in which row r's hypothesis stood when position j was fed
+ * For row r and head h the kernel FIRST files k and v of the step in slot [r][p] of the caches, then leaves
+ *   out[r][h*dk + d] = sum_{j=0..p} softmax_j(scale * q . k_j) * v_j[d]
+ * where position j < p is read from cache row anc[r][j] (clamped to [0, R); row r itself when anc is NULL) and position p
+ * from the row's own qkv.  Every position 0..p is visible (the reference's subsequent mask has no padding term).
+ * Writes: out rows, and slot [r][p] of kc / vc by row r alone -- no other cache byte is touched, and no launch reads a slot
+ * it writes, so there is no race inside a launch; a search that calls this once per step and layer writes every slot once.
+ * Passing the table for every layer follows the beam's ancestry (a cache-free recompute gives the same numbers); passing
+ * NULL leaves each cache with its row index, which is what the reference's un-reordered per-layer cache computes for its
+ * layers >= 1.  Neither moves a cache row.
+ * Limits: 0 <= p < Umax <= 4096; head dims dk = 16, 32, 64, 128; R, H <= 65535; ld_qkv, row_stride and pos_stride multiples
+ * of 4 floats, qkv and kc 16-byte aligned.  fp32 throughout.  No allocation, no synchronisation. */
+F5E_API int f5e_attn_decode_f32(f5e_stream st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                        int pos_stride, const int* anc, int ld_anc, float* out, int ldo, int R, int Umax, int H, int dk, int p,
+                        float scale);
+/* One step of the beam search (asr_model.py:374-403) for B utterances of `beam` rows each, one workgroup per utterance.
+ *   logits  f32 [B*beam][ld_logits >= V]: RAW decoder outputs of step p; the kernel normalises each row itself (fp32,
+ *           max-subtracted: (x - max) - log(sum exp(x - max)), as f5e_log_softmax_rows)
+ *   score   f32 [B*beam], in and out: the rows' accumulated log-probabilities.  Start: 0, -inf, ..., -inf per utterance
+ *   hyp_in / anc_in  i32 [B*beam][ld]: the tables before the step (hyp column 0 = sos; hyp columns 0..p, anc columns < p)
+ *   hyp_out / anc_out i32 [B*beam][ld]: the tables after it; DIFFERENT buffers (the gather crosses rows)
+ *   last    i32 [B*beam] out: the class every new row ends in (hyp_out column p + 1, contiguous for the next embedding)
+ *   alive   i32 [B] out: rows of the utterance not ending in eos after this step
+ *   done_at i32 [B] in/out, -1 at the start: set to p ONCE, at the first step after which alive[b] is 0
+ * Semantics: a row is finished iff p > 0 and its last token hyp_in[r][p] is eos (sos may equal eos: step 0 has no finished
+ * row).  First prune: the `beam` largest classes of every unfinished row; a finished row contributes the single candidate
+ * (score + 0, eos) and beam - 1 candidates at -inf.  Candidate value = score + log p in fp32.  Second prune: the `beam`
+ * largest of the utterance's beam^2 candidates become rows 0..beam-1 in descending order; new row q gets its parent's
+ * hypothesis with the class appended at column p + 1 and its parent's ancestry with the parent's (global) row at column p.
+ * Ties: lower class first in the first prune, lower (parent row, rank) first in the second.
+ * Containment: columns > p + 1 of hyp_out, columns > p of anc_out and every input table are untouched.
+ * Limits: 1 <= beam <= 16, beam <= V, 0 <= eos < V, ld >= p + 2, B <= 65535.  No allocation, no synchronisation. */
+F5E_API int f5e_beam_step(f5e_stream st, const float* logits, long long ld_logits, float* score, const int* hyp_in,
+                  const int* anc_in, int* hyp_out, int* anc_out, int ld, int* last, int* alive, int* done_at, int B, int V,
+                  int beam, int p, int eos);
+
 /* ---------------------------------------------------------------- fused DiT evaluation ----------------------- */
 
 typedef struct f5e_dit_block_weights {

@@ -54,6 +54,9 @@ SIGNATURES = {
     "f5e_ctc_greedy": [_P, _P, _LL, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I],
     "f5e_ctc_beam_workspace_bytes": [_I, _I, _I, C.POINTER(C.c_ulonglong)],
     "f5e_ctc_beam": [_P, _P, _LL, _I, _P, _I, _I, _P, _I, _P, _P, _P, C.c_ulonglong, _I, _I, _I],
+    "f5e_ctc_beam_state_bytes": [_I, _I, _I, _I, C.POINTER(C.c_ulonglong)],
+    "f5e_ctc_beam_state_init": [_P, _P, C.c_ulonglong, _I, _I, _I, _I],
+    "f5e_ctc_beam_chunk": [_P, _P, _LL, _I, _P, _I, _I, _I, _I, _P, C.c_ulonglong, _P, _I, _P, _P, _I, _I, _I],
     "f5e_token_logp": [_P, _P, _LL, _P, _P, _LL, _I],
     "f5e_log_softmax_rows": [_P, _P, _LL, _P, _LL, _LL, _I],
     "f5e_stft_logmel": [_P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I],

@@ -557,6 +557,102 @@ def ctc_beam_search(scores: Tensor, t_len: Tensor, beam: int, blank: int = 0, *,
     return hyp, hyp_len, score
 
 
+class CTCBeamState:
+    """The resumable search's state: ``buf`` (device memory, opaque) and the geometry it was initialised for."""
+
+    def __init__(self, buf: Tensor, B: int, T_cap: int, chunk_cap: int, beam: int):
+        self.buf, self.B, self.T_cap, self.chunk_cap, self.beam = buf, B, T_cap, chunk_cap, beam
+
+    @property
+    def nbytes(self) -> int:
+        return self.buf.numel() * self.buf.element_size()
+
+    def init(self) -> "CTCBeamState":
+        """f5e_ctc_beam_state_init: every sequence back at the empty prefix (one small launch, no memset)."""
+        require_device()
+        check(lib().f5e_ctc_beam_state_init(_stream(), _p(self.buf, None, "state"), self.nbytes, self.B, self.T_cap,
+                                            self.chunk_cap, self.beam), "f5e_ctc_beam_state_init")
+        return self
+
+
+def _beam_state_geometry(B: int, T_cap: int, chunk_cap: int, beam: int, name: str):
+    B, T_cap, chunk_cap, beam = int(B), int(T_cap), int(chunk_cap), int(beam)
+    if not 1 <= beam <= 16:
+        raise _C.F5EError(f"{name}: beam must lie in 1..16, got {beam}")
+    if not (1 <= B <= 65535 and 1 <= T_cap <= 1 << 20 and 1 <= chunk_cap <= 16384):
+        raise _C.F5EError(f"{name}: need 1 <= B <= 65535, 1 <= T_cap <= 2^20 and 1 <= chunk_cap <= 16384 "
+                          f"(got {B}, {T_cap}, {chunk_cap})")
+    return B, T_cap, chunk_cap, beam
+
+
+def ctc_beam_state_bytes(B: int, T_cap: int, chunk_cap: int, beam: int) -> int:
+    """Bytes of the resumable search's state (host call)."""
+    B, T_cap, chunk_cap, beam = _beam_state_geometry(B, T_cap, chunk_cap, beam, "ctc_beam_state_bytes")
+    n = C.c_ulonglong()
+    check(lib().f5e_ctc_beam_state_bytes(B, T_cap, chunk_cap, beam, C.byref(n)), "f5e_ctc_beam_state_bytes")
+    return int(n.value)
+
+
+def ctc_beam_state(B: int, T_cap: int, chunk_cap: int, beam: int, *, buf: Optional[Tensor] = None,
+                   device="cuda") -> CTCBeamState:
+    """An initialised state of ``ctc_beam_chunk`` for B sequences of up to T_cap frames in all, fed at most chunk_cap frames
+    per call, at beam size ``beam``.  ``buf``: caller-owned device memory of at least ``ctc_beam_state_bytes`` bytes
+    (allocated here when None)."""
+    B, T_cap, chunk_cap, beam = _beam_state_geometry(B, T_cap, chunk_cap, beam, "ctc_beam_state")
+    require_device()
+    need = ctc_beam_state_bytes(B, T_cap, chunk_cap, beam)
+    if buf is None:
+        buf = torch.empty((need + 7) // 8, dtype=torch.int64, device=device)
+    if not buf.is_cuda or not buf.is_contiguous() or buf.numel() * buf.element_size() < need or buf.data_ptr() % 8:
+        raise _C.F5EError(f"ctc_beam_state: buf must be contiguous, 8-byte aligned device memory of >= {need} bytes")
+    return CTCBeamState(buf, B, T_cap, chunk_cap, beam).init()
+
+
+def ctc_beam_chunk(scores: Tensor, n_frames: Tensor, state: CTCBeamState, blank: int = 0, *, want_result: bool = True,
+                   ld_hyp: Optional[int] = None, hyp: Optional[Tensor] = None, hyp_len: Optional[Tensor] = None,
+                   score: Optional[Tensor] = None):
+    """One chunk of the resumable CTC prefix beam search (f5e_ctc_beam_chunk): scores f32 [B, T_chunk, V] as in
+    ``ctc_beam_search``, n_frames i32 [B] on the device (the chunk's frames that belong to each sequence; 0 = idle) ->
+    (hyp i32 [B, beam, ld_hyp], hyp_len i32 [B, beam], score f32 [B, beam]): the result on every frame fed so far, in the
+    layout of ``ctc_beam_search`` and, after the last chunk, bit for bit what one ``ctc_beam_search`` call on all the frames
+    returns.  ``want_result=False`` skips the readout and returns None.  ld_hyp defaults to ``state.T_cap``."""
+    B, T, V = _ctc_scores(scores, "ctc_beam_chunk")
+    if not isinstance(state, CTCBeamState):
+        raise _C.F5EError("ctc_beam_chunk: state must come from ctc_beam_state")
+    beam = state.beam
+    if B != state.B or not 1 <= T <= state.chunk_cap:
+        raise _C.F5EError(f"ctc_beam_chunk: scores [{B}, {T}, {V}] against a state for B = {state.B}, chunk_cap = "
+                          f"{state.chunk_cap}: need the same B and 1 <= T_chunk <= chunk_cap")
+    if n_frames.dtype != I32 or not n_frames.is_cuda or n_frames.numel() != B:
+        raise _C.F5EError(f"ctc_beam_chunk: n_frames must be an i32 GPU tensor [{B}]")
+    if beam > V or not 0 <= int(blank) < V:
+        raise _C.F5EError(f"ctc_beam_chunk: need beam ({beam}) <= V ({V}) and 0 <= blank < V")
+    require_device()
+    dev = scores.device
+    if want_result:
+        if hyp is not None:
+            if hyp.ndim != 3 or not hyp.is_contiguous():
+                raise _C.F5EError(f"ctc_beam_chunk: hyp must be a contiguous i32 tensor [{B}, {beam}, ld_hyp]")
+            ld_hyp = hyp.shape[2]
+        ld_hyp = state.T_cap if ld_hyp is None else int(ld_hyp)
+        hyp = torch.empty(B, beam, ld_hyp, dtype=I32, device=dev) if hyp is None else hyp
+        hyp_len = torch.empty(B, beam, dtype=I32, device=dev) if hyp_len is None else hyp_len
+        score = torch.empty(B, beam, dtype=F32, device=dev) if score is None else score
+        if ld_hyp < 1 or hyp.shape != (B, beam, ld_hyp) or hyp_len.shape != (B, beam) or score.shape != (B, beam) or \
+                not (hyp_len.is_contiguous() and score.is_contiguous()):
+            raise _C.F5EError(f"ctc_beam_chunk: hyp [{B}, {beam}, ld_hyp >= 1], hyp_len / score [{B}, {beam}], contiguous")
+    elif hyp is not None or hyp_len is not None or score is not None:
+        raise _C.F5EError("ctc_beam_chunk: want_result=False takes no output tensors")
+    else:
+        ld_hyp = 0
+    check(lib().f5e_ctc_beam_chunk(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0),
+                                   scores.stride(1) if T > 1 else max(V, scores.stride(1)), _p(n_frames, I32, "n_frames"),
+                                   T, V, int(blank), beam, _p(state.buf, None, "state"), state.nbytes,
+                                   _p(hyp, I32, "hyp"), ld_hyp, _p(hyp_len, I32, "hyp_len"), _p(score, F32, "score"),
+                                   B, state.T_cap, state.chunk_cap), "f5e_ctc_beam_chunk")
+    return (hyp, hyp_len, score) if want_result else None
+
+
 def token_logp(logits: Tensor, target: Tensor, out: Optional[Tensor] = None):
     """out[r] = logits[r, target[r]] - logsumexp(logits[r]) (f5e_token_logp): logits f32 [rows, V] on the device (row stride
     free, unit class stride), target i32 [rows]; a negative target gives 0."""

@@ -166,38 +166,82 @@ class CTCAligner:
         feats, feats_len = self.featCal(audio)
         return feats, feats_len.to(self.device), secs
 
+    def _check_decoding(self, decoding_chunk_size: int, simulate_streaming: bool) -> None:
+        """The model's check of the streaming parameters for the one utterance handled here, before any feature is computed."""
+        self.model._check_decoding(torch.empty(1, 0, 0), decoding_chunk_size, simulate_streaming)
+
+    def _text(self, ids) -> str:
+        return "".join(self.inverse.get(int(i), "") for i in ids).replace("▁", " ").strip()
+
     @torch.no_grad()
     def transcribe(self, audio, sr: Optional[int] = None, mode: str = "ctc_greedy_search", beam_size: int = 10,
-                   ctc_weight: float = 0.5, reverse_weight: float = 0.0) -> str:
+                   ctc_weight: float = 0.5, reverse_weight: float = 0.0, *, decoding_chunk_size: int = -1,
+                   num_decoding_left_chunks: int = -1, simulate_streaming: bool = False) -> str:
         """``mode``: one of the reference's ``ctc_greedy_search`` (the default), ``ctc_prefix_beam_search`` (the best of the
-        n-best at ``beam_size``) and ``attention_rescoring`` (that list re-ranked by the attention decoder)."""
+        n-best at ``beam_size``) and ``attention_rescoring`` (that list re-ranked by the attention decoder).  The three
+        keyword-only arguments are the reference's (``ConformerPPG._check_decoding``): by default the encoder sees the whole
+        recording; ``decoding_chunk_size > 0`` with ``simulate_streaming=True`` runs it chunk by chunk."""
+        stream = dict(decoding_chunk_size=decoding_chunk_size, num_decoding_left_chunks=num_decoding_left_chunks,
+                      simulate_streaming=simulate_streaming)
         if mode not in DECODE_MODES:
             raise _C.F5EError(f"CTCAligner.transcribe: unknown mode {mode!r} (one of {', '.join(DECODE_MODES)})")
         if mode == "attention_rescoring" and getattr(self.model, "decoder_type", None) is None:
             raise _C.F5EError("CTCAligner.transcribe: attention_rescoring needs a model built with its attention decoder "
                               "(CTCAligner(decoder=True) / build_ppg_model(decoder=True))")
+        self._check_decoding(decoding_chunk_size, simulate_streaming)
         feats, lens, _ = self._feats(audio, sr)
         if mode == "ctc_greedy_search":
-            ids = self.model.ctc_greedy_search(feats, lens, pad_id=-1)[0][0]
+            ids = self.model.ctc_greedy_search(feats, lens, pad_id=-1, **stream)[0][0]
         elif mode == "ctc_prefix_beam_search":
-            ids = self.model.ctc_prefix_beam_search(feats, lens, beam_size)[0][0][0]
+            ids = self.model.ctc_prefix_beam_search(feats, lens, beam_size, **stream)[0][0][0]
         else:
             ids = self.model.attention_rescoring(feats, lens, beam_size, ctc_weight=ctc_weight,
-                                                 reverse_weight=reverse_weight)[0][0]
-        return "".join(self.inverse.get(i, "") for i in ids).replace("▁", " ").strip()
+                                                 reverse_weight=reverse_weight, **stream)[0][0]
+        return self._text(ids)
 
     @torch.no_grad()
-    def recognize(self, audio, sr: Optional[int] = None, beam_size: int = 10, reorder_cache: bool = False) -> str:
+    def recognize(self, audio, sr: Optional[int] = None, beam_size: int = 10, reorder_cache: bool = False, *,
+                  decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1,
+                  simulate_streaming: bool = False) -> str:
         """The reference's decoding mode ``attention`` (wenet/bin/recognize.py -> ASRModel.recognize): beam search over the
         attention decoder; the ids up to the first eos, detokenised as ``transcribe`` does.  It is a method of its own and
         not a ``transcribe`` mode.  Needs a model built with its attention decoder."""
         if getattr(self.model, "decoder_type", None) is None:
             raise _C.F5EError("CTCAligner.recognize needs a model built with its attention decoder "
                               "(CTCAligner(decoder=True) / build_ppg_model(decoder=True))")
+        self._check_decoding(decoding_chunk_size, simulate_streaming)
         feats, lens, _ = self._feats(audio, sr)
-        row = self.model.recognize(feats, lens, beam_size, reorder_cache=reorder_cache)[0][0].cpu().tolist()
+        row = self.model.recognize(feats, lens, beam_size, reorder_cache=reorder_cache,
+                                   decoding_chunk_size=decoding_chunk_size, num_decoding_left_chunks=num_decoding_left_chunks,
+                                   simulate_streaming=simulate_streaming)[0][0].cpu().tolist()
         ids = row[:row.index(self.model.eos)] if self.model.eos in row else row
-        return "".join(self.inverse.get(i, "") for i in ids).replace("▁", " ").strip()
+        return self._text(ids)
+
+    def stream(self, **kw):
+        """A ``StreamingRecognizer`` (ppg/streaming_asr.py; the keywords of ``ConformerPPG.streaming_recognizer``) whose
+        ``partial_text()`` / ``finish_text()`` detokenise as ``transcribe`` does."""
+        rec = self.model.streaming_recognizer(**kw)
+        rec.detokenize = self._text
+        return rec
+
+    def transcribe_stream(self, chunks, sr: int = 16000, mode: str = "ctc_prefix_beam_search", ctc_weight: float = 0.5,
+                          reverse_weight: float = 0.0, **kw):
+        """A generator over ``chunks``, an iterable of 16 kHz mono sample blocks: the partial text after every block, then
+        the final text (``mode``: ``ctc_prefix_beam_search`` or ``attention_rescoring``).  ``kw``: the keywords of
+        ``stream``.  The arguments are checked, and the recogniser is built, when this is called, not at the first
+        ``next``."""
+        from .streaming_asr import STREAM_MODES, check_sample_rate
+        check_sample_rate(sr)
+        if mode not in STREAM_MODES:
+            raise _C.F5EError(f"CTCAligner.transcribe_stream: unknown mode {mode!r} (one of {', '.join(STREAM_MODES)})")
+        rec = self.stream(**kw)
+
+        def run():
+            for block in chunks:
+                rec.accept_waveform(block)
+                yield rec.partial_text()
+            yield rec.finish_text(mode, ctc_weight, reverse_weight)
+        return run()
 
     @torch.no_grad()
     def align(self, audio, sr: Optional[int], text: str) -> List[WordSpan]:

@@ -346,18 +346,51 @@ class ConformerPPG(nn.Module):
             raise _C.F5EError("PPG extractor: built without the CTC head (ConformerPPG(ctc=True) / build_ppg_model(ctc=True))")
         return self.engine()
 
-    def _ctc_scores(self, speech: Tensor, speech_lengths: Tensor, use_linear: bool) -> Tuple[Tensor, Tensor, Tensor]:
-        """-> (CTC logits [B, T', V], valid frames i32 [B] on the device, the same on the host)."""
+    def _check_decoding(self, speech: Tensor, decoding_chunk_size: int, simulate_streaming: bool) -> bool:
+        """The reference's encoder choice (asr_model.py:281-307) as far as it is built, checked on the host before anything
+        touches the device -> whether the chunk-by-chunk encoder runs.  ``decoding_chunk_size`` < 0: full context (the
+        default); 0: refused (the reference's four decode methods assert it); > 0 with ``simulate_streaming``: the
+        chunk-by-chunk loop, batch 1 and a chunk-trained model; > 0 without: the reference's masked one-pass encoder, which
+        is not built."""
+        chunk = int(decoding_chunk_size)
+        if chunk == 0:
+            raise _C.F5EError("PPG extractor: decoding_chunk_size must not be 0 (negative: full context; positive: chunk size)")
+        if chunk < 0:
+            return False
+        if not simulate_streaming:
+            raise _C.F5EError("PPG extractor: decoding_chunk_size > 0 without simulate_streaming is the masked one-pass "
+                              "encoder, which is out of scope here: pass simulate_streaming=True (chunk by chunk)")
+        self._require_stream(speech)
+        return True
+
+    def _encoder_out(self, eng: "ConformerEngine", speech: Tensor, speech_lengths: Tensor, decoding_chunk_size: int = -1,
+                     num_decoding_left_chunks: int = -1, simulate_streaming: bool = False) -> Tuple[Tensor, Tensor]:
+        """``ASRModel._forward_encoder`` -> (encoder output [B, T', D], valid frames i32 [B] on the host): the ONE place where
+        the decode methods pick their encoder.  Chunk by chunk, every frame the loop yields is valid (its mask is all ones,
+        encoder.py:352-354) and ``speech_lengths`` is not used, as there."""
+        if self._check_decoding(speech, decoding_chunk_size, simulate_streaming):
+            enc = eng.forward_chunk_by_chunk(speech, int(decoding_chunk_size), int(num_decoding_left_chunks))
+            return enc, torch.tensor([enc.shape[1]], dtype=I32)
+        return eng._encode(speech, speech_lengths)
+
+    def _ctc_scores(self, speech: Tensor, speech_lengths: Tensor, use_linear: bool,
+                    stream: Tuple[int, int, bool] = (-1, -1, False)) -> Tuple[Tensor, Tensor, Tensor]:
+        """-> (CTC logits [B, T', V], valid frames i32 [B] on the device, the same on the host).  ``stream``:
+        (decoding_chunk_size, num_decoding_left_chunks, simulate_streaming) of ``_encoder_out``."""
+        self._check_decoding(speech, stream[0], stream[2])           # caller bugs first: they are the same on any device
         eng = self._require_ctc()
-        enc, lens_host = eng._encode(speech, speech_lengths)
+        enc, lens_host = self._encoder_out(eng, speech, speech_lengths, *stream)
         if use_linear:
             enc = eng.head(enc)[0]
         return eng.ctc_logits(enc), lens_host.to(enc.device), lens_host
 
     @torch.no_grad()
     def ctc_greedy_search(self, speech: Tensor, speech_lengths: Tensor, use_linear: bool = False,
-                          pad_id: Optional[int] = None) -> Tuple[List[List[int]], Tensor]:
-        """reference asr_model.py:416-459 (full context; the streaming modes are not built) -> (hyps, scores [B, 1]).
+                          pad_id: Optional[int] = None, *, decoding_chunk_size: int = -1,
+                          num_decoding_left_chunks: int = -1, simulate_streaming: bool = False) -> Tuple[List[List[int]], Tensor]:
+        """reference asr_model.py:416-459 -> (hyps, scores [B, 1]).  ``decoding_chunk_size`` / ``num_decoding_left_chunks`` /
+        ``simulate_streaming`` are the reference's (``_check_decoding``): the defaults decode with the full context; a
+        positive chunk size with ``simulate_streaming=True`` runs the encoder chunk by chunk (batch 1).
         Argmax, collapse and the frame log-probabilities run on the device (f5e_ctc_greedy) straight from the logits.
 
         The reference DECODES from the encoder output, although its training forward feeds ``linear(encoder_out)`` to the
@@ -368,7 +401,8 @@ class ConformerPPG(nn.Module):
         utterance of a batch ends in a trailing eos.  ``scores`` equals ``.values`` of the reference's ``topk_prob.max(1)``
         (the best frame's top-1 log-probability, padded frames included)."""
         assert speech.shape[0] == speech_lengths.shape[0]
-        logits, frame_lens, _ = self._ctc_scores(speech, speech_lengths, use_linear)
+        logits, frame_lens, _ = self._ctc_scores(speech, speech_lengths, use_linear,
+                                                 (decoding_chunk_size, num_decoding_left_chunks, simulate_streaming))
         hyp, hyp_len, logp = ops.ctc_greedy(logits, frame_lens, blank=0, pad_id=self.eos if pad_id is None else pad_id,
                                             want_logp=True)
         hyp_h, len_h = hyp.cpu(), hyp_len.cpu().tolist()
@@ -420,33 +454,46 @@ class ConformerPPG(nn.Module):
                 for b in range(len(n_h))]
 
     @torch.no_grad()
-    def ctc_prefix_beam_search(self, speech: Tensor, speech_lengths: Tensor, beam_size: int,
-                               use_linear: bool = False) -> List[List[Tuple[Tuple[int, ...], float]]]:
-        """reference asr_model.py:461-578 (full context) for a batch of ANY size -> per utterance the n-best list of
+    def ctc_prefix_beam_search(self, speech: Tensor, speech_lengths: Tensor, beam_size: int, use_linear: bool = False, *,
+                               decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1,
+                               simulate_streaming: bool = False) -> List[List[Tuple[Tuple[int, ...], float]]]:
+        """reference asr_model.py:461-578 (encoder choice as in ``ctc_greedy_search``) for a batch of ANY size -> per utterance the n-best list of
         (ids, score = logaddexp(pb, pnb)), best first; at batch 1, ``[0]`` is the reference's ``_ctc_prefix_beam_search``
         list.  The search runs on the device (f5e_ctc_beam) straight from the logits, frames past an utterance skipped.
         ``use_linear`` as in ``ctc_greedy_search``."""
         assert speech.shape[0] == speech_lengths.shape[0]
         check_beam(beam_size, self.vocab_size)
-        logits, frame_lens, _ = self._ctc_scores(speech, speech_lengths, use_linear)
+        logits, frame_lens, _ = self._ctc_scores(speech, speech_lengths, use_linear,
+                                                 (decoding_chunk_size, num_decoding_left_chunks, simulate_streaming))
         return self._nbest(logits, frame_lens, beam_size)
 
     @torch.no_grad()
     def attention_rescoring(self, speech: Tensor, speech_lengths: Tensor, beam_size: int, ctc_weight: float = 0.0,
-                            reverse_weight: float = 0.0, use_linear: bool = False) -> List[Tuple[Tuple[int, ...], float]]:
-        """reference asr_model.py:580-677 for a batch of any size -> per utterance (ids, score) of the n-best entry the
+                            reverse_weight: float = 0.0, use_linear: bool = False, *, decoding_chunk_size: int = -1,
+                            num_decoding_left_chunks: int = -1,
+                            simulate_streaming: bool = False) -> List[Tuple[Tuple[int, ...], float]]:
+        """reference asr_model.py:580-677 (encoder choice as in ``ctc_greedy_search``) for a batch of any size -> per utterance (ids, score) of the n-best entry the
         attention decoder likes best:  sum_j logp[j][w_j] + logp[len][eos], with reverse_weight > 0 mixed as
         score (1 - rw) + r_score rw with the right-to-left decoder's sum (taken at len - j - 1), plus ctc_weight x the CTC
         score; the first maximum wins.  The decoder runs ONCE per batch on the device: the memory's key / value projections
         once per utterance (the reference repeats the encoder output beam_size times), every hypothesis' queries in one
         launch; f5e_token_logp leaves one float per target, summed here in double precision as the reference does."""
         assert speech.shape[0] == speech_lengths.shape[0]
+        self._check_decoding(speech, decoding_chunk_size, simulate_streaming)
         eng = self._require_decoder(reverse_weight)
         self._require_ctc()
         K = check_beam(beam_size, self.vocab_size)
-        enc, lens_host = eng._encode(speech, speech_lengths)
+        enc, lens_host = self._encoder_out(eng, speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks,
+                                           simulate_streaming)
         frame_lens = lens_host.to(enc.device)
         nbest = self._nbest(eng.ctc_logits(eng.head(enc)[0] if use_linear else enc), frame_lens, K)
+        return self._rescore(eng, enc, lens_host, nbest, K, ctc_weight, reverse_weight)
+
+    def _rescore(self, eng: "ConformerEngine", enc: Tensor, lens_host: Tensor, nbest, K: int, ctc_weight: float,
+                 reverse_weight: float) -> List[Tuple[Tuple[int, ...], float]]:
+        """The decoder pass of ``attention_rescoring`` over ``nbest`` (per utterance the list of (ids, CTC score)) and the
+        encoder output it came from."""
+        frame_lens = lens_host.to(enc.device)
         B, dev = len(nbest), enc.device
         U1 = max(len(h) for hyps in nbest for h, _ in hyps) + 1 if any(nbest) else 1
         packs = [rescoring_inputs([h for h, _ in hyps], self.sos, self.eos, rows=K) for hyps in nbest]
@@ -476,8 +523,9 @@ class ConformerPPG(nn.Module):
 
     @torch.no_grad()
     def recognize(self, speech: Tensor, speech_lengths: Tensor, beam_size: int = 10, *, reorder_cache: bool = False,
-                  nbest: bool = False, sync_every: int = 4) -> Tuple[Tensor, Tensor]:
-        """reference asr_model.py:309-414 (full context): beam search over the attention decoder (the left one of a
+                  nbest: bool = False, sync_every: int = 4, decoding_chunk_size: int = -1,
+                  num_decoding_left_chunks: int = -1, simulate_streaming: bool = False) -> Tuple[Tensor, Tensor]:
+        """reference asr_model.py:309-414 (encoder choice as in ``ctc_greedy_search``): beam search over the attention decoder (the left one of a
         bitransformer, decoder.py:294) -> (best_hyps i64 [B, L], best_scores f32 [B]) on the device: ``hyps[:, 1:]`` of each
         utterance's max-score row, eos-padded, L as the reference's early stop leaves it.  ``nbest=True`` returns the whole
         beam instead, (hyps [B, beam, L], scores [B, beam]) in beam order (best first).
@@ -494,8 +542,10 @@ class ConformerPPG(nn.Module):
         K = check_beam(beam_size, self.vocab_size) if self.decoder_type is not None else 0
         if int(sync_every) < 1:
             raise _C.F5EError(f"recognize: sync_every must be >= 1 (got {sync_every})")
+        self._check_decoding(speech, decoding_chunk_size, simulate_streaming)
         eng = self._require_decoder()
-        enc, lens_host = eng._encode(speech, speech_lengths)
+        enc, lens_host = self._encoder_out(eng, speech, speech_lengths, decoding_chunk_size, num_decoding_left_chunks,
+                                           simulate_streaming)
         mem_len = lens_host.to(enc.device) if int(lens_host.min()) < enc.shape[1] else None
         hyps, scores = eng.attention_beam_search("left", enc, mem_len, K, self.sos, self.eos, bool(reorder_cache),
                                                  int(sync_every))
@@ -538,6 +588,14 @@ class ConformerPPG(nn.Module):
                               "use_dynamic_chunk in encoder_conf)")
         if xs.shape[0] != 1:
             raise _C.F5EError(f"PPG extractor: streaming runs one utterance at a time (batch {xs.shape[0]})")
+
+    def streaming_recognizer(self, beam_size: int = 10, decoding_chunk_size: int = 16, num_decoding_left_chunks: int = -1,
+                             max_seconds: float = 60.0, use_linear: bool = False):
+        """A ``StreamingRecognizer`` (ppg/streaming_asr.py) on this model: audio in as it arrives, the n-best list of the
+        resumable CTC prefix beam search out after every block, ``finish()`` for the final result or its attention
+        rescoring.  Building it allocates the search state for ``max_seconds`` of audio."""
+        from .streaming_asr import StreamingRecognizer
+        return StreamingRecognizer(self, beam_size, decoding_chunk_size, num_decoding_left_chunks, max_seconds, use_linear)
 
     @torch.no_grad()
     def forward_encoder_chunk(self, xs: Tensor, offset: int, required_cache_size: int,

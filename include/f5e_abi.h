@@ -298,6 +298,33 @@ F5E_API int f5e_ctc_beam(f5e_stream st, const float* scores, long long batch_str
                  int beam, int* hyp, int ld_hyp, int* hyp_len, float* score, void* workspace,
                  unsigned long long workspace_bytes, int B, int T, int V);
 
+/* The same search, resumable (csrc/ctc_beam.hip): the frames of a sequence arrive in chunks, and after the last chunk hyp /
+ * hyp_len / score equal those of ONE f5e_ctc_beam call on all the frames bit for bit, however the frames were cut (empty
+ * chunks included): a frame's first prune depends on that frame alone, the recurrence is the same code doing the same fp32
+ * operations in the same order, and trie node numbers use the absolute frame index.
+ * state: opaque, caller-owned DEVICE memory of f5e_ctc_beam_state_bytes(B, T_cap, chunk_cap, beam) bytes, 8-byte aligned; per
+ * sequence the frames consumed, the beam (node, parent, last token, length, hash, pb, pnb, entry count), the trie of T_cap x
+ * beam nodes and the first-prune scratch of one chunk (chunk_cap x beam pairs); sizes and offsets are 64-bit.
+ * f5e_ctc_beam_state_init: one small launch (no host-side memset, capturable) that puts every sequence at the empty prefix
+ * and records the geometry; the rest of the state needs no initial value.
+ * f5e_ctc_beam_chunk: scores f32 [B][T_chunk][V] with the strides of f5e_ctc_beam; n_frames DEVICE int [B] = how many of the
+ * chunk's frames belong to each sequence (0: idle this call).  Two launches: the first prune of the chunk, then one workgroup
+ * per sequence that loads its beam, runs n_frames[b] frames, stores the beam and adds to the frames consumed.  hyp / hyp_len
+ * / score: all null (no readout), or all given: the result so far in the layout of f5e_ctc_beam (hyp i32 [B][beam][ld_hyp]);
+ * the readout does not change the state, so it can be repeated (a call with n_frames = 0 is a pure readout).
+ * B, T_cap, chunk_cap and beam are those of state_init (the host needs them for the grid and the offsets); T_chunk <=
+ * chunk_cap.  A sequence FAILS when n_frames[b] < 0, n_frames[b] > T_chunk or consumed + n_frames[b] > T_cap: it gets -1 /
+ * length -1 / -inf rows in this call and in every later one (the state marks it dead until the next state_init), writes
+ * nothing outside its own share of the state, and the other sequences are untouched.  A state whose recorded geometry is not
+ * the call's (or that was never initialised) fails every sequence and is not written.  1 <= beam <= 16, beam <= V,
+ * chunk_cap <= 16384, T_cap <= 2^20, B <= 65535.  No allocation, no synchronisation. */
+F5E_API int f5e_ctc_beam_state_bytes(int B, int T_cap, int chunk_cap, int beam, unsigned long long* bytes_out_host);
+F5E_API int f5e_ctc_beam_state_init(f5e_stream st, void* state, unsigned long long state_bytes, int B, int T_cap,
+                            int chunk_cap, int beam);
+F5E_API int f5e_ctc_beam_chunk(f5e_stream st, const float* scores, long long batch_stride, int ld, const int* n_frames,
+                       int T_chunk, int V, int blank, int beam, void* state, unsigned long long state_bytes, int* hyp,
+                       int ld_hyp, int* hyp_len, float* score, int B, int T_cap, int chunk_cap);
+
 /* out[r] = logits[r][target[r]] - logsumexp(logits[r][0..V)) for `rows` rows of row stride ld (fp32, max-subtracted), one wave
  * per row: the terms of the reference's rescoring sum (ppg/asr_model.py:660-670) without the copy of [N, U, V]
  * log-probabilities to the host.  target[r] < 0 gives 0 (a padded position), target[r] >= V gives NaN.  No allocation, no

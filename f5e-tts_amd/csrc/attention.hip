@@ -49,9 +49,47 @@ struct AttnArgs {
   int S, H, rows_per_seq, n_pad;
   int n_main;         // workgroups beyond it only prefetch (NSPLIT >= 2 launches)
   F5ePrefetch pf;
+#ifdef F5E_TOOLS
+  unsigned long long* trace;   // tools build: [workgroup][wave][8] timestamps of the traced kernel builds (f5e_debug_attn_trace)
+#endif
 };
 
-template <int NSPLIT>
+// In-kernel timeline of the TOOLS build (tools/attn_timeline.py): ATTN_STAMP(i) reads the shader clock into ts[i],
+// ATTN_LANDED(n, i) first waits until at most n of the wave's vector loads are outstanding.  The waits and fences exist in
+// the traced instantiations only (TRC); the shipped library compiles neither.
+#ifdef F5E_TOOLS
+#define ATTN_STAMP(i)                                                                                    \
+  do {                                                                                                   \
+    if constexpr (TRC) {                                                                                 \
+      __builtin_amdgcn_sched_barrier(0);                                                                 \
+      asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts[i]) :: "memory");                    \
+      __builtin_amdgcn_sched_barrier(0);                                                                 \
+    }                                                                                                    \
+  } while (0)
+#define ATTN_LANDED(n, i)                                                                                \
+  do {                                                                                                   \
+    if constexpr (TRC) {                                                                                 \
+      __builtin_amdgcn_sched_barrier(0);                                                                 \
+      asm volatile("s_waitcnt vmcnt(" #n ")\n\ts_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(ts[i]) :: "memory"); \
+      __builtin_amdgcn_sched_barrier(0);                                                                 \
+    }                                                                                                    \
+  } while (0)
+#define ATTN_TRACE_OUT()                                                                                 \
+  do {                                                                                                   \
+    if constexpr (TRC) {                                                                                 \
+      if (lane == 0 && a.trace) {                                                                        \
+        unsigned long long* tp = a.trace + ((size_t)blockIdx.x * (blockDim.x >> 6) + wave) * 8;          \
+        for (int i = 0; i < 8; ++i) tp[i] = ts[i];                                                       \
+      }                                                                                                  \
+    }                                                                                                    \
+  } while (0)
+#else
+#define ATTN_STAMP(i) do {} while (0)
+#define ATTN_LANDED(n, i) do {} while (0)
+#define ATTN_TRACE_OUT() do {} while (0)
+#endif
+
+template <int NSPLIT, bool TRC = false>
 __global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) {   // 2 waves per SIMD: <= 256 VGPRs
   // merge buffers: per extra wave, per lane: 32 O values + m + l
   __shared__ __attribute__((aligned(16))) float red[(NSPLIT > 1 ? NSPLIT - 1 : 1) * 64 * 34];
@@ -63,6 +101,8 @@ __global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) { 
     f5e_prefetch_run<NSPLIT * 64>(a.pf, (int)blockIdx.x - a.n_main, threadIdx.x, red);
     return;
   }
+  [[maybe_unused]] unsigned long long ts[8] = {};   // tools build, traced instantiation only
+  ATTN_STAMP(0);
 
   const int qtiles = (a.rows_per_seq + 31) / 32;
   // XCD-aware order: blocks with equal blockIdx%8 share an XCD (and its L2); give each XCD a contiguous range of
@@ -136,6 +176,7 @@ __global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) { 
     if (t64 < ntiles) load_tile(t64);
   };
   auto checked_tile = [&](bool first) {   // row sums checked against ROWSUM_LIMIT, running maximum moved when needed
+    if (first) { ATTN_LANDED(0, 2); } else { ATTN_LANDED(0, 3); }
     const int cur = advance();
     // ---- S^T: st[t][reg] = score(key = 64 cur + 32 t + (reg&3) + 8 (reg>>2) + 4 hh, query = ql), log2 domain ----
     f32x16 st[2];
@@ -169,6 +210,7 @@ __global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) { 
   if (t64 < ntiles) checked_tile(true);
   const int nfull = (ntiles * 64 > kv_len) ? ntiles - 1 : ntiles;   // steps without a key mask
   while (t64 < nfull) {
+    ATTN_LANDED(0, 3);
     advance();
     auto kfrag = [&](int t, int ks) { return ck[t][ks]; };
     auto vfrag = [&](int t, int s, int dt) { return cv[t][s][dt]; };
@@ -194,8 +236,13 @@ __global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) { 
       }
       *(f32x2*)(red + (wave - 1) * 64 * 34 + 64 * 32 + lane * 2) = f32x2{m_run, l_run};
     }
+    ATTN_STAMP(4);
     __syncthreads();
-    if (wave > 0) return;
+    ATTN_STAMP(5);
+    if (wave > 0) {
+      ATTN_TRACE_OUT();
+      return;
+    }
 #pragma unroll
     for (int w = 1; w < NSPLIT; ++w) {
       const f32x4* sq = (const f32x4*)(red + (w - 1) * 64 * 34);
@@ -242,6 +289,210 @@ __global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) { 
         *(uint4*)(a.o + ((size_t)seq * a.rows_per_seq + q_row) * a.ldo + head * 64 + c * 8) = v;
     }
   }
+  ATTN_STAMP(6);
+  ATTN_TRACE_OUT();
+}
+
+// ---- batch-1 variant: every wave owns at most two 64-key steps -------------------------------------------------------
+// attn_fwd_kernel<4> at ntiles <= 8 (N <= 512: 15 q-tiles x 32 (s, head) = 480 workgroups at C2) with the same grid, XCD
+// order, prefetch hosting and arithmetic, but a launch that is mostly cold-L2 latency gets its loads and its tail rearranged:
+//   * Q and the fragments of BOTH of the wave's tiles (wave, wave + 4; indices clamped to the padded extent, so every load
+//     is unconditional and in bounds) are requested back to back at entry, before kv_len (a scalar load) is consumed: one
+//     cold round trip per wave instead of kv_len -> first tile -> second tile.  Whether a step is COMPUTED is still decided
+//     by ntiles; a tile that was loaded but lies past kv_len never reaches an MFMA.  The steps read their own register
+//     sets (no copy).  The overflow re-run requests both tiles again, as attn_fwd_kernel does: keeping all 128 fragment
+//     registers alive across both steps for it spilled (60-68 bytes of scratch per lane at 256 VGPRs); dying after their
+//     step they leave the kernel at 246 VGPRs without scratch.
+//   * the tail runs on four waves: all of them park (O, m, l) in LDS; after ONE barrier wave w merges accumulator quad w of
+//     both d halves, starting from wave 0's partial and folding in waves 1, 2, 3 in that order with attn_fwd_kernel's
+//     expressions (m and l redundantly in every wave), normalises and writes its 16-byte pieces into the row-major staging
+//     tile; after a second barrier each wave issues one of the four store instructions.
+// Every output element sees the operations of attn_fwd_kernel<4> in the same order: the two kernels agree bit for bit.
+template <bool TRC>
+__global__ __launch_bounds__(256, 2) void attn_fwd_b1_kernel(AttnArgs a) {   // 2 waves per SIMD: <= 256 VGPRs
+  constexpr int NSPLIT = 4, PART = 64 * 34;   // one partial: per lane 32 O values + m + l
+  // [4 partials][PART] + the 32 x 64 bf16 output tile in 144-byte rows
+  __shared__ __attribute__((aligned(16))) float red[NSPLIT * PART + 32 * 36];
+
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int ql = lane & 31, hh = lane >> 5;
+  if ((int)blockIdx.x >= a.n_main) {   // grid-tail workgroups: Infinity-Cache prefetch only (first 4 KiB of red)
+    f5e_prefetch_run<NSPLIT * 64>(a.pf, (int)blockIdx.x - a.n_main, threadIdx.x, red);
+    return;
+  }
+  // Nothing is outstanding here, so this vmcnt(0) lgkmcnt(0) costs nothing -- but the compiler sees a path from the prefetch
+  // branch's LDS-DMAs to this point, and while it believes one pending it turns the first wait below into vmcnt(0): the
+  // first step would wait for the second tile too.  With the explicit wait every fragment gets its own counted vmcnt(N).
+  __builtin_amdgcn_s_waitcnt(0x0070);
+  [[maybe_unused]] unsigned long long ts[8] = {};   // tools build, traced instantiation only
+  ATTN_STAMP(0);
+
+  const int qtiles = (a.rows_per_seq + 31) / 32;
+  int bid = blockIdx.x;
+  {   // XCD-aware order, as in attn_fwd_kernel
+    const int nblk = a.n_main;
+    const int q8 = nblk >> 3, r8 = nblk & 7;
+    const int xcd = bid & 7, idx = bid >> 3;
+    bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
+  }
+  const int qt = bid % qtiles;
+  bid /= qtiles;
+  const int head = bid % a.H;
+  const int seq = bid / a.H;
+  const size_t sh = (size_t)seq * a.H + head;
+
+  const bf16* Qg = a.q + sh * a.n_pad * 64;
+  const bf16* Kg = a.k + sh * a.n_pad * 64;
+  const bf16* Vg = a.v + sh * a.n_pad * 64;
+
+  bf16x8 qf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8*)(Qg + ((size_t)(qt * 4 + ks) * 32 + ql) * 16 + hh * 8);
+  // both tiles' fragments, [step][t32][ks] and [step][t32][s16][dt]; a clamped index re-reads the last padded tile
+  bf16x8 kf[2][2][4], vf[2][2][2][2];
+  const int last64 = a.n_pad / 64 - 1;
+  auto load_k = [&](int st) {
+    const int t64 = min(wave + st * NSPLIT, last64);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+        kf[st][t][ks] = *(const bf16x8*)(Kg + ((((size_t)t64 * 2 + t) * 4 + ks) * 32 + ql) * 16 + hh * 8);
+  };
+  auto load_v = [&](int st) {
+    const int t64 = min(wave + st * NSPLIT, last64);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int s = 0; s < 2; ++s)
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+          vf[st][t][s][dt] = *(const bf16x8*)(Vg + ((((((size_t)t64 * 2 + t) * 2 + s) * 2 + dt) * 32 + ql) * 2 + hh) * 8);
+  };
+  load_k(0);
+  load_v(0);
+  load_k(1);
+  load_v(1);
+  // kv_len: a scalar load through the constant address space, in flight beside the 36 vector loads above
+  const int kv_len = a.kv_len ? min(load_uniform_i32(a.kv_len + seq), a.rows_per_seq) : a.rows_per_seq;
+  const int ntiles = (kv_len + 63) / 64;  // 64-key steps; the host guarantees ntiles <= 2 NSPLIT
+  ATTN_LANDED(32, 1);   // Q
+  ATTN_LANDED(16, 2);   // first tile
+
+  f32x16 oacc[2], minit;
+  float m_run, l_val;
+  auto pass_begin = [&]() {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { oacc[0][r] = 0.f; oacc[1][r] = 0.f; minit[r] = 0.f; }
+    m_run = -INFINITY;
+    l_val = 0.f;
+  };
+  auto checked_tile = [&](const bf16x8 (&ck)[2][4], const bf16x8 (&cv)[2][2][2], int cur, bool first) {
+    f32x16 st[2];
+    auto qk = [&](f32x16 (&d)[2], const f32x16& c) {
+#pragma unroll
+      for (int t = 0; t < 2; ++t) {
+        d[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ck[t][0], qf[0], c, 0, 0, 0);
+#pragma unroll
+        for (int ks = 1; ks < 4; ++ks) d[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ck[t][ks], qf[ks], d[t], 0, 0, 0);
+      }
+    };
+    softmax_step(qk, first, cur * 64 + 64 > kv_len, cur * 64 + 4 * hh, kv_len, st, minit, m_run, l_val, oacc);
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        bf16x8 pf;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pf[j] = (bf16)st[t][8 * s + j];
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+          oacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cv[t][s][dt], pf, oacc[dt], 0, 0, 0);
+      }
+  };
+
+  // attn_fwd_kernel's fast pass for at most two steps: the first establishes m_run, a FULL second step runs unchecked, a
+  // partial one (the sequence's last tile) checked; the wave repeats both in the checked form if anything overflowed.
+  const bool own0 = wave < ntiles, own1 = wave + NSPLIT < ntiles;
+  const int nfull = (ntiles * 64 > kv_len) ? ntiles - 1 : ntiles;   // steps without a key mask
+  pass_begin();
+  if (own0) checked_tile(kf[0], vf[0], wave, true);
+  if (own1) {
+    ATTN_LANDED(0, 3);    // second tile
+    if (wave + NSPLIT < nfull) {
+      auto kfrag = [&](int t, int ks) { return kf[1][t][ks]; };
+      auto vfrag = [&](int t, int s, int dt) { return vf[1][t][s][dt]; };
+      fast_step(kfrag, vfrag, qf, minit, l_val, oacc);
+    } else {
+      checked_tile(kf[1], vf[1], wave + NSPLIT, false);
+    }
+  }
+  if (__builtin_amdgcn_ballot_w64(!accum_finite(l_val, oacc)) != 0) {   // wave-uniform; waves are independent until the merge
+    pass_begin();
+    load_k(0);
+    load_v(0);
+    load_k(1);
+    load_v(1);
+    if (own0) checked_tile(kf[0], vf[0], wave, true);
+    if (own1) checked_tile(kf[1], vf[1], wave + NSPLIT, false);
+  }
+
+  // ---- every wave parks its partial: [8 quads][64 lanes] f32x4 (lane-contiguous) + [64 lanes] (m, l) ----
+  {
+    const float l_w = add_xor32(l_val);   // the two key halves of a query meet once, here
+    f32x4* dq = (f32x4*)(red + wave * PART);
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      dq[g * 64 + lane] = f32x4{oacc[0][4 * g], oacc[0][4 * g + 1], oacc[0][4 * g + 2], oacc[0][4 * g + 3]};
+      dq[(4 + g) * 64 + lane] = f32x4{oacc[1][4 * g], oacc[1][4 * g + 1], oacc[1][4 * g + 2], oacc[1][4 * g + 3]};
+    }
+    *(f32x2*)(red + wave * PART + 64 * 32 + lane * 2) = f32x2{m_run, l_w};
+  }
+  ATTN_STAMP(4);
+  __syncthreads();
+  ATTN_STAMP(5);
+
+  // ---- wave w merges quad g = w of both d halves: wave 0's partial, then waves 1, 2, 3 folded in, in that order ----
+  char* stg = (char*)(red + NSPLIT * PART);
+  {
+    const int g = wave;
+    f32x4 o0 = ((const f32x4*)red)[g * 64 + lane], o1 = ((const f32x4*)red)[(4 + g) * 64 + lane];
+    const f32x2 ml0 = *(const f32x2*)(red + 64 * 32 + lane * 2);
+    float m_mrg = ml0[0], l_run = ml0[1];
+#pragma unroll
+    for (int w = 1; w < NSPLIT; ++w) {
+      const f32x4* sq = (const f32x4*)(red + w * PART);
+      const f32x2 ml = *(const f32x2*)(red + w * PART + 64 * 32 + lane * 2);
+      const float m_new = fmaxf(m_mrg, ml[0]);
+      // a wave that saw no tile has m = -inf, l = 0, O = 0: its factor is exp2(-inf) = 0 (m_new is finite because
+      // wave 0 always owns tile 0 when kv_len > 0)
+      const float fa = fast_exp2(m_mrg - m_new), fb = fast_exp2(ml[0] - m_new);
+      const f32x4 s0 = sq[g * 64 + lane], s1 = sq[(4 + g) * 64 + lane];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        o0[r] = o0[r] * fa + s0[r] * fb;
+        o1[r] = o1[r] * fa + s1[r] * fb;
+      }
+      l_run = l_run * fa + ml[1] * fb;
+      m_mrg = m_new;
+    }
+    // normalise; oacc[dt][4 g + r] = O[q = ql][d = 32 dt + r + 8 g + 4 hh] -> this wave's two 8-byte pieces of row ql
+    const float inv = l_run > 0.f ? 1.0f / l_run : 0.f;
+    *(bf16x4*)(stg + ql * 144 + 16 * g + 8 * hh) = f2bf4(o0[0] * inv, o0[1] * inv, o0[2] * inv, o0[3] * inv);
+    *(bf16x4*)(stg + ql * 144 + 64 + 16 * g + 8 * hh) = f2bf4(o1[0] * inv, o1[1] * inv, o1[2] * inv, o1[3] * inv);
+  }
+  __syncthreads();
+  // ---- the tile leaves as 4 instructions of 8 full 128-byte row segments each: one per wave ----
+  {
+    const int r = wave * 8 + (lane >> 3), c = lane & 7;
+    const int q_row = qt * 32 + r;
+    const uint4 v = *(const uint4*)(stg + r * 144 + c * 16);
+    if (q_row < a.rows_per_seq)
+      *(uint4*)(a.o + ((size_t)seq * a.rows_per_seq + q_row) * a.ldo + head * 64 + c * 8) = v;
+  }
+  ATTN_STAMP(6);
+  ATTN_TRACE_OUT();
 }
 
 
@@ -420,6 +671,16 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_lds_kernel(AttnArgs a) {
 
 }  // namespace
 
+// Diagnostics hook of the TOOLS build only (make tools-lib -> libf5e_hip_tools.so, -DF5E_TOOLS; tools/attn_timeline.py): while
+// buf != NULL the 4-way split launches of f5e_flash_attn run their stamped instantiation, which writes per workgroup and wave
+// 8 uint64: s_memtime at [0] entry, [1] Q landed, [2] first tile landed, [3] second tile landed, [4] at the merge barrier,
+// [5] past it, [6] last store issued ([7] unused; the general loop waits for Q and its first tile at once: [1] stays 0).
+// Process-wide, not for concurrent callers; the shipped library has no process-wide mutable state and does not export it.
+#ifdef F5E_TOOLS
+static unsigned long long* g_attn_trace = nullptr;
+extern "C" void f5e_debug_attn_trace(void* buf) { g_attn_trace = (unsigned long long*)buf; }
+#endif
+
 int f5e_flash_attn_pf(hipStream_t st, const void* q, const void* k, const void* v, void* o, int ldo, const int* kv_len,
                       int S, int H, int rows_per_seq, int n_pad, int splits, const F5ePrefetch* pf) {
   F5E_REQUIRE(q && k && v && o, "flash_attn: null pointer");
@@ -478,7 +739,27 @@ int f5e_flash_attn_pf(hipStream_t st, const void* q, const void* k, const void* 
     case 4: {
       const int npf = f5e_prefetch_wgs(pf);
       if (npf) a.pf = *pf;
-      hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(grid + npf), dim3(256), 0, st, a);
+      // every wave owns at most two key steps (N <= 512): the entry-loaded, four-wave-tail kernel; the general loop past it
+      const bool two_steps = (rows_per_seq + 63) / 64 <= 8;
+#ifdef F5E_TOOLS
+      // tools build only (tools/attn_timeline.py): F5E_ATTN_VARIANT=4 keeps the general loop at every size; while a trace
+      // buffer is set the stamped instantiation of whichever kernel is selected runs
+      static const int variant4 = getenv("F5E_ATTN_VARIANT") ? atoi(getenv("F5E_ATTN_VARIANT")) : 0;
+      a.trace = g_attn_trace;
+      if (a.trace || variant4 == 4) {
+        if (two_steps && variant4 != 4) {
+          if (a.trace) hipLaunchKernelGGL(attn_fwd_b1_kernel<true>, dim3(grid + npf), dim3(256), 0, st, a);
+          else hipLaunchKernelGGL(attn_fwd_b1_kernel<false>, dim3(grid + npf), dim3(256), 0, st, a);
+        } else if (a.trace) {
+          hipLaunchKernelGGL((attn_fwd_kernel<4, true>), dim3(grid + npf), dim3(256), 0, st, a);
+        } else {
+          hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(grid + npf), dim3(256), 0, st, a);
+        }
+        break;
+      }
+#endif
+      if (two_steps) hipLaunchKernelGGL(attn_fwd_b1_kernel<false>, dim3(grid + npf), dim3(256), 0, st, a);
+      else hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(grid + npf), dim3(256), 0, st, a);
       break;
     }
     default: F5E_REQUIRE(false, "flash_attn: splits must be 0 (auto), -1 (LDS-shared), 1, 2 or 4");

@@ -555,6 +555,8 @@ F5E_API int f5e_timer_read_ops(void* timer, int* ops_out_host, int max_out, int*
  * buf != NULL, f5e_convpos launches a build of its kernels that writes 8 timestamps per workgroup.  This is
  * process-wide mutable state, which is why the shipped libf5e_hip.so neither contains nor exports it. */
 F5E_API void f5e_debug_convpos_trace(void* buf);
+/* The same for the 4-way split launches of f5e_flash_attn (tools/attn_timeline.py): 8 timestamps per workgroup and wave. */
+F5E_API void f5e_debug_attn_trace(void* buf);
 #endif
 
 /* One DiT.sample evaluation for S = branches * B sequences (backbones/dit.py:452-470 after the cached embeddings). */

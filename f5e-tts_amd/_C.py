@@ -52,6 +52,8 @@ SIGNATURES = {
     "f5e_ctc_align_workspace_bytes": [_I, _I, _I, C.POINTER(C.c_ulonglong)],
     "f5e_ctc_align": [_P, _P, _LL, _I, _P, _I, _P, _P, _I, _P, _P, _P, _P, _P, C.c_ulonglong, _I, _I, _I, _I],
     "f5e_ctc_greedy": [_P, _P, _LL, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I],
+    "f5e_ctc_loss_workspace_bytes": [_I, _I, C.POINTER(C.c_ulonglong)],
+    "f5e_ctc_loss": [_P, _P, _LL, _I, _P, _I, _P, _P, _I, _P, _P, C.c_ulonglong, _I, _I, _I, _I],
     "f5e_ctc_beam_workspace_bytes": [_I, _I, _I, C.POINTER(C.c_ulonglong)],
     "f5e_ctc_beam": [_P, _P, _LL, _I, _P, _I, _I, _P, _I, _P, _P, _P, C.c_ulonglong, _I, _I, _I],
     "f5e_ctc_beam_state_bytes": [_I, _I, _I, _I, C.POINTER(C.c_ulonglong)],

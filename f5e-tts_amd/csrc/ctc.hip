@@ -1,7 +1,7 @@
-// CTC decoding on the device: forced alignment (f5e_ctc_align) and best-path search (f5e_ctc_greedy) over the scores of the
-// ASR model's CTC head.  Replaces the reference's host routes: wenet/utils/ctc_util.py::forced_align (a Python double loop
-// that builds a tensor per cell) and ASRModel.ctc_greedy_search (asr_model.py:416-459: log_softmax, topk, D2H, a Python
-// collapse per utterance).
+// CTC decoding on the device: forced alignment (f5e_ctc_align), best-path search (f5e_ctc_greedy) and the likelihood of a
+// transcript (f5e_ctc_loss) over the scores of the ASR model's CTC head.  Replaces the reference's host routes:
+// wenet/utils/ctc_util.py::forced_align (a Python double loop that builds a tensor per cell) and
+// ASRModel.ctc_greedy_search (asr_model.py:416-459: log_softmax, topk, D2H, a Python collapse per utterance).
 //
 // ---- f5e_ctc_align.  The extended sequence ext has S = 2 l + 1 states (blank, y0, blank, y1, ..., blank).
 //   alpha[0][0] = scores[0][blank], alpha[0][1] = scores[0][y0], everything else -inf;
@@ -30,6 +30,22 @@
 // max - logsumexp, the raw ids parked in `hyp`.  Kernel 2: one workgroup per sequence collapses its row in place (keep frame
 // t iff its id is not blank and differs from frame t-1's), compacting with ballot / popcount prefix sums, 1024 frames per
 // round in frame order (a kept id lands at or before its own frame, and a round reads its frames before it writes).
+//
+// ---- f5e_ctc_loss.  log P(labels | frames) = log of the sum over ALL CTC paths: wenet/transformer/ctc.py::CTC.forward
+// (torch.nn.CTCLoss, reduction "sum") per utterance and negated.  The recurrence of f5e_ctc_align with logaddexp in place
+// of max, on log-probabilities lp[t][v] = scores[t][v] - logsumexp(scores[t][:]):
+//   alpha[0][0] = lp[0][blank], alpha[0][1] = lp[0][y0], everything else -inf;
+//   alpha[t][s] = logaddexp(alpha[t-1][s], alpha[t-1][s-1], alpha[t-1][s-2] (skip allowed)) + lp[t][ext[s]],
+//   logp = logaddexp(alpha[t_len-1][S-1], alpha[t_len-1][S-2]),
+// fp32, logaddexp(a, b) = max + log1p(exp(-|a - b|)) applied pairwise ((stay, s-1), then s-2); two -inf give -inf.  "Skip
+// allowed" = ext[s] is a label, s >= 3 and the label differs from the one before it: adjacent equal labels are ordinary
+// input here (they need a blank between them), and l = 0 (S = 1, the all-blank path) is legal.
+// Kernel 1: one wave per frame < t_len writes logsumexp of the row into the workspace (max + log1p(sum over the OTHER
+// classes of exp(x - max)), as f5e_ctc_greedy's frame_logp; 0 for a row of -inf, which keeps its lp at -inf).  It is a launch
+// of its own because inside the serial kernel a V-wide reduction would sit on the dependent chain of every frame.
+// Kernel 2: the mapping of ctc_align_kernel (states dealt to lanes in runs of 64, wave_ror1 for s-1 and s-2, one wave up to
+// 256 states, beyond that up to 16 waves and the LDS pair with one barrier per row, emissions and the row's normaliser
+// fetched CTC_R rows ahead) without the decision words and the backtrack.
 #include "f5e_common.h"
 
 namespace {
@@ -315,6 +331,170 @@ __global__ __launch_bounds__(1024) void ctc_collapse_kernel(int* __restrict__ hy
   if (tid == 0) hyp_len[b] = count;
 }
 
+// ---------------------------------------------------------------- loss (sum over paths)
+
+__device__ __forceinline__ float ctc_logaddexp(float a, float b) {
+  const float m = fmaxf(a, b);
+  const float r = m + log1pf(expf(-fabsf(a - b)));   // one operand -inf: exp(-inf) = 0, r = m
+  return m == -__builtin_inff() ? m : r;             // both -inf: a - b is NaN, the sum of no paths is -inf
+}
+
+// one wave per frame < t_len: logsumexp over V into lse[b][t]
+__global__ __launch_bounds__(256) void ctc_frame_lse_kernel(const float* __restrict__ scores, long long batch_stride, int ld,
+                                                             const int* __restrict__ t_len_p, float* __restrict__ lse, int T,
+                                                             int V) {
+  const int lane = threadIdx.x & 63, t = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
+  if (t >= T || t >= t_len_p[b]) return;   // wave-uniform
+  const float* row = scores + (long long)b * batch_stride + (long long)t * ld;
+  float m = -__builtin_inff();
+  int arg = 0x7fffffff;
+  for (int v = lane; v < V; v += 64) {
+    const float x = row[v];
+    if (x > m) m = x, arg = v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oa = __shfl_xor(arg, o, 64);
+    if (om > m || (om == m && oa < arg)) m = om, arg = oa;
+  }
+  // the winner's own term is exactly 1: log1p of the rest keeps the bits that log(1 + eps) would drop on a confident frame
+  float sum = 0.f;
+  if (arg != 0x7fffffff)                   // wave-uniform; a row of -inf has no winner (x - m would be NaN)
+    for (int v = lane; v < V; v += 64) sum += v == arg ? 0.f : expf(row[v] - m);
+  sum = wave_sum(sum);
+  if (lane == 0) lse[(long long)b * T + t] = arg != 0x7fffffff ? m + log1pf(sum) : 0.f;
+}
+
+template <int CPT, bool MULTI>
+__global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_loss_kernel(
+    const float* __restrict__ scores, long long batch_stride, int ld, const int* __restrict__ labels, int ld_lab,
+    const int* __restrict__ t_len_p, const int* __restrict__ l_len_p, int blank, float* __restrict__ logp,
+    const float* __restrict__ lse, int T, int L, int V) {
+  __shared__ float edge[2][16][2];                   // alpha of the last / second-to-last state of every wave
+  __shared__ float fin[2];                           // alpha[t_len - 1][S - 1], [S - 2]
+  __shared__ int n_bad;                              // adjacent equal labels + labels outside [0, V)
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nt = blockDim.x;
+  const int t_len = t_len_p[b], l_len = l_len_p[b];
+  const int* lab = labels + (long long)b * ld_lab;
+  const float NEG = -__builtin_inff();
+
+  if (tid == 0) n_bad = 0, fin[0] = NEG, fin[1] = NEG;   // S = 1 has no state S - 2
+  __syncthreads();
+  const bool in_range = l_len >= 0 && l_len <= L && t_len >= 1 && t_len <= T;
+  int repeats = 0;
+  if (in_range) {
+    int bad = 0;
+    for (int i = tid; i < l_len; i += nt) {
+      const int y = lab[i];
+      if (y < 0 || y >= V) bad += 1 << 16;           // a label that is no class: no path (and no gather out of the row)
+      else if (i > 0 && y == lab[i - 1]) bad += 1;   // equal neighbours need a blank frame between them
+    }
+    if (bad) atomicAdd(&n_bad, bad);
+    __syncthreads();
+    repeats = n_bad;
+  }
+  if (!(in_range && repeats < (1 << 16) && t_len >= l_len + repeats)) {   // workgroup-uniform: no CTC path
+    if (tid == 0) logp[b] = NEG;
+    return;
+  }
+
+  const float* E = scores + (long long)b * batch_stride;
+  const float* N = lse + (long long)b * T;
+  const int S = 2 * l_len + 1;
+  int cls[CPT];
+  bool live[CPT], skip[CPT];
+#pragma unroll
+  for (int c = 0; c < CPT; ++c) {
+    const int s = (w * CPT + c) * 64 + lane;
+    live[c] = s < S;
+    const bool is_lab = live[c] && (s & 1);
+    const int y = is_lab ? lab[s >> 1] : blank;
+    cls[c] = y;
+    skip[c] = is_lab && s >= 3 && y != lab[(s >> 1) - 1];
+  }
+
+  float prev[CPT], cur[CTC_R][CPT], nxt[CTC_R][CPT], cur_n[CTC_R], nxt_n[CTC_R];
+#pragma unroll
+  for (int c = 0; c < CPT; ++c) prev[c] = NEG;
+
+  auto load_rows = [&](float (&dst)[CTC_R][CPT], float (&norm)[CTC_R], int t0) {
+#pragma unroll
+    for (int r = 0; r < CTC_R; ++r) {
+      const int t = min(t0 + r, t_len - 1);
+      const float* row = E + (long long)t * ld;
+      norm[r] = N[t];
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) dst[r][c] = row[cls[c]];
+    }
+  };
+
+  // x shifted by one state: out[s] = x[s - 1]; e = x of the last state of the wave to the left
+  auto shift = [&](const float (&x)[CPT], float e, float (&out)[CPT]) {
+    float rot[CPT];
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) rot[c] = wave_ror1(x[c]);
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) out[c] = lane > 0 ? rot[c] : (c > 0 ? rot[c > 0 ? c - 1 : 0] : e);
+  };
+
+  auto step = [&](int t, const float (&em)[CPT], float norm) {
+    if (t == 0) {
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) prev[c] = (w * CPT + c) * 64 + lane < 2 && live[c] ? em[c] - norm : NEG;
+    } else {
+      float e1 = NEG, e2 = NEG;
+      if (MULTI && w > 0) {
+        e1 = edge[(t + 1) & 1][w - 1][0];
+        e2 = edge[(t + 1) & 1][w - 1][1];
+      }
+      float p1[CPT], p2[CPT];
+      shift(prev, e1, p1);       // alpha[t-1][s-1]; state 0 gets e1 = -inf (it can only stay)
+      shift(p1, e2, p2);         // alpha[t-1][s-2]
+#pragma unroll
+      for (int c = 0; c < CPT; ++c) {
+        const float sum = ctc_logaddexp(ctc_logaddexp(prev[c], p1[c]), skip[c] ? p2[c] : NEG);
+        prev[c] = live[c] ? sum + (em[c] - norm) : NEG;
+      }
+    }
+    if (MULTI) {
+      if (lane == 63) edge[t & 1][w][0] = prev[CPT - 1];
+      if (lane == 62) edge[t & 1][w][1] = prev[CPT - 1];
+      __syncthreads();
+    }
+  };
+
+  auto steps = [&](int t0, const float (&rows)[CTC_R][CPT], const float (&norm)[CTC_R]) {
+#pragma unroll
+    for (int r = 0; r < CTC_R; ++r)
+      if (t0 + r < t_len) step(t0 + r, rows[r], norm[r]);   // workgroup-uniform
+  };
+  load_rows(cur, cur_n, 0);
+  for (int t0 = 0; t0 < t_len; t0 += 2 * CTC_R) {   // the two register sets swap roles: no copies
+    load_rows(nxt, nxt_n, t0 + CTC_R);
+    steps(t0, cur, cur_n);
+    load_rows(cur, cur_n, t0 + 2 * CTC_R);
+    steps(t0 + CTC_R, nxt, nxt_n);
+  }
+
+#pragma unroll
+  for (int c = 0; c < CPT; ++c) {
+    const int s = (w * CPT + c) * 64 + lane;
+    if (s == S - 1) fin[0] = prev[c];
+    if (s == S - 2) fin[1] = prev[c];
+  }
+  __syncthreads();
+  if (tid == 0) logp[b] = ctc_logaddexp(fin[0], fin[1]);
+}
+
+template <int CPT, bool MULTI>
+void ctc_loss_launch(hipStream_t st, int threads, const float* scores, long long batch_stride, int ld, const int* labels,
+                     int ld_lab, const int* t_len, const int* l_len, int blank, float* logp, const float* lse, int B, int T,
+                     int L, int V) {
+  hipLaunchKernelGGL((ctc_loss_kernel<CPT, MULTI>), dim3((unsigned)B), dim3((unsigned)threads), 0, st, scores, batch_stride,
+                     ld, labels, ld_lab, t_len, l_len, blank, logp, lse, T, L, V);
+}
+
 int ctc_w64(int L) { return (2 * L + 1 + 63) / 64; }
 
 }  // namespace
@@ -350,6 +530,40 @@ int f5e_ctc_align(hipStream_t st, const float* scores, long long batch_stride, i
   else CTC_GO(4, true, 64 * ((W64 + 3) / 4));
 #undef CTC_GO
   F5E_LAUNCH_CHECK("ctc_align");
+  return F5E_OK;
+}
+
+int f5e_ctc_loss_workspace_bytes(int B, int T, unsigned long long* bytes_out_host) {
+  F5E_REQUIRE(bytes_out_host, "ctc_loss_workspace_bytes: null output");
+  F5E_REQUIRE(B > 0 && T > 0 && T <= CTC_MAX_T, "ctc_loss_workspace_bytes: need B > 0 and 0 < T <= %d", CTC_MAX_T);
+  *bytes_out_host = (unsigned long long)B * (unsigned long long)T * 4ull;   // the normaliser of every frame
+  return F5E_OK;
+}
+
+int f5e_ctc_loss(hipStream_t st, const float* scores, long long batch_stride, int ld, const int* labels, int ld_labels,
+                 const int* t_len, const int* l_len, int blank, float* logp, void* workspace,
+                 unsigned long long workspace_bytes, int B, int T, int L, int V) {
+  F5E_REQUIRE(scores && (labels || L == 0) && t_len && l_len && logp && workspace, "ctc_loss: null operand");
+  F5E_REQUIRE(B > 0 && B <= 65535 && T > 0 && T <= CTC_MAX_T && L >= 0 && L <= CTC_MAX_L,
+              "ctc_loss: need 0 < B <= 65535, 0 < T <= %d and 0 <= L <= %d", CTC_MAX_T, CTC_MAX_L);
+  F5E_REQUIRE(V >= 2 && blank >= 0 && blank < V, "ctc_loss: need V >= 2 and 0 <= blank < V");
+  F5E_REQUIRE(ld >= V && ld_labels >= L && (B == 1 || batch_stride >= (long long)(T - 1) * ld + V),
+              "ctc_loss: ld / ld_labels / batch_stride too small");
+  F5E_REQUIRE(workspace_bytes >= (unsigned long long)B * T * 4ull && ((uintptr_t)workspace & 3) == 0,
+              "ctc_loss: workspace smaller than f5e_ctc_loss_workspace_bytes or not 4-byte aligned");
+  float* lse = (float*)workspace;
+  hipLaunchKernelGGL(ctc_frame_lse_kernel, dim3((unsigned)((T + 3) / 4), (unsigned)B), dim3(256), 0, st, scores, batch_stride,
+                     ld, t_len, lse, T, V);
+  const int W64 = ctc_w64(L);
+#define CTC_GO(CPT, MULTI, THREADS)                                                                                         \
+  ctc_loss_launch<CPT, MULTI>(st, THREADS, scores, batch_stride, ld, labels, ld_labels, t_len, l_len, blank, logp, lse, B, \
+                              T, L, V)
+  if (W64 == 1) CTC_GO(1, false, 64);
+  else if (W64 == 2) CTC_GO(2, false, 64);
+  else if (W64 <= 4) CTC_GO(4, false, 64);
+  else CTC_GO(4, true, 64 * ((W64 + 3) / 4));
+#undef CTC_GO
+  F5E_LAUNCH_CHECK("ctc_loss");
   return F5E_OK;
 }
 

@@ -4,7 +4,9 @@ resolution (flag > TOML > module default, including the ``x or default`` quirk t
 
 Beyond the reference: ``--mode tts|vc`` reach the PPG / codebook model family (``sample_tts`` through the same text
 chunking; ``--source_audio`` converted to the prompt's voice through ``utils_infer.infer_vc_process``), which the
-reference only drives from its eval scripts.  Without the new flags ``main`` does what it always did."""
+reference only drives from its eval scripts.  ``--best_of N`` draws N candidates per text chunk and keeps the one the ASR
+model's CTC head finds most consistent with the text (``--asr_model`` / ``--asr_config`` / ``--asr_dict``, the names of
+``speech_edit.py``; ``--seed`` makes the draw reproducible).  Without the new flags ``main`` does what it always did."""
 from __future__ import annotations
 
 import argparse
@@ -58,7 +60,32 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ppg_config", type=str, help="vc: PPG train.yaml (default: ppg_config.config of the model yaml)")
     p.add_argument("--ppg_stream", action="store_true",
                    help="vc: extract the PPGs chunk by chunk (for conversion models trained on streaming PPGs)")
+    p.add_argument("--best_of", type=int, default=1,
+                   help="cfg / tts: draw N candidates per text chunk and keep the one the ASR model scores highest "
+                        "(needs --asr_model, --asr_config and --asr_dict)")
+    p.add_argument("--seed", type=int, help="cfg / tts: candidate i of chunk c is sampled with seed + c * best_of + i, the "
+                                            "chunks counted through all [voice] segments of the text")
+    p.add_argument("--asr_model", type=str, help="best_of: ASR checkpoint with a CTC head (a PPG model's .pt)")
+    p.add_argument("--asr_config", type=str, help="best_of: the ASR model's train.yaml")
+    p.add_argument("--asr_dict", type=str, help="best_of: the ASR model's symbol table (`token id` lines)")
     return p
+
+
+def require_scorer_args(args: argparse.Namespace) -> None:
+    """--best_of is checked before anything is loaded."""
+    if args.best_of < 1:
+        raise SystemExit("--best_of must be at least 1")
+    if args.best_of > 1:
+        missing = [f"--{k}" for k in ("asr_model", "asr_config", "asr_dict") if not getattr(args, k)]
+        if missing:
+            raise SystemExit(f"--best_of {args.best_of} ranks the candidates with an ASR model: {', '.join(missing)} missing")
+
+
+def next_segment_seed(seed: int, n_chunks: int, best_of: int) -> int:
+    """``--seed`` numbers the candidates of the whole run: a ``[voice]`` segment of n chunks uses seed .. seed + n * best_of
+    - 1 (candidate i of its chunk c: seed + c * best_of + i), and the next segment starts behind them -- with the same seed
+    again, two segments would be sampled from identical noise."""
+    return seed + n_chunks * best_of
 
 
 # local vocoder directories when the config names none (reference infer_cli.py:264-267; no download here)
@@ -148,12 +175,15 @@ def split_voices(gen_text: str):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    require_scorer_args(args)
     config = {}
     if args.config:
         import tomli
         with open(args.config, "rb") as f:
             config = tomli.load(f)
     s = resolve_settings(args, config)
+    if s["mode"] == "vc" and args.best_of > 1:
+        raise SystemExit("--best_of is for text-to-speech (--mode cfg / tts); voice conversion has no text to score")
     if s["gen_file"]:
         with open(s["gen_file"], "r", encoding="utf-8") as f:
             s["gen_text"] = f.read()
@@ -176,6 +206,13 @@ def main(argv=None):
                          vocab_file=s["vocab_file"], device=s["device"], **family)
     if s["mode"] == "vc":
         return main_vc(s, mc, model, vocoder)
+    rank = {}
+    if args.best_of > 1 or args.seed is not None:
+        rank = dict(best_of=args.best_of, seed=args.seed, report=[])
+        if args.best_of > 1:
+            from ..ppg.ctc_align import CTCAligner
+            rank["scorer"] = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, s["device"])
+            rank["scorer"].warm()
     voices = dict(config.get("voices", {}))
     voices["main"] = {"ref_audio": s["ref_audio"], "ref_text": s["ref_text"]}
     for v in voices.values():   # reference infer_cli.py:297-303
@@ -188,7 +225,10 @@ def main(argv=None):
                                      cross_fade_duration=s["cross_fade_duration"], nfe_step=s["nfe_step"],
                                      cfg_strength=s["cfg_strength"], sway_sampling_coef=s["sway_sampling_coef"],
                                      speed=s["speed"], fix_duration=s["fix_duration"], device=s["device"],
-                                     mode=s["mode"], alpha_spk=s["alpha_spk"], alpha_txt=s["alpha_txt"])
+                                     mode=s["mode"], alpha_spk=s["alpha_spk"], alpha_txt=s["alpha_txt"], **rank)
+        if rank.get("seed") is not None:    # the next [voice] segment goes on where this one's chunks stopped
+            rank["seed"] = next_segment_seed(rank["seed"], len(rank["report"]), args.best_of)
+            rank["report"].clear()
         segments.append(seg)
         if s["save_chunk"]:
             os.makedirs(os.path.join(s["output_dir"], "chunks"), exist_ok=True)

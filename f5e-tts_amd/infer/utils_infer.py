@@ -12,6 +12,7 @@ the ASCII path is self-contained.
 from __future__ import annotations
 
 import hashlib
+import math
 import os
 import re
 import tempfile
@@ -278,15 +279,39 @@ def plan_batch(ref_audio_len: int, ref_text: str, gen_text: str, speed_: float, 
     return ref_audio_len + int(ref_audio_len / ref_text_len * gen_text_len / local_speed), local_speed
 
 
+def pick_best(scores) -> int:
+    """Index of the first maximum among the finite scores; NaN and -inf rank last; 0 when no score is finite."""
+    best, at = None, 0
+    for i, v in enumerate(scores):
+        if math.isfinite(v) and (best is None or v > best):
+            best, at = v, i
+    return at
+
+
 def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocoder, mel_spec_type="vocos", progress=None,
                         target_rms=0.1, cross_fade_duration=0.15, nfe_step=32, cfg_strength=2.0,
                         sway_sampling_coef=-1, speed=1, fix_duration=None, device=None, streaming=False,
-                        chunk_size=2048, mode="cfg", alpha_spk=2.5, alpha_txt=3.0):
+                        chunk_size=2048, mode="cfg", alpha_spk=2.5, alpha_txt=3.0, best_of=1, scorer=None, seed=None,
+                        report=None):
     """Generator like the reference's: yields (final_wave, sample_rate, combined_spectrogram) or, when streaming,
     (chunk, sample_rate) pieces.  mode "tts" (PPG / codebook models): ``sample_tts`` with alpha_spk / alpha_txt in place
-    of ``sample`` with cfg_strength (reference eval_infer_batch_tts.py:203-214)."""
+    of ``sample`` with cfg_strength (reference eval_infer_batch_tts.py:203-214).
+
+    Best-of-N (beyond the reference; off by default): ``best_of=N`` draws N candidates per text chunk, each its own batch-1
+    call with its own seed (one batch would be N copies: the sampler seeds every batch item alike), scores the N waveforms
+    in ONE ``scorer.score_batch(stack [N, n], 24000, gen_text)`` call against the chunk's own text (``ppg.ctc_align.
+    CTCAligner`` is such a scorer: log P(text | audio) under the ASR model's CTC head) and keeps the first maximum; NaN and
+    -inf rank last, and candidate 0 stays when no score is finite.  ``seed``: candidate i of chunk c runs with seed + c *
+    best_of + i; None draws the seeds from the global CPU generator on the calling thread, in submission order.
+    ``report``: a list that receives one dict per chunk, {"seeds", "scores", "chosen"}."""
     if mode not in ("cfg", "tts"):
         raise ValueError(f"infer_batch_process: mode {mode!r} (cfg / tts; voice conversion is infer_vc_process)")
+    best_of = int(best_of)
+    if best_of < 1:
+        raise ValueError(f"infer_batch_process: best_of must be at least 1 (got {best_of})")
+    if best_of > 1 and (scorer is None or not hasattr(scorer, "score_batch")):
+        raise ValueError("infer_batch_process: best_of > 1 needs a scorer with score_batch(waves, sr, text) "
+                         "(ppg.ctc_align.CTCAligner)")
     audio, sr = ref_audio
     if audio.shape[0] > 1:
         audio = torch.mean(audio, dim=0, keepdim=True)
@@ -326,9 +351,44 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
         wave_, generated = res
         return wave_.squeeze().cpu().numpy(), generated[0].cpu().numpy()
 
+    def draw_seed():
+        return int(torch.randint(0, 2 ** 31 - 1, (1,)).item())
+
+    def best_of_n(gen_text, seeds):
+        """N candidates of one chunk, one scorer call, the first maximum -> (what ``process_batch`` returns for the winner,
+        the chunk's report entry)."""
+        cands = [process_batch(gen_text, seed=s) for s in seeds]
+        stack = torch.stack([w.reshape(-1) for w, _ in cands]).to(torch.float32)
+        scores = [float(v) for v in torch.as_tensor(scorer.score_batch(stack, target_sample_rate, gen_text)).reshape(-1).tolist()]
+        chosen = pick_best(scores)
+        return cands[chosen], {"seeds": list(seeds), "scores": scores, "chosen": chosen}
+
+    # plain: the call that always existed, process_batch(gen_text) with the sampler's own noise draw; otherwise every
+    # candidate's seed is fixed here, on the calling thread, before any chunk runs
+    plain = best_of == 1 and seed is None
+    if not plain:
+        chunk_seeds = [[seed + c * best_of + i if seed is not None else draw_seed() for i in range(best_of)]
+                       for c in range(len(gen_text_batches))]
+
+    def run_chunk(c):
+        """-> (chunk c on the host, its report entry or None); callable from a worker thread: it touches no shared state."""
+        if plain:
+            return to_host(process_batch(gen_text_batches[c])), None
+        if best_of == 1:
+            return (to_host(process_batch(gen_text_batches[c], seed=chunk_seeds[c][0])),
+                    {"seeds": list(chunk_seeds[c]), "scores": [], "chosen": 0})
+        res, entry = best_of_n(gen_text_batches[c], chunk_seeds[c])
+        return to_host(res), entry
+
+    def note(entry):
+        """The report grows on the calling thread, in chunk order."""
+        if report is not None and entry is not None:
+            report.append(entry)
+
     if streaming:
-        for gen_text in gen_text_batches:
-            w, _ = to_host(process_batch(gen_text))
+        for c in range(len(gen_text_batches)):
+            (w, _), entry = run_chunk(c)
+            note(entry)
             for j in range(0, len(w), chunk_size):
                 yield w[j: j + chunk_size], target_sample_rate
         return
@@ -342,12 +402,22 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
     # this thread keeps the result independent of thread timing (a different noise stream than the serial default).
     workers = max(1, min(4, int(os.environ.get("F5E_INFER_WORKERS", "1"))))
     if workers == 1 or len(gen_text_batches) < 2:
-        results = [to_host(r) for r in [process_batch(g) for g in gen_text_batches]]
+        if plain:
+            results = [to_host(r) for r in [process_batch(g) for g in gen_text_batches]]
+        else:
+            results = []
+            for c in range(len(gen_text_batches)):
+                res, entry = run_chunk(c)
+                results.append(res)
+                note(entry)
     else:
-        seeds = [int(torch.randint(0, 2 ** 31 - 1, (1,)).item()) for _ in gen_text_batches]
+        # one work item per chunk, candidates included; a plain call draws its per-chunk seed here as it always did
+        work = [(g, draw_seed()) for g in gen_text_batches] if plain else list(range(len(gen_text_batches)))
         import threading
         tls = threading.local()
         main_stream = torch.cuda.current_stream()
+        if best_of > 1 and hasattr(scorer, "warm"):
+            scorer.warm()                                  # build its engine once, here, not once per worker that gets there first
 
         def on_own_stream(a):
             # the samplers run on the caller's current stream: every worker brings its own, ordered behind this thread's
@@ -355,10 +425,13 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
                 tls.stream = torch.cuda.Stream()
                 tls.stream.wait_stream(main_stream)
             with torch.cuda.stream(tls.stream):
-                return to_host(process_batch(*a))
+                return (to_host(process_batch(*a)), None) if plain else run_chunk(a)
 
         with ThreadPoolExecutor(max_workers=workers) as ex:
-            results = list(ex.map(on_own_stream, zip(gen_text_batches, seeds)))
+            done = list(ex.map(on_own_stream, work))       # in submission order, whichever worker finished first
+        results = [res for res, _ in done]
+        for _, entry in done:
+            note(entry)
     waves = [r[0] for r in results]
     specs = [r[1] for r in results]
     if waves:
@@ -370,7 +443,8 @@ def infer_batch_process(ref_audio, ref_text, gen_text_batches, model_obj, vocode
 def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_type=mel_spec_type, show_info=print,
                   progress=None, target_rms=target_rms, cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
                   cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed,
-                  fix_duration=fix_duration, device=device, mode="cfg", alpha_spk=2.5, alpha_txt=3.0):
+                  fix_duration=fix_duration, device=device, mode="cfg", alpha_spk=2.5, alpha_txt=3.0, best_of=1,
+                  scorer=None, seed=None, report=None):
     audio, sr = load_wav(ref_audio)
     secs = audio.shape[-1] / sr
     max_chars = int(len(ref_text.encode("utf-8")) / secs * (22 - secs))
@@ -381,7 +455,7 @@ def infer_process(ref_audio, ref_text, gen_text, model_obj, vocoder, mel_spec_ty
                                     cross_fade_duration=cross_fade_duration, nfe_step=nfe_step,
                                     cfg_strength=cfg_strength, sway_sampling_coef=sway_sampling_coef, speed=speed,
                                     fix_duration=fix_duration, device=device, mode=mode, alpha_spk=alpha_spk,
-                                    alpha_txt=alpha_txt))
+                                    alpha_txt=alpha_txt, best_of=best_of, scorer=scorer, seed=seed, report=report))
 
 
 # ----------------------------------------- voice conversion (reference eval_infer_batch_vc.py:214-238, utils_eval.py:284-336)

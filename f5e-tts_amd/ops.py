@@ -513,6 +513,44 @@ def ctc_greedy(scores: Tensor, t_len: Tensor, blank: int = 0, pad_id: int = -1, 
     return hyp, hyp_len, frame_logp
 
 
+def ctc_loss_workspace_bytes(B: int, T: int) -> int:
+    """Scratch bytes of ``ctc_loss`` for B sequences of up to T frames (host call)."""
+    n = C.c_ulonglong()
+    check(lib().f5e_ctc_loss_workspace_bytes(B, T, C.byref(n)), "f5e_ctc_loss_workspace_bytes")
+    return int(n.value)
+
+
+def ctc_loss(scores: Tensor, labels: Tensor, t_len: Tensor, l_len: Tensor, blank: int = 0, *,
+             logp: Optional[Tensor] = None, workspace: Optional[Tensor] = None) -> Tensor:
+    """CTC likelihood of a transcript (f5e_ctc_loss): scores f32 [B, T, V] as in ``ctc_align`` (raw logits or
+    log-probabilities, the kernel normalises every frame; only read), labels i32 [B, L] (L may be 0; adjacent equal labels
+    are fine), t_len / l_len i32 [B] on the device -> logp f32 [B] = log of the sum over all CTC paths =
+    ``-torch.nn.functional.ctc_loss(reduction="none")``; -inf for a sequence without a path.  No gradient.  workspace: a
+    device tensor of at least ``ctc_loss_workspace_bytes`` bytes (allocated here when None)."""
+    B, T, V = _ctc_scores(scores, "ctc_loss")
+    if labels.ndim != 2 or labels.shape[0] != B or (labels.shape[1] > 1 and labels.stride(1) != 1) or \
+            labels.dtype != I32 or not labels.is_cuda:
+        raise _C.F5EError(f"ctc_loss: labels must be an i32 GPU tensor [{B}, L] with unit label stride")
+    require_device()
+    L = labels.shape[1]
+    dev = scores.device
+    if logp is None:
+        logp = torch.empty(B, dtype=F32, device=dev)
+    if t_len.numel() != B or l_len.numel() != B or logp.shape != (B,):
+        raise _C.F5EError(f"ctc_loss: lengths [{B}], logp [{B}]")
+    need = ctc_loss_workspace_bytes(B, T)
+    if workspace is None:
+        workspace = torch.empty((need + 3) // 4, dtype=F32, device=dev)
+    nbytes = workspace.numel() * workspace.element_size()
+    # the stride of a size-1 dimension is arbitrary (0 for a NumPy new axis) and never used
+    ld, ld_labels = (scores.stride(1) if T > 1 else max(V, scores.stride(1))), (labels.stride(0) if B > 1 and L > 0 else L)
+    check(lib().f5e_ctc_loss(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0), ld,
+                             C.c_void_p(labels.data_ptr() if L > 0 else None), ld_labels, _p(t_len, I32, "t_len"),
+                             _p(l_len, I32, "l_len"), int(blank), _p(logp, F32, "logp"), _p(workspace, None, "workspace"),
+                             nbytes, B, T, L, V), "f5e_ctc_loss")
+    return logp
+
+
 def ctc_beam_workspace_bytes(B: int, T: int, beam: int) -> int:
     """Scratch bytes of ``ctc_beam_search`` for B sequences of up to T frames at beam size ``beam`` (host call)."""
     n = C.c_ulonglong()

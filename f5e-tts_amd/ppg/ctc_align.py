@@ -134,9 +134,10 @@ DECODE_MODES = ("ctc_greedy_search", "ctc_prefix_beam_search", "attention_rescor
 
 class CTCAligner:
     """``align(audio, sr, text)`` -> word-level timestamps; ``transcribe(audio, sr, mode=...)`` -> text (greedy by default;
-    ``attention_rescoring`` needs ``decoder=True`` or a model built with its attention decoder).  ``tokenize``: optional
-    ``text -> (words, ids per word)`` in place of ``default_tokenize`` (BPE models bring their own).  ``model`` /
-    ``symbol_table``: an already built ``ConformerPPG(ctc=True)`` and table instead of the three paths."""
+    ``attention_rescoring`` needs ``decoder=True`` or a model built with its attention decoder); ``score(audio, sr, text)``
+    / ``score_batch(waves, sr, text)`` -> log P(text | audio) under the CTC head, the ranking of best-of-N synthesis.
+    ``tokenize``: optional ``text -> (words, ids per word)`` in place of ``default_tokenize`` (BPE models bring their own).
+    ``model`` / ``symbol_table``: an already built ``ConformerPPG(ctc=True)`` and table instead of the three paths."""
 
     def __init__(self, ppg_model_path: Optional[str] = None, ppg_config: Optional[str] = None,
                  dict_path: Optional[str] = None, device="cuda", tokenize: Optional[Callable] = None, *, model=None,
@@ -254,3 +255,50 @@ class CTCAligner:
         if int(al.align[0, 0]) < 0:                                   # the kernel's "no path" row: never build spans from it
             raise _C.F5EError("CTCAligner.align: the text has no CTC path through this recording")
         return word_spans(words, ids, al.tok_end[0].cpu().tolist(), int(al.frame_lens[0]), total_s=secs)
+
+    def warm(self) -> None:
+        """Build what the first call would build lazily (the model's engine, the fbank's device buffers), on the calling
+        thread: worker threads that share this object then find it ready."""
+        self.model.engine()
+        if self.featCal.window.device.type != "cuda":
+            self.featCal.to(self.device)
+
+    def _labels(self, text: str, name: str) -> List[int]:
+        labels = [i for row in self.tokenize(text)[1] for i in row]
+        if not labels:
+            raise ValueError(f"CTCAligner.{name}: no character of the text is in the symbol table")
+        return labels
+
+    @torch.no_grad()
+    def score(self, audio, sr: Optional[int], text: str, use_linear: bool = False) -> float:
+        """log P(text | audio) in nats: the sum over ALL CTC paths of the text's tokens (``ConformerPPG.ctc_loss`` negated;
+        ``align`` gives the best single path).  -inf when the text has no path through the recording.  ``use_linear`` as in
+        ``ConformerPPG.ctc_greedy_search``: False scores what the reference decodes with, True what the CTC head was
+        trained on."""
+        labels = self._labels(text, "score")
+        feats, lens, _ = self._feats(audio, sr)
+        logits, frame_lens, _ = self.model._ctc_scores(feats, lens, use_linear)
+        return float(self._logp(logits, frame_lens, labels)[0])
+
+    def _logp(self, logits, frame_lens, labels: List[int]) -> torch.Tensor:
+        from .. import ops
+        N = logits.shape[0]
+        lab = torch.tensor([labels], dtype=torch.int32, device=logits.device).expand(N, -1).contiguous()
+        l_len = torch.full((N,), len(labels), dtype=torch.int32, device=logits.device)
+        return ops.ctc_loss(logits, lab, frame_lens, l_len, blank=0)
+
+    @torch.no_grad()
+    def score_batch(self, waves: torch.Tensor, sr: int, text: str, use_linear: bool = False) -> torch.Tensor:
+        """``score`` for N waveforms of one length against ONE text: waves f32 [N, n] on the device -> log-likelihoods f32
+        [N] on the device (nothing is copied to the host: the caller decides when to wait).  One pass: device resampler,
+        fbank, the encoder at batch N, f5e_ctc_loss.  This method is the scorer protocol of
+        ``infer.utils_infer.infer_batch_process(best_of=N, scorer=...)``: any object that has it can rank candidates."""
+        from ..infer import audio as A
+        if not (torch.is_tensor(waves) and waves.ndim == 2 and waves.is_cuda):
+            raise _C.F5EError("CTCAligner.score_batch: waves must be a GPU tensor [N, n]; there is no CPU path")
+        labels = self._labels(text, "score_batch")
+        audio = A.resample_device(waves.to(torch.float32), sr, 16000)
+        feats, _ = self.featCal(audio)                                # equal lengths: every row has all the frames
+        lens = torch.full((feats.shape[0],), feats.shape[1], dtype=torch.int64)   # host values, as the encoder wants them
+        logits, frame_lens, _ = self.model._ctc_scores(feats, lens, use_linear)
+        return self._logp(logits, frame_lens, labels)

@@ -251,6 +251,23 @@ def check_ctc_lengths(labels, label_lengths, frame_lens, L: int, vocab: Optional
                               f"labels + adjacent repeats ({l} + {rep}) <= encoder frames ({t})")
 
 
+def check_ctc_loss_lengths(labels, label_lengths, frame_lens, L: int, vocab: Optional[int] = None) -> None:
+    """``check_ctc_lengths`` for the CTC likelihood, where an empty transcript and adjacent equal labels are ordinary input:
+    0 <= l <= L and frames >= max(1, l + adjacent equal labels) (device lengths get -inf from the kernel instead).
+    ``frame_lens=None``: what can be said before the encoder ran (the label lengths and the id range)."""
+    for b, l in enumerate(label_lengths):
+        l = int(l)
+        row = [int(v) for v in labels[b][:max(l, 0)]] if labels is not None else []
+        if vocab is not None and any(not 0 <= v < vocab for v in row):
+            raise _C.F5EError(f"ctc_loss: sequence {b} has no CTC path: label ids must lie in [0, {vocab})")
+        rep = sum(1 for i in range(1, len(row)) if row[i] == row[i - 1])
+        if not 0 <= l <= L:
+            raise _C.F5EError(f"ctc_loss: sequence {b} has no CTC path: need 0 <= labels ({l}) <= {L}")
+        if frame_lens is not None and int(frame_lens[b]) < max(1, l + rep):
+            raise _C.F5EError(f"ctc_loss: sequence {b} has no CTC path: need labels + adjacent repeats ({l} + {rep}) <= "
+                              f"encoder frames ({int(frame_lens[b])}) and at least one frame")
+
+
 class ConformerPPG(nn.Module):
     """The part of the reference ``ASRModel`` that ``extract`` touches (asr_model.py:221-244), same state_dict names:
     ``encoder.*``, ``linear.*``, ``ce.fc.*``.  Decoder keys of a checkpoint are not on this path and are skipped by
@@ -341,10 +358,11 @@ class ConformerPPG(nn.Module):
             return eng.head(eng.forward_chunk_by_chunk(speech, 16, 17))
         return self.engine().forward(speech, speech_lengths)
 
-    def _require_ctc(self) -> "ConformerEngine":
+    def _require_ctc(self, engine: bool = True) -> Optional["ConformerEngine"]:
+        """``engine=False``: only the check, for callers that validate more on the host before the engine is built."""
         if not self.has_ctc:
             raise _C.F5EError("PPG extractor: built without the CTC head (ConformerPPG(ctc=True) / build_ppg_model(ctc=True))")
-        return self.engine()
+        return self.engine() if engine else None
 
     def _check_decoding(self, speech: Tensor, decoding_chunk_size: int, simulate_streaming: bool) -> bool:
         """The reference's encoder choice (asr_model.py:281-307) as far as it is built, checked on the host before anything
@@ -436,6 +454,59 @@ class ConformerPPG(nn.Module):
         l_len = torch.as_tensor(label_lengths, dtype=I32).to(dev)
         out = ops.ctc_align(logits, labels.to(dev, I32).contiguous(), frame_lens, l_len, blank=0)
         return CTCAlignment(*out, frame_lens)
+
+    @staticmethod
+    def _ctc_text(text, text_lengths, B: int, name: str):
+        """ids as a [B, L] tensor or a list of lists -> (labels i32 [B, L] tensor, lengths: list or tensor [B]); shapes checked."""
+        if not torch.is_tensor(text):
+            rows = [list(r) for r in text]
+            if text_lengths is None:
+                text_lengths = [len(r) for r in rows]
+            elif len(text_lengths) == len(rows) and not (torch.is_tensor(text_lengths) and text_lengths.is_cuda):
+                for b, (n, r) in enumerate(zip(text_lengths, rows)):      # the padding below is the blank id, not a label
+                    if int(n) > len(r):
+                        raise _C.F5EError(f"{name}: text_lengths[{b}] = {int(n)} exceeds the {len(r)} ids of row {b}")
+            L = max([len(r) for r in rows] + [0])
+            text = torch.tensor([r + [0] * (L - len(r)) for r in rows], dtype=I32).reshape(len(rows), L)
+        if text_lengths is None and text.ndim == 2:
+            text_lengths = [text.shape[1]] * text.shape[0]
+        if text.ndim != 2 or text.shape[0] != B or len(text_lengths) != B:
+            raise _C.F5EError(f"{name}: text [B, L] and text_lengths [B] for a batch of {B}")
+        return text, text_lengths
+
+    @torch.no_grad()
+    def ctc_loss(self, speech: Tensor, speech_lengths: Tensor, text, text_lengths=None, use_linear: bool = True,
+                 reduce: bool = True) -> Tensor:
+        """The eval-mode value of the reference's CTC branch (asr_model.py:146-151, 170-172 with wenet/transformer/ctc.py:32-50):
+        encoder, ``linear`` (the training forward applies it before the CTC head, hence ``use_linear=True`` here, unlike the
+        decode methods), ``ctc_lo``, then the CTC loss, summed over all paths on the device (f5e_ctc_loss) straight from the
+        logits.  ``reduce=True``: ``sum_b(-logp[b]) / B``, a 0-d device tensor -- ``CTC.forward``'s "sum, then batch-size
+        average"; ``reduce=False``: ``-logp`` f32 [B] (+inf for an utterance without a CTC path).
+
+        ``text``: ids, a [B, L] tensor or a list of lists; entries past ``text_lengths`` are ignored, whatever they hold (the
+        reference pads with -1).  An empty transcript and adjacent equal ids are legal.  Lengths that start on the host are
+        validated there (F5EError) before anything touches the device; device lengths that admit no path give +inf.
+
+        No gradient is offered: this is a score, not a training loss."""
+        assert speech.shape[0] == speech_lengths.shape[0]
+        self._require_ctc(engine=False)
+        B = speech.shape[0]
+        text, text_lengths = self._ctc_text(text, text_lengths, B, "ctc_loss")
+        host = None
+        if not (torch.is_tensor(text_lengths) and text_lengths.is_cuda):
+            # every length that starts on the host is validated there, with the ids when they are host values too: first
+            # what does not need the encoder's frame counts, then (below) the path condition against them
+            host = (None if text.is_cuda else text.tolist(),
+                    text_lengths.tolist() if torch.is_tensor(text_lengths) else [int(v) for v in text_lengths])
+            check_ctc_loss_lengths(*host, None, text.shape[1], self.vocab_size)
+        logits, frame_lens, lens_host = self._ctc_scores(speech, speech_lengths, use_linear)
+        if host is not None:
+            check_ctc_loss_lengths(*host, lens_host.tolist(), text.shape[1], self.vocab_size)
+        dev = logits.device
+        l_len = torch.as_tensor(text_lengths, dtype=I32).to(dev)
+        labels = text.to(dev, I32).contiguous()
+        nll = -ops.ctc_loss(logits, labels, frame_lens, l_len, blank=0)
+        return nll.sum() / B if reduce else nll
 
     def _require_decoder(self, reverse_weight: float = 0.0) -> "ConformerEngine":
         if self.decoder_type is None:

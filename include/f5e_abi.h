@@ -273,6 +273,24 @@ F5E_API int f5e_ctc_align(f5e_stream st, const float* scores, long long batch_st
 F5E_API int f5e_ctc_greedy(f5e_stream st, const float* scores, long long batch_stride, int ld, const int* t_len, int blank,
                    int pad_id, int* hyp, int* hyp_len, float* frame_logp, int B, int T, int V);
 
+/* CTC likelihood of a transcript (csrc/ctc.hip; reference ppg/wenet/transformer/ctc.py::CTC.forward, i.e.
+ * torch.nn.CTCLoss, per utterance and negated).  scores / labels / t_len / l_len: the layout and meaning of f5e_ctc_align
+ * (lengths are DEVICE int [B]; scores is only read), raw logits OR log-probabilities: every frame is normalised here
+ * (x - logsumexp of its row), so both give the same value up to rounding.  logp f32 [B] = log of the sum over ALL CTC paths
+ * of labels[b][:l_len] through frames [0, t_len) = -CTCLoss(reduction "none"): the forward recurrence over the
+ * blank-interleaved sequence (S = 2 l + 1 states; stay, s-1, and s-2 where the label differs from the one before it) in
+ * fp32 with logaddexp = max + log1p(exp(-|d|)); true -inf log-probabilities are legal and never give NaN.  Adjacent equal
+ * labels are ordinary input (they need t_len >= l_len + repeats); l_len = 0 is legal (the all-blank path, the sum of the
+ * blank log-probabilities; L = 0 with labels NULL too).  A sequence without a path (t_len < l_len + repeats, a label outside
+ * [0, V), l_len < 0 or > L, t_len < 1 or > T) gets -inf, where torch returns +inf loss; the other sequences are untouched.
+ * workspace: f5e_ctc_loss_workspace_bytes(B, T) bytes (f32 [B][T], the normaliser of every frame, written by a first launch
+ * of one wave per frame) of caller-owned scratch, 4-byte aligned, contents irrelevant.  T <= 16384, L <= 2047, B <= 65535.
+ * No gradient.  No allocation, no synchronisation. */
+F5E_API int f5e_ctc_loss_workspace_bytes(int B, int T, unsigned long long* bytes_out_host);
+F5E_API int f5e_ctc_loss(f5e_stream st, const float* scores, long long batch_stride, int ld, const int* labels, int ld_labels,
+                 const int* t_len, const int* l_len, int blank, float* logp, void* workspace,
+                 unsigned long long workspace_bytes, int B, int T, int L, int V);
+
 /* CTC prefix beam search (csrc/ctc_beam.hip; reference ppg/asr_model.py:461-546, batched, on the device).  scores f32
  * [B][T][V] in the layout of f5e_ctc_align, raw logits OR log-probabilities: every frame is normalised here as
  * (x - max) - log1p(sum over the other classes of exp(x - max)), so both give the same lists and scores.  t_len: DEVICE

@@ -77,6 +77,12 @@ SIGNATURES = {
     "f5e_mha_f32": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F],
     "f5e_attn_decode_f32": [_P, _P, _I, _P, _P, _LL, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F],
     "f5e_beam_step": [_P, _P, _LL, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I],
+    "f5e_layer_mix_inorm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
+    "f5e_res2_dconv": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],
+    "f5e_time_stats": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I],
+    "f5e_se_scale": [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I],
+    "f5e_bias_tanh": [_P, _P, _I, _P, _I, _I, _I, _I, _I],
+    "f5e_attn_stats_pool": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I],
     "f5e_dit_forward": [_P, _P],
     "f5e_sample_loop": [_P, _P],
     "f5e_workspace_bytes": [_P, _P],

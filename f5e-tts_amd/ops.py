@@ -1069,6 +1069,120 @@ def mha_f32(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float, B: int = 
     return out
 
 
+# ---- ECAPA-TDNN speaker encoder (csrc/ecapa.hip) ----
+
+RES2_TILE = 16   # output frames per workgroup of f5e_res2_dconv (RES2_TT of csrc/ecapa.hip)
+
+
+def _btc(t: Tensor, name: str, vec: int = 4):
+    """(pointer, row stride, B, T, C) of a channels-last f32 [B, T, C] view whose frames are evenly spaced over the whole
+    batch (stride(0) == T * stride(1)): a contiguous tensor or a column slice of one."""
+    if t.ndim != 3 or min(t.shape) < 1:
+        raise _C.F5EError(f"{name} must be a non-empty [B, T, C] tensor (got shape {tuple(t.shape)})")
+    B, T, Cc = t.shape
+    ld = t.stride(1) if T > 1 else (t.stride(0) if B > 1 else Cc)   # the stride of a size-1 dimension is arbitrary
+    if (Cc > 1 and t.stride(2) != 1) or (B > 1 and t.stride(0) != T * ld):
+        raise _C.F5EError(f"{name}: need unit channel stride and evenly spaced frames (strides {tuple(t.stride())})")
+    p, ld = _rows(t.as_strided((B * T, Cc), (ld, 1)), (F32,), name, Cc, vec=vec)
+    return p, ld, B, T, Cc
+
+
+def _len(length: Optional[Tensor], B: int, name: str):
+    if length is None:
+        return None
+    if not length.is_cuda or length.dtype != I32 or length.shape != (B,):
+        raise _C.F5EError(f"{name}: lengths must be an i32 GPU tensor [{B}] (got {length.dtype} {tuple(length.shape)} on "
+                          f"{length.device})")
+    return _p(length, I32, "lengths")
+
+
+def layer_mix_inorm(hs: Tensor, feature_weight: Tensor, lengths: Optional[Tensor], x: Tensor, mask: Tensor):
+    """f5e_layer_mix_inorm: hs f32 [L, B, T, F] -> x f32 [B, T, F] (softmax-weighted layer mix + 1e-6, instance norm over
+    t < lengths[b], zero beyond) and mask f32 [B, T] (1 where t < lengths[b])."""
+    if hs.ndim != 4:
+        raise _C.F5EError(f"layer_mix_inorm: hs must be [L, B, T, F] (got {tuple(hs.shape)})")
+    L, B, T, F = hs.shape
+    if feature_weight.shape != (L,) or x.shape != (B, T, F) or mask.shape != (B, T):
+        raise _C.F5EError(f"layer_mix_inorm: feature_weight [{L}], x [{B}, {T}, {F}], mask [{B}, {T}] (got "
+                          f"{tuple(feature_weight.shape)}, {tuple(x.shape)}, {tuple(mask.shape)})")
+    require_device()
+    check(lib().f5e_layer_mix_inorm(_stream(), _p(hs, F32, "hs"), _p(feature_weight, F32, "feature_weight"),
+                                    _len(lengths, B, "layer_mix_inorm"), _p(x, F32, "x"), _p(mask, F32, "mask"),
+                                    L, B, T, F), "f5e_layer_mix_inorm")
+    return x, mask
+
+
+def res2_dconv(x: Tensor, y: Tensor, w_packed: Tensor, bias: Tensor, bn_scale: Tensor, bn_shift: Tensor,
+               lengths: Optional[Tensor], dilation: int, first: int = 0, count: int = 7):
+    """f5e_res2_dconv: steps [first, first + count) of the Res2 chain on x f32 [B, T, 8 w] -> y (same shape, no aliasing);
+    w_packed f32 [7, w, 3 w] (k = tap * w + ic), bias / bn_scale / bn_shift f32 [7, w]."""
+    xp, ldx, B, T, Cc = _btc(x, "res2_dconv: x", vec=1)
+    yp, ldy, By, Ty, Cy = _btc(y, "res2_dconv: y", vec=1)
+    w = Cc // 8
+    if (By, Ty, Cy) != (B, T, Cc) or w_packed.shape != (7, w, 3 * w) or any(t.shape != (7, w) for t in (bias, bn_scale, bn_shift)):
+        raise _C.F5EError(f"res2_dconv: y like x {tuple(x.shape)}, w_packed [7, {w}, {3 * w}], bias / bn_scale / bn_shift "
+                          f"[7, {w}]")
+    require_device()
+    check(lib().f5e_res2_dconv(_stream(), xp, ldx, yp, ldy, _p(w_packed, F32, "w_packed"), _p(bias, F32, "bias"),
+                               _p(bn_scale, F32, "bn_scale"), _p(bn_shift, F32, "bn_shift"),
+                               _len(lengths, B, "res2_dconv"), B, T, Cc, int(dilation), int(first), int(count)),
+          "f5e_res2_dconv")
+    return y
+
+
+def time_stats(x: Tensor, lengths: Optional[Tensor], mean: Tensor, std: Optional[Tensor] = None):
+    """f5e_time_stats: mean over t < lengths[b] of x f32 [B, T, C] -> mean f32 [B, C]; std (optional, same row stride as
+    mean) = sqrt(unbiased variance + 1e-10).  mean / std may be column slices of one [B, >= C] buffer."""
+    xp, ldx, B, T, Cc = _btc(x, "time_stats: x")
+    mp, ldm = _rows(mean, (F32,), "time_stats: mean", Cc)
+    sp = None
+    if std is not None:
+        sp, lds = _rows(std, (F32,), "time_stats: std", Cc)
+        if lds != ldm or std.shape[0] != B:
+            raise _C.F5EError("time_stats: std must share mean's row stride and row count")
+    if mean.shape[0] != B:
+        raise _C.F5EError(f"time_stats: mean must have {B} rows")
+    require_device()
+    check(lib().f5e_time_stats(_stream(), xp, ldx, _len(lengths, B, "time_stats"), mp, sp, ldm, B, T, Cc), "f5e_time_stats")
+    return mean, std
+
+
+def se_scale(x: Tensor, gate: Tensor, resid: Tensor, out: Tensor):
+    """f5e_se_scale: out = x * sigmoid(gate[b]) + resid; x / resid / out f32 [B, T, C] views, gate f32 [B, C] logits."""
+    xp, ldx, B, T, Cc = _btc(x, "se_scale: x")
+    rp, ldr, *rs = _btc(resid, "se_scale: resid")
+    op, ldo, *os_ = _btc(out, "se_scale: out")
+    if rs != [B, T, Cc] or os_ != [B, T, Cc] or gate.shape != (B, Cc):
+        raise _C.F5EError(f"se_scale: resid / out like x {tuple(x.shape)}, gate [{B}, {Cc}]")
+    require_device()
+    check(lib().f5e_se_scale(_stream(), xp, ldx, _p(gate, F32, "gate"), rp, ldr, op, ldo, B, T, Cc), "f5e_se_scale")
+    return out
+
+
+def bias_tanh(x: Tensor, add: Tensor):
+    """f5e_bias_tanh: x f32 [B, T, N] <- tanh(x + add[b]) in place; add f32 [1, N] or [B, N]."""
+    xp, ldx, B, T, N = _btc(x, "bias_tanh: x", vec=1)
+    ap, lda = _rows(add, (F32,), "bias_tanh: add", N, vec=1)
+    if add.shape[0] not in (1, B):
+        raise _C.F5EError(f"bias_tanh: add must have 1 or {B} rows")
+    require_device()
+    check(lib().f5e_bias_tanh(_stream(), xp, ldx, ap, lda, add.shape[0], B, T, N), "f5e_bias_tanh")
+    return x
+
+
+def attn_stats_pool(x: Tensor, logits: Tensor, lengths: Optional[Tensor], out: Tensor):
+    """f5e_attn_stats_pool: x, logits f32 [B, T, C] -> out f32 [B, 2 C] = [weighted mean | weighted std], the weights being
+    the softmax of the logits over t < lengths[b]."""
+    xp, ldx, B, T, Cc = _btc(x, "attn_stats_pool: x")
+    lp, ldl, *ls = _btc(logits, "attn_stats_pool: logits")
+    if ls != [B, T, Cc] or out.shape != (B, 2 * Cc):
+        raise _C.F5EError(f"attn_stats_pool: logits like x {tuple(x.shape)}, out [{B}, {2 * Cc}]")
+    require_device()
+    check(lib().f5e_attn_stats_pool(_stream(), xp, ldx, lp, ldl, _len(lengths, B, "attn_stats_pool"), _p(out, F32, "out"),
+                                    B, T, Cc), "f5e_attn_stats_pool")
+    return out
+
+
 def dit_forward(plan: "_C.DitPlan"):
     require_device()
     check(lib().f5e_dit_forward(_stream(), C.byref(plan)), "f5e_dit_forward")

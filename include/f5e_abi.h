@@ -603,6 +603,57 @@ typedef struct f5e_loop_plan {
 } f5e_loop_plan;
 F5E_API int f5e_sample_loop(f5e_stream st, const f5e_loop_plan* loop);
 
+/* ---------------------------------------------------------------- ECAPA-TDNN speaker encoder (csrc/ecapa.hip) */
+/* The head of the reference's SIM metric (eval/ecapa_tdnn.py, eval/utils_eval.py::run_sim) from the stack of WavLM hidden
+ * states to the embedding.  Channels-last f32 [B][T][C]; len = DEVICE int [B] or NULL (every row has T frames), clamped to
+ * [0, T].  Frames t >= len[b] are written as ZERO by every op below and are left out of every statistic, so row b of a padded
+ * batch equals the B = 1 run on its first len[b] frames whatever the padding holds (finite or not: it is never read by
+ * f5e_layer_mix_inorm, and every later tensor is zero there).  The 1x1 / k5 convolutions and the linears are f5e_gemm_f32
+ * (+ f5e_im2col) with BatchNorm(eval) folded into ch_scale / addend and `mask` as row_scale.  No allocation, no
+ * synchronisation, nothing read back: all of it is capturable. */
+
+/* x[b][t][f] = InstanceNorm_t(sum_l softmax(feature_weight)_l * hs[l][b][t][f] + 1e-6)   (ecapa_tdnn.py:284-295): biased
+ * variance about the mean over t < len[b], eps 1e-5, no affine.  hs f32 [L][B][T][F] is read ONCE (first launch: mix,
+ * written to x); the statistics come from the mixed values (second launch, in place on x).  mask f32 [B][T] = t < len[b].
+ * L <= 256, F % 4 == 0, hs and x 16-byte aligned. */
+F5E_API int f5e_layer_mix_inorm(f5e_stream st, const float* hs, const float* feature_weight, const int* len, float* x,
+                        float* mask, int L, int B, int T, int F);
+
+/* Steps [first, first + count) of Res2Conv1dReluBn (ecapa_tdnn.py:37-53; scale 8, so C = 8 w): for i = 0..6
+ * sp = x_i (i = 0) or sp + x_i;  sp = bn_i(relu(conv_i(sp)));  y_i = sp;  and y_7 = x_7 (written when first + count = 7),
+ * x_i / y_i = columns [i w, (i + 1) w).  conv_i: w -> w, 3 taps at `dilation`, zero padded; frames outside [0, len[b]) are
+ * zero at EVERY step.  w_packed f32 [7][w][3 w] with k = tap * w + ic; bias / bn_scale / bn_shift f32 [7][w].  One launch:
+ * a workgroup owns 16 output frames and recomputes a halo of count * dilation frames per side, so T is unbounded; the step
+ * weights and two [16 + 2 count dilation][w] images live in LDS, which bounds w (160 KiB: w = 64 takes 89 KiB at
+ * dilation 4; w = 128 does not fit).  first > 0 reads y_{first-1} of an EARLIER launch (seven launches of one step each
+ * give the same bits).  x and y must not alias.  C % 8 == 0. */
+F5E_API int f5e_res2_dconv(f5e_stream st, const float* x, int ldx, float* y, int ldy, const float* w_packed, const float* bias,
+                   const float* bn_scale, const float* bn_shift, const int* len, int B, int T, int C, int dilation,
+                   int first, int count);
+
+/* mean[b][c] = mean over t < len[b] of x[b][t][c]  (SE_Connect, ecapa_tdnn.py:81); std_out (NULL to skip) =
+ * sqrt(unbiased variance + 1e-10) (the global context of AttentiveStatsPool, :148-149; len < 2 gives 1e-5, where torch
+ * gives NaN).  mean / std_out rows have stride ld_out.  C, ldx, ld_out multiples of 4, 16-byte aligned. */
+F5E_API int f5e_time_stats(f5e_stream st, const float* x, int ldx, const int* len, float* mean, float* std_out, int ld_out,
+                   int B, int T, int C);
+
+/* out[b][t][c] = x[b][t][c] * sigmoid(gate[b][c]) + resid[b][t][c]   (ecapa_tdnn.py:83-84, :127); gate f32 [B][C] holds
+ * the LOGITS of SE_Connect.linear2.  C and every ld a multiple of 4, 16-byte aligned. */
+F5E_API int f5e_se_scale(f5e_stream st, const float* x, int ldx, const float* gate, const float* resid, int ldr, float* out,
+                 int ldo, int B, int T, int C);
+
+/* x[b][t][j] = tanh(x[b][t][j] + add[add_rows == 1 ? 0 : b][j]) in place   (ecapa_tdnn.py:155: the bias of pooling.linear1,
+ * plus, with global_context_att, the row's constant context term).  add_rows = 1 or B. */
+F5E_API int f5e_bias_tanh(f5e_stream st, float* x, int ldx, const float* add, int ld_add, int add_rows, int B, int T, int N);
+
+/* Attentive statistics pooling (ecapa_tdnn.py:157-161): alpha = softmax over t < len[b] of logits[b][t][c];
+ * out[b] = [sum alpha x | sqrt(clamp(sum alpha x^2 - mean^2, min = 1e-9))], f32 [B][2 C].  One pass with an online softmax
+ * (running maximum, rescaled sums), so logits of any finite size neither overflow nor lose the row; the second moment is
+ * carried about the running weighted mean (the same quantity without the cancellation of the two sums).  len = 0 gives
+ * [0 | sqrt(1e-9)].  C, ldx, ldl multiples of 4, 16-byte aligned. */
+F5E_API int f5e_attn_stats_pool(f5e_stream st, const float* x, int ldx, const float* logits, int ldl, const int* len,
+                        float* out, int B, int T, int C);
+
 /* ---------------------------------------------------------------- hipGraph capture --------------------------- */
 F5E_API int f5e_graph_begin(f5e_stream st);
 F5E_API int f5e_graph_end(f5e_stream st, void** graph_exec_out);

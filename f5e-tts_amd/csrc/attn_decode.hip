@@ -113,13 +113,6 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(const float* __restrict
   }
 }
 
-// order-preserving float -> unsigned key; NaN ranks as -inf
-__device__ __forceinline__ unsigned step_key(float v) {
-  if (v != v) v = -__builtin_inff();
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 __global__ __launch_bounds__(1024) void beam_step_kernel(const float* __restrict__ logits, long long ld_logits, float* score,
                                                           const int* __restrict__ hyp_in, const int* __restrict__ anc_in,
                                                           int* __restrict__ hyp_out, int* __restrict__ anc_out, int ld,
@@ -140,7 +133,7 @@ __global__ __launch_bounds__(1024) void beam_step_kernel(const float* __restrict
     if (finished) {
       if (lane < K) {
         const float v = lane == 0 ? sc : NEG;
-        c_val[w * K + lane] = v, c_key[w * K + lane] = step_key(v), c_cls[w * K + lane] = eos;
+        c_val[w * K + lane] = v, c_key[w * K + lane] = rank_key(v), c_cls[w * K + lane] = eos;
       }
     } else {
       const float* row = logits + r * ld_logits;
@@ -169,7 +162,7 @@ __global__ __launch_bounds__(1024) void beam_step_kernel(const float* __restrict
         if (lane == 0) {
           const bool none = arg == 0x7fffffff;   // fewer than K comparable values (NaN in the row)
           const float v = none ? NEG : sc + ((m - m0) - lse);
-          c_val[w * K + k] = v, c_key[w * K + k] = step_key(v), c_cls[w * K + k] = none ? eos : arg;
+          c_val[w * K + k] = v, c_key[w * K + k] = rank_key(v), c_cls[w * K + k] = none ? eos : arg;
         }
         pv = m, pi = arg;
       }

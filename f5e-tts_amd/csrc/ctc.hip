@@ -269,18 +269,13 @@ __global__ __launch_bounds__(256) void ctc_frame_argmax_kernel(const float* __re
   if (t >= T) return;   // wave-uniform
   const float* row = scores + (long long)b * batch_stride + (long long)t * ld;
   float m = -__builtin_inff();
-  int arg = 0x7fffffff;
+  int arg = WAVE_NONE;
   for (int v = lane; v < V; v += 64) {
     const float x = row[v];
     if (x > m) m = x, arg = v;   // ascending v per lane: the first maximum stays
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float om = __shfl_xor(m, o, 64);
-    const int oa = __shfl_xor(arg, o, 64);
-    if (om > m || (om == m && oa < arg)) m = om, arg = oa;
-  }
-  if (arg == 0x7fffffff) arg = 0;   // a row of -inf / NaN: class 0, like an argmax over equal values
+  wave_argmax(m, arg);
+  if (arg == WAVE_NONE) arg = 0;   // a row of -inf / NaN: class 0, like an argmax over equal values
   if (frame_logp) {                 // wave-uniform
     // max - logsumexp = -log(1 + sum over the OTHER classes of exp(x - max)): the winner's own term is exactly 1, and a
     // confident frame's log-probability is close to 0, where log(sum) would keep only the bits of 1 + eps that fp32 holds
@@ -333,12 +328,6 @@ __global__ __launch_bounds__(1024) void ctc_collapse_kernel(int* __restrict__ hy
 
 // ---------------------------------------------------------------- loss (sum over paths)
 
-__device__ __forceinline__ float ctc_logaddexp(float a, float b) {
-  const float m = fmaxf(a, b);
-  const float r = m + log1pf(expf(-fabsf(a - b)));   // one operand -inf: exp(-inf) = 0, r = m
-  return m == -__builtin_inff() ? m : r;             // both -inf: a - b is NaN, the sum of no paths is -inf
-}
-
 // one wave per frame < t_len: logsumexp over V into lse[b][t]
 __global__ __launch_bounds__(256) void ctc_frame_lse_kernel(const float* __restrict__ scores, long long batch_stride, int ld,
                                                              const int* __restrict__ t_len_p, float* __restrict__ lse, int T,
@@ -353,7 +342,7 @@ __global__ __launch_bounds__(256) void ctc_frame_lse_kernel(const float* __restr
     if (x > m) m = x, arg = v;
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
+  for (int o = 32; o > 0; o >>= 1) {   // wave_argmax written out: with the call this launch measured 0.2 % slower per f5e_ctc_loss
     const float om = __shfl_xor(m, o, 64);
     const int oa = __shfl_xor(arg, o, 64);
     if (om > m || (om == m && oa < arg)) m = om, arg = oa;
@@ -453,7 +442,7 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_loss_kernel(
       shift(p1, e2, p2);         // alpha[t-1][s-2]
 #pragma unroll
       for (int c = 0; c < CPT; ++c) {
-        const float sum = ctc_logaddexp(ctc_logaddexp(prev[c], p1[c]), skip[c] ? p2[c] : NEG);
+        const float sum = logaddexp_f(logaddexp_f(prev[c], p1[c]), skip[c] ? p2[c] : NEG);
         prev[c] = live[c] ? sum + (em[c] - norm) : NEG;
       }
     }
@@ -484,7 +473,7 @@ __global__ __launch_bounds__(MULTI ? 1024 : 64) void ctc_loss_kernel(
     if (s == S - 2) fin[1] = prev[c];
   }
   __syncthreads();
-  if (tid == 0) logp[b] = ctc_logaddexp(fin[0], fin[1]);
+  if (tid == 0) logp[b] = logaddexp_f(fin[0], fin[1]);
 }
 
 template <int CPT, bool MULTI>
@@ -496,6 +485,18 @@ void ctc_loss_launch(hipStream_t st, int threads, const float* scores, long long
 }
 
 int ctc_w64(int L) { return (2 * L + 1 + 63) / 64; }
+
+// the operand checks that f5e_ctc_align and f5e_ctc_loss share (after their own null and range checks); name = "ctc_align" /
+// "ctc_loss", need_bytes / align = what the entry point asks of its workspace
+int ctc_check_common(const char* name, long long batch_stride, int ld, int ld_labels, int blank, const void* workspace,
+                     unsigned long long workspace_bytes, unsigned long long need_bytes, int align, int B, int T, int L, int V) {
+  F5E_REQUIRE(V >= 2 && blank >= 0 && blank < V, "%s: need V >= 2 and 0 <= blank < V", name);
+  F5E_REQUIRE(ld >= V && ld_labels >= L && (B == 1 || batch_stride >= (long long)(T - 1) * ld + V),
+              "%s: ld / ld_labels / batch_stride too small", name);
+  F5E_REQUIRE(workspace_bytes >= need_bytes && ((uintptr_t)workspace & (uintptr_t)(align - 1)) == 0,
+              "%s: workspace smaller than f5e_%s_workspace_bytes or not %d-byte aligned", name, name, align);
+  return F5E_OK;
+}
 
 }  // namespace
 
@@ -514,20 +515,15 @@ int f5e_ctc_align(hipStream_t st, const float* scores, long long batch_stride, i
   F5E_REQUIRE(scores && labels && t_len && l_len && align && workspace, "ctc_align: null operand");
   F5E_REQUIRE(B > 0 && T > 0 && T <= CTC_MAX_T && L > 0 && L <= CTC_MAX_L,
               "ctc_align: need B > 0, 0 < T <= %d and 0 < L <= %d", CTC_MAX_T, CTC_MAX_L);
-  F5E_REQUIRE(V >= 2 && blank >= 0 && blank < V, "ctc_align: need V >= 2 and 0 <= blank < V");
-  F5E_REQUIRE(ld >= V && ld_labels >= L && (B == 1 || batch_stride >= (long long)(T - 1) * ld + V),
-              "ctc_align: ld / ld_labels / batch_stride too small");
   const int W64 = ctc_w64(L);
-  F5E_REQUIRE(workspace_bytes >= (unsigned long long)B * T * W64 * 16ull && ((uintptr_t)workspace & 7) == 0,
-              "ctc_align: workspace smaller than f5e_ctc_align_workspace_bytes or not 8-byte aligned");
+  if (int e = ctc_check_common("ctc_align", batch_stride, ld, ld_labels, blank, workspace, workspace_bytes,
+                               (unsigned long long)B * T * W64 * 16ull, 8, B, T, L, V))
+    return e;
   unsigned long long* dec = (unsigned long long*)workspace;
 #define CTC_GO(CPT, MULTI, THREADS)                                                                                         \
   ctc_align_launch<CPT, MULTI>(st, THREADS, scores, batch_stride, ld, labels, ld_labels, t_len, l_len, blank, align,        \
                                tok_start, tok_end, score, dec, B, T, L, V, W64)
-  if (W64 == 1) CTC_GO(1, false, 64);
-  else if (W64 == 2) CTC_GO(2, false, 64);
-  else if (W64 <= 4) CTC_GO(4, false, 64);
-  else CTC_GO(4, true, 64 * ((W64 + 3) / 4));
+  F5E_SLOT_LADDER(W64, CTC_GO);
 #undef CTC_GO
   F5E_LAUNCH_CHECK("ctc_align");
   return F5E_OK;
@@ -546,11 +542,9 @@ int f5e_ctc_loss(hipStream_t st, const float* scores, long long batch_stride, in
   F5E_REQUIRE(scores && (labels || L == 0) && t_len && l_len && logp && workspace, "ctc_loss: null operand");
   F5E_REQUIRE(B > 0 && B <= 65535 && T > 0 && T <= CTC_MAX_T && L >= 0 && L <= CTC_MAX_L,
               "ctc_loss: need 0 < B <= 65535, 0 < T <= %d and 0 <= L <= %d", CTC_MAX_T, CTC_MAX_L);
-  F5E_REQUIRE(V >= 2 && blank >= 0 && blank < V, "ctc_loss: need V >= 2 and 0 <= blank < V");
-  F5E_REQUIRE(ld >= V && ld_labels >= L && (B == 1 || batch_stride >= (long long)(T - 1) * ld + V),
-              "ctc_loss: ld / ld_labels / batch_stride too small");
-  F5E_REQUIRE(workspace_bytes >= (unsigned long long)B * T * 4ull && ((uintptr_t)workspace & 3) == 0,
-              "ctc_loss: workspace smaller than f5e_ctc_loss_workspace_bytes or not 4-byte aligned");
+  if (int e = ctc_check_common("ctc_loss", batch_stride, ld, ld_labels, blank, workspace, workspace_bytes,
+                               (unsigned long long)B * T * 4ull, 4, B, T, L, V))
+    return e;
   float* lse = (float*)workspace;
   hipLaunchKernelGGL(ctc_frame_lse_kernel, dim3((unsigned)((T + 3) / 4), (unsigned)B), dim3(256), 0, st, scores, batch_stride,
                      ld, t_len, lse, T, V);
@@ -558,10 +552,7 @@ int f5e_ctc_loss(hipStream_t st, const float* scores, long long batch_stride, in
 #define CTC_GO(CPT, MULTI, THREADS)                                                                                         \
   ctc_loss_launch<CPT, MULTI>(st, THREADS, scores, batch_stride, ld, labels, ld_labels, t_len, l_len, blank, logp, lse, B, \
                               T, L, V)
-  if (W64 == 1) CTC_GO(1, false, 64);
-  else if (W64 == 2) CTC_GO(2, false, 64);
-  else if (W64 <= 4) CTC_GO(4, false, 64);
-  else CTC_GO(4, true, 64 * ((W64 + 3) / 4));
+  F5E_SLOT_LADDER(W64, CTC_GO);
 #undef CTC_GO
   F5E_LAUNCH_CHECK("ctc_loss");
   return F5E_OK;

@@ -38,17 +38,14 @@ constexpr int BEAM_MAX_K = 16;
 constexpr int BEAM_MAX_T = 16384;
 constexpr int BEAM_MAX_C = BEAM_MAX_K + BEAM_MAX_K * BEAM_MAX_K;   // candidates per frame
 
-__device__ __forceinline__ float logaddexp_f(float a, float b) {
+// The search keeps this spelling beside logaddexp_f (f5e_common.h): the two agree bit for bit on every non-NaN input, but the
+// early return skips the transcendentals of the many (-inf, -inf) candidates, and with the shared form f5e_ctc_beam measured
+// 0.4-0.7 % slower.  (On a NaN operand this one drops the NaN; the search's operands are NaN only for a row of scores that
+// holds NaN or +inf or nothing but -inf.)
+__device__ __forceinline__ float beam_logaddexp(float a, float b) {
   const float m = fmaxf(a, b), n = fminf(a, b);
   if (!(m > -__builtin_inff())) return m;   // both -inf
   return m + log1pf(expf(n - m));
-}
-
-// order-preserving float -> unsigned key, never 0 (0 = "no candidate"); NaN ranks as -inf
-__device__ __forceinline__ unsigned rank_key(float v) {
-  if (v != v) v = -__builtin_inff();
-  const unsigned u = __builtin_bit_cast(unsigned, v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
 __device__ __forceinline__ unsigned hash_step(unsigned h, int tok) {
@@ -69,18 +66,13 @@ __global__ __launch_bounds__(256) void ctc_beam_topk_kernel(const float* __restr
   int pi = -1;
   for (int r = 0; r < K; ++r) {
     float m = NEG;
-    int arg = 0x7fffffff;
+    int arg = WAVE_NONE;
     for (int v = lane; v < V; v += 64) {
       const float x = row[v];
       const bool after = x < pv || (x == pv && v > pi);
-      if (after && (arg == 0x7fffffff || x > m)) m = x, arg = v;   // ascending v per lane: the first maximum stays
+      if (after && (arg == WAVE_NONE || x > m)) m = x, arg = v;   // ascending v per lane: the first maximum stays
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float om = __shfl_xor(m, o, 64);
-      const int oa = __shfl_xor(arg, o, 64);
-      if (om > m || (om == m && oa < arg)) m = om, arg = oa;
-    }
+    wave_argmax(m, arg);
     if (r == 0) {
       float sum = 0.f;
       for (int v = lane; v < V; v += 64) sum += v == arg ? 0.f : expf(row[v] - m);
@@ -89,7 +81,7 @@ __global__ __launch_bounds__(256) void ctc_beam_topk_kernel(const float* __restr
     }
     if (lane == 0) {
       const long long o = ((long long)b * T_ws + t) * K + r;   // T_ws >= T: the sequence's share of the scratch
-      const bool none = arg == 0x7fffffff;   // fewer than K comparable values (NaN in the row)
+      const bool none = arg == WAVE_NONE;   // fewer than K comparable values (NaN in the row)
       top_id[o] = none ? -1 : arg;
       top_lp[o] = none ? NEG : (m - m0) - lse;
     }
@@ -151,7 +143,7 @@ __device__ __forceinline__ void beam_frames(BeamLds& L, const int* __restrict__ 
       node_p = L.node[cur][p], len_p = L.len[cur][p];
       const int last_p = L.last[cur][p];
       const float pb = L.pb[cur][p], pnb = L.pnb[cur][p];
-      const float both = logaddexp_f(pb + ps, pnb + ps);
+      const float both = beam_logaddexp(pb + ps, pnb + ps);
       if (s == blank) {
         L.s_blank[p] = both, L.f_blank[p] = 1;
       } else {
@@ -187,8 +179,8 @@ __device__ __forceinline__ void beam_frames(BeamLds& L, const int* __restrict__ 
       k = 0;
       if (c < nb && (L.f_blank[c] | L.f_rep[c] | L.f_merge[c])) {
         n_pb = L.f_blank[c] ? L.s_blank[c] : NEG;
-        n_pnb = logaddexp_f(L.f_rep[c] ? L.s_rep[c] : NEG, L.f_merge[c] ? L.s_merge[c] : NEG);
-        k = rank_key(logaddexp_f(n_pb, n_pnb));
+        n_pnb = beam_logaddexp(L.f_rep[c] ? L.s_rep[c] : NEG, L.f_merge[c] ? L.s_merge[c] : NEG);
+        k = rank_key(beam_logaddexp(n_pb, n_pnb));
       }
       L.key[c] = k;
     }
@@ -239,7 +231,7 @@ __device__ __forceinline__ void beam_backtrace(const BeamLds& L, int fin, const 
     float sc = -__builtin_inff();
     if (c < nb) {
       len = L.len[fin][c];
-      sc = logaddexp_f(L.pb[fin][c], L.pnb[fin][c]);
+      sc = beam_logaddexp(L.pb[fin][c], L.pnb[fin][c]);
       int node = L.node[fin][c];
       for (int pos = len - 1; pos >= 0 && node > 0; --pos) {
         if (pos < ld_hyp) H[(long long)c * ld_hyp + pos] = trie_tok[node - 1];
@@ -360,12 +352,8 @@ __global__ __launch_bounds__(256) void token_logp_kernel(const float* __restrict
     return;
   }
   const float* row = logits + r * ld;
-  float m = -__builtin_inff();
-  for (int v = lane; v < V; v += 64) m = fmaxf(m, row[v]);
-  m = wave_max(m);
-  float sum = 0.f;
-  for (int v = lane; v < V; v += 64) sum += expf(row[v] - m);
-  sum = wave_sum(sum);
+  float m;
+  const float sum = wave_row_sum_exp(row, V, m);
   if (lane == 0) out[r] = (row[tg] - m) - logf(sum);
 }
 
@@ -376,12 +364,8 @@ __global__ __launch_bounds__(256) void log_softmax_rows_kernel(const float* x, l
   const long long r = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;   // wave-uniform
   const float* row = x + r * ldx;
-  float m = -__builtin_inff();
-  for (int v = lane; v < V; v += 64) m = fmaxf(m, row[v]);
-  m = wave_max(m);
-  float sum = 0.f;
-  for (int v = lane; v < V; v += 64) sum += expf(row[v] - m);
-  const float lse = logf(wave_sum(sum));
+  float m;
+  const float lse = logf(wave_row_sum_exp(row, V, m));
   for (int v = lane; v < V; v += 64) out[r * ldo + v] = (row[v] - m) - lse;   // a lane rewrites only what it alone read
 }
 

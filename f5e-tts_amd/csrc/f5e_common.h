@@ -141,6 +141,16 @@ int f5e_gemm_bf16_qkv_rope_pf(hipStream_t st, const void* A, int lda, const void
 int f5e_flash_attn_pf(hipStream_t st, const void* q, const void* k, const void* v, void* o, int ldo, const int* kv_len,
                       int S, int H, int rows_per_seq, int n_pad, int splits, const F5ePrefetch* pf);
 
+// The dispatch ladder of the one-workgroup-per-sequence scans (mas.hip, ctc.hip) on W64 = 64-state slots of a row: one wave
+// with 1, 2 or 4 slots per lane up to 256 states, beyond that waves of 4 slots.  GO(CPT, MULTI, THREADS) launches.
+#define F5E_SLOT_LADDER(W64, GO)                    \
+  do {                                              \
+    if ((W64) == 1) GO(1, false, 64);               \
+    else if ((W64) == 2) GO(2, false, 64);          \
+    else if ((W64) <= 4) GO(4, false, 64);          \
+    else GO(4, true, 64 * (((W64) + 3) / 4));       \
+  } while (0)
+
 // No synchronisation here: only picks up launch-configuration errors, so every op stays graph-capturable.
 #define F5E_LAUNCH_CHECK(name)                                                   \
   do {                                                                           \
@@ -214,6 +224,43 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
+}
+
+// ---- per-row wave reductions of the decoders and scorers (ctc.hip, ctc_beam.hip, attn_decode.hip): one wave per row of V
+// values, lane l holding elements l, l + 64, ...
+constexpr int WAVE_NONE = 0x7fffffff;   // "no element" as an index: above every real one
+// First maximum wins: every lane gives its (m, arg) and gets the wave's largest m with the LOWEST arg among equal maxima.
+__device__ __forceinline__ void wave_argmax(float& m, int& arg) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64);
+    const int oa = __shfl_xor(arg, o, 64);
+    if (om > m || (om == m && oa < arg)) m = om, arg = oa;
+  }
+}
+// The two passes of a row's log-softmax: m = the row maximum, returns the sum of exp(x - m): logsumexp = m + logf(sum).  (The
+// CTC frame kernels and the beam's first prune use another form, log1pf of the sum over the classes other than the winner; it
+// stays with them.)
+__device__ __forceinline__ float wave_row_sum_exp(const float* __restrict__ row, int V, float& m) {
+  const int lane = threadIdx.x & 63;
+  m = -__builtin_inff();
+  for (int v = lane; v < V; v += 64) m = fmaxf(m, row[v]);
+  m = wave_max(m);
+  float sum = 0.f;
+  for (int v = lane; v < V; v += 64) sum += expf(row[v] - m);
+  return wave_sum(sum);
+}
+// order-preserving float -> unsigned key, never 0 (0 = "no candidate"); NaN ranks as -inf
+__device__ __forceinline__ unsigned rank_key(float v) {
+  if (v != v) v = -__builtin_inff();
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+// log(exp(a) + exp(b)) = max + log1p(exp(-|a - b|)).  A NaN operand gives NaN (fmaxf alone would drop it).
+__device__ __forceinline__ float logaddexp_f(float a, float b) {
+  const float m = fmaxf(a, b);
+  const float r = m + log1pf(expf(-fabsf(a - b)));   // one operand -inf: exp(-inf) = 0, r = m
+  return m == -__builtin_inff() ? m : r;             // both -inf: a - b is NaN, the sum of no paths is -inf
 }
 __device__ __forceinline__ float gelu_tanh_f(float x) {
   // 0.5 x (1 + tanh(u)), u = sqrt(2/pi) (x + 0.044715 x^3)  ==  x / (1 + exp(-2u))  ==  x * rcp(1 + exp2(x * p(x^2))),

@@ -191,15 +191,10 @@ int f5e_mas_path(hipStream_t st, const float* logp, long long batch_stride, int 
   F5E_REQUIRE(workspace_bytes >= (unsigned long long)B * Ty * W64 * 8ull && ((uintptr_t)workspace & 7) == 0,
               "mas_path: workspace smaller than f5e_mas_workspace_bytes or not 8-byte aligned");
   unsigned long long* dec = (unsigned long long*)workspace;
-  if (W64 == 1)
-    mas_launch<1, false>(st, 64, logp, batch_stride, ld, t_y, t_x, token_of_frame, durations, dec, B, Ty, Tx, W64);
-  else if (W64 == 2)
-    mas_launch<2, false>(st, 64, logp, batch_stride, ld, t_y, t_x, token_of_frame, durations, dec, B, Ty, Tx, W64);
-  else if (W64 <= 4)
-    mas_launch<4, false>(st, 64, logp, batch_stride, ld, t_y, t_x, token_of_frame, durations, dec, B, Ty, Tx, W64);
-  else
-    mas_launch<4, true>(st, 64 * ((W64 + 3) / 4), logp, batch_stride, ld, t_y, t_x, token_of_frame, durations, dec, B, Ty, Tx,
-                        W64);
+#define MAS_GO(CPT, MULTI, THREADS) \
+  mas_launch<CPT, MULTI>(st, THREADS, logp, batch_stride, ld, t_y, t_x, token_of_frame, durations, dec, B, Ty, Tx, W64)
+  F5E_SLOT_LADDER(W64, MAS_GO);
+#undef MAS_GO
   F5E_LAUNCH_CHECK("mas_path");
   return F5E_OK;
 }

@@ -428,10 +428,7 @@ def mas_path(logp: Tensor, t_y: Tensor, t_x: Tensor, token_of_frame: Tensor, dur
     if t_y.numel() != B or t_x.numel() != B or token_of_frame.shape != (B, Ty) or \
             (durations is not None and durations.shape != (B, Tx)):
         raise _C.F5EError(f"mas_path: lengths [{B}], token_of_frame [{B}, {Ty}], durations [{B}, {Tx}]")
-    need = mas_workspace_bytes(B, Ty, Tx)
-    if workspace is None:
-        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=logp.device)
-    nbytes = workspace.numel() * workspace.element_size()
+    workspace, nbytes = _workspace(workspace, mas_workspace_bytes(B, Ty, Tx), torch.int64, logp.device)
     check(lib().f5e_mas_path(_stream(), C.c_void_p(logp.data_ptr()), logp.stride(0), logp.stride(1), _p(t_y, I32, "t_y"),
                              _p(t_x, I32, "t_x"), _p(token_of_frame, I32, "token_of_frame"),
                              _p(durations, I32, "durations"), _p(workspace, None, "workspace"), nbytes, B, Ty, Tx),
@@ -450,6 +447,19 @@ def _ctc_scores(scores: Tensor, name: str):
     if scores.ndim != 3 or not scores.is_cuda or scores.dtype != F32 or scores.stride(2) != 1:
         raise _C.F5EError(f"{name}: scores must be an f32 GPU tensor [B, T, V] with unit class stride; there is no CPU path")
     return scores.shape
+
+
+def _row_stride(t: Tensor, width: int) -> int:
+    """Row stride of a [.., rows, width] view: the stride of a size-1 dimension is arbitrary (0 for a NumPy new axis) and
+    never used, so one row reports at least its own width."""
+    return t.stride(-2) if t.shape[-2] > 1 else max(width, t.stride(-2))
+
+
+def _workspace(workspace: Optional[Tensor], need: int, dtype, device):
+    """(workspace, its bytes): ``need`` bytes of ``dtype`` words are allocated when the caller passed None."""
+    if workspace is None:
+        workspace = torch.empty((need + dtype.itemsize - 1) // dtype.itemsize, dtype=dtype, device=device)
+    return workspace, workspace.numel() * workspace.element_size()
 
 
 def ctc_align(scores: Tensor, labels: Tensor, t_len: Tensor, l_len: Tensor, blank: int = 0, *,
@@ -476,12 +486,8 @@ def ctc_align(scores: Tensor, labels: Tensor, t_len: Tensor, l_len: Tensor, blan
             any(o is not None and o.shape != (B, L) for o in (tok_start, tok_end)) or \
             (score is not None and score.shape != (B,)):
         raise _C.F5EError(f"ctc_align: lengths [{B}], align [{B}, {T}], tok_start / tok_end [{B}, {L}], score [{B}]")
-    need = ctc_align_workspace_bytes(B, T, L)
-    if workspace is None:
-        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
-    nbytes = workspace.numel() * workspace.element_size()
-    # the stride of a size-1 dimension is arbitrary (0 for a NumPy new axis) and never used
-    ld, ld_labels = (scores.stride(1) if T > 1 else max(V, scores.stride(1))), (labels.stride(0) if B > 1 else L)
+    workspace, nbytes = _workspace(workspace, ctc_align_workspace_bytes(B, T, L), torch.int64, dev)
+    ld, ld_labels = _row_stride(scores, V), (labels.stride(0) if B > 1 else L)
     check(lib().f5e_ctc_align(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0), ld,
                               C.c_void_p(labels.data_ptr()), ld_labels, _p(t_len, I32, "t_len"),
                               _p(l_len, I32, "l_len"), int(blank), _p(align, I32, "align"), _p(tok_start, I32, "tok_start"),
@@ -506,8 +512,7 @@ def ctc_greedy(scores: Tensor, t_len: Tensor, blank: int = 0, pad_id: int = -1, 
     if t_len.numel() != B or hyp.shape != (B, T) or hyp_len.shape != (B,) or \
             (frame_logp is not None and frame_logp.shape != (B, T)):
         raise _C.F5EError(f"ctc_greedy: t_len / hyp_len [{B}], hyp / frame_logp [{B}, {T}]")
-    check(lib().f5e_ctc_greedy(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0),
-                               scores.stride(1) if T > 1 else max(V, scores.stride(1)),
+    check(lib().f5e_ctc_greedy(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0), _row_stride(scores, V),
                                _p(t_len, I32, "t_len"), int(blank), int(pad_id), _p(hyp, I32, "hyp"),
                                _p(hyp_len, I32, "hyp_len"), _p(frame_logp, F32, "frame_logp"), B, T, V), "f5e_ctc_greedy")
     return hyp, hyp_len, frame_logp
@@ -538,12 +543,8 @@ def ctc_loss(scores: Tensor, labels: Tensor, t_len: Tensor, l_len: Tensor, blank
         logp = torch.empty(B, dtype=F32, device=dev)
     if t_len.numel() != B or l_len.numel() != B or logp.shape != (B,):
         raise _C.F5EError(f"ctc_loss: lengths [{B}], logp [{B}]")
-    need = ctc_loss_workspace_bytes(B, T)
-    if workspace is None:
-        workspace = torch.empty((need + 3) // 4, dtype=F32, device=dev)
-    nbytes = workspace.numel() * workspace.element_size()
-    # the stride of a size-1 dimension is arbitrary (0 for a NumPy new axis) and never used
-    ld, ld_labels = (scores.stride(1) if T > 1 else max(V, scores.stride(1))), (labels.stride(0) if B > 1 and L > 0 else L)
+    workspace, nbytes = _workspace(workspace, ctc_loss_workspace_bytes(B, T), F32, dev)
+    ld, ld_labels = _row_stride(scores, V), (labels.stride(0) if B > 1 and L > 0 else L)
     check(lib().f5e_ctc_loss(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0), ld,
                              C.c_void_p(labels.data_ptr() if L > 0 else None), ld_labels, _p(t_len, I32, "t_len"),
                              _p(l_len, I32, "l_len"), int(blank), _p(logp, F32, "logp"), _p(workspace, None, "workspace"),
@@ -584,12 +585,9 @@ def ctc_beam_search(scores: Tensor, t_len: Tensor, beam: int, blank: int = 0, *,
     if ld_hyp < 1 or hyp.shape != (B, beam, ld_hyp) or hyp_len.shape != (B, beam) or score.shape != (B, beam) or \
             not (hyp_len.is_contiguous() and score.is_contiguous()):
         raise _C.F5EError(f"ctc_beam_search: hyp [{B}, {beam}, ld_hyp >= 1], hyp_len / score [{B}, {beam}], contiguous")
-    need = ctc_beam_workspace_bytes(B, T, beam)
-    if workspace is None:
-        workspace = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
-    nbytes = workspace.numel() * workspace.element_size()
-    check(lib().f5e_ctc_beam(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0),
-                             scores.stride(1) if T > 1 else max(V, scores.stride(1)), _p(t_len, I32, "t_len"), int(blank),
+    workspace, nbytes = _workspace(workspace, ctc_beam_workspace_bytes(B, T, beam), torch.int64, dev)
+    check(lib().f5e_ctc_beam(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0), _row_stride(scores, V),
+                             _p(t_len, I32, "t_len"), int(blank),
                              beam, _p(hyp, I32, "hyp"), ld_hyp, _p(hyp_len, I32, "hyp_len"), _p(score, F32, "score"),
                              _p(workspace, None, "workspace"), nbytes, B, T, V), "f5e_ctc_beam")
     return hyp, hyp_len, score
@@ -683,8 +681,8 @@ def ctc_beam_chunk(scores: Tensor, n_frames: Tensor, state: CTCBeamState, blank:
         raise _C.F5EError("ctc_beam_chunk: want_result=False takes no output tensors")
     else:
         ld_hyp = 0
-    check(lib().f5e_ctc_beam_chunk(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0),
-                                   scores.stride(1) if T > 1 else max(V, scores.stride(1)), _p(n_frames, I32, "n_frames"),
+    check(lib().f5e_ctc_beam_chunk(_stream(), C.c_void_p(scores.data_ptr()), scores.stride(0), _row_stride(scores, V),
+                                   _p(n_frames, I32, "n_frames"),
                                    T, V, int(blank), beam, _p(state.buf, None, "state"), state.nbytes,
                                    _p(hyp, I32, "hyp"), ld_hyp, _p(hyp_len, I32, "hyp_len"), _p(score, F32, "score"),
                                    B, state.T_cap, state.chunk_cap), "f5e_ctc_beam_chunk")

@@ -105,6 +105,23 @@ def test_kernel_equals_restatement_4096x4096_square_and_wide(ops):
     check_against_restatement(ops, dev, logp, [4000], [257])
 
 
+@pytest.mark.parametrize("Tx", [63, 64, 65, 127, 128, 129, 255, 256, 257])
+def test_kernel_equals_restatement_across_slot_and_wave_boundaries(ops, Tx):
+    """Tx around 64, 128 and 256 columns: one, two and four slots per lane, then the step from one wave to several (the dispatch
+    ladder of f5e_mas_path); the second sequence is shorter in both directions."""
+    Ty = Tx + 37
+    logp = seeded(2, Ty, Tx, 70 + Tx)
+    check_against_restatement(ops, logp.cuda(), logp, [Ty, Ty - 5], [Tx, Tx - 1])
+
+
+@pytest.mark.parametrize("Ty", [5, 7, 8, 9, 15, 16, 17, 63, 64, 65, 129])
+def test_kernel_equals_restatement_across_prefetch_and_backtrack_rounds(ops, Ty):
+    """Five tokens, Ty around the prefetch depth (8 rows per register set, 16 per turn of the row pipeline) and around the
+    64 rows that one backtrack round resolves."""
+    logp = seeded(2, Ty, 5, 400 + Ty)
+    check_against_restatement(ops, logp.cuda(), logp, [Ty, Ty - 5 if Ty > 9 else Ty], [5, 4])
+
+
 def test_kernel_on_a_strided_batch_with_ld_above_tx(ops):
     """A column-sliced view (ld = 200 > Tx = 130) of every other matrix of a batch (batch stride = 2 matrices)."""
     big = seeded(4, 300, 200, 64).cuda()

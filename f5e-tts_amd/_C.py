@@ -83,6 +83,13 @@ SIGNATURES = {
     "f5e_se_scale": [_P, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I],
     "f5e_bias_tanh": [_P, _P, _I, _P, _I, _I, _I, _I, _I],
     "f5e_attn_stats_pool": [_P, _P, _I, _P, _I, _P, _P, _I, _I, _I],
+    "f5e_wav_norm": [_P, _P, _I, _P, _P, _I, _P, _P, _P, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I, _I],
+    "f5e_wav_norm_partials": [_I, _I, C.POINTER(C.c_ulonglong)],
+    "f5e_wavlm_conv0": [_P, _P, _I, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _I],
+    "f5e_layernorm_gelu": [_P, _P, _I, _P, _I, _P, _P, _LL, _I, _F],
+    "f5e_wavlm_posconv": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
+    "f5e_wavlm_gate": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I],
+    "f5e_relbias_attn_f32": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _F],
     "f5e_dit_forward": [_P, _P],
     "f5e_sample_loop": [_P, _P],
     "f5e_workspace_bytes": [_P, _P],

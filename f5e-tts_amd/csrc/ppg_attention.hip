@@ -4,6 +4,8 @@
 // extractor (encoder.py:210-355), where a query in chunk c = t / chunk sees keys [max(0, (c - left) chunk), (c + 1) chunk).
 //
 //   f5e_relpos_attn   out[q, h] = softmax_k(((q+u)_h . k_h[k] + (q+v)_h . p_h[k]) * scale) . v_h over the query's band
+//   f5e_relbias_attn_f32   WavLM's self-attention (gated relative-position bias, computed on the fly from a [H][2 Tt - 1] table):
+//                     out[q, h] = softmax_k(q_h . k_h[k] * scale + gate[b][h][q] * table[h][k - q + Tt - 1]) . v_h, keys < kv_len[b]
 //
 // One wave per (sequence, head, 16-query tile), no LDS.  Everything is computed TRANSPOSED on v_mfma_f32_16x16x4_f32 so
 // that no accumulator ever changes lanes:
@@ -19,8 +21,9 @@
 
 namespace {
 
-// One argument block for both entry points.  f5e_relpos_attn: Tq == Tk == T, pos and D (= H dk, the offset of the q + v half
-// of a qu row) set, causal unused.  f5e_mha_f32: pos / D / chunk / left unused, q_begin 0.
+// One argument block for all entry points.  f5e_relpos_attn: Tq == Tk == T, pos and D (= H dk, the offset of the q + v half
+// of a qu row) set, causal unused.  f5e_mha_f32: pos / D / chunk / left unused, q_begin 0.  f5e_relbias_attn_f32: as f5e_mha_f32
+// without causal, Tq == Tk, plus gate [B][H][Tq], table [H][2 Tt - 1] and Tt >= Tq.
 struct AttnArgs {
   const float *q, *k, *pos, *v;
   float* out;
@@ -28,14 +31,21 @@ struct AttnArgs {
   int ldq, ldk, ldp, ldv, ldo;
   int Tq, Tk, D, q_begin, chunk, left, causal;
   float scale;
+  const float *gate, *table;
+  int Tt;
 };
+
+enum { ATTN_PLAIN = 0, ATTN_RELPOS = 1, ATTN_RELBIAS = 2 };
 
 // The wave tile.  RELPOS: the second score product (q + v) . p, the chunk band, and a query at or beyond the key length
 // yields zeros.  Otherwise (f5e_mha_f32, the attention decoder's self- and source attention, attention.py:79-111): the band
 // of query i is [0, min(i + 1, len)) when causal and [0, len) otherwise, so a query below the key length is NOT required:
 // every query row is computed, and one with no visible key yields zeros (the reference's masked_fill after the softmax).
-template <int DK, bool RELPOS>
+// RELBIAS: the band is [0, len) for every query below len; a query at or beyond len yields zeros (as RELPOS).  The bias of
+// register r is ONE gather from the head's table at key - query + Tt - 1, scaled by the query's gate.
+template <int DK, int MODE>
 __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
+  constexpr bool RELPOS = MODE == ATTN_RELPOS, RELBIAS = MODE == ATTN_RELBIAS;
   constexpr int NB = DK / 16;
   const int lane = threadIdx.x, c16 = lane & 15, g = lane >> 4;
   const int q0 = a.q_begin + blockIdx.x * 16, hd = blockIdx.y, b = blockIdx.z;
@@ -55,10 +65,20 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
     q_ok = q_in && q0 + c16 < len;
     lo_q = band_lo(qr), hi_q = q_ok ? band_hi(qr) : 0;
     t_lo = band_lo(q0) & ~15, t_hi = q0 < len ? band_hi(q_last) : 0;
+  } else if constexpr (RELBIAS) {
+    q_ok = q_in && q0 + c16 < len;
+    lo_q = 0, hi_q = q_ok ? len : 0;
+    t_lo = 0, t_hi = q0 < len ? len : 0;
   } else {
     q_ok = q_in;
     lo_q = 0, hi_q = q_ok ? (a.causal ? min(qr + 1, len) : len) : 0;
     t_lo = 0, t_hi = a.causal ? min(q_last + 1, len) : len;
+  }
+  float gq = 0.f;
+  const float* tab = nullptr;
+  if constexpr (RELBIAS) {
+    gq = a.gate[((size_t)b * gridDim.y + hd) * a.Tq + qr];
+    tab = a.table + (size_t)hd * (2 * a.Tt - 1);
   }
 
   f32x4 qa[NB], qb[RELPOS ? NB : 1];
@@ -97,7 +117,10 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
       const int key = kt + 4 * g + r;
       const bool seen = key >= lo_q && key < hi_q;
       if constexpr (RELPOS) p[r] = seen ? (s0[r] + s1[r]) * a.scale : -INFINITY;
-      else p[r] = seen ? s0[r] * a.scale : -INFINITY;
+      else if constexpr (RELBIAS) {
+        const int ti = min(max(key - qr + a.Tt - 1, 0), 2 * a.Tt - 2);   // a seen key is in range; the clamp is for the others
+        p[r] = seen ? s0[r] * a.scale + gq * tab[ti] : -INFINITY;
+      } else p[r] = seen ? s0[r] * a.scale : -INFINITY;
       mx = fmaxf(mx, p[r]);
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
@@ -133,14 +156,14 @@ __global__ __launch_bounds__(64) void attn_f32_kernel(AttnArgs a) {
   }
 }
 
-template <bool RELPOS>
+template <int MODE>
 void launch_attn(hipStream_t st, const AttnArgs& a, int H, int B, int dk) {
   const dim3 grid((unsigned)((a.Tq - a.q_begin + 15) / 16), (unsigned)H, (unsigned)B);
   switch (dk) {
-    case 16: hipLaunchKernelGGL((attn_f32_kernel<16, RELPOS>), grid, dim3(64), 0, st, a); break;
-    case 32: hipLaunchKernelGGL((attn_f32_kernel<32, RELPOS>), grid, dim3(64), 0, st, a); break;
-    case 64: hipLaunchKernelGGL((attn_f32_kernel<64, RELPOS>), grid, dim3(64), 0, st, a); break;
-    default: hipLaunchKernelGGL((attn_f32_kernel<128, RELPOS>), grid, dim3(64), 0, st, a); break;
+    case 16: hipLaunchKernelGGL((attn_f32_kernel<16, MODE>), grid, dim3(64), 0, st, a); break;
+    case 32: hipLaunchKernelGGL((attn_f32_kernel<32, MODE>), grid, dim3(64), 0, st, a); break;
+    case 64: hipLaunchKernelGGL((attn_f32_kernel<64, MODE>), grid, dim3(64), 0, st, a); break;
+    default: hipLaunchKernelGGL((attn_f32_kernel<128, MODE>), grid, dim3(64), 0, st, a); break;
   }
 }
 
@@ -161,7 +184,7 @@ extern "C" int f5e_relpos_attn(hipStream_t st, const float* qu, int ldq, const f
   F5E_REQUIRE((((uintptr_t)qu | (uintptr_t)k | (uintptr_t)pos | (uintptr_t)out) & 15) == 0,
               "relpos_attn: qu, k, pos and out must be 16-byte aligned");
   const AttnArgs a{qu, k, pos, v, out, kv_len, ldq, ldk, ldp, ldv, ldo, T, T, (int)D, q_begin, chunk, left_chunks, 0, scale};
-  launch_attn<true>(st, a, H, B, dk);
+  launch_attn<ATTN_RELPOS>(st, a, H, B, dk);
   F5E_LAUNCH_CHECK("relpos_attn");
   return F5E_OK;
 }
@@ -178,7 +201,25 @@ extern "C" int f5e_mha_f32(hipStream_t st, const float* q, int ldq, const float*
               "mha_f32: row strides must cover the heads (H dk) and those of q, k and out be multiples of 4 floats");
   F5E_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)out) & 15) == 0, "mha_f32: q, k and out must be 16-byte aligned");
   const AttnArgs a{q, k, nullptr, v, out, kv_len, ldq, ldk, 0, ldv, ldo, Tq, Tk, 0, 0, 0, -1, causal ? 1 : 0, scale};
-  launch_attn<false>(st, a, H, B, dk);
+  launch_attn<ATTN_PLAIN>(st, a, H, B, dk);
   F5E_LAUNCH_CHECK("mha_f32");
+  return F5E_OK;
+}
+
+extern "C" int f5e_relbias_attn_f32(hipStream_t st, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                    float* out, int ldo, const float* gate, const float* table, int Tt, const int* kv_len, int B,
+                                    int T, int H, int dk, float scale) {
+  F5E_REQUIRE(q && k && v && out && gate && table, "relbias_attn_f32: null operand");
+  F5E_REQUIRE(dk == 16 || dk == 32 || dk == 64, "relbias_attn_f32: head dim %d is not built (16, 32 and 64 are)", dk);
+  const long long D = (long long)H * dk;
+  F5E_REQUIRE(B > 0 && B <= 65535 && T > 0 && H > 0 && H <= 65535 && Tt >= T && Tt <= (1 << 29),
+              "relbias_attn_f32: bad shape (B=%d T=%d H=%d Tt=%d; the table must cover Tt >= T)", B, T, H, Tt);
+  F5E_REQUIRE(ldq >= D && ldk >= D && ldv >= D && ldo >= D && ldq % 4 == 0 && ldk % 4 == 0 && ldo % 4 == 0,
+              "relbias_attn_f32: row strides must cover the heads (H dk) and those of q, k and out be multiples of 4 floats");
+  F5E_REQUIRE((((uintptr_t)q | (uintptr_t)k | (uintptr_t)out) & 15) == 0, "relbias_attn_f32: q, k and out must be 16-byte aligned");
+  AttnArgs a{q, k, nullptr, v, out, kv_len, ldq, ldk, 0, ldv, ldo, T, T, 0, 0, 0, -1, 0, scale};
+  a.gate = gate, a.table = table, a.Tt = Tt;
+  launch_attn<ATTN_RELBIAS>(st, a, H, B, dk);
+  F5E_LAUNCH_CHECK("relbias_attn_f32");
   return F5E_OK;
 }

@@ -1,6 +1,6 @@
 """ECAPA-TDNN speaker encoder of the SIM metric (mirror of reference eval/ecapa_tdnn.py), the half the reference owns: from the
 stack of WavLM hidden states to the embedding.  The WavLM-large upstream (s3prl through ``torch.hub`` in the reference) is
-not built here; ``forward`` takes its hidden states, ``embed_wavs`` takes a user-supplied upstream callable.
+``eval/wavlm.py``; ``forward`` takes its hidden states, ``embed_wavs`` takes an upstream callable (a ``WavLM`` instance is one).
 
 Same parameter and buffer names as the reference head (``feature_weight``, ``layer1.conv.weight``,
 ``layer2.Res2Conv1dReluBn.convs.0.weight``, ``...bns.0.running_var``, ``layer2.SE_Connect.linear1.weight``,

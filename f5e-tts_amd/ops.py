@@ -1181,6 +1181,142 @@ def attn_stats_pool(x: Tensor, logits: Tensor, lengths: Optional[Tensor], out: T
     return out
 
 
+# ---- WavLM upstream (csrc/wavlm.hip, f5e_relbias_attn_f32 of csrc/ppg_attention.hip) ----
+
+def wav_norm_partials(B: int, S: int) -> int:
+    """Floats of scratch that ``wav_norm`` needs for B rows of S samples (host arithmetic)."""
+    n = C.c_ulonglong(0)
+    check(lib().f5e_wav_norm_partials(int(B), int(S), C.byref(n)), "f5e_wav_norm_partials")
+    return int(n.value)
+
+
+def wav_norm(wav: Tensor, lengths: Optional[Tensor], out: Tensor, partials: Tensor, frames: Optional[Tensor] = None,
+             mask: Optional[Tensor] = None, conv_kernels=(), conv_strides=()):
+    """f5e_wav_norm: wav f32 [B, S] -> out f32 [B, S] normalised over each row's first lengths[b] samples, zero beyond;
+    frames i32 [B] = frame count after the valid convolutions (conv_kernels, conv_strides); mask f32 [B, Tm] = t < frames[b]."""
+    if wav.ndim != 2 or out.shape != wav.shape:
+        raise _C.F5EError(f"wav_norm: wav and out must be [B, S] of one shape (got {tuple(wav.shape)}, {tuple(out.shape)})")
+    B, S = wav.shape
+    wp, ldw = _rows(wav, (F32,), "wav_norm: wav", S, vec=1)
+    op, ldo = _rows(out, (F32,), "wav_norm: out", S, vec=1)
+    if len(conv_kernels) != len(conv_strides) or len(conv_kernels) > 8:
+        raise _C.F5EError("wav_norm: conv_kernels and conv_strides must have one length, at most 8")
+    if partials.dtype != F32 or partials.numel() < wav_norm_partials(B, S):
+        raise _C.F5EError(f"wav_norm: partials must hold {wav_norm_partials(B, S)} floats (wav_norm_partials)")
+    if frames is not None and (frames.dtype != I32 or frames.shape != (B,)):
+        raise _C.F5EError(f"wav_norm: frames must be i32 [{B}]")
+    t_mask = 0
+    if mask is not None:
+        if mask.ndim != 2 or mask.shape[0] != B or not 0 < mask.shape[1] <= S:
+            raise _C.F5EError(f"wav_norm: mask must be [{B}, 1..{S}] (got {tuple(mask.shape)})")
+        t_mask = mask.shape[1]
+    n = len(conv_kernels)
+    ks, ss = (C.c_int * max(n, 1))(*[int(v) for v in conv_kernels]), (C.c_int * max(n, 1))(*[int(v) for v in conv_strides])
+    require_device()
+    check(lib().f5e_wav_norm(_stream(), wp, ldw, _len(lengths, B, "wav_norm"), op, ldo, _p(partials, F32, "partials"),
+                             _p(frames, I32, "frames"), _p(mask, F32, "mask"), t_mask, ks, ss, n, B, S), "f5e_wav_norm")
+    return out
+
+
+def wavlm_conv0(wav: Tensor, w: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor, out: Tensor, T0: Optional[int] = None):
+    """f5e_wavlm_conv0: wav f32 [B, S], w f32 [C, 10] -> out f32 [B, P >= T0, C] (frames C floats apart, rows any stride >= T0 C):
+    Conv1d(1 -> C, k 10, stride 5) + LayerNorm(C) + GELU in one pass; T0 defaults to (S - 10) // 5 + 1."""
+    if wav.ndim != 2 or w.ndim != 2 or w.shape[1] != 10 or out.ndim != 3 or out.shape[0] != wav.shape[0] or out.shape[2] != w.shape[0]:
+        raise _C.F5EError(f"wavlm_conv0: wav [B, S], w [C, 10], out [B, P, C] (got {tuple(wav.shape)}, {tuple(w.shape)}, {tuple(out.shape)})")
+    B, S = wav.shape
+    Cc = w.shape[0]
+    T0 = (S - 10) // 5 + 1 if T0 is None else int(T0)
+    if S < 10 or not 0 < T0 <= min((S - 10) // 5 + 1, out.shape[1]):
+        raise _C.F5EError(f"wavlm_conv0: T0 = {T0} frames do not fit S = {S} samples / out {tuple(out.shape)}")
+    if not out.is_cuda or out.dtype != F32 or out.stride(2) != 1 or (out.shape[1] > 1 and out.stride(1) != Cc):
+        raise _C.F5EError("wavlm_conv0: out must be an f32 GPU tensor whose frames are C floats apart")
+    bstride = out.stride(0) if B > 1 else max(out.stride(0), T0 * Cc)
+    wp, ldw = _rows(wav, (F32,), "wavlm_conv0: wav", S, vec=1)
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        if t is not None and t.numel() != Cc:
+            raise _C.F5EError(f"wavlm_conv0: {nm} must have C = {Cc} elements")
+    require_device()
+    check(lib().f5e_wavlm_conv0(_stream(), wp, ldw, _p(w, F32, "w"), _p(bias, F32, "bias"), _p(gamma, F32, "gamma"),
+                                _p(beta, F32, "beta"), C.c_void_p(out.data_ptr()), bstride, B, S, T0, Cc), "f5e_wavlm_conv0")
+    return out
+
+
+def layernorm_gelu(x: Tensor, out: Tensor, gamma: Tensor, beta: Tensor, eps: float = 1e-5):
+    """f5e_layernorm_gelu: out = GELU(erf)(LayerNorm(x) * gamma + beta); x, out f32 [rows, C] row-strided views, out may be x."""
+    if x.ndim != 2 or out.shape != x.shape or gamma.numel() != x.shape[1] or beta.numel() != x.shape[1]:
+        raise _C.F5EError(f"layernorm_gelu: x and out [rows, C], gamma / beta [C] (got {tuple(x.shape)}, {tuple(out.shape)})")
+    rows, Cc = x.shape
+    (xp, ldx), (op, ldo) = _rows(x, (F32,), "layernorm_gelu: x", Cc, vec=1), _rows(out, (F32,), "layernorm_gelu: out", Cc, vec=1)
+    require_device()
+    check(lib().f5e_layernorm_gelu(_stream(), xp, ldx, op, ldo, _p(gamma, F32, "gamma"), _p(beta, F32, "beta"), rows, Cc,
+                                   float(eps)), "f5e_layernorm_gelu")
+    return out
+
+
+def pack_wavlm_posconv_weight(w: Tensor, groups: int) -> Tensor:
+    """Conv1d weight [D][D / groups][taps] (weight norm already folded) -> f32 [groups][taps][oc][ic] as f5e_wavlm_posconv reads it."""
+    D, cg, taps = w.shape
+    if D % groups or D // groups != cg:
+        raise _C.F5EError(f"pack_wavlm_posconv_weight: weight {tuple(w.shape)} does not belong to {groups} groups")
+    return w.reshape(groups, cg, cg, taps).permute(0, 3, 1, 2).to(F32).contiguous()
+
+
+def wavlm_posconv(x: Tensor, w_packed: Tensor, bias: Tensor, frames: Optional[Tensor], out: Tensor, pad: Optional[int] = None):
+    """f5e_wavlm_posconv: x, out f32 [B, T, D] -> out = x + GELU(conv(x) + bias) below frames[b], zero beyond."""
+    xp, ldx, B, T, D = _btc(x, "wavlm_posconv: x")
+    op, ldo, *os_ = _btc(out, "wavlm_posconv: out")
+    if w_packed.ndim != 4:
+        raise _C.F5EError("wavlm_posconv: w_packed must be [groups, taps, cg, cg] (pack_wavlm_posconv_weight)")
+    G, taps, cg, cg2 = w_packed.shape
+    if os_ != [B, T, D] or cg != cg2 or G * cg != D or bias.numel() != D or x.data_ptr() == out.data_ptr():
+        raise _C.F5EError(f"wavlm_posconv: out like x {tuple(x.shape)} (no aliasing), w_packed [G, taps, D / G, D / G], bias [D]")
+    pad = taps // 2 if pad is None else int(pad)
+    require_device()
+    check(lib().f5e_wavlm_posconv(_stream(), xp, ldx, _p(w_packed, F32, "w_packed"), _p(bias, F32, "bias"),
+                                  _len(frames, B, "wavlm_posconv"), op, ldo, B, T, D, G, taps, pad), "f5e_wavlm_posconv")
+    return out
+
+
+def wavlm_gate(x: Tensor, w_gate: Tensor, b_gate: Tensor, head_const: Tensor, gate: Tensor):
+    """f5e_wavlm_gate: x f32 [B * T, >= H dk] (the layer's normed input) -> gate f32 [B, H, T]."""
+    if gate.ndim != 3 or x.ndim != 2 or w_gate.ndim != 2 or w_gate.shape[0] != 8:
+        raise _C.F5EError("wavlm_gate: x [B * T, D], w_gate [8, dk], gate [B, H, T]")
+    B, H, T = gate.shape
+    dk = w_gate.shape[1]
+    if x.shape[0] != B * T or b_gate.numel() != 8 or head_const.numel() != H:
+        raise _C.F5EError(f"wavlm_gate: x needs {B * T} rows, b_gate 8 and head_const {H} elements")
+    xp, ldx = _rows(x, (F32,), "wavlm_gate: x", H * dk)
+    require_device()
+    check(lib().f5e_wavlm_gate(_stream(), xp, ldx, _p(w_gate, F32, "w_gate"), _p(b_gate, F32, "b_gate"),
+                               _p(head_const, F32, "head_const"), _p(gate, F32, "gate"), B, T, H, dk), "f5e_wavlm_gate")
+    return gate
+
+
+def relbias_attn(q: Tensor, k: Tensor, v: Tensor, gate: Tensor, table: Tensor, heads: int, scale: float,
+                 kv_len: Optional[Tensor] = None, out: Optional[Tensor] = None):
+    """f5e_relbias_attn_f32: q / k / v f32 [B * T, D] row-strided views, gate f32 [B, H, T], table f32 [H, 2 Tt - 1] (Tt >= T)
+    -> out f32 [B * T, D]; scores scale q.k + gate[b, h, i] table[h, j - i + Tt - 1] over keys j < kv_len[b]; a query at or
+    beyond kv_len[b] yields zeros."""
+    if q.ndim != 2 or gate.ndim != 3 or table.ndim != 2:
+        raise _C.F5EError("relbias_attn: q [B * T, D], gate [B, H, T], table [H, 2 Tt - 1]")
+    M, D = q.shape
+    B, H, T = gate.shape
+    Tt = (table.shape[1] + 1) // 2
+    if H != heads or M != B * T or D % heads or k.shape != (M, D) or v.shape != (M, D) or table.shape != (H, 2 * Tt - 1) or \
+            Tt < T or (out is not None and out.shape != (M, D)):
+        raise _C.F5EError(f"relbias_attn: inconsistent shapes q {tuple(q.shape)} k {tuple(k.shape)} v {tuple(v.shape)} gate "
+                          f"{tuple(gate.shape)} table {tuple(table.shape)} heads={heads}")
+    (qp, ldq), (kp, ldk), (vp, ldv) = _rows(q, (F32,), "relbias_attn: q", D), _rows(k, (F32,), "relbias_attn: k", D), \
+        _rows(v, (F32,), "relbias_attn: v", D, vec=1)
+    require_device()
+    out = torch.empty(M, D, dtype=F32, device=q.device) if out is None else out
+    op, ldo = _rows(out, (F32,), "relbias_attn: out", D)
+    check(lib().f5e_relbias_attn_f32(_stream(), qp, ldq, kp, ldk, vp, ldv, op, ldo, _p(gate, F32, "gate"),
+                                     _p(table, F32, "table"), Tt, _len(kv_len, B, "relbias_attn"), B, T, heads, D // heads,
+                                     float(scale)), "f5e_relbias_attn_f32")
+    return out
+
+
 def dit_forward(plan: "_C.DitPlan"):
     require_device()
     check(lib().f5e_dit_forward(_stream(), C.byref(plan)), "f5e_dit_forward")

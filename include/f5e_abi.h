@@ -654,6 +654,56 @@ F5E_API int f5e_bias_tanh(f5e_stream st, float* x, int ldx, const float* add, in
 F5E_API int f5e_attn_stats_pool(f5e_stream st, const float* x, int ldx, const float* logits, int ldl, const int* len,
                         float* out, int B, int T, int C);
 
+/* ---------------------------------------------------------------- WavLM upstream (csrc/wavlm.hip, csrc/ppg_attention.hip) */
+/* The upstream of the SIM metric (WavLM-large through s3prl in the reference, eval/ecapa_tdnn.py:171-199): from 16 kHz audio
+ * to the stack of hidden states that f5e_layer_mix_inorm takes.  fp32, channels-last, eval mode.  The strided convolutions 1-6
+ * of the extractor, the projections and the feed-forward are f5e_gemm_f32 / f5e_layernorm; these are the rest.  Per-row lengths
+ * are DEVICE int [B] (NULL: every row is full).  No allocation, no synchronisation, nothing read back: all of it is
+ * capturable. */
+
+/* out[b][i] = (wav[b][i] - mean_b) / sqrt(var_b + 1e-5) for i < len[b], ZERO for len[b] <= i < S: mean and biased variance over
+ * the row's valid samples (s3prl's F.layer_norm(wav, wav.shape)).  frames[b] (NULL to skip) = the frame count after the
+ * n_conv <= 8 valid convolutions given by HOST arrays conv_kernels_host / conv_strides_host: n <- (n - k) / s + 1, 0 once
+ * n < k.  mask (NULL to skip) f32 [B][t_mask] = t < frames[b], t_mask <= S.  Two launches: rows are cut into chunks of 4096
+ * samples, one workgroup each; `partials` is scratch of f5e_wav_norm_partials(B, S) floats.  A chunk's statistics depend on
+ * the valid samples only, so a padded row gives the bits of its B = 1 run. */
+F5E_API int f5e_wav_norm(f5e_stream st, const float* wav, int ldw, const int* len, float* out, int ldo, float* partials,
+                 int* frames, float* mask, int t_mask, const int* conv_kernels_host, const int* conv_strides_host,
+                 int n_conv, int B, int S);
+F5E_API int f5e_wav_norm_partials(int B, int S, unsigned long long* floats_out_host);
+
+/* Layer 0 of the extractor in one pass: Conv1d(1 -> C, k = 10, stride 5, no padding; w f32 [C][10], bias [C] or NULL) +
+ * LayerNorm over C (gamma, beta, eps 1e-5) + GELU(erf).  wav f32 [B][S] (row stride ldw) -> out[b][t][c], t < T0 <=
+ * (S - 10) / 5 + 1, frames of a row C floats apart, rows out_bstride floats apart.  C <= 512. */
+F5E_API int f5e_wavlm_conv0(f5e_stream st, const float* wav, int ldw, const float* w, const float* bias, const float* gamma,
+                    const float* beta, float* out, long long out_bstride, int B, int S, int T0, int C);
+
+/* out[r] = GELU(erf)(LayerNorm_C(x[r]) * gamma + beta), one pass, out may be x.  C <= 1024. */
+F5E_API int f5e_layernorm_gelu(f5e_stream st, const float* x, int ldx, float* out, int ldo, const float* gamma,
+                       const float* beta, long long rows, int C, float eps);
+
+/* out[b][t] = x[b][t] + GELU(erf)(conv(x)[b][t] + bias) for t < frames[b], ZERO for frames[b] <= t < T.  conv: Conv1d(D, D,
+ * k = taps, padding = pad, groups) evaluated at t = 0 .. T - 1 (for an even k with pad = k / 2 that is the reference's conv
+ * with its last output frame dropped); frames outside [0, frames[b]) READ as zero whatever the buffer holds.  x, out f32
+ * [B * T][D] (row strides ldx, ldo; no aliasing).  w_packed f32 [groups][taps][D / groups (oc)][D / groups (ic)] is the
+ * weight-norm-folded weight.  v_mfma_f32_16x16x4_f32; D / groups a multiple of 4; 16-byte aligned operands. */
+F5E_API int f5e_wavlm_posconv(f5e_stream st, const float* x, int ldx, const float* w_packed, const float* bias,
+                      const int* frames, float* out, int ldo, int B, int T, int D, int groups, int taps, int pad);
+
+/* gate[b][h][t] = a (b' const[h] - 1) + 2,  a = sigmoid(sum p[0:4]), b' = sigmoid(sum p[4:8]),
+ * p = w_gate x[b][t][h dk : (h + 1) dk] + b_gate   (w_gate f32 [8][dk], b_gate [8], head_const [H]; x = the layer's NORMED
+ * input, f32 [B * T][>= H dk]).  dk a multiple of 4, at most 128. */
+F5E_API int f5e_wavlm_gate(f5e_stream st, const float* x, int ldx, const float* w_gate, const float* b_gate,
+                   const float* head_const, float* gate, int B, int T, int H, int dk);
+
+/* Self-attention with the gated relative-position bias computed on the fly (no [H][T][T] tensor exists):
+ *   s[i][j] = scale q_i . k_j + gate[b][h][i] table[h][j - i + Tt - 1]   over keys j < kv_len[b]
+ * q, k, v, out f32 [B * T][>= H dk]; gate f32 [B][H][T]; table f32 [H][2 Tt - 1], Tt >= T.  The wave tile of f5e_mha_f32.  A
+ * query at or beyond kv_len[b] yields ZEROS.  dk in {16, 32, 64}. */
+F5E_API int f5e_relbias_attn_f32(f5e_stream st, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                         float* out, int ldo, const float* gate, const float* table, int Tt, const int* kv_len, int B,
+                         int T, int H, int dk, float scale);
+
 /* ---------------------------------------------------------------- hipGraph capture --------------------------- */
 F5E_API int f5e_graph_begin(f5e_stream st);
 F5E_API int f5e_graph_end(f5e_stream st, void** graph_exec_out);

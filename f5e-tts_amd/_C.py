@@ -35,6 +35,7 @@ SIGNATURES = {
     "f5e_convpos": [_P, _P, _I, _P, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I],
     "f5e_dwconv7": [_P, _P, _P, _P, _P, _I, _I, _I],
     "f5e_im2col": [_P, _P, _P, _I, _I, _I, _I, _I],
+    "f5e_conv2d_sub_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I],
     "f5e_sinus_embed": [_P, _P, _P, _P, _I, _I, _F],
     "f5e_rope_table": [_P, _P, _P, _I, _I],
     "f5e_text_gather": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I],

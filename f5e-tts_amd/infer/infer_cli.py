@@ -211,7 +211,7 @@ def main(argv=None):
         rank = dict(best_of=args.best_of, seed=args.seed, report=[])
         if args.best_of > 1:
             from ..ppg.ctc_align import CTCAligner
-            rank["scorer"] = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, s["device"])
+            rank["scorer"] = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, s["device"], asr=True)
             rank["scorer"].warm()
     voices = dict(config.get("voices", {}))
     voices["main"] = {"ref_audio": s["ref_audio"], "ref_text": s["ref_text"]}

@@ -174,7 +174,7 @@ def main(argv=None):
     aligner = None
     if parts is None:
         from ..ppg.ctc_align import CTCAligner
-        aligner = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, args.device)
+        aligner = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, args.device, asr=True)
     wave, sr, _mel = speech_edit_process(args.audio, args.origin_text, args.target_text, model, vocoder,
                                          parts_to_edit=parts, fix_duration=fix, aligner=aligner,
                                          mel_spec_type=args.vocoder_name, nfe_step=args.nfe_step,

@@ -320,6 +320,37 @@ def im2col(x: Tensor, col: Tensor, ksize: int, pad: int):
     return col
 
 
+def pack_conv2d_sub_weight(w: Tensor) -> Tensor:
+    """Conv2d weight [C_out][C_in][kt][kf] -> [C_out][kt][kf][C_in], the [N][K] matrix of ``conv2d_sub``."""
+    return w.permute(0, 2, 3, 1).contiguous()
+
+
+def conv2d_sub(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], stride: int, *, out: Optional[Tensor] = None,
+               act: int = ACT_RELU) -> Tensor:
+    """Strided Conv2d without padding as an implicit GEMM (f5e_conv2d_sub_f32): x f32 [B, T_in, F_in, C] channels-last,
+    w_packed f32 [C, kt, kf, C] (``pack_conv2d_sub_weight``), bias f32 [C] or None -> act(conv) f32 [B, T_out, F_out, C].
+    No workspace.  Everything is refused here or by the library before any launch."""
+    require_device()
+    if x.ndim != 4 or w_packed.ndim != 4:
+        raise _C.F5EError(f"conv2d_sub: x [B, T, F, C] and w [C, kt, kf, C] (got {tuple(x.shape)}, {tuple(w_packed.shape)})")
+    B, T_in, F_in, Cc = x.shape
+    N, kt, kf, Cw = w_packed.shape
+    if N != Cc or Cw != Cc or Cc % 16:
+        raise _C.F5EError(f"conv2d_sub: a C -> C convolution with C a multiple of 16 (x has {Cc}, w is {tuple(w_packed.shape)})")
+    if T_in < kt or F_in < kf or stride < 1:
+        raise _C.F5EError(f"conv2d_sub: input [{T_in}, {F_in}] is smaller than the kernel [{kt}, {kf}] (stride {stride})")
+    if bias is not None and bias.numel() != Cc:
+        raise _C.F5EError(f"conv2d_sub: bias must have C = {Cc} elements")
+    T_out, F_out = (T_in - kt) // stride + 1, (F_in - kf) // stride + 1
+    if out is None:
+        out = torch.empty(B, T_out, F_out, Cc, device=x.device, dtype=F32)
+    if tuple(out.shape) != (B, T_out, F_out, Cc):
+        raise _C.F5EError(f"conv2d_sub: out must be [{B}, {T_out}, {F_out}, {Cc}] (got {tuple(out.shape)})")
+    check(lib().f5e_conv2d_sub_f32(_stream(), _p(x, F32, "x"), _p(w_packed, F32, "w_packed"), _p(bias, F32, "bias"),
+                                   _p(out, F32, "out"), B, T_in, F_in, Cc, kt, kf, stride, act), "f5e_conv2d_sub_f32")
+    return out
+
+
 def sinus_embed(t: Tensor, freqs: Tensor, out: Tensor, scale: float = 1000.0):
     require_device()
     E, dim = out.shape

@@ -15,7 +15,7 @@ import torch
 from .. import _C
 
 FRAME_SHIFT_S = 0.01      # kaldi fbank: 10 ms
-SUBSAMPLING = 2           # Conv2dSubsampling2, the `conv2d` front-end built here
+SUBSAMPLING = 2           # Conv2dSubsampling2, the `conv2d` front-end: the default where no model says its rate
 
 
 class WordSpan(NamedTuple):
@@ -141,17 +141,19 @@ class CTCAligner:
 
     def __init__(self, ppg_model_path: Optional[str] = None, ppg_config: Optional[str] = None,
                  dict_path: Optional[str] = None, device="cuda", tokenize: Optional[Callable] = None, *, model=None,
-                 symbol_table: Optional[Dict[str, int]] = None, decoder: bool = False):
-        from .ppg_model import build_ppg_model, kaldiFbank
+                 symbol_table: Optional[Dict[str, int]] = None, decoder: bool = False, asr: bool = False):
+        from .ppg_model import build_asr_model, build_ppg_model, kaldiFbank
         self.device = device
-        self.model = model if model is not None else build_ppg_model(ppg_model_path, ppg_config, device, ctc=True,
-                                                                           decoder=decoder)
+        build = build_asr_model if asr else build_ppg_model      # asr: also the 4x / 6x / 8x fronts and layer-norm conv modules
+        self.model = model if model is not None else build(ppg_model_path, ppg_config, device, ctc=True, decoder=decoder)
         if not getattr(self.model, "has_ctc", False):
             raise _C.F5EError("CTCAligner: the model was built without its CTC head (ctc=True)")
         self.table = dict(symbol_table) if symbol_table is not None else read_symbol_table(dict_path)
         self.inverse = {v: k for k, v in self.table.items()}
         self.tokenize = tokenize or (lambda text: default_tokenize(text, self.table))
         self.featCal = kaldiFbank().eval()
+        # seconds per encoder frame: the fbank shift times the model's subsampling rate (20 ms for the 2x front)
+        self.frame_s = FRAME_SHIFT_S * int(getattr(self.model, "subsampling_rate", SUBSAMPLING))
 
     def _feats(self, audio, sr):
         from ..infer import audio as A
@@ -254,7 +256,8 @@ class CTCAligner:
         al = self.model.ctc_forced_align(feats, lens, [labels])       # host ids and lengths: validated there (F5EError)
         if int(al.align[0, 0]) < 0:                                   # the kernel's "no path" row: never build spans from it
             raise _C.F5EError("CTCAligner.align: the text has no CTC path through this recording")
-        return word_spans(words, ids, al.tok_end[0].cpu().tolist(), int(al.frame_lens[0]), total_s=secs)
+        return word_spans(words, ids, al.tok_end[0].cpu().tolist(), int(al.frame_lens[0]), frame_s=self.frame_s,
+                          total_s=secs)
 
     def warm(self) -> None:
         """Build what the first call would build lazily (the model's engine, the fbank's device buffers), on the calling

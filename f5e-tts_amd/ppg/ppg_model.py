@@ -13,7 +13,12 @@ subsampling for 20 ms PPG frames, ``rel_pos``, macaron feed-forward, convolution
 ``causal`` either way).  ``extract(stream=False)`` decodes with the full context; ``extract(stream=True)`` reproduces the
 reference's chunk-by-chunk loop (``BaseEncoder.forward_chunk_by_chunk(speech, 16, 17)``, encoder.py:293-355) as ONE pass
 with a banded attention kernel (``f5e_relpos_attn``) and a chunk-isolated or causal depthwise convolution
-(``f5e_dwconv_stream``); ``forward_encoder_chunk`` is the incremental form with explicit caches.  Other encoder variants
+(``f5e_dwconv_stream``); ``forward_encoder_chunk`` is the incremental form with explicit caches.
+
+``ConformerPPG.from_asr_config`` / ``build_asr_model`` build the same model as a RECOGNISER on stock wenet encoders: the
+reference's 4x / 6x / 8x fronts (``input_layer: conv2d4 / conv2d6 / conv2d8``, Conv2dSubsampling4 / 6 / 8; their C -> C
+strided convolutions run as an implicit GEMM, ``f5e_conv2d_sub_f32``) and ``cnn_module_norm: layer_norm``.  The extractor's
+own door (``from_config`` / ``build_ppg_model``) stays 2x and batch-norm: the DiT needs 20 ms PPGs.  Other encoder variants
 raise F5EError.
 """
 from __future__ import annotations
@@ -73,6 +78,61 @@ class _Subsampling2(nn.Module):
         self.out = nn.Sequential(nn.Linear(odim * ((idim - 1) // 2), odim))
 
 
+# ``input_layer`` -> subsampling rate, and the (kernel, stride) of every convolution of the stack (subsampling.py:68-280:
+# Conv2dSubsampling2 / 4 / 6 / 8; the first is Conv2d(1, C, 3, 2), the others Conv2d(C, C, k, s)).  Lengths, masks, the right
+# context and the streaming windows all follow from this table.
+CNN_MODULE_NORMS = ("batch_norm", "layer_norm")
+INPUT_LAYERS = {"conv2d": 2, "conv2d4": 4, "conv2d6": 6, "conv2d8": 8}
+SUBSAMPLING_CONVS = {2: ((3, 2),), 4: ((3, 2), (3, 2)), 6: ((3, 2), (5, 3)), 8: ((3, 2), (3, 2), (3, 2))}
+
+
+def _convs(rate: int):
+    if rate not in SUBSAMPLING_CONVS:
+        raise _C.F5EError(f"PPG extractor: subsampling rate {rate} is not built (2, 4, 6 or 8)")
+    return SUBSAMPLING_CONVS[rate]
+
+
+def right_context(rate: int = 2) -> int:
+    """``embed.right_context``: sum of (kernel - 1) * frame rate of the layer -> 2 / 6 / 10 / 14."""
+    rc, step = 0, 1
+    for k, s in _convs(rate):
+        rc, step = rc + (k - 1) * step, step * s
+    return rc
+
+
+def subsampled_frames(n: int, rate: int = 2) -> int:
+    """Output frames of the stack on ``n`` frames (or bins): n <- (n - k) // s + 1 per convolution, 0 once n < k."""
+    for k, s in _convs(rate):
+        n = (n - k) // s + 1 if n >= k else 0
+    return n
+
+
+def subsampled_len(length: int, T: int, rate: int = 2) -> int:
+    """Valid frames the reference's sliced pad mask leaves to an utterance of ``length`` frames padded to ``T``:
+    ``mask[:, :, :-2:2]`` for a (3, 2) convolution, ``[:, :, :-4:3]`` for (5, 3), chained (subsampling.py:119-280)."""
+    idx = range(T)
+    for k, s in _convs(rate):
+        idx = idx[:-(k - 1):s]
+    return sum(1 for i in idx if i < int(length))
+
+
+class _Subsampling(nn.Module):
+    """Conv2dSubsampling4 / 6 / 8 by the reference's parameter names: ``conv.{0,2,4}`` (ReLUs between) and ``out.0`` (4x)
+    or ``linear`` (6x, 8x)."""
+
+    def __init__(self, idim, odim, rate):
+        super().__init__()
+        mods = []
+        for i, (k, s) in enumerate(_convs(rate)):
+            mods += [nn.Conv2d(1 if i == 0 else odim, odim, k, s), nn.ReLU()]
+        self.conv = nn.Sequential(*mods)
+        width = odim * subsampled_frames(idim, rate)
+        if rate == 4:
+            self.out = nn.Sequential(nn.Linear(width, odim))
+        else:
+            self.linear = nn.Linear(width, odim)
+
+
 class _RelMHA(nn.Module):
     def __init__(self, heads, d):
         super().__init__()
@@ -92,32 +152,32 @@ class _FFN(nn.Module):
 
 
 class _ConvModule(nn.Module):
-    def __init__(self, d, k):
+    def __init__(self, d, k, norm="batch_norm"):
         super().__init__()
         self.pointwise_conv1 = nn.Conv1d(d, 2 * d, 1)
         self.depthwise_conv = nn.Conv1d(d, d, k, padding=(k - 1) // 2, groups=d)
-        self.norm = nn.BatchNorm1d(d)
+        self.norm = nn.BatchNorm1d(d) if norm == "batch_norm" else nn.LayerNorm(d)        # convolution.py:63-69
         self.pointwise_conv2 = nn.Conv1d(d, d, 1)
 
 
 class _ConformerLayer(nn.Module):
-    def __init__(self, d, heads, units, k):
+    def __init__(self, d, heads, units, k, cnn_norm="batch_norm"):
         super().__init__()
         self.self_attn = _RelMHA(heads, d)
         self.feed_forward, self.feed_forward_macaron = _FFN(d, units), _FFN(d, units)
-        self.conv_module = _ConvModule(d, k)
+        self.conv_module = _ConvModule(d, k, cnn_norm)
         for n in ("norm_ff", "norm_mha", "norm_ff_macaron", "norm_conv", "norm_final"):
             setattr(self, n, nn.LayerNorm(d, eps=1e-5))
         self.concat_linear = nn.Linear(2 * d, d)      # a checkpoint key of the reference layer; unused (concat_after False)
 
 
 class _Encoder(nn.Module):
-    def __init__(self, idim, d, heads, units, blocks, k, cmvn):
+    def __init__(self, idim, d, heads, units, blocks, k, cmvn, rate=2, cnn_norm="batch_norm"):
         super().__init__()
         self.global_cmvn = cmvn
-        self.embed = _Subsampling2(idim, d)
+        self.embed = _Subsampling2(idim, d) if rate == 2 else _Subsampling(idim, d, rate)
         self.after_norm = nn.LayerNorm(d, eps=1e-5)
-        self.encoders = nn.ModuleList([_ConformerLayer(d, heads, units, k) for _ in range(blocks)])
+        self.encoders = nn.ModuleList([_ConformerLayer(d, heads, units, k, cnn_norm) for _ in range(blocks)])
 
 
 class _CE(nn.Module):
@@ -279,10 +339,18 @@ class ConformerPPG(nn.Module):
                  linear_units: int = 2048, num_blocks: int = 6, cnn_module_kernel: int = 15,
                  global_cmvn: Optional[Tuple[Tensor, Tensor]] = None, causal: bool = False,
                  use_dynamic_chunk: bool = False, static_chunk_size: int = 0, ctc: bool = False,
-                 decoder: Optional[str] = None, decoder_conf: Optional[dict] = None):
+                 decoder: Optional[str] = None, decoder_conf: Optional[dict] = None, input_layer: str = "conv2d",
+                 cnn_module_norm: str = "batch_norm"):
         super().__init__()
+        if input_layer not in INPUT_LAYERS or cnn_module_norm not in CNN_MODULE_NORMS:
+            raise _C.F5EError(f"PPG extractor: input_layer {input_layer!r} / cnn_module_norm {cnn_module_norm!r} are not built "
+                              f"(one of {', '.join(INPUT_LAYERS)}; {', '.join(CNN_MODULE_NORMS)})")
+        self.input_layer, self.cnn_module_norm = input_layer, cnn_module_norm
+        self.subsampling_rate = INPUT_LAYERS[input_layer]
+        self.right_context = right_context(self.subsampling_rate)
         cm = _GlobalCMVN(global_cmvn[0].float(), global_cmvn[1].float()) if global_cmvn is not None else None
-        self.encoder = _Encoder(input_dim, output_size, attention_heads, linear_units, num_blocks, cnn_module_kernel, cm)
+        self.encoder = _Encoder(input_dim, output_size, attention_heads, linear_units, num_blocks, cnn_module_kernel, cm,
+                                self.subsampling_rate, cnn_module_norm)
         self.linear = nn.Linear(output_size, output_size)
         self.ce = _CE(output_size, vocab_size + 1)
         if ctc:
@@ -309,13 +377,26 @@ class ConformerPPG(nn.Module):
     def from_config(cls, configs: dict, ctc: bool = False, decoder: bool = False) -> "ConformerPPG":
         """``init_asr_model`` (asr_model.py:814-859) for the supported encoder family; ``decoder=True`` also builds the
         attention decoder the config names (``decoder`` -- bitransformer when absent, as there -- and ``decoder_conf``)."""
+        return cls._from_config(configs, ctc, decoder, ("conv2d",), ("batch_norm",))
+
+    @classmethod
+    def from_asr_config(cls, configs: dict, ctc: bool = True, decoder: bool = False) -> "ConformerPPG":
+        """``from_config`` for a recogniser rather than the PPG extractor: also the reference's 4x / 6x / 8x fronts
+        (``input_layer`` conv2d4 / conv2d6 / conv2d8: Conv2dSubsampling4 / 6 / 8) and ``cnn_module_norm: layer_norm``; the
+        CTC head by default.  The DiT needs 20 ms PPGs, so ``from_config`` keeps refusing these."""
+        return cls._from_config(configs, ctc, decoder, tuple(INPUT_LAYERS), CNN_MODULE_NORMS)
+
+    @classmethod
+    def _from_config(cls, configs: dict, ctc: bool, decoder: bool, input_layers, norms) -> "ConformerPPG":
         enc = dict(configs.get("encoder_conf") or {})
         if configs.get("encoder", "conformer") != "conformer":
             raise _C.F5EError("PPG extractor: only `encoder: conformer` is built for MI355X")
-        bad = {k: enc[k] for k, want in dict(input_layer="conv2d", pos_enc_layer_type="rel_pos", normalize_before=True,
+        bad = {k: enc[k] for k, want in dict(pos_enc_layer_type="rel_pos", normalize_before=True,
                                              concat_after=False, macaron_style=True, use_cnn_module=True,
-                                             cnn_module_norm="batch_norm", activation_type="swish", use_emb=False,
+                                             activation_type="swish", use_emb=False,
                                              positionwise_conv_kernel_size=1).items() if k in enc and enc[k] != want}
+        bad.update({k: enc[k] for k, ok in (("input_layer", input_layers), ("cnn_module_norm", norms))
+                    if k in enc and enc[k] not in ok})
         if bad:
             raise _C.F5EError(f"PPG extractor: unsupported encoder_conf entries {bad}")
         cmvn = None
@@ -327,7 +408,8 @@ class ConformerPPG(nn.Module):
                    causal=enc.get("causal", False), use_dynamic_chunk=enc.get("use_dynamic_chunk", False),
                    static_chunk_size=enc.get("static_chunk_size", 0), ctc=ctc,
                    decoder=configs.get("decoder", "bitransformer") if decoder else None,
-                   decoder_conf=configs.get("decoder_conf") if decoder else None)
+                   decoder_conf=configs.get("decoder_conf") if decoder else None,
+                   input_layer=enc.get("input_layer", "conv2d"), cnn_module_norm=enc.get("cnn_module_norm", "batch_norm"))
 
     def _apply(self, fn, *a, **kw):
         self._engine = None
@@ -721,18 +803,35 @@ class ConformerEngine:
         self.heads, self.causal = heads, bool(causal)
         cw, cb = f("encoder.embed.conv.0.weight"), f("encoder.embed.conv.0.bias")        # [C, 1, 3, 3]
         C = cw.shape[0]
-        ow = f("encoder.embed.out.0.weight")                                             # [D, C * F2]
+        # the front by its parameter names (subsampling.py): conv.2 / conv.4 are the C -> C convolutions of the 4x / 6x / 8x
+        # stacks (6x: a 5 x 5 kernel), whose Linear is ``out.0`` (2x, 4x) or ``linear`` (6x, 8x)
+        c2 = sd.get("encoder.embed.conv.2.weight")
+        self.rate = 2 if c2 is None else (8 if "encoder.embed.conv.4.weight" in sd else (6 if c2.shape[-1] == 5 else 4))
+        self.right_context = right_context(self.rate)
+        self.context = self.right_context + 1
+        lin = "encoder.embed.out.0." if self.rate in (2, 4) else "encoder.embed.linear."
+        if lin + "weight" not in sd:
+            raise _C.F5EError(f"PPG extractor: a {self.rate}x subsampling front needs {lin}weight in the state_dict")
+        ow = f(lin + "weight")                                                           # [D, C * F']
         self.dim = D = ow.shape[0]
-        F2 = ow.shape[1] // C
+        F2, Fo = (idim - 1) // 2, subsampled_frames(idim, self.rate)                     # bins after conv.0 / after the stack
         self.idim = idim
-        if (idim - 1) // 2 != F2:
-            raise _C.F5EError(f"PPG extractor: embed.out expects {F2} subsampled bins, input_dim {idim} gives {(idim - 1) // 2}")
+        if Fo < 1 or ow.shape[1] != C * Fo:
+            raise _C.F5EError(f"PPG extractor: embed.out expects {ow.shape[1] // C} subsampled bins, input_dim {idim} gives {Fo}")
         # Conv2d(1, C, 3, stride 2) over [T, idim] as ONE dense GEMM per frame triple: row n = c * F2 + f' of a Toeplitz
         # matrix holds w[c, 0, i, j] at column i * idim + 2 f' + j.  Global CMVN ((x - mean) * istd, per feature) is
         # linear in x, so it folds into these weights and a per-row bias (weights-only transform, done once).
+        # Rates 4 / 6 / 8: row n = f' * C + c instead, so that the GEMM emits the channels-last [T1, F2, C] activation that
+        # f5e_conv2d_sub_f32 reads; its weights go to [C][kt][kf][C], and the Linear's columns from (c, f) to (f, c) order.
         toe = torch.zeros(C * F2, 3 * idim, device=dv)
         n = torch.arange(C * F2, device=dv)
-        c_idx, f_idx = n // F2, n % F2
+        c_idx, f_idx = (n // F2, n % F2) if self.rate == 2 else (n % C, n // C)
+        self.sub_convs = [(ops.pack_conv2d_sub_weight(f(f"encoder.embed.conv.{2 * i}.weight")),
+                           f(f"encoder.embed.conv.{2 * i}.bias"), s) for i, (_, s) in enumerate(_convs(self.rate)) if i]
+        if self.rate != 2:
+            if C % 16:
+                raise _C.F5EError(f"PPG extractor: the {self.rate}x front's convolutions need a multiple of 16 channels (got {C})")
+            ow = ow.view(D, C, Fo).permute(0, 2, 1).reshape(D, Fo * C).contiguous()
         for i in range(3):
             for j in range(3):
                 toe[n, i * idim + 2 * f_idx + j] = cw[c_idx, 0, i, j]
@@ -743,8 +842,8 @@ class ConformerEngine:
             bias = bias - (toe * (s3 * m3)[None, :]).sum(1)
             toe = toe * s3[None, :]
         self.sub_w, self.sub_b = toe.contiguous(), bias.contiguous()
-        self.sub_k = 3 * idim
-        self.out_w, self.out_b = ow, f("encoder.embed.out.0.bias")
+        self.sub_k, self.sub_c = 3 * idim, C
+        self.out_w, self.out_b = ow, f(lin + "bias")
         self.xscale = math.sqrt(D)
         dk = D // heads
         self.layers = []
@@ -755,7 +854,10 @@ class ConformerEngine:
             u, v = f(p + "self_attn.pos_bias_u").reshape(-1), f(p + "self_attn.pos_bias_v").reshape(-1)
             cm = p + "conv_module."
             dw, db = f(cm + "depthwise_conv.weight")[:, 0, :], f(cm + "depthwise_conv.bias")       # [D, k]
-            s = f(cm + "norm.weight") / torch.sqrt(f(cm + "norm.running_var") + 1e-5)             # eval-mode BatchNorm1d
+            # cnn_module_norm: eval-mode BatchNorm1d folds into the depthwise weights; layer_norm (no running statistics in
+            # the state_dict) stays a LayerNorm over channels behind the depthwise convolution (convolution.py:122-128)
+            bn = cm + "norm.running_var" in sd
+            s = f(cm + "norm.weight") / torch.sqrt(f(cm + "norm.running_var") + 1e-5) if bn else torch.ones_like(db)
             if not self.causal and dw.shape[1] % 2 == 0:
                 raise _C.F5EError(f"PPG extractor: cnn_module_kernel {dw.shape[1]} must be odd unless causal")
             pb1 = f(cm + "pointwise_conv1.bias")
@@ -772,7 +874,8 @@ class ConformerEngine:
                 wp=f(p + "self_attn.linear_pos.weight"),
                 pw1=f(cm + "pointwise_conv1.weight")[:, :, 0].contiguous(), pb1=f(cm + "pointwise_conv1.bias"),
                 dw=(dw * s[:, None]).t().contiguous(),
-                db=((db - f(cm + "norm.running_mean")) * s + f(cm + "norm.bias")).contiguous(),
+                db=((db - f(cm + "norm.running_mean")) * s + f(cm + "norm.bias")).contiguous() if bn else db,
+                cn=None if bn else (f(cm + "norm.weight"), f(cm + "norm.bias")),
                 # causal: what the depthwise conv sees left of an utterance is GLU(pointwise_conv1(0)) (the reference pads
                 # zeros BEFORE pointwise_conv1, convolution.py:103-119)
                 fill=(pb1[:D] * torch.sigmoid(pb1[D:])).contiguous(),
@@ -976,7 +1079,7 @@ class ConformerEngine:
         xs = self._subsample(feats.to(dv, F32).contiguous())
         T2 = xs.shape[0] // B
         lens_h = lens.detach().to("cpu", torch.long)
-        len2 = torch.tensor([int(((torch.arange(0, T - 2, 2)) < int(n)).sum()) for n in lens_h], dtype=I32)  # mask[:, :, :-2:2]
+        len2 = torch.tensor([subsampled_len(int(n), T, self.rate) for n in lens_h], dtype=I32)  # mask[:, :, :-2:2] ...
         pos = self.pos_table(T2)
         # masks whenever ANY item is shorter than the padded length (reference BaseEncoder always builds them from xs_lens,
         # ppg/wenet/transformer/encoder.py: also for a single padded utterance); all-full batches need none
@@ -1004,13 +1107,16 @@ class ConformerEngine:
     # whatever the number of chunks); forward_chunk runs the same kernels on [cached rows ; new rows].
 
     def _subsample(self, x: Tensor) -> Tensor:
-        """Conv2dSubsampling2 (+ folded CMVN) + xscale of [B, T, idim] -> [B * T', D]: patches of 3 frames at stride 2 ->
-        ReLU(Toeplitz GEMM), one strided GEMM per item -> Linear -> x * sqrt(d) (RelPositionalEncoding)."""
+        """Conv2dSubsampling2 / 4 / 6 / 8 (+ folded CMVN) + xscale of [B, T, idim] -> [B * T', D]: patches of 3 frames at
+        stride 2 -> ReLU(Toeplitz GEMM), one strided GEMM per item -> (rates 4 / 6 / 8: the C -> C convolutions as implicit
+        GEMMs on the channels-last activation, f5e_conv2d_sub_f32) -> Linear -> x * sqrt(d) (RelPositionalEncoding).
+        Padded frames of a ragged batch are convolved as they are, as the reference does: a valid frame next to the
+        padding sees whatever the padding holds."""
         B, T, idim = x.shape
         if idim != self.idim:
             raise _C.F5EError(f"PPG extractor: features have {idim} bins, the model expects {self.idim}")
-        if T < 3:
-            raise _C.F5EError("PPG extractor: needs at least 3 feature frames")
+        if T < self.context:
+            raise _C.F5EError(f"PPG extractor: needs at least {self.context} feature frames")
         dv, T2 = self.device, (T - 3) // 2 + 1
         col = torch.empty(B, T, self.sub_k, device=dv)
         ops.im2col(x, col, 3, 0)
@@ -1019,6 +1125,11 @@ class ConformerEngine:
         for b in range(B):
             ops.gemm_f32(patches[b * T:(b + 1) * T:2], self.sub_w, self.sub_b, out=h[b * T2:(b + 1) * T2], M=T2,
                          act=ops.ACT_RELU)
+        C = self.sub_c
+        for w, bias, stride in self.sub_convs:
+            h = ops.conv2d_sub(h.view(B, T2, -1, C), w, bias, stride)
+            T2 = h.shape[1]
+        h = h.view(B * T2, -1)
         xs = torch.empty(B * T2, self.dim, device=dv)
         ops.gemm_f32(h, self.out_w, self.out_b, out=xs)
         ops.axpby(xs, None, xs, self.xscale, 0.0, 0.0)
@@ -1069,6 +1180,8 @@ class ConformerEngine:
         ops.gemm_f32(src, L["pw1"], L["pb1"], out=S.pw)
         ops.glu(S.pw, S.gl)
         ops.dwconv_stream(S.gl3, L["dw"], L["db"], S.dwo3, **dw)
+        if L["cn"] is not None:
+            _ln(S.dwoq, S.dwoq, L["cn"])
         ops.gemm_f32(S.dwoq, L["pw2"], L["pb2"], out=hq, a_act=ops.ACT_SILU, row_scale=keep)
         ops.axpby(xq, hq, xq, 1.0, 1.0)
         # feed-forward + final norm
@@ -1129,12 +1242,13 @@ class ConformerEngine:
         return src, dict(causal=True), src[-left:].t().unsqueeze(0).contiguous()
 
     @staticmethod
-    def stream_frames(num_frames: int, chunk: int) -> int:
-        """Encoder frames the reference's loop yields (encoder.py:328-343): windows of 2 (chunk - 1) + 3 feature frames at
-        stride 2 chunk, starting while ``cur < num_frames - 3 + 1``; each window of n frames gives (n - 3) // 2 + 1."""
-        window, total = 2 * (chunk - 1) + 3, 0
-        for cur in range(0, num_frames - 3 + 1, 2 * chunk):
-            total += (min(cur + window, num_frames) - cur - 3) // 2 + 1
+    def stream_frames(num_frames: int, chunk: int, rate: int = 2, context: int = 3) -> int:
+        """Encoder frames the reference's loop yields (encoder.py:328-343): windows of rate (chunk - 1) + context feature
+        frames at stride rate chunk, starting while ``cur < num_frames - context + 1``; each window of n frames gives what
+        the subsampling stack leaves of n.  The defaults are the 2x front (window 2 (chunk - 1) + 3, (n - 3) // 2 + 1)."""
+        window, total = rate * (chunk - 1) + context, 0
+        for cur in range(0, num_frames - context + 1, rate * chunk):
+            total += subsampled_frames(min(cur + window, num_frames) - cur, rate)
         return total
 
     def forward_chunk_by_chunk(self, feats: Tensor, decoding_chunk_size: int, num_decoding_left_chunks: int = -1) -> Tensor:
@@ -1144,7 +1258,7 @@ class ConformerEngine:
         if feats.shape[0] != 1:
             raise _C.F5EError(f"PPG extractor: streaming runs one utterance at a time (batch {feats.shape[0]})")
         xs = self._subsample(feats.to(self.device, F32).contiguous())
-        n = self.stream_frames(feats.shape[1], decoding_chunk_size)
+        n = self.stream_frames(feats.shape[1], decoding_chunk_size, self.rate, self.context)
         if n > xs.shape[0]:
             raise _C.F5EError(f"PPG extractor: the streaming loop yields {n} frames, the subsampling {xs.shape[0]}")
         xs = xs[:n]
@@ -1250,6 +1364,27 @@ def build_ppg_model(ppg_model_path, ppg_config, device="cpu", ctc: bool = False,
     """reference ppg/ppg_model.py:11-29: yaml -> model (cmvn path fallback next to the checkpoint) -> checkpoint keys that
     exist in the model are loaded, the rest (the attention decoder unless ``decoder=True``; the CTC head unless ``ctc=True``)
     ignored."""
+    return _build_model(ppg_model_path, ppg_config, device, ctc, decoder, asr=False)
+
+
+def check_input_layer(input_layer: str, checkpoint_keys) -> None:
+    """Upstream wenet names its 4x front ``conv2d``; here (as in the reference) ``conv2d`` is the 2x front and 4x is
+    ``conv2d4``.  A config that says ``conv2d`` over a checkpoint that holds a second convolution would load the wrong
+    Linear shape: refuse it by name instead."""
+    if input_layer == "conv2d" and "encoder.embed.conv.2.weight" in checkpoint_keys:
+        raise _C.F5EError("ASR model: the config says `input_layer: conv2d` (the 2x front here) but the checkpoint holds "
+                          "encoder.embed.conv.2.weight, a second subsampling convolution: this is an upstream wenet model "
+                          "whose `conv2d` means 4x -- use `input_layer: conv2d4`")
+
+
+def build_asr_model(model_path, config, device="cpu", ctc: bool = True, decoder: bool = False):
+    """``build_ppg_model`` for a recogniser (``ConformerPPG.from_asr_config``): the 2x / 4x / 6x / 8x fronts, either
+    ``cnn_module_norm``, the CTC head by default.  A 2x batch-norm model gives the model ``build_ppg_model(ctc=True)``
+    gives."""
+    return _build_model(model_path, config, device, ctc, decoder, asr=True)
+
+
+def _build_model(ppg_model_path, ppg_config, device, ctc: bool, decoder: bool, asr: bool):
     import yaml
     with open(ppg_config, "r") as fin:
         ppg_configs = yaml.safe_load(fin)
@@ -1257,8 +1392,10 @@ def build_ppg_model(ppg_model_path, ppg_config, device="cpu", ctc: bool = False,
         old = ppg_configs["cmvn_file"]
         ppg_configs["cmvn_file"] = os.path.join(os.path.dirname(ppg_model_path), "global_cmvn")
         print(f"{old} not exist, use {ppg_configs['cmvn_file']}")
-    model = ConformerPPG.from_config(ppg_configs, ctc=ctc, decoder=decoder)
+    model = (ConformerPPG.from_asr_config if asr else ConformerPPG.from_config)(ppg_configs, ctc=ctc, decoder=decoder)
     checkpoint = torch.load(ppg_model_path, map_location="cpu", weights_only=True)
+    if asr:
+        check_input_layer(model.input_layer, checkpoint.keys())
     model_dict = model.state_dict()
     model_dict.update({k: v for k, v in checkpoint.items() if k in model_dict})
     model.load_state_dict(model_dict)

@@ -28,17 +28,20 @@ FRAMES_PER_SECOND = 100        # kaldi fbank: 10 ms shift
 STREAM_MODES = ("ctc_prefix_beam_search", "attention_rescoring")
 
 
-def ready_windows(num_frames: int, cur: int, chunk: int, final: bool) -> List[Tuple[int, int]]:
+def ready_windows(num_frames: int, cur: int, chunk: int, final: bool, rate: int = 2,
+                  context: int = 3) -> List[Tuple[int, int]]:
     """The feature windows [start, end) of the reference's loop that can run NOW: ``num_frames`` feature frames of the
-    utterance have arrived, the next window starts at ``cur``.  A window is 2 (chunk - 1) + 3 frames at stride 2 chunk.  Before
+    utterance have arrived, the next window starts at ``cur``.  A window is rate (chunk - 1) + context frames at stride rate
+    chunk (``rate``: the model's subsampling rate, ``context`` = its right context + 1; the defaults are the 2x front).  Before
     the end of the utterance only complete windows run (what follows cannot change them); with ``final`` the loop's own bound
-    applies, a last short window running while at least 3 frames remain from its start.  Fed a whole utterance at once (cur
-    = 0, final) this is ``range(0, num_frames - 3 + 1, 2 * chunk)`` with ``end = min(cur + window, num_frames)``."""
+    applies, a last short window running while at least ``context`` frames remain from its start.  Fed a whole utterance at
+    once (cur = 0, final) this is ``range(0, num_frames - context + 1, rate * chunk)`` with ``end = min(cur + window,
+    num_frames)``."""
     if chunk < 1:
         raise _C.F5EError(f"streaming: decoding_chunk_size must be positive (got {chunk})")
-    window, stride = 2 * (chunk - 1) + 3, 2 * chunk
+    window, stride = rate * (chunk - 1) + context, rate * chunk
     out = []
-    while cur + window <= num_frames or (final and cur < num_frames - 3 + 1):
+    while cur + window <= num_frames or (final and cur < num_frames - context + 1):
         out.append((cur, min(cur + window, num_frames)))
         cur += stride
     return out
@@ -87,7 +90,8 @@ class StreamingRecognizer:
         self.use_linear, self.detokenize = bool(use_linear), detokenize
         self.eng = model._require_ctc()
         self.device = self.eng.device
-        self.T_cap = max(1, ConformerEngine.stream_frames(self.max_frames, self.chunk))
+        self.rate, self.context = self.eng.rate, self.eng.context       # the model's subsampling front
+        self.T_cap = max(1, ConformerEngine.stream_frames(self.max_frames, self.chunk, self.rate, self.context))
         self.state = ops.ctc_beam_state(1, self.T_cap, self.chunk, self.beam, device=self.device)
         self.fbank = kaldiFbank().eval().to(self.device)
         self.V = self.eng.ctc_w.shape[0]
@@ -156,7 +160,7 @@ class StreamingRecognizer:
     def _run(self, final: bool) -> int:
         """One forward_chunk, one CTC projection and one search call per window that is ready."""
         eng, added, base = self.eng, 0, self.cur
-        for a, b in ready_windows(self.num_frames, self.cur, self.chunk, final):
+        for a, b in ready_windows(self.num_frames, self.cur, self.chunk, final, self.rate, self.context):
             y, *self.caches = eng.forward_chunk(self.feats[None, a - base:b - base], self.offset, self.chunk * self.left,
                                                 *self.caches)
             n = y.shape[1]
@@ -167,7 +171,7 @@ class StreamingRecognizer:
                                want_result=False)
             self.offset += n
             added += n
-            self.cur = a + 2 * self.chunk
+            self.cur = a + self.rate * self.chunk
         self.feats = self.feats[self.cur - base:] if self.cur > base else self.feats
         return added
 

@@ -184,6 +184,16 @@ F5E_API int f5e_dwconv7(f5e_stream st, const float* x, const float* w_t, const f
 /* col[b][t][j*Cin + ic] = x[b][t + j - pad][ic] (0 outside [0, T)). */
 F5E_API int f5e_im2col(f5e_stream st, const float* x, float* col, int B, int T, int Cin, int ksize, int pad);
 
+/* Strided Conv2d(C, C, [kt, kf], stride) without padding, channels-last, as an implicit GEMM on the exact-fp32 MFMA
+ * (csrc/subsample.hip): the second / third convolution of the wenet Conv2dSubsampling4 / 6 / 8 stacks.
+ *   y[b][to][fo][n] = act(bias[n] + sum_{i, j, c} x[b][to * stride + i][fo * stride + j][c] * w[n][i][j][c])
+ * x f32 [B][T_in][F_in][C], w f32 [C][kt][kf][C] (the torch weight [C_out][C_in][kt][kf] permuted on the host), bias f32 [C]
+ * or NULL, y f32 [B][T_out][F_out][C] with T_out = (T_in - kt) / stride + 1, F_out = (F_in - kf) / stride + 1.  act:
+ * F5E_ACT_NONE or F5E_ACT_RELU.  C % 16 == 0, kt, kf in 1..8, all pointers 16-byte aligned, B * T_in * F_in < 2^31.  No
+ * workspace: the loader gathers the K = kt * kf * C operand row from x (kt contiguous runs of kf * C floats). */
+F5E_API int f5e_conv2d_sub_f32(f5e_stream st, const float* x, const float* w, const float* bias, float* y, int B, int T_in,
+                       int F_in, int C, int kt, int kf, int stride, int act);
+
 /* ---------------------------------------------------------------- sampler elementwise ------------------------ */
 
 /* out[e] = cat(sin(a), cos(a)), a = (scale * t[e]) * freqs[k]   (modules.py:154-161; freqs = host constant [dim/2]) */

@@ -91,6 +91,10 @@ SIGNATURES = {
     "f5e_wavlm_posconv": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
     "f5e_wavlm_gate": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I],
     "f5e_relbias_attn_f32": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _F],
+    "f5e_whisper_logmel_partials": [_I, _I, C.POINTER(C.c_ulonglong)],
+    "f5e_whisper_logmel": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I],
+    "f5e_cross_attn_decode_f32": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F],
+    "f5e_greedy_pick": [_P, _P, _LL, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I],
     "f5e_dit_forward": [_P, _P],
     "f5e_sample_loop": [_P, _P],
     "f5e_workspace_bytes": [_P, _P],

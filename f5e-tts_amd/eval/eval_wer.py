@@ -4,6 +4,11 @@
 
     python -m f5e_tts_amd.eval.eval_wer --gen_wav_dir D --metalst F --lang en|zh --asr_model M --asr_config C --asr_dict T
                                         [--mode ctc_greedy_search|ctc_prefix_beam_search|attention_rescoring]
+    python -m f5e_tts_amd.eval.eval_wer --gen_wav_dir D --metalst F --lang en --asr whisper --whisper_dir W [--language english]
+
+``--asr whisper`` is the reference's English recogniser of the voice-conversion and LibriSpeech evaluations
+(``run_asr_wer_whisper_large_v3``, eval/utils_eval.py:631-712: whisper-large-v3, greedy, prompt ``english / transcribe``) on the
+device (eval/whisper.py), with that function's own clean-up (``normalize_whisper_en``) in place of ``normalize``.
 
 Host code.  Deviations from the reference, parity unpinned (``jiwer``, ``zhon`` and ``zhconv`` are not dependencies here):
   * punctuation is ``string.punctuation`` plus every character of Unicode category P* (the reference: ``zhon.hanzi.punctuation
@@ -18,6 +23,7 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import re
 import string
 import unicodedata
 from pathlib import Path
@@ -38,6 +44,68 @@ def normalize(text: str, lang: str) -> str:
     text = "".join(ch for ch in text if not is_punctuation(ch))
     text = text.replace("  ", " ")
     return " ".join(text) if lang == "zh" else text.lower()
+
+
+_SMALL = ("zero one two three four five six seven eight nine ten eleven twelve thirteen fourteen fifteen sixteen seventeen "
+          "eighteen nineteen").split()
+_TENS = "- - twenty thirty forty fifty sixty seventy eighty ninety".split()
+
+
+def spell_number(n: int) -> str:
+    """British-style cardinal, as the reference spells digits in a Whisper hypothesis (utils_eval.py:566-603): "and" after the
+    hundreds when anything follows, and after the thousands when less than a hundred follows."""
+    if n == 0:
+        return _SMALL[0]
+    words = []
+    if n >= 1000000:
+        words.append(spell_number(n // 1000000) + " million")
+        n %= 1000000
+    if n >= 1000:
+        words.append(spell_number(n // 1000) + " thousand")
+        n %= 1000
+        if 0 < n < 100:
+            words.append("and")
+    if n >= 100:
+        words.append(_SMALL[n // 100] + " hundred")
+        n %= 100
+        if n:
+            words.append("and")
+    if n >= 20:
+        words.append(_TENS[n // 10])
+        n %= 10
+    if n:
+        words.append(_SMALL[n])
+    return " ".join(words).replace(" and zero", "").replace("  ", " ")
+
+
+def replace_mixed_numbers(text: str) -> str:
+    """Every run of digits spelled out and set off by spaces ("18th" -> "eighteen th"); whitespace runs collapse
+    (utils_eval.py:605-616)."""
+    parts = [spell_number(int(p)) if p.isdigit() else p for p in re.findall(r"\d+|\D+", text)]
+    return re.sub(r"\s+", " ", " ".join(parts)).strip()
+
+
+def replace_special(text: str) -> str:
+    """utils_eval.py:618-627: a "$" moves to a closing "dollars", "supercomputer" splits, "18th" / "19th" are spelled.  (After
+    ``replace_mixed_numbers`` and the punctuation pass of ``normalize_whisper_en`` only the second can still apply; the order
+    is the reference's.)"""
+    if "$" in text:
+        text = text.replace("$", "") + "dollars"
+    return text.replace("supercomputer", "super computer").replace("18th", "eighteenth").replace("19th", "nineteenth")
+
+
+def normalize_whisper_en(text: str, hypo: bool) -> str:
+    """The clean-up of the reference's Whisper WER path in its order (utils_eval.py:674-693).  Both sides: ASCII punctuation and
+    the typographic apostrophe removed, ONE pass of double space -> space, lower case.  The hypothesis also: "-" -> " " (a no-op
+    by then: the hyphen went with the punctuation, "twenty-one" is "twentyone"), everything but word characters, whitespace and
+    "'" removed, digits spelled out, ``replace_special``."""
+    for ch in string.punctuation:
+        text = text.replace(ch, "")
+    text = text.replace("\u2019", "").replace("  ", " ")
+    if not hypo:
+        return text.lower()
+    text = re.sub(r"[^\w\s']", "", text.replace("-", " ")).lower()
+    return replace_special(replace_mixed_numbers(text))
 
 
 def word_errors(ref: Sequence, hyp: Sequence) -> Tuple[int, int, int, int]:
@@ -79,17 +147,23 @@ def wer(truth: str, hypo: str) -> float:
 
 
 def run_asr_wer(items: Iterable[Tuple[str, str, str]], aligner, lang: str, mode: str = "ctc_greedy_search",
-                **decode) -> List[Dict]:
+                whisper_cleanup: bool = False, **decode) -> List[Dict]:
     """``items``: (gen_wav, prompt_wav, truth) as ``eval_sim.get_test_set`` returns them; ``aligner``: anything with
     ``transcribe(wav_path, None, mode=..., **decode) -> str`` (a ``CTCAligner``).  -> the reference's per-utterance dicts
-    ``{"wav", "truth", "hypo", "wer"}`` with the RAW texts."""
+    ``{"wav", "truth", "hypo", "wer"}`` with the RAW texts.  ``whisper_cleanup``: ``normalize_whisper_en`` instead of
+    ``normalize`` (the reference's Whisper path, ``en`` only)."""
+    if whisper_cleanup and lang != "en":
+        raise NotImplementedError("the Whisper WER path is the reference's English recogniser: --lang en")
     if lang not in LANGS:
         raise NotImplementedError(f"lang {lang!r}: only 'zh' and 'en' are supported")
     results = []
     for gen_wav, _prompt_wav, truth in items:
         hypo = aligner.transcribe(gen_wav, None, mode=mode, **decode)
-        results.append({"wav": Path(gen_wav).stem, "truth": truth, "hypo": hypo,
-                        "wer": wer(normalize(truth, lang), normalize(hypo, lang))})
+        if whisper_cleanup:
+            score = wer(normalize_whisper_en(truth, False), normalize_whisper_en(hypo, True))
+        else:
+            score = wer(normalize(truth, lang), normalize(hypo, lang))
+        results.append({"wav": Path(gen_wav).stem, "truth": truth, "hypo": hypo, "wer": score})
     return results
 
 
@@ -99,23 +173,36 @@ def main(argv=None, aligner=None) -> float:
     ap.add_argument("--metalst", required=True, help="utt|prompt_text|prompt_wav|gt_text per line")
     ap.add_argument("--gen_wav_dir", required=True)
     ap.add_argument("--lang", required=True, choices=LANGS)
-    ap.add_argument("--asr_model", required=aligner is None, help="wenet conformer checkpoint (CTC head; decoder for rescoring)")
-    ap.add_argument("--asr_config", required=aligner is None, help="its train.yaml (input_layer conv2d / conv2d4 / conv2d6 / conv2d8)")
-    ap.add_argument("--asr_dict", required=aligner is None, help="its `token id` symbol table")
+    ap.add_argument("--asr", default="wenet", choices=("wenet", "whisper"),
+                    help="wenet: the project's conformer recogniser; whisper: the reference's English WER recogniser on the device")
+    ap.add_argument("--whisper_dir", default=None, help="--asr whisper: a local whisper-large-v3 directory (config.json, "
+                    "generation_config.json, model.safetensors, vocab.json, added_tokens.json)")
+    ap.add_argument("--language", default="english", help="--asr whisper: the language token of the forced prompt")
+    ap.add_argument("--asr_model", default=None, help="wenet conformer checkpoint (CTC head; decoder for rescoring)")
+    ap.add_argument("--asr_config", default=None, help="its train.yaml (input_layer conv2d / conv2d4 / conv2d6 / conv2d8)")
+    ap.add_argument("--asr_dict", default=None, help="its `token id` symbol table")
     ap.add_argument("--mode", default="ctc_greedy_search",
                     choices=("ctc_greedy_search", "ctc_prefix_beam_search", "attention_rescoring"))
     ap.add_argument("--beam_size", type=int, default=10)
     ap.add_argument("--out", default=None, help="per-utterance JSON (default: <gen_wav_dir>/_wer_results.json)")
     ap.add_argument("--device", default="cuda")
     args = ap.parse_args(argv)
+    if aligner is None:
+        need = ("whisper_dir",) if args.asr == "whisper" else ("asr_model", "asr_config", "asr_dict")
+        missing = [f"--{n}" for n in need if getattr(args, n) is None]
+        if missing:
+            ap.error(f"the following arguments are required: {', '.join(missing)}")
     test_set = get_test_set(args.metalst, args.gen_wav_dir)
     if not test_set:
         raise SystemExit(f"{args.metalst}: no utterance has a generated wav under {args.gen_wav_dir}")
-    if aligner is None:
+    if aligner is None and args.asr == "whisper":
+        from .whisper import WhisperRecognizer
+        aligner = WhisperRecognizer(args.whisper_dir, args.device, args.language)
+    elif aligner is None:
         from ..ppg.ctc_align import CTCAligner
         aligner = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, args.device, asr=True,
                              decoder=args.mode == "attention_rescoring")
-    results = run_asr_wer(test_set, aligner, args.lang, args.mode, beam_size=args.beam_size)
+    results = run_asr_wer(test_set, aligner, args.lang, args.mode, whisper_cleanup=args.asr == "whisper", beam_size=args.beam_size)
     for r in results:
         print(f"{r['wav']}\t{r['wer']:.4f}\t{r['hypo']}")
     mean = sum(r["wer"] for r in results) / len(results)

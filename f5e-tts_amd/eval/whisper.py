@@ -1,0 +1,604 @@
+"""Whisper on the device: the recogniser the reference loads through ``transformers`` -- ``openai/whisper-large-v3-turbo`` to
+transcribe a prompt without text (infer/utils_infer.py:148-179) and ``whisper-large-v3`` with the forced prompt
+``english / transcribe`` for the English WER (eval/utils_eval.py:631-672).  Greedy decoding, fp32, eval mode, no CPU path:
+f5e_whisper_logmel, f5e_cross_attn_decode_f32 and f5e_greedy_pick (csrc/whisper.hip) plus f5e_im2col, f5e_gemm_f32, f5e_layernorm,
+f5e_mha_f32, f5e_attn_decode_f32 and f5e_text_gather.  The sub-modules only HOLD the weights, under the Hugging Face
+parameter names, so ``load_state_dict`` takes a ``WhisperForConditionalGeneration`` state dict:
+
+    model.encoder.conv1.{weight,bias}, model.encoder.conv2.*, model.encoder.embed_positions.weight,
+    model.encoder.layers.{i}.self_attn.{q,v,out}_proj.{weight,bias}, .self_attn.k_proj.weight (no bias),
+    .self_attn_layer_norm.*, .fc1.*, .fc2.*, .final_layer_norm.*, model.encoder.layer_norm.*,
+    model.decoder.embed_tokens.weight, model.decoder.embed_positions.weight,
+    model.decoder.layers.{i}.self_attn.*, .encoder_attn.* (k_proj again without bias), .self_attn_layer_norm.*,
+    .encoder_attn_layer_norm.*, .fc1.*, .fc2.*, .final_layer_norm.*, model.decoder.layer_norm.*
+    (proj_out.weight is tied to model.decoder.embed_tokens.weight: accepted and dropped)
+
+Out of scope: beam search and temperature fallback, timestamps, long-form chunking, language detection (``language`` is
+required), bf16 / fp16 weights (fp16 checkpoints are widened), a graph-captured step.
+
+Ragged batches: samples at or beyond ``lens[b]`` count as zero, and the row is zero-padded to the chunk length as the feature
+extractor does; Whisper attends those frames, and so does this.  Row b of a batch equals its own B = 1 run."""
+from __future__ import annotations
+
+import json
+import math
+import os
+import struct
+import warnings
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from .. import _C, ops
+
+Tensor = torch.Tensor
+F32, I32 = torch.float32, torch.int32
+SAMPLE_RATE, N_FFT, HOP = 16000, 400, 160
+
+LANGUAGE_NAMES = {"english": "en", "chinese": "zh", "mandarin": "zh", "german": "de", "spanish": "es", "russian": "ru",
+                  "korean": "ko", "french": "fr", "japanese": "ja", "portuguese": "pt", "turkish": "tr", "polish": "pl",
+                  "catalan": "ca", "dutch": "nl", "arabic": "ar", "swedish": "sv", "italian": "it", "indonesian": "id",
+                  "hindi": "hi", "finnish": "fi", "vietnamese": "vi", "hebrew": "he", "ukrainian": "uk", "greek": "el",
+                  "cantonese": "yue"}
+
+
+@dataclass
+class WhisperConfig:
+    """Defaults = whisper-large-v3 (the turbo model has decoder_layers = 4)."""
+    vocab_size: int = 51866
+    num_mel_bins: int = 128
+    d_model: int = 1280
+    encoder_layers: int = 32
+    encoder_attention_heads: int = 20
+    encoder_ffn_dim: int = 5120
+    decoder_layers: int = 32
+    decoder_attention_heads: int = 20
+    decoder_ffn_dim: int = 5120
+    max_source_positions: int = 1500
+    max_target_positions: int = 448
+    eos_token_id: int = 50257
+    decoder_start_token_id: int = 50258
+    activation_function: str = "gelu"
+    scale_embedding: bool = False
+    # generation_config.json
+    suppress_tokens: Tuple[int, ...] = ()
+    begin_suppress_tokens: Tuple[int, ...] = ()
+    lang_to_id: Dict[str, int] = field(default_factory=dict)
+    task_to_id: Dict[str, int] = field(default_factory=dict)
+    no_timestamps_token_id: Optional[int] = None
+
+    @classmethod
+    def from_dicts(cls, config: dict, generation: Optional[dict] = None) -> "WhisperConfig":
+        names = {f for f in cls.__dataclass_fields__}
+        kw = {k: v for k, v in config.items() if k in names and v is not None}
+        for k, v in (generation or {}).items():
+            if k in ("suppress_tokens", "begin_suppress_tokens", "lang_to_id", "task_to_id", "no_timestamps_token_id") and v is not None:
+                kw[k] = v
+        for k in ("suppress_tokens", "begin_suppress_tokens"):
+            kw[k] = tuple(int(t) for t in kw.get(k) or ())
+        eos = kw.get("eos_token_id")
+        if isinstance(eos, (list, tuple)):
+            kw["eos_token_id"] = int(eos[0])
+        return cls(**kw)
+
+    def check(self) -> None:
+        def refuse(name, why):
+            raise _C.F5EError(f"Whisper: {name} = {getattr(self, name)!r} is not built: {why}")
+        if self.num_mel_bins not in (80, 128):
+            refuse("num_mel_bins", "the front-end has 80 or 128 filters")
+        if self.activation_function != "gelu":
+            refuse("activation_function", "only the erf GELU is")
+        if self.scale_embedding:
+            refuse("scale_embedding", "no released checkpoint scales its embeddings")
+        for side in ("encoder", "decoder"):
+            D, H = self.d_model, getattr(self, side + "_attention_heads")
+            if D % H or D // H not in (16, 32, 64, 128):
+                refuse(side + "_attention_heads", f"head dim {D / H:g} (16, 32, 64 and 128 are)")
+            if getattr(self, side + "_ffn_dim") % 4 or getattr(self, side + "_layers") < 1:
+                refuse(side + "_ffn_dim", "a multiple of 4, and at least one layer")
+        if self.d_model % 4 or self.max_source_positions < 1 or self.max_source_positions > 4096:
+            refuse("max_source_positions", "1 .. 4096 positions, d_model a multiple of 4")
+        if not 2 <= self.max_target_positions <= 4096:
+            refuse("max_target_positions", "2 .. 4096")
+        if not 0 <= self.eos_token_id < self.vocab_size or not 0 <= self.decoder_start_token_id < self.vocab_size:
+            refuse("eos_token_id", "eos and decoder_start_token_id must be ids of the vocabulary")
+
+
+# ---- host constants of the front-end (float64, rounded once) ------------------------------------------------------------------
+def hann_window(n: int = N_FFT) -> np.ndarray:
+    """Periodic Hann."""
+    return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n, dtype=np.float64) / n)
+
+
+def _hz_to_mel(f):
+    f = np.asarray(f, dtype=np.float64)
+    return np.where(f >= 1000.0, 15.0 + np.log(np.maximum(f, 1e-300) / 1000.0) * (27.0 / np.log(6.4)), 3.0 * f / 200.0)
+
+
+def _mel_to_hz(m):
+    m = np.asarray(m, dtype=np.float64)
+    return np.where(m >= 15.0, 1000.0 * np.exp((np.log(6.4) / 27.0) * (m - 15.0)), 200.0 * m / 3.0)
+
+
+def mel_filters(n_mels: int, n_fft: int = N_FFT, sr: int = SAMPLE_RATE) -> np.ndarray:
+    """Slaney mel scale, Slaney (area) normalisation, 0 .. sr / 2: float64 [n_fft / 2 + 1][n_mels], the extractor's
+    ``mel_filters``."""
+    bins = n_fft // 2 + 1
+    fft_freqs = np.linspace(0.0, sr // 2, bins)
+    edges = _mel_to_hz(np.linspace(_hz_to_mel(0.0), _hz_to_mel(sr / 2.0), n_mels + 2))
+    diff = np.diff(edges)
+    slopes = edges[None, :] - fft_freqs[:, None]
+    fb = np.maximum(0.0, np.minimum(-slopes[:, :-2] / diff[:-1], slopes[:, 2:] / diff[1:]))
+    return fb * (2.0 / (edges[2:n_mels + 2] - edges[:n_mels]))[None, :]
+
+
+def dft_twiddle(n: int = N_FFT) -> np.ndarray:
+    a = 2.0 * np.pi * np.arange(n, dtype=np.float64) / n
+    return np.stack([np.cos(a), np.sin(a)], 1)
+
+
+def sinusoids(length: int, channels: int, max_timescale: float = 10000.0) -> Tensor:
+    """The encoder's fixed position table (what a fresh ``WhisperEncoder`` holds; checkpoints carry it too)."""
+    inc = math.log(max_timescale) / (channels // 2 - 1)
+    inv = torch.exp(-inc * torch.arange(channels // 2, dtype=torch.float32))
+    t = torch.arange(length, dtype=torch.float32)[:, None] * inv[None, :]
+    return torch.cat([t.sin(), t.cos()], 1)
+
+
+# ---- byte-level detokenisation ------------------------------------------------------------------------------------------------
+def bytes_to_unicode() -> Dict[int, str]:
+    """GPT-2's byte -> printable character table: the printable Latin-1 bytes map to themselves, the others to 256, 257, ..."""
+    keep = set(range(ord("!"), ord("~") + 1)) | set(range(0xA1, 0xAD)) | set(range(0xAE, 0x100))
+    table, n = {}, 0
+    for b in range(256):
+        if b in keep:
+            table[b] = chr(b)
+        else:
+            table[b] = chr(256 + n)
+            n += 1
+    return table
+
+
+_U2B = {c: b for b, c in bytes_to_unicode().items()}
+
+
+def decode_pieces(id_to_piece: Dict[int, str], first_special: int, ids: Sequence[int], skip_special_tokens: bool = True) -> str:
+    """Byte-level BPE pieces -> text: the pieces' characters back to bytes, UTF-8 with ``errors="replace"`` (a character split
+    across tokens is joined first).  Ids at or above ``first_special`` are dropped (or, kept, spelled as they are)."""
+    out, raw = [], bytearray()
+    for i in ids:
+        i = int(i)
+        if i >= first_special:
+            if not skip_special_tokens and i in id_to_piece:
+                out.append(raw.decode("utf-8", errors="replace"))
+                raw = bytearray()
+                out.append(id_to_piece[i])
+            continue
+        piece = id_to_piece.get(i)
+        if piece is None:
+            continue
+        raw.extend(_U2B[c] for c in piece if c in _U2B)
+    out.append(raw.decode("utf-8", errors="replace"))
+    return "".join(out)
+
+
+# ---- checkpoint reading (the safetensors container: u64 header length, JSON header, raw little-endian data) ---------------------
+_ST_DTYPES = {"F32": np.dtype("<f4"), "F16": np.dtype("<f2"), "BF16": np.dtype("<u2"), "F64": np.dtype("<f8")}
+
+
+def read_safetensors(path: str) -> Dict[str, Tensor]:
+    """Every floating tensor of a ``.safetensors`` file as float32 (fp16 and bf16 are widened, which is exact)."""
+    out = {}
+    with open(path, "rb") as f:
+        (n,) = struct.unpack("<Q", f.read(8))
+        header = json.loads(f.read(n).decode("utf-8"))
+        base = 8 + n
+        for name, meta in header.items():
+            if name == "__metadata__" or meta["dtype"] not in _ST_DTYPES:
+                continue
+            lo, hi = meta["data_offsets"]
+            f.seek(base + lo)
+            arr = np.frombuffer(f.read(hi - lo), dtype=_ST_DTYPES[meta["dtype"]])
+            if meta["dtype"] == "BF16":
+                arr = (arr.astype(np.uint32) << 16).view(np.float32)
+            out[name] = torch.from_numpy(np.array(arr, dtype=np.float32).reshape(meta["shape"]))
+    return out
+
+
+# ---- weight holders -------------------------------------------------------------------------------------------------------------
+class _Attn(nn.Module):
+    def __init__(self, D: int):
+        super().__init__()
+        self.q_proj, self.v_proj, self.out_proj = nn.Linear(D, D), nn.Linear(D, D), nn.Linear(D, D)
+        self.k_proj = nn.Linear(D, D, bias=False)
+
+
+class _EncLayer(nn.Module):
+    def __init__(self, D: int, FF: int):
+        super().__init__()
+        self.self_attn, self.self_attn_layer_norm = _Attn(D), nn.LayerNorm(D)
+        self.fc1, self.fc2, self.final_layer_norm = nn.Linear(D, FF), nn.Linear(FF, D), nn.LayerNorm(D)
+
+
+class _DecLayer(_EncLayer):
+    def __init__(self, D: int, FF: int):
+        super().__init__(D, FF)
+        self.encoder_attn, self.encoder_attn_layer_norm = _Attn(D), nn.LayerNorm(D)
+
+
+class _Encoder(nn.Module):
+    def __init__(self, cfg: WhisperConfig):
+        super().__init__()
+        D = cfg.d_model
+        self.conv1 = nn.Conv1d(cfg.num_mel_bins, D, 3, padding=1)
+        self.conv2 = nn.Conv1d(D, D, 3, stride=2, padding=1)
+        self.embed_positions = nn.Embedding(cfg.max_source_positions, D)
+        self.layers = nn.ModuleList([_EncLayer(D, cfg.encoder_ffn_dim) for _ in range(cfg.encoder_layers)])
+        self.layer_norm = nn.LayerNorm(D)
+        with torch.no_grad():
+            self.embed_positions.weight.copy_(sinusoids(cfg.max_source_positions, D))
+
+
+class _Decoder(nn.Module):
+    def __init__(self, cfg: WhisperConfig):
+        super().__init__()
+        D = cfg.d_model
+        self.embed_tokens = nn.Embedding(cfg.vocab_size, D)
+        self.embed_positions = nn.Embedding(cfg.max_target_positions, D)
+        self.layers = nn.ModuleList([_DecLayer(D, cfg.decoder_ffn_dim) for _ in range(cfg.decoder_layers)])
+        self.layer_norm = nn.LayerNorm(D)
+
+
+class _Model(nn.Module):
+    def __init__(self, cfg: WhisperConfig):
+        super().__init__()
+        self.encoder, self.decoder = _Encoder(cfg), _Decoder(cfg)
+
+
+def _f(t: Tensor, dev) -> Tensor:
+    return t.detach().to(dev, F32).contiguous()
+
+
+class Whisper(nn.Module):
+    def __init__(self, config: Optional[WhisperConfig] = None):
+        super().__init__()
+        self.cfg = cfg = config or WhisperConfig()
+        cfg.check()
+        self.model = _Model(cfg)
+        self.id_to_piece: Dict[int, str] = {}
+        self.first_special = cfg.eos_token_id
+        self._folded = None
+        super().train(False)
+        for p in self.parameters():
+            p.requires_grad_(False)
+
+    # ---- loading ---------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_pretrained_dir(cls, path: str) -> "Whisper":
+        """A local Hugging Face model directory: ``config.json``, ``generation_config.json``, ``model.safetensors`` (or
+        ``model.safetensors.index.json`` and its shards), ``vocab.json`` and ``added_tokens.json``."""
+        def js(name, required=True):
+            p = os.path.join(path, name)
+            if not os.path.exists(p):
+                if required:
+                    raise _C.F5EError(f"Whisper.from_pretrained_dir: {p} is missing")
+                return None
+            with open(p, encoding="utf-8") as f:
+                return json.load(f)
+        model = cls(WhisperConfig.from_dicts(js("config.json"), js("generation_config.json", False)))
+        index = js("model.safetensors.index.json", False)
+        files = sorted(set(index["weight_map"].values())) if index else ["model.safetensors"]
+        sd = {}
+        for name in files:
+            p = os.path.join(path, name)
+            if not os.path.exists(p):
+                raise _C.F5EError(f"Whisper.from_pretrained_dir: {p} is missing")
+            sd.update(read_safetensors(p))
+        model.load_state_dict(sd)
+        vocab = js("vocab.json", False)
+        if vocab is not None:
+            model.set_vocab(vocab, js("added_tokens.json", False))
+        return model
+
+    def set_vocab(self, vocab: Dict[str, int], added: Optional[Dict[str, int]] = None) -> None:
+        """``vocab.json`` (piece -> id) and ``added_tokens.json`` (special -> id); the first special id is the lowest added id
+        (the eos id when there is no such file)."""
+        self.id_to_piece = {int(i): p for p, i in vocab.items()}
+        self.first_special = self.cfg.eos_token_id
+        if added:
+            self.id_to_piece.update({int(i): p for p, i in added.items()})
+            self.first_special = min(min(int(i) for i in added.values()), self.cfg.eos_token_id)
+
+    def decode_ids(self, ids: Sequence[int], skip_special_tokens: bool = True) -> str:
+        if not self.id_to_piece:
+            raise _C.F5EError("Whisper.decode_ids: no vocabulary is loaded (set_vocab / from_pretrained_dir with vocab.json)")
+        return decode_pieces(self.id_to_piece, self.first_special, ids, skip_special_tokens)
+
+    def load_state_dict(self, state_dict, strict: bool = True, **kw):
+        sd = {k: v for k, v in state_dict.items() if k != "proj_out.weight"}       # tied to model.decoder.embed_tokens.weight
+        self._folded = None
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    def train(self, mode: bool = True):
+        if mode:
+            raise _C.F5EError("Whisper: training is out of scope (eval mode only)")
+        return super().train(False)
+
+    def _apply(self, fn, *a, **kw):
+        self._folded = None
+        return super()._apply(fn, *a, **kw)
+
+    # ---- weights as the kernels take them, once per load -----------------------------------------------------------------------
+    @staticmethod
+    def _attn_weights(a: _Attn, dev, cross: bool) -> dict:
+        D = a.q_proj.weight.shape[0]
+        zero = torch.zeros(D, dtype=F32, device=a.q_proj.bias.device)
+        if cross:      # q alone per step; k | v once per utterance
+            return dict(w_q=_f(a.q_proj.weight, dev), b_q=_f(a.q_proj.bias, dev),
+                        w_kv=_f(torch.cat([a.k_proj.weight, a.v_proj.weight], 0), dev), b_kv=_f(torch.cat([zero, a.v_proj.bias]), dev),
+                        w_o=_f(a.out_proj.weight, dev), b_o=_f(a.out_proj.bias, dev))
+        return dict(w_qkv=_f(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0), dev),
+                    b_qkv=_f(torch.cat([a.q_proj.bias, zero, a.v_proj.bias]), dev),      # k_proj has no bias: zeros in the k third
+                    w_o=_f(a.out_proj.weight, dev), b_o=_f(a.out_proj.bias, dev))
+
+    def _fold(self) -> dict:
+        dev = self.model.decoder.embed_tokens.weight.device
+        if self._folded is not None and self._folded["device"] == dev:
+            return self._folded
+        if dev.type != "cuda":
+            raise _C.F5EError(f"Whisper lives on {dev}: move it to the GPU (there is no CPU path)")
+        cfg, enc, dec = self.cfg, self.model.encoder, self.model.decoder
+
+        def ln(m):
+            return _f(m.weight, dev), _f(m.bias, dev)
+
+        def common(lyr):
+            return dict(ln1=ln(lyr.self_attn_layer_norm), sa=self._attn_weights(lyr.self_attn, dev, False), ln3=ln(lyr.final_layer_norm),
+                        w1=_f(lyr.fc1.weight, dev), b1=_f(lyr.fc1.bias, dev), w2=_f(lyr.fc2.weight, dev), b2=_f(lyr.fc2.bias, dev))
+        fd = dict(device=dev,
+                  window=torch.from_numpy(hann_window()).to(dev, F32), twiddle=torch.from_numpy(dft_twiddle()).to(dev, F32).contiguous(),
+                  fb=torch.from_numpy(mel_filters(cfg.num_mel_bins)).to(dev, F32).contiguous(),
+                  # tap-major conv weights: k = tap * C_in + ic, the column order of f5e_im2col
+                  c1_w=_f(enc.conv1.weight.permute(0, 2, 1).reshape(cfg.d_model, -1), dev), c1_b=_f(enc.conv1.bias, dev),
+                  c2_w=_f(enc.conv2.weight.permute(0, 2, 1).reshape(cfg.d_model, -1), dev), c2_b=_f(enc.conv2.bias, dev),
+                  enc_pos=_f(enc.embed_positions.weight, dev), enc_ln=ln(enc.layer_norm), enc=[common(l) for l in enc.layers],
+                  emb=_f(dec.embed_tokens.weight, dev), dec_pos=_f(dec.embed_positions.weight, dev), dec_ln=ln(dec.layer_norm), dec=[])
+        for lyr in dec.layers:
+            d = common(lyr)
+            d.update(ln2=ln(lyr.encoder_attn_layer_norm), ca=self._attn_weights(lyr.encoder_attn, dev, True))
+            fd["dec"].append(d)
+        fd["suppress"] = torch.tensor(list(cfg.suppress_tokens), dtype=I32, device=dev) if cfg.suppress_tokens else None
+        fd["begin_suppress"] = torch.tensor(list(cfg.begin_suppress_tokens), dtype=I32, device=dev) if cfg.begin_suppress_tokens else None
+        self._folded = fd
+        return fd
+
+    # ---- front-end + encoder --------------------------------------------------------------------------------------------------
+    @property
+    def n_frames(self) -> int:
+        return 2 * self.cfg.max_source_positions
+
+    def _check_audio(self, wav: Tensor, lens, name: str) -> Tuple[Tensor, Optional[Tensor]]:
+        if not isinstance(wav, Tensor) or wav.ndim != 2 or wav.dtype != F32 or wav.shape[0] < 1 or wav.shape[1] < 1:
+            raise _C.F5EError(f"Whisper.{name}: wav must be a non-empty float32 tensor [B, S]")
+        if not wav.is_cuda:
+            raise _C.F5EError(f"Whisper.{name}: wav lives on {wav.device}; there is no CPU path")
+        B, S = wav.shape
+        if lens is not None and not (isinstance(lens, Tensor) and lens.is_cuda):
+            host = [int(v) for v in (lens.tolist() if isinstance(lens, Tensor) else lens)]
+            if len(host) != B or min(host) < 0 or max(host) > S:
+                raise _C.F5EError(f"Whisper.{name}: lens must be {B} values in [0, {S}]; got {host}")
+            lens = torch.tensor(host, dtype=I32).to(wav.device)
+        elif lens is not None and (lens.dtype != I32 or lens.shape != (B,)):
+            raise _C.F5EError(f"Whisper.{name}: lens must be i32 [{B}] (got {lens.dtype} {tuple(lens.shape)})")
+        return wav.contiguous(), lens
+
+    @torch.no_grad()
+    def features(self, wav: Tensor, lens=None) -> Tensor:
+        """wav f32 [B, S] at 16 kHz on the GPU -> the extractor's features, channels-last: f32 [B, 2 * max_source_positions,
+        num_mel_bins].  Rows are zero-padded (or cut) to the chunk length."""
+        wav, lens = self._check_audio(wav, lens, "features")
+        fd = self._fold()
+        return ops.whisper_logmel(wav, lens, fd["window"], fd["twiddle"], fd["fb"], self.n_frames)
+
+    def _enc_layer(self, x: Tensor, p: dict, B: int, H: int, bufs: dict) -> None:
+        D = x.shape[1]
+        xn, qkv, ao, ff = bufs["xn"], bufs["qkv"], bufs["ao"], bufs["ff"]
+        ops.layernorm(x, xn, *p["ln1"], eps=1e-5)
+        ops.gemm_f32(xn, p["sa"]["w_qkv"], p["sa"]["b_qkv"], out=qkv)
+        ops.mha_f32(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], H, (D // H) ** -0.5, B=B, out=ao)
+        ops.gemm_f32(ao, p["sa"]["w_o"], p["sa"]["b_o"], out=x, addend=x)
+        ops.layernorm(x, xn, *p["ln3"], eps=1e-5)
+        ops.gemm_f32(xn, p["w1"], p["b1"], out=ff, act=ops.ACT_GELU_ERF)
+        ops.gemm_f32(ff, p["w2"], p["b2"], out=x, addend=x)
+
+    @torch.no_grad()
+    def encode_features(self, feats: Tensor) -> Tensor:
+        """feats f32 [B, T, num_mel_bins] (channels-last, T = 2 * max_source_positions) -> the encoder's last hidden state f32
+        [B, T / 2, d_model]."""
+        cfg, fd = self.cfg, self._fold()
+        B, T, M = feats.shape
+        D, Tp = cfg.d_model, cfg.max_source_positions
+        if T != 2 * Tp or M != cfg.num_mel_bins or feats.dtype != F32 or not feats.is_cuda:
+            raise _C.F5EError(f"Whisper.encode_features: feats must be f32 [B, {2 * Tp}, {cfg.num_mel_bins}] on the GPU")
+        dev = feats.device
+        col1 = ops.im2col(feats.contiguous(), torch.empty(B, T, 3 * M, dtype=F32, device=dev), 3, 1)
+        h1 = torch.empty(B * T, D, dtype=F32, device=dev)
+        ops.gemm_f32(col1.view(B * T, 3 * M), fd["c1_w"], fd["c1_b"], out=h1, act=ops.ACT_GELU_ERF)
+        col2 = ops.im2col(h1.view(B, T, D), torch.empty(B, T, 3 * D, dtype=F32, device=dev), 3, 1)
+        x = torch.empty(B * Tp, D, dtype=F32, device=dev)
+        # stride 2: output frame t reads im2col row 2 t (T is even, so this holds across the rows of a batch): lda doubled
+        ops.gemm_f32(torch.as_strided(col2, (B * Tp, 3 * D), (6 * D, 1)), fd["c2_w"], fd["c2_b"], out=x, act=ops.ACT_GELU_ERF,
+                     addend=fd["enc_pos"])
+        del col1, h1, col2
+        M_ = B * Tp
+        bufs = dict(xn=torch.empty(M_, D, dtype=F32, device=dev), qkv=torch.empty(M_, 3 * D, dtype=F32, device=dev),
+                    ao=torch.empty(M_, D, dtype=F32, device=dev), ff=torch.empty(M_, cfg.encoder_ffn_dim, dtype=F32, device=dev))
+        for p in fd["enc"]:
+            self._enc_layer(x, p, B, cfg.encoder_attention_heads, bufs)
+        ops.layernorm(x, x, *fd["enc_ln"], eps=1e-5)
+        return x.view(B, Tp, D)
+
+    @torch.no_grad()
+    def cross_kv(self, enc_out: Tensor) -> List[Tuple[Tensor, Tensor]]:
+        """Every decoder layer's cross keys and values, once per utterance: views [B, Tp, D] of one [B, Tp, 2 D] buffer each."""
+        fd = self._fold()
+        B, Tp, D = enc_out.shape
+        out = []
+        for p in fd["dec"]:
+            kv = torch.empty(B * Tp, 2 * D, dtype=F32, device=enc_out.device)
+            ops.gemm_f32(enc_out.view(B * Tp, D), p["ca"]["w_kv"], p["ca"]["b_kv"], out=kv)
+            kv = kv.view(B, Tp, 2 * D)
+            out.append((kv[..., :D], kv[..., D:]))
+        return out
+
+    @torch.no_grad()
+    def encode(self, wav: Tensor, lens=None) -> List[Tuple[Tensor, Tensor]]:
+        """wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> (K, V) per decoder layer, f32 [B, Tp, D] views."""
+        return self.cross_kv(self.encode_features(self.features(wav, lens)))
+
+    # ---- decoder ---------------------------------------------------------------------------------------------------------------
+    def _dec_state(self, R: int, Umax: int, dev) -> dict:
+        cfg = self.cfg
+        D, V = cfg.d_model, cfg.vocab_size
+        Vp = (V + 3) // 4 * 4
+        z = lambda *s: torch.empty(*s, dtype=F32, device=dev)   # noqa: E731
+        return dict(x=z(R, 1, D), xn=z(R, D), qkv=z(R, 3 * D), ao=z(R, D), q=z(R, D), ff=z(R, cfg.decoder_ffn_dim),
+                    logits=z(R, Vp)[:, :V], caches=[(z(R, Umax, D), z(R, Umax, D)) for _ in range(cfg.decoder_layers)])
+
+    def _dec_step(self, st: dict, kv: List[Tuple[Tensor, Tensor]], last: Tensor, p: int, want_logits: bool) -> Optional[Tensor]:
+        """Feeds the tokens ``last`` i32 [R] at position p through the cached decoder; -> logits f32 [R, V] of position p + 1."""
+        cfg, fd = self.cfg, self._fold()
+        D, H = cfg.d_model, cfg.decoder_attention_heads
+        scale = (D // H) ** -0.5
+        R = last.shape[0]
+        x3, xn, qkv, ao, q, ff = st["x"], st["xn"], st["qkv"], st["ao"], st["q"], st["ff"]
+        ops.text_gather(last.view(R, 1), fd["emb"], fd["dec_pos"][p:p + 1], None, x3)
+        x = x3.view(R, D)
+        for lp, (kc, vc), (K, Vv) in zip(fd["dec"], st["caches"], kv):
+            ops.layernorm(x, xn, *lp["ln1"], eps=1e-5)
+            ops.gemm_f32(xn, lp["sa"]["w_qkv"], lp["sa"]["b_qkv"], out=qkv)
+            ops.attn_decode_f32(qkv, kc, vc, p, H, scale, out=ao)
+            ops.gemm_f32(ao, lp["sa"]["w_o"], lp["sa"]["b_o"], out=x, addend=x)
+            ops.layernorm(x, xn, *lp["ln2"], eps=1e-5)
+            ops.gemm_f32(xn, lp["ca"]["w_q"], lp["ca"]["b_q"], out=q)
+            ops.cross_attn_decode_f32(q, K, Vv, H, scale, rows_per_utt=R // K.shape[0], out=ao)
+            ops.gemm_f32(ao, lp["ca"]["w_o"], lp["ca"]["b_o"], out=x, addend=x)
+            ops.layernorm(x, xn, *lp["ln3"], eps=1e-5)
+            ops.gemm_f32(xn, lp["w1"], lp["b1"], out=ff, act=ops.ACT_GELU_ERF)
+            ops.gemm_f32(ff, lp["w2"], lp["b2"], out=x, addend=x)
+        if not want_logits:
+            return None
+        ops.layernorm(x, xn, *fd["dec_ln"], eps=1e-5)
+        return ops.gemm_f32(xn, fd["emb"], None, out=st["logits"])
+
+    @torch.no_grad()
+    def decoder_logits(self, kv: List[Tuple[Tensor, Tensor]], ids: Tensor) -> Tensor:
+        """Teacher forcing through the cached step: ids i32 [B, U] on the device -> logits f32 [B, U, V] (position u predicts
+        token u + 1)."""
+        B, U = ids.shape
+        if U > self.cfg.max_target_positions:
+            raise _C.F5EError(f"Whisper.decoder_logits: {U} tokens exceed max_target_positions = {self.cfg.max_target_positions}")
+        st = self._dec_state(B, U, ids.device)
+        out = torch.empty(B, U, self.cfg.vocab_size, dtype=F32, device=ids.device)
+        ids = ids.to(I32)
+        for p in range(U):
+            out[:, p] = self._dec_step(st, kv, ids[:, p].contiguous(), p, True)
+        return out
+
+    def prompt_ids(self, language: str, task: str = "transcribe") -> List[int]:
+        """``<|startoftranscript|> <|lang|> <|task|> <|notimestamps|>``: what the reference's forced_decoder_ids produce."""
+        cfg = self.cfg
+        if not language:
+            raise _C.F5EError("Whisper: language is required (language detection is out of scope)")
+        code = LANGUAGE_NAMES.get(language.lower(), language.lower())
+        key = code if code.startswith("<|") else f"<|{code}|>"
+        if key not in cfg.lang_to_id:
+            raise _C.F5EError(f"Whisper: language {language!r} is not in generation_config.lang_to_id "
+                              f"({', '.join(sorted(cfg.lang_to_id)[:8])}, ...)")
+        if task not in cfg.task_to_id:
+            raise _C.F5EError(f"Whisper: task {task!r} is not in generation_config.task_to_id ({sorted(cfg.task_to_id)})")
+        if cfg.no_timestamps_token_id is None:
+            raise _C.F5EError("Whisper: generation_config has no no_timestamps_token_id")
+        return [cfg.decoder_start_token_id, cfg.lang_to_id[key], cfg.task_to_id[task], cfg.no_timestamps_token_id]
+
+    @torch.no_grad()
+    def generate_from_kv(self, kv: List[Tuple[Tensor, Tensor]], prompt: Sequence[int], max_new_tokens: Optional[int] = None,
+                         sync_every: int = 8) -> Tuple[Tensor, Tensor]:
+        cfg, fd = self.cfg, self._fold()
+        B = kv[0][0].shape[0]
+        dev = kv[0][0].device
+        n0 = len(prompt)
+        Umax = cfg.max_target_positions if max_new_tokens is None else min(cfg.max_target_positions, n0 + int(max_new_tokens))
+        if n0 < 1 or n0 >= Umax or sync_every < 1:
+            raise _C.F5EError(f"Whisper.generate: a prompt of {n0} tokens leaves no room below {Umax} positions (or sync_every < 1)")
+        eos = cfg.eos_token_id
+        tokens = torch.full((B, Umax), eos, dtype=I32, device=dev)
+        tokens[:, :n0] = torch.tensor(list(prompt), dtype=I32, device=dev)
+        last = tokens[:, 0].clone()
+        done = torch.zeros(B, dtype=I32, device=dev)
+        alive = torch.full((1,), B, dtype=I32, device=dev)
+        st = self._dec_state(B, Umax, dev)
+        for p in range(Umax - 1):
+            forced = p + 1 < n0
+            logits = self._dec_step(st, kv, last, p, not forced)
+            if forced:                       # all prompt tokens but the last go through the same cached step; nothing is picked
+                last.copy_(tokens[:, p + 1])
+                continue
+            ops.greedy_pick(logits, tokens, last, done, alive, p, eos, suppress=fd["suppress"], begin_suppress=fd["begin_suppress"],
+                            first_step=p + 1 == n0)
+            if (p + 2 - n0) % sync_every == 0 and int(alive.item()) == 0:
+                break
+        # a finished row holds eos from its end on (done rows keep getting eos; untouched columns were eos from the start)
+        gen = tokens[:, n0:]
+        is_eos = gen == eos
+        first = torch.where(is_eos.any(1), is_eos.to(torch.int64).argmax(1) + 1, torch.full((B,), Umax - n0, dtype=torch.int64, device=dev))
+        return tokens, (first + n0).to(I32)
+
+    @torch.no_grad()
+    def generate(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe",
+                 max_new_tokens: Optional[int] = None, sync_every: int = 8) -> Tuple[Tensor, Tensor]:
+        """Greedy recognition of B utterances, one row each: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row ->
+        (tokens i32 [B, U] starting with the prompt, eos from a row's end on; n i32 [B] = tokens of every row, its closing eos
+        included when it ended by itself).  The host reads the alive count every ``sync_every`` steps; the result does not
+        depend on it.  The bound is ``max_target_positions`` (or the prompt + ``max_new_tokens``)."""
+        prompt = self.prompt_ids(language, task)
+        return self.generate_from_kv(self.encode(wav, lens), prompt, max_new_tokens, sync_every)
+
+
+class WhisperRecognizer:
+    """The duck type ``eval_wer.run_asr_wer`` and ``preprocess_ref_audio_text`` take: ``transcribe(wav_or_path, sr) -> str``."""
+
+    def __init__(self, path: str, device="cuda", language: str = "en"):
+        self.device = torch.device(device)
+        self.language = language
+        self.model = Whisper.from_pretrained_dir(path).to(self.device)
+        self.model.prompt_ids(language)                      # a language the checkpoint does not know fails here, not per file
+        self._warned = set()
+
+    @torch.no_grad()
+    def transcribe(self, audio, sr: Optional[int] = None, mode=None, **ignored) -> str:
+        from ..infer import audio as A
+        from ..infer.utils_infer import load_wav
+        name = audio if isinstance(audio, str) else None
+        if isinstance(audio, str):
+            audio, sr = load_wav(audio)
+        if sr is None:
+            raise _C.F5EError("WhisperRecognizer.transcribe: a tensor needs its sample rate")
+        audio = torch.as_tensor(audio, dtype=F32)
+        if audio.ndim == 1:
+            audio = audio.unsqueeze(0)
+        if audio.shape[0] > 1:
+            audio = audio.mean(0, keepdim=True)
+        audio = A.resample_device(audio.to(self.device, F32), int(sr), SAMPLE_RATE)
+        limit = HOP * self.model.n_frames
+        if audio.shape[-1] > limit:
+            if name not in self._warned:
+                self._warned.add(name)
+                warnings.warn(f"WhisperRecognizer: {name or 'audio'} is {audio.shape[-1] / SAMPLE_RATE:.1f} s long; only the first "
+                              f"{limit / SAMPLE_RATE:.0f} s are transcribed (long-form chunking is out of scope)")
+            audio = audio[:, :limit]
+        tokens, n = self.model.generate(audio.contiguous(), None, self.language)
+        return self.model.decode_ids(tokens[0, :int(n[0])].tolist()).strip()

@@ -68,6 +68,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--asr_model", type=str, help="best_of: ASR checkpoint with a CTC head (a PPG model's .pt)")
     p.add_argument("--asr_config", type=str, help="best_of: the ASR model's train.yaml")
     p.add_argument("--asr_dict", type=str, help="best_of: the ASR model's symbol table (`token id` lines)")
+    p.add_argument("--whisper_dir", type=str, help="a local whisper-large-v3(-turbo) directory: a voice whose ref_text is empty "
+                                                   "is transcribed with it (without it an empty ref_text is an error)")
+    p.add_argument("--ref_language", type=str, default="english", help="--whisper_dir: the language spoken in the reference audio")
     return p
 
 
@@ -215,8 +218,12 @@ def main(argv=None):
             rank["scorer"].warm()
     voices = dict(config.get("voices", {}))
     voices["main"] = {"ref_audio": s["ref_audio"], "ref_text": s["ref_text"]}
+    transcriber = None
+    if args.whisper_dir and any(not v["ref_text"].strip() for v in voices.values()):
+        from ..eval.whisper import WhisperRecognizer
+        transcriber = WhisperRecognizer(args.whisper_dir, s["device"], args.ref_language)
     for v in voices.values():   # reference infer_cli.py:297-303
-        v["ref_audio"], v["ref_text"] = U.preprocess_ref_audio_text(v["ref_audio"], v["ref_text"])
+        v["ref_audio"], v["ref_text"] = U.preprocess_ref_audio_text(v["ref_audio"], v["ref_text"], transcriber=transcriber)
     segments = []
     for voice, text in split_voices(s["gen_text"]):
         v = voices.get(voice, voices["main"])

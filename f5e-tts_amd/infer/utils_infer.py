@@ -4,9 +4,9 @@ cross-fade rules.  Everything between ``model_obj.sample`` and ``vocoder.decode`
 here is host glue (text chunking, wav I/O, numpy cross-fade) exactly as in the reference.  ``infer_vc_process`` is the
 voice-conversion counterpart (PPG models, ``sample_vc``), which the reference only offers as an eval driver.
 
-Resampling and the pydub-style silence clipping live in ``infer/audio.py``.  Not rebuilt (out of scope,
-SURVEY section 8): the Whisper ASR fallback of ``preprocess_ref_audio_text`` (an empty ``ref_text`` is an error here),
-HF-hub downloads (no network).  Chinese g2p needs the optional ``jieba`` + ``pypinyin`` packages;
+Resampling and the pydub-style silence clipping live in ``infer/audio.py``.  The Whisper ASR fallback of
+``preprocess_ref_audio_text`` is opt-in: hand it a ``transcriber`` (``eval.whisper.WhisperRecognizer``); without one an empty
+``ref_text`` is an error.  Not rebuilt (out of scope, SURVEY section 8): HF-hub downloads (no network).  Chinese g2p needs the optional ``jieba`` + ``pypinyin`` packages;
 the ASCII path is self-contained.
 """
 from __future__ import annotations
@@ -223,9 +223,11 @@ def _write_segment(path: str, seg: A.Segment) -> None:
 _ref_audio_cache = {}
 
 
-def preprocess_ref_audio_text(ref_audio_orig, ref_text, clip_short=True, show_info=print):
+def preprocess_ref_audio_text(ref_audio_orig, ref_text, clip_short=True, show_info=print, transcriber=None):
     """Reference infer/utils_infer.py:293-352: clip the clip to <= 12 s at silences, strip silent edges, add 50 ms of
-    silence, write a temporary wav; make ref_text end in ". ".  Returns (wav path, ref_text)."""
+    silence, write a temporary wav; make ref_text end in ". ".  Returns (wav path, ref_text).  ``transcriber``: anything with
+    ``transcribe(wav_path) -> str`` (an ``eval.whisper.WhisperRecognizer``); with one, an empty ``ref_text`` is replaced by
+    the transcript of the clipped prompt, as the reference does with whisper-large-v3-turbo (:148-179, :341)."""
     show_info("Converting audio...")
     seg = A.clip_reference(_read_segment(ref_audio_orig), clip_short=clip_short, note=show_info)
     with tempfile.NamedTemporaryFile(delete=False, suffix=".wav") as f:
@@ -237,6 +239,9 @@ def preprocess_ref_audio_text(ref_audio_orig, ref_text, clip_short=True, show_in
         if audio_hash in _ref_audio_cache:
             show_info("Using cached reference text...")
             ref_text = _ref_audio_cache[audio_hash]
+        elif transcriber is not None:
+            show_info("No reference text provided, transcribing reference audio...")
+            _ref_audio_cache[audio_hash] = ref_text = transcriber.transcribe(ref_audio).strip()
         else:
             raise ValueError("ref_text is empty: the reference falls back to Whisper ASR here (utils_infer.py:341), "
                              "which is outside this build; pass the transcript of the reference audio")

@@ -1348,6 +1348,90 @@ def relbias_attn(q: Tensor, k: Tensor, v: Tensor, gate: Tensor, table: Tensor, h
     return out
 
 
+# ---- Whisper (csrc/whisper.hip) ----
+
+WHISPER_N_FFT, WHISPER_HOP = 400, 160
+
+
+def whisper_logmel_partials(B: int, T: int) -> int:
+    """Scratch floats of ``whisper_logmel`` for B rows of T frames (host arithmetic)."""
+    n = C.c_ulonglong(0)
+    check(lib().f5e_whisper_logmel_partials(int(B), int(T), C.byref(n)), "f5e_whisper_logmel_partials")
+    return int(n.value)
+
+
+def whisper_logmel(wav: Tensor, lengths: Optional[Tensor], window: Tensor, twiddle: Tensor, fb: Tensor, T: int, *,
+                   out: Optional[Tensor] = None, partials: Optional[Tensor] = None) -> Tensor:
+    """f5e_whisper_logmel: wav f32 [B, S] (row-strided view), lengths i32 [B] on the device or None, window f32 [400], twiddle f32
+    [400, 2] = (cos, sin)(2 pi i / 400), fb f32 [201, n_mels] -> out f32 [B, T, n_mels]: the features of
+    ``WhisperFeatureExtractor`` for rows zero-padded (or cut) to 160 T samples."""
+    if wav.ndim != 2 or fb.ndim != 2:
+        raise _C.F5EError("whisper_logmel: wav [B, S] and fb [201, n_mels]; there is no CPU path")
+    B, S = wav.shape
+    n_mels = fb.shape[1]
+    if window.shape != (WHISPER_N_FFT,) or twiddle.shape != (WHISPER_N_FFT, 2) or fb.shape[0] != WHISPER_N_FFT // 2 + 1:
+        raise _C.F5EError(f"whisper_logmel: window [400], twiddle [400, 2], fb [201, n_mels] (got {tuple(window.shape)}, "
+                          f"{tuple(twiddle.shape)}, {tuple(fb.shape)})")
+    wp, ldw = _rows(wav, (F32,), "whisper_logmel: wav", S, vec=1)
+    require_device()
+    T = int(T)
+    out = torch.empty(B, T, n_mels, dtype=F32, device=wav.device) if out is None else out
+    if tuple(out.shape) != (B, T, n_mels):
+        raise _C.F5EError(f"whisper_logmel: out must be [{B}, {T}, {n_mels}] (got {tuple(out.shape)})")
+    need = whisper_logmel_partials(B, T) if T > 0 else 0
+    partials = torch.empty(max(need, 1), dtype=F32, device=wav.device) if partials is None else partials
+    if partials.numel() < need:
+        raise _C.F5EError(f"whisper_logmel: partials needs {need} floats (whisper_logmel_partials)")
+    check(lib().f5e_whisper_logmel(_stream(), wp, min(ldw, 0x7fffffff), _len(lengths, B, "whisper_logmel"),
+                                   _p(window, F32, "window"), _p(twiddle, F32, "twiddle"), _p(fb, F32, "fb"), _p(out, F32, "out"),
+                                   _p(partials, F32, "partials"), B, T, WHISPER_N_FFT, WHISPER_HOP, n_mels), "f5e_whisper_logmel")
+    return out
+
+
+def cross_attn_decode_f32(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float, rows_per_utt: int = 1,
+                          kv_len: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """f5e_cross_attn_decode_f32: q f32 [R, D] (row-strided view), k / v f32 [B, Tk, D] (evenly spaced frames, unit channel
+    stride) with B = R / rows_per_utt -> out f32 [R, D]: one query per row and head over the keys of the row's utterance;
+    kv_len i32 [B] on the device limits the keys (None: all Tk)."""
+    if q.ndim != 2 or k.ndim != 3 or v.ndim != 3 or k.shape != v.shape:
+        raise _C.F5EError("cross_attn_decode_f32: q [R, D] and k, v [B, Tk, D] of one shape; there is no CPU path")
+    R, D = q.shape
+    kp, ldk, B, Tk, Dk = _btc(k, "cross_attn_decode_f32: k")
+    vp, ldv, _, _, _ = _btc(v, "cross_attn_decode_f32: v", vec=1)
+    if Dk != D or D % heads or rows_per_utt < 1 or R != B * rows_per_utt or (out is not None and out.shape != (R, D)):
+        raise _C.F5EError(f"cross_attn_decode_f32: inconsistent shapes q {tuple(q.shape)} k {tuple(k.shape)} heads={heads} "
+                          f"rows_per_utt={rows_per_utt}")
+    qp, ldq = _rows(q, (F32,), "cross_attn_decode_f32: q", D)
+    require_device()
+    out = torch.empty(R, D, dtype=F32, device=q.device) if out is None else out
+    op, ldo = _rows(out, (F32,), "cross_attn_decode_f32: out", D, vec=1)
+    check(lib().f5e_cross_attn_decode_f32(_stream(), qp, ldq, kp, ldk, vp, ldv, op, ldo, _len(kv_len, B, "cross_attn_decode_f32"),
+                                          R, rows_per_utt, Tk, heads, D // heads, float(scale)), "f5e_cross_attn_decode_f32")
+    return out
+
+
+def greedy_pick(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, p: int, eos: int, *,
+                V: Optional[int] = None, suppress: Optional[Tensor] = None, begin_suppress: Optional[Tensor] = None,
+                first_step: bool = False):
+    """f5e_greedy_pick: logits f32 [R, >= V] (row-strided view, only read), tokens i32 [R, >= p + 2], last / done i32 [R], alive
+    i32 [1], suppress / begin_suppress i32 lists on the device.  Writes tokens[:, p + 1], last, done (0 -> 1) and alive."""
+    if logits.ndim != 2 or tokens.ndim != 2:
+        raise _C.F5EError("greedy_pick: logits [R, >= V] and tokens [R, >= p + 2]; there is no CPU path")
+    R = logits.shape[0]
+    V = logits.shape[1] if V is None else int(V)
+    lp, ld = _rows(logits, (F32,), "greedy_pick: logits", V, vec=1)
+    tp, ld_tok = _rows(tokens, (I32,), "greedy_pick: tokens", int(p) + 2, vec=1)
+    if tokens.shape[0] != R or last.shape != (R,) or done.shape != (R,) or alive.numel() != 1:
+        raise _C.F5EError(f"greedy_pick: tokens [{R}, .], last [{R}], done [{R}], alive [1]")
+    require_device()
+    check(lib().f5e_greedy_pick(_stream(), lp, ld, _p(suppress, I32, "suppress"), suppress.numel() if suppress is not None else 0,
+                                _p(begin_suppress, I32, "begin_suppress"),
+                                begin_suppress.numel() if begin_suppress is not None else 0, 1 if first_step else 0, tp, ld_tok,
+                                _p(last, I32, "last"), _p(done, I32, "done"), _p(alive, I32, "alive"), R, V, int(p), int(eos)),
+          "f5e_greedy_pick")
+    return last
+
+
 def dit_forward(plan: "_C.DitPlan"):
     require_device()
     check(lib().f5e_dit_forward(_stream(), C.byref(plan)), "f5e_dit_forward")

@@ -714,6 +714,51 @@ F5E_API int f5e_relbias_attn_f32(f5e_stream st, const float* q, int ldq, const f
                          float* out, int ldo, const float* gate, const float* table, int Tt, const int* kv_len, int B,
                          int T, int H, int dk, float scale);
 
+/* ---------------------------------------------------------------- Whisper (csrc/whisper.hip) ----------------- */
+/* Greedy Whisper recognition (reference infer/utils_infer.py:148-179, eval/utils_eval.py:631-672): the log-mel front-end, the
+ * single-query cross-attention of a cached decoder step and the per-step greedy pick.  The convolution stem, the encoder and the
+ * rest of the decoder step are f5e_im2col / f5e_gemm_f32 / f5e_layernorm / f5e_mha_f32 / f5e_attn_decode_f32 / f5e_text_gather.
+ * fp32, no allocation, no synchronisation, nothing read back. */
+
+/* WhisperFeatureExtractor on the device.  wav f32 [B][ldw], len DEVICE int [B] (NULL: the whole row): samples at or beyond
+ * min(len[b], ldw) count as ZERO whatever the buffer holds, and the row is taken as hop * T samples long (the extractor's zero
+ * padding to the chunk length; ldw may be shorter or longer).  Frame f < T covers [f hop - n_fft / 2, f hop + n_fft / 2) of that
+ * row, reflect-padded at both ends (no edge repeat), times window f32 [n_fft] (periodic Hann); power re^2 + im^2 of the
+ * n_fft / 2 + 1 bins by a direct DFT against twiddle f32 [n_fft][2] = (cos, sin)(2 pi i / n_fft); times fb f32
+ * [n_fft / 2 + 1][n_mels] (Slaney); log10(max(., 1e-10)); max(x, rowmax_b - 8) with rowmax_b the maximum over all T * n_mels
+ * values of utterance b; (x + 4) / 4.  (Frame T of the extractor's T + 1 is the one it drops: it is not computed.)
+ * out f32 [B][T][n_mels], channels-last.  Two launches; partials: scratch of f5e_whisper_logmel_partials(B, T) floats (one
+ * maximum per workgroup, folded in a fixed order: no float atomics).  F5E_ERR_UNSUPPORTED unless n_fft = 400, hop = 160 and
+ * n_mels is 80 or 128; T >= 2. */
+F5E_API int f5e_whisper_logmel_partials(int B, int T, unsigned long long* floats_out_host);
+F5E_API int f5e_whisper_logmel(f5e_stream st, const float* wav, int ldw, const int* len, const float* window,
+                       const float* twiddle, const float* fb, float* out, float* partials, int B, int T, int n_fft, int hop,
+                       int n_mels);
+
+/* Single-query cross-attention of a decoder step: for row r < R and head h, with u = r / rows_per_utt,
+ *   out[r][h*dk + d] = sum_{j < n} softmax_j(scale * q[r][h*dk + :] . k[u][j][h*dk + :]) * v[u][j][h*dk + d],
+ * n = kv_len[u] clamped to [0, Tk] (DEVICE int [R / rows_per_utt]) or Tk when kv_len is NULL (Whisper attends its zero-padded
+ * frames: it passes NULL).  n = 0 yields zeros.  q, out [R][>= H*dk]; k, v [R / rows_per_utt][Tk][>= H*dk], computed once per
+ * utterance; each operand has its own row stride.  One workgroup of four waves per (row, head): the waves split the keys, each
+ * keeps a maximum, a sum and a context, merged through LDS.  Columns beyond H*dk of out are not touched.
+ * dk = 16, 32, 64, 128 (else F5E_ERR_UNSUPPORTED); Tk <= 4096; R, H <= 65535; ldq, ldk multiples of 4 floats, q and k 16-byte
+ * aligned. */
+F5E_API int f5e_cross_attn_decode_f32(f5e_stream st, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                              float* out, int ldo, const int* kv_len, int R, int rows_per_utt, int Tk, int H, int dk,
+                              float scale);
+
+/* One greedy decoding step for R rows (transformers' SuppressTokensLogitsProcessor / SuppressTokensAtBeginLogitsProcessor +
+ * argmax + the eos bookkeeping of generate), one workgroup per row over logits f32 [R][ld >= V] (only read).
+ *   suppress i32 [n_sup]: classes at -inf at every step; begin_suppress i32 [n_beg]: also at -inf iff first_step != 0 (ids
+ *   outside [0, V) are ignored); the pick is the LOWEST index among the equal maxima of what is left (0 if nothing is).
+ *   A row with done[r] != 0 gets eos and stays done; otherwise the pick t goes to tokens[r][p + 1] and last[r] (contiguous, for
+ *   the next f5e_text_gather), and t == eos sets done[r] = 1.  alive (one i32) = the rows with done[r] == 0 after the step.
+ * Writes tokens[r][p + 1], last[r], done[r] (only from 0 to 1) and *alive -- nothing else.  tokens i32 [R][ld_tok >= p + 2].
+ * V <= 262144, 0 <= eos < V. */
+F5E_API int f5e_greedy_pick(f5e_stream st, const float* logits, long long ld, const int* suppress, int n_sup,
+                    const int* begin_suppress, int n_beg, int first_step, int* tokens, int ld_tok, int* last, int* done,
+                    int* alive, int R, int V, int p, int eos);
+
 /* ---------------------------------------------------------------- hipGraph capture --------------------------- */
 F5E_API int f5e_graph_begin(f5e_stream st);
 F5E_API int f5e_graph_end(f5e_stream st, void** graph_exec_out);

@@ -232,3 +232,40 @@ def synthetic_mel(n_frames: int, batch: int = 1, seed: int = 99, n_mels: int = 1
     slow = F.interpolate(torch.randn(batch, n_mels, max(2, n_frames // 8), generator=g), size=n_frames, mode="linear",
                          align_corners=True)
     return (env + 1.5 * slow + 0.5 * torch.randn(batch, n_mels, n_frames, generator=g)).float()
+
+
+def whisper_config_fields(large: str = "large-v3", **kw) -> Dict:
+    """The config.json / generation_config.json fields of whisper-large-v3 or -large-v3-turbo (public model cards) that
+    ``f5e_tts_amd.eval.whisper.WhisperConfig`` takes; ``kw`` overrides (fewer layers for quick runs)."""
+    f = dict(vocab_size=51866, num_mel_bins=128, d_model=1280, encoder_layers=32, encoder_attention_heads=20, encoder_ffn_dim=5120,
+             decoder_layers=4 if large == "large-v3-turbo" else 32, decoder_attention_heads=20, decoder_ffn_dim=5120,
+             max_source_positions=1500, max_target_positions=448, eos_token_id=50257, decoder_start_token_id=50258,
+             suppress_tokens=(1, 2, 7, 8, 9, 10, 14, 25, 50258, 50359, 50360, 50361, 50362, 50363), begin_suppress_tokens=(220, 50257),
+             lang_to_id={"<|en|>": 50259, "<|zh|>": 50260}, task_to_id={"translate": 50359, "transcribe": 50360},
+             no_timestamps_token_id=50364)
+    f.update(kw)
+    return f
+
+
+def init_whisper_state(shapes: Dict[str, tuple], seed: int = 99, gain: float = 1.0, device="cpu") -> State:
+    """Seeded weights for the Hugging Face parameter names of a Whisper (``shapes``: name -> shape, e.g. from a fresh module's
+    ``state_dict()``): matrices N(0, gain / fan_in), biases N(0, 0.02), LayerNorm weights 1 + N(0, 0.1), token embedding
+    N(0, 0.02 gain), decoder positions N(0, 0.02); the encoder's sinusoids are left to the module (not returned).  ``device``:
+    where the draws are made (the full-size models have 1.5e9 parameters; a GPU stream of draws differs from the CPU's)."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    out = {}
+    for name, shape in shapes.items():
+        shape = tuple(shape)
+        if name == "model.encoder.embed_positions.weight":
+            continue
+        r = torch.randn(shape, generator=g, device=device)
+        if "layer_norm" in name:
+            out[name] = 1.0 + 0.1 * r if name.endswith("weight") else 0.1 * r
+        elif name.endswith("embed_tokens.weight"):
+            out[name] = 0.02 * gain * r
+        elif name.endswith("embed_positions.weight") or name.endswith("bias"):
+            out[name] = 0.02 * r
+        else:
+            fan_in = math.prod(shape[1:])
+            out[name] = r * math.sqrt(gain / fan_in)
+    return out

@@ -324,6 +324,13 @@ extern "C" int f5e_gemm_f32(hipStream_t st, const float* A, int lda, int a_rows,
   F5E_REQUIRE(K % 4 == 0 && lda % 4 == 0 && ldw % 4 == 0, "gemm_f32: K, lda, ldw must be multiples of 4 (K=%d)", K);
   F5E_REQUIRE(a_rows > 0, "gemm_f32: a_rows must be positive");
   if (addend) F5E_REQUIRE(add_rows > 0, "gemm_f32: add_rows must be positive");
+  // rows of an operand that is written, or read once per output element, must not overlap (A and W rows may)
+  if (M > 1) {
+    if (out) F5E_REQUIRE(ldo >= N, "gemm_f32: ldo=%d must be at least N=%d", ldo, N);
+    if (out_bf16) F5E_REQUIRE(ldo_bf16 >= N, "gemm_f32: ldo_bf16=%d must be at least N=%d", ldo_bf16, N);
+    if (addend && add_rows > 1) F5E_REQUIRE(ld_add >= N, "gemm_f32: ld_add=%d must be at least N=%d", ld_add, N);
+  }
+  F5E_REQUIRE(lda >= 0 && ldw >= 0, "gemm_f32: lda, ldw must not be negative");
   Gemm32Args a{};
   a.A = A; a.lda = lda; a.a_rows = a_rows; a.a_act = a_act; a.W = W; a.ldw = ldw; a.bias = bias; a.act = act;
   a.ch_scale = ch_scale; a.addend = addend; a.ld_add = ld_add; a.add_rows = add_rows > 0 ? add_rows : 1;

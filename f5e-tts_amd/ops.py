@@ -251,27 +251,88 @@ def l2norm(x: Tensor, out: Tensor, g: Tensor):
     return out
 
 
+def _shape3(x: Tensor, name: str):
+    """(B, T, C) of a [B, T, C] activation; the pointer checks (f32, GPU, contiguous) stay with ``_p``."""
+    if x.ndim != 3 or min(x.shape) < 1:
+        raise _C.F5EError(f"{name} must be a non-empty [B, T, C] tensor (got shape {tuple(x.shape)})")
+    return x.shape
+
+
+def _shaped(t: Tensor, shape, name: str):
+    if tuple(t.shape) != tuple(shape):
+        raise _C.F5EError(f"{name} must be {list(shape)} (got shape {tuple(t.shape)})")
+
+
 def grn(x: Tensor, out: Tensor, gamma: Tensor, beta: Tensor, ws: Tensor):
+    """out = gamma (x gx / (mean_c gx + 1e-6)) + beta + x, gx = the L2 norm over T; x, out f32 [B, T, C], gamma, beta f32 [C],
+    ws: f32 scratch of at least B * C elements (receives gx).  Everything is refused here, before any launch."""
+    B, T, Cc = _shape3(x, "grn: x")
+    _shaped(out, x.shape, "grn: out")
+    _shaped(gamma, (Cc,), "grn: gamma")
+    _shaped(beta, (Cc,), "grn: beta")
+    if ws.numel() < B * Cc:
+        raise _C.F5EError(f"grn: ws must hold B * C = {B * Cc} elements (got {ws.numel()})")
     require_device()
-    B, T, Cc = x.shape
     check(lib().f5e_grn(_stream(), _p(x, F32, "x"), _p(out, F32, "out"), _p(ws, F32, "ws"), _p(gamma, F32, "gamma"),
                         _p(beta, F32, "beta"), B, T, Cc), "f5e_grn")
     return out
+
+
+def _gemm_view(t: Tensor, dtype, name: str, cols: int, rows: int, overlap: bool = False):
+    """A row-strided operand of ``gemm_f32`` of which the kernel touches ``cols`` elements in each of ``rows`` rows: 2-D,
+    ``dtype``, on the GPU, unit column stride, at least ``cols`` wide, and the storage behind the view holds
+    (rows - 1) * row stride + cols elements.  Any alignment (the scalar epilogue and the plain kernel take what the vector
+    paths cannot).  ``overlap``: rows may overlap (row stride < cols), for operands that are only read."""
+    if t.ndim != 2 or not t.is_cuda or t.dtype != dtype or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise _C.F5EError(f"gemm_f32: {name} must be a 2-D {dtype} GPU tensor with unit column stride (got {t.dtype}, "
+                          f"{t.device}, shape {tuple(t.shape)}, strides {tuple(t.stride())})")
+    if t.shape[1] < cols:
+        raise _C.F5EError(f"gemm_f32: {name} has {t.shape[1]} columns, fewer than the {cols} the problem needs")
+    ld = t.stride(0)
+    if rows > 1 and ld < (0 if overlap else cols):
+        raise _C.F5EError(f"gemm_f32: {name}: row stride {ld} is smaller than the {cols} columns of a row")
+    if rows <= t.shape[0]:
+        return                        # inside the view itself, which torch keeps inside its storage
+    have = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+    need = (rows - 1) * ld + cols
+    if have < need:
+        raise _C.F5EError(f"gemm_f32: {name}: {rows} rows of stride {ld} need {need} elements, the storage holds {have}")
 
 
 def gemm_f32(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, out: Optional[Tensor] = None,
              out_bf16: Optional[Tensor] = None, M: Optional[int] = None, a_act: int = ACT_NONE, act: int = ACT_NONE,
              ch_scale: Optional[Tensor] = None, addend: Optional[Tensor] = None, row_scale: Optional[Tensor] = None,
              K: Optional[int] = None):
-    """fp32 MFMA GEMM; ``a`` [a_rows, >=K] and ``w`` [N, >=K] may be column-sliced views (row stride = ld)."""
+    """fp32 MFMA GEMM; ``a`` [a_rows, >=K] and ``w`` [N, >=K] may be column-sliced views (row stride = ld; ``a``'s may be
+    smaller than its width: overlapping rows).  out f32 / out_bf16 bf16 [>= M rows of storage, >= N] and addend f32
+    [add_rows, >= N] are row-strided views with unit column stride, of any alignment; bias, ch_scale [>= N] and row_scale
+    [>= M] are contiguous.  Row m reads a[m % a_rows] and addend[m % add_rows].  Everything is refused here, before any launch."""
     require_device()
-    a_rows = a.shape[0]
-    K = a.shape[1] if K is None else K
-    N = w.shape[0]
-    M = a_rows if M is None else M
     for t, nm in ((a, "a"), (w, "w")):
-        if not t.is_cuda or t.dtype != F32 or t.stride(1) != 1:
-            raise _C.F5EError(f"gemm_f32: {nm} must be an f32 GPU tensor with unit column stride")
+        if t.ndim != 2 or not t.is_cuda or t.dtype != F32 or (t.stride(1) != 1 and t.shape[1] > 1):
+            raise _C.F5EError(f"gemm_f32: {nm} must be a 2-D f32 GPU tensor with unit column stride")
+    a_rows = a.shape[0]
+    K = a.shape[1] if K is None else int(K)
+    N = w.shape[0]
+    M = a_rows if M is None else int(M)
+    if K > a.shape[1] or K > w.shape[1]:
+        raise _C.F5EError(f"gemm_f32: K = {K} is larger than a's width {a.shape[1]} or w's width {w.shape[1]}")
+    if out is None and out_bf16 is None:
+        raise _C.F5EError("gemm_f32: needs out or out_bf16")
+    if M > 0 and N > 0 and K > 0:     # the library refuses the empty problem itself
+        _gemm_view(a, F32, "a", K, min(M, a_rows), overlap=True)
+        _gemm_view(w, F32, "w", K, N, overlap=True)
+        if out is not None:
+            _gemm_view(out, F32, "out", N, M)
+        if out_bf16 is not None:
+            _gemm_view(out_bf16, BF, "out_bf16", N, M)
+        if addend is not None:
+            if addend.ndim == 2 and addend.shape[0] < 1:      # its data_ptr() is null: the library would see no addend at all
+                raise _C.F5EError("gemm_f32: addend must have at least one row")
+            _gemm_view(addend, F32, "addend", N, min(M, addend.shape[0]) if addend.ndim == 2 else 1)
+        for t, nm, n in ((bias, "bias", N), (ch_scale, "ch_scale", N), (row_scale, "row_scale", M)):
+            if t is not None and t.numel() < n:
+                raise _C.F5EError(f"gemm_f32: {nm} must hold at least {n} elements (got {t.numel()})")
     ad = addend
     check(lib().f5e_gemm_f32(
         _stream(), C.c_void_p(a.data_ptr()), a.stride(0), a_rows, a_act, C.c_void_p(w.data_ptr()), w.stride(0),
@@ -306,16 +367,27 @@ def convpos(x: Tensor, w_packed: Tensor, bias: Tensor, S: int, N: int, *, out_bf
 
 
 def dwconv7(x: Tensor, w_t: Tensor, bias: Tensor, out: Tensor):
+    """Depthwise Conv1d(C, C, 7, padding 3), channels-last: x, out f32 [B, T, C], w_t f32 [7, C] (tap-major), bias f32 [C].
+    Everything is refused here or by the library (C % 4), before any launch."""
+    B, T, Cc = _shape3(x, "dwconv7: x")
+    _shaped(out, x.shape, "dwconv7: out")
+    _shaped(w_t, (7, Cc), "dwconv7: w_t")
+    _shaped(bias, (Cc,), "dwconv7: bias")
     require_device()
-    B, T, Cc = x.shape
     check(lib().f5e_dwconv7(_stream(), _p(x, F32, "x"), _p(w_t, F32, "w_t"), _p(bias, F32, "bias"), _p(out, F32, "out"),
                             B, T, Cc), "f5e_dwconv7")
     return out
 
 
 def im2col(x: Tensor, col: Tensor, ksize: int, pad: int):
+    """col[b, t, j * Cin + ic] = x[b, t + j - pad, ic], zero outside [0, T): x f32 [B, T, Cin], col f32 [B, T, ksize * Cin].
+    Everything is refused here, before any launch."""
+    B, T, Cin = _shape3(x, "im2col: x")
+    ksize, pad = int(ksize), int(pad)
+    if ksize < 1 or pad < 0:
+        raise _C.F5EError(f"im2col: needs ksize >= 1 and pad >= 0 (got {ksize}, {pad})")
+    _shaped(col, (B, T, ksize * Cin), "im2col: col")
     require_device()
-    B, T, Cin = x.shape
     check(lib().f5e_im2col(_stream(), _p(x, F32, "x"), _p(col, F32, "col"), B, T, Cin, ksize, pad), "f5e_im2col")
     return col
 

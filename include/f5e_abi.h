@@ -162,7 +162,9 @@ F5E_API int f5e_grn(f5e_stream st, const float* x, float* y, float* gx_ws, const
 /* ---------------------------------------------------------------- exact-fp32 GEMM (once per call) ------------ */
 
 /* C[m][n] = ((act(sum_k actA(A[m % a_rows][k]) W[n][k] + bias[n])) * ch_scale[n] + addend[m % add_rows][n]) * row_scale[m]
- * written to out (f32) and/or out_bf16.  K, lda, ldw multiples of 4.  NULL skips a term.
+ * written to out (f32) and/or out_bf16.  K, lda, ldw multiples of 4.  NULL skips a term.  Rows of A and W may overlap
+ * (lda, ldw >= 0); with M > 1, ldo and ldo_bf16 must be at least N, and ld_add too when add_rows > 1.  Any alignment of the
+ * pointers and the other leading dimensions is taken (16-byte friendly operands take the faster paths).
  * Replaces the fp32 F.linear calls of TimestepEmbedding, AdaLN emb, TextEmbedding, PPGEmbedding, InputEmbedding.proj
  * (x columns per step; cond/text/ppg columns once per call) and Vocos. */
 F5E_API int f5e_gemm_f32(f5e_stream st, const float* A, int lda, int a_rows, int a_act, const float* W, int ldw,

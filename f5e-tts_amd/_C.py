@@ -95,6 +95,11 @@ SIGNATURES = {
     "f5e_whisper_logmel": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I],
     "f5e_cross_attn_decode_f32": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _F],
     "f5e_greedy_pick": [_P, _P, _LL, _P, _I, _P, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I],
+    "f5e_w2v_conv0_gn_partials": [_I, _I, _I, C.POINTER(C.c_ulonglong)],
+    "f5e_w2v_conv0_gn": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _LL, _P, _P, _I, C.POINTER(C.c_int), C.POINTER(C.c_int), _I, _I,
+                         _I, _I, _F],
+    "f5e_lstm_f32": [_P, _P, _LL, _P, _P, _P, _P, _I, _I, _I, _I],
+    "f5e_score_mean": [_P, _P, _LL, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F],
     "f5e_dit_forward": [_P, _P],
     "f5e_sample_loop": [_P, _P],
     "f5e_workspace_bytes": [_P, _P],

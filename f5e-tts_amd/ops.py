@@ -1504,6 +1504,116 @@ def greedy_pick(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, aliv
     return last
 
 
+# ---- UTMOS (csrc/utmos.hip) ----
+
+LSTM_MAX_H, LSTM_MAX_B, LSTM_MAX_T = 1024, 16, 4096
+
+
+def w2v_conv0_gn_partials(B: int, S: int, C_: int) -> int:
+    """Floats of scratch that ``w2v_conv0_gn`` needs for B rows of S samples and C channels (host arithmetic)."""
+    n = C.c_ulonglong(0)
+    check(lib().f5e_w2v_conv0_gn_partials(int(B), int(S), int(C_), C.byref(n)), "f5e_w2v_conv0_gn_partials")
+    return int(n.value)
+
+
+def w2v_conv0_gn(wav: Tensor, w: Tensor, bias: Optional[Tensor], gamma: Tensor, beta: Tensor, lengths: Optional[Tensor],
+                 out: Tensor, partials: Tensor, frames: Optional[Tensor] = None, mask: Optional[Tensor] = None,
+                 conv_kernels=(), conv_strides=(), eps: float = 1e-5):
+    """f5e_w2v_conv0_gn: wav f32 [B, S], w f32 [C, 10] -> out f32 [B, P >= T0, C] (frames C floats apart, rows any stride >=
+    T0 C), T0 = (S - 10) // 5 + 1: Conv1d(1 -> C, k 10, stride 5) + GroupNorm(C groups) over each row's own (lengths[b] - 10) //
+    5 + 1 frames + GELU, zero from there to T0; frames i32 [B] and mask f32 [B, Tm] as ``wav_norm`` writes them."""
+    if wav.ndim != 2 or w.ndim != 2 or w.shape[1] != 10 or out.ndim != 3 or out.shape[0] != wav.shape[0] or out.shape[2] != w.shape[0]:
+        raise _C.F5EError(f"w2v_conv0_gn: wav [B, S], w [C, 10], out [B, P, C] (got {tuple(wav.shape)}, {tuple(w.shape)}, {tuple(out.shape)})")
+    B, S = wav.shape
+    Cc = w.shape[0]
+    T0 = (S - 10) // 5 + 1
+    if S < 10 or out.shape[1] < T0:
+        raise _C.F5EError(f"w2v_conv0_gn: S = {S} samples give {max(T0, 0)} frames; out {tuple(out.shape)} must hold at least one and all of them")
+    if not out.is_cuda or out.dtype != F32 or out.stride(2) != 1 or (out.shape[1] > 1 and out.stride(1) != Cc):
+        raise _C.F5EError("w2v_conv0_gn: out must be an f32 GPU tensor whose frames are C floats apart")
+    bstride = out.stride(0) if B > 1 else max(out.stride(0), T0 * Cc)
+    if bstride < T0 * Cc:
+        raise _C.F5EError(f"w2v_conv0_gn: the batch stride of out ({bstride}) must cover T0 * C = {T0 * Cc} floats")
+    wp, ldw = _rows(wav, (F32,), "w2v_conv0_gn: wav", S, vec=1)
+    for t, nm in ((bias, "bias"), (gamma, "gamma"), (beta, "beta")):
+        if t is not None and t.numel() != Cc:
+            raise _C.F5EError(f"w2v_conv0_gn: {nm} must have C = {Cc} elements")
+    if len(conv_kernels) != len(conv_strides) or len(conv_kernels) > 8:
+        raise _C.F5EError("w2v_conv0_gn: conv_kernels and conv_strides must have one length, at most 8")
+    need = w2v_conv0_gn_partials(B, S, Cc)
+    if partials.dtype != F32 or partials.numel() < need:
+        raise _C.F5EError(f"w2v_conv0_gn: partials must hold {need} floats (w2v_conv0_gn_partials)")
+    if frames is not None and (frames.dtype != I32 or frames.shape != (B,)):
+        raise _C.F5EError(f"w2v_conv0_gn: frames must be i32 [{B}]")
+    t_mask = 0
+    if mask is not None:
+        if mask.ndim != 2 or mask.shape[0] != B or not 0 < mask.shape[1] <= S:
+            raise _C.F5EError(f"w2v_conv0_gn: mask must be [{B}, 1..{S}] (got {tuple(mask.shape)})")
+        t_mask = mask.shape[1]
+    n = len(conv_kernels)
+    ks, ss = (C.c_int * max(n, 1))(*[int(v) for v in conv_kernels]), (C.c_int * max(n, 1))(*[int(v) for v in conv_strides])
+    require_device()
+    check(lib().f5e_w2v_conv0_gn(_stream(), wp, ldw, _p(w, F32, "w"), _p(bias, F32, "bias"), _p(gamma, F32, "gamma"),
+                                 _p(beta, F32, "beta"), _len(lengths, B, "w2v_conv0_gn"), _p(partials, F32, "partials"),
+                                 C.c_void_p(out.data_ptr()), bstride, _p(frames, I32, "frames"), _p(mask, F32, "mask"), t_mask,
+                                 ks, ss, n, B, S, Cc, float(eps)), "f5e_w2v_conv0_gn")
+    return out
+
+
+def pack_lstm_weight(w_hh: Tensor) -> Tensor:
+    """W_hh f32 [ND, 4 H, H] (PyTorch's ``weight_hh_l0`` and ``weight_hh_l0_reverse`` stacked; gate order i, f, g, o) -> f32
+    [ND, H, H / 64, 64, 4] as f5e_lstm_f32 reads it: packed[d, u, j, l, g] = W_hh[d, g H + u, 64 j + l]."""
+    if w_hh.ndim != 3 or w_hh.shape[1] != 4 * w_hh.shape[2] or w_hh.shape[0] not in (1, 2) or w_hh.shape[2] % 64 or \
+            not 64 <= w_hh.shape[2] <= LSTM_MAX_H:
+        raise _C.F5EError(f"pack_lstm_weight: w_hh must be [ND, 4 H, H] with ND 1 or 2 and H a multiple of 64 up to {LSTM_MAX_H} "
+                          f"(got {tuple(w_hh.shape)})")
+    ND, _, H = w_hh.shape
+    return w_hh.detach().to(F32).reshape(ND, 4, H, H // 64, 64).permute(0, 2, 3, 4, 1).contiguous()
+
+
+def lstm_f32(xg: Tensor, w_hh_packed: Tensor, lengths: Optional[Tensor], out: Tensor, cell: Tensor):
+    """f5e_lstm_f32: xg f32 [B * T, >= ND 4 H] (row-strided view; x W_ih^T + b_ih + b_hh of every direction), w_hh_packed from
+    ``pack_lstm_weight``, lengths i32 [B] on the device or None, out f32 [B, T, ND H], cell f32 scratch of ND B H elements.
+    One launch per time step; packed-sequence semantics, out[b, t >= lengths[b]] = 0."""
+    if w_hh_packed.ndim != 5 or w_hh_packed.shape[2:] != (w_hh_packed.shape[1] // 64, 64, 4) or out.ndim != 3 or xg.ndim != 2:
+        raise _C.F5EError("lstm_f32: xg [B * T, ND 4 H], w_hh_packed [ND, H, H / 64, 64, 4] (pack_lstm_weight), out [B, T, ND H]; "
+                          "there is no CPU path")
+    ND, H = w_hh_packed.shape[:2]
+    B, T, W = out.shape
+    if W != ND * H or xg.shape[0] != B * T or ND not in (1, 2) or H % 64 or not 64 <= H <= LSTM_MAX_H or \
+            not 1 <= B <= LSTM_MAX_B or not 1 <= T <= LSTM_MAX_T:
+        raise _C.F5EError(f"lstm_f32: out {tuple(out.shape)} / xg {tuple(xg.shape)} do not fit ND = {ND}, H = {H} (H a multiple of "
+                          f"64 up to {LSTM_MAX_H}, B <= {LSTM_MAX_B}, 1 <= T <= {LSTM_MAX_T})")
+    xp, ldxg = _rows(xg, (F32,), "lstm_f32: xg", ND * 4 * H, vec=1)
+    if cell.dtype != F32 or cell.numel() < ND * B * H:
+        raise _C.F5EError(f"lstm_f32: cell must hold ND B H = {ND * B * H} floats")
+    if w_hh_packed.data_ptr() % 16:
+        raise _C.F5EError("lstm_f32: w_hh_packed must be 16-byte aligned")
+    require_device()
+    check(lib().f5e_lstm_f32(_stream(), xp, ldxg, _p(w_hh_packed, F32, "w_hh_packed"), _len(lengths, B, "lstm_f32"),
+                             _p(out, F32, "out"), _p(cell, F32, "cell"), B, T, H, ND), "f5e_lstm_f32")
+    return out
+
+
+def score_mean(hid: Tensor, w2: Tensor, b2: Optional[Tensor], frames: Optional[Tensor], out: Tensor, B: int,
+               scale: float = 1.0, offset: float = 0.0, frame_scores: Optional[Tensor] = None):
+    """f5e_score_mean: hid f32 [B * T, >= F] (row-strided view), w2 f32 [F], b2 f32 [1] or None, frames i32 [B] on the device or
+    None -> out f32 [B] = scale * mean over t < frames[b] of (hid[b T + t] . w2 + b2) + offset; frame_scores f32 [B, T]
+    (optional) receives the per-frame values, zero beyond frames[b]."""
+    if hid.ndim != 2 or w2.ndim != 1 or B < 1 or hid.shape[0] % B or hid.shape[0] == 0:
+        raise _C.F5EError(f"score_mean: hid [B * T, >= F], w2 [F] (got {tuple(hid.shape)}, {tuple(w2.shape)}, B = {B}); there is no "
+                          f"CPU path")
+    T, F = hid.shape[0] // B, w2.shape[0]
+    hp, ldh = _rows(hid, (F32,), "score_mean: hid", F, vec=1)
+    if out.shape != (B,) or (b2 is not None and b2.numel() != 1) or (frame_scores is not None and frame_scores.shape != (B, T)):
+        raise _C.F5EError(f"score_mean: out [{B}], b2 [1], frame_scores [{B}, {T}]")
+    require_device()
+    check(lib().f5e_score_mean(_stream(), hp, ldh, _p(w2, F32, "w2"), _p(b2, F32, "b2"), _len(frames, B, "score_mean"),
+                               _p(frame_scores, F32, "frame_scores"), _p(out, F32, "out"), B, T, F, float(scale), float(offset)),
+          "f5e_score_mean")
+    return out
+
+
 def dit_forward(plan: "_C.DitPlan"):
     require_device()
     check(lib().f5e_dit_forward(_stream(), C.byref(plan)), "f5e_dit_forward")

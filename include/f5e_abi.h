@@ -761,6 +761,48 @@ F5E_API int f5e_greedy_pick(f5e_stream st, const float* logits, long long ld, co
                     const int* begin_suppress, int n_beg, int first_step, int* tokens, int ld_tok, int* last, int* done,
                     int* alive, int R, int V, int p, int eos);
 
+/* ---------------------------------------------------------------- UTMOS (csrc/utmos.hip) ---------------------- */
+/* The UTMOS predictor (utmos22_strong, reference eval/eval_utmos.py): a wav2vec2-base upstream (group-norm feature extractor,
+ * post-LayerNorm encoder), a BiLSTM over its frames and a per-frame score averaged per utterance.  The strided convolutions 1-6,
+ * the projections, the attention and the feed-forward are f5e_gemm_f32 / f5e_layernorm / f5e_wavlm_posconv / f5e_mha_f32; these
+ * are the rest.  fp32, channels-last, per-row lengths DEVICE int [B] (NULL: every row is full).  No allocation, no
+ * synchronisation, nothing read back, no floating-point atomics (every reduction runs in a fixed order): all of it is
+ * capturable, and a replay gives the bits of the eager run. */
+
+/* Layer 0 of the group-norm extractor: out[b][t][c] = GELU(erf)(gamma[c] (y - mean_bc) / sqrt(var_bc + eps) + beta[c]) with
+ * y = Conv1d(1 -> C, k = 10, stride 5, no padding; w f32 [C][10], bias [C] or NULL) of row b of wav f32 [B][S] (row stride ldw)
+ * and mean / biased variance of channel c over the T0_b = (len[b] - 10) / 5 + 1 frames of ITS OWN row (0 below 10 samples; len
+ * clamped to [0, S]), so row b of a padded batch equals its B = 1 run whatever the padding holds.  Frames t in [T0_b, T0),
+ * T0 = (S - 10) / 5 + 1, are written as ZERO; frames of `out` at or beyond T0 are not touched.  Frames of a row are C floats
+ * apart, rows out_bstride >= T0 C floats.  Two launches, both recompute the 10 taps: per-chunk (mean, M2) of 256 frames (the
+ * count follows from T0_b), merged per channel in ascending order by Chan's pairwise update in double (never E[x^2] - mean^2),
+ * then the apply pass; T0_b = 1 gives GELU(beta) exactly.  `partials`: scratch of f5e_w2v_conv0_gn_partials(B, S, C) floats.
+ * Also writes what f5e_wav_norm does for the layers above: frames[b] (NULL to skip) = the frame count of len[b] samples after the
+ * n_conv <= 8 valid convolutions of the HOST arrays, and mask (NULL to skip) f32 [B][t_mask] = t < frames[b], t_mask <= S. */
+F5E_API int f5e_w2v_conv0_gn_partials(int B, int S, int C, unsigned long long* floats_out_host);
+F5E_API int f5e_w2v_conv0_gn(f5e_stream st, const float* wav, int ldw, const float* w, const float* bias, const float* gamma,
+                     const float* beta, const int* len, float* partials, float* out, long long out_bstride, int* frames,
+                     float* mask, int t_mask, const int* conv_kernels_host, const int* conv_strides_host, int n_conv, int B,
+                     int S, int C, float eps);
+
+/* The recurrence of a single-layer LSTM, ND = 1 (forward) or 2 (bidirectional) directions, PyTorch gate order i, f, g, o, zero
+ * initial state.  xg f32 [B * T][>= ND 4 H] (row stride ldxg) holds x W_ih^T + b_ih + b_hh of both directions, column
+ * d 4 H + gate H + unit (one f5e_gemm_f32 beforehand); w_hh_packed f32 [ND][H (unit)][H / 64][64][4 (gate)] with
+ * w_hh_packed[d][u][j][l][g] = W_hh[d][g H + u][64 j + l], 16-byte aligned; out f32 [B][T][ND H]; cell: scratch f32 [ND][B][H]
+ * (no need to clear it).  Packed-sequence semantics: direction 0 walks t = 0 .. len[b] - 1, direction 1 walks len[b] - 1 .. 0,
+ * so a padded row equals its own B = 1 run; out[b][t >= len[b]] = 0 and rows of xg at or beyond len[b] are never read (len
+ * clamped to [0, T]).  T launches, one per time step, both directions and all rows in each; a workgroup owns 4 hidden units with
+ * all four gate rows, reads h of the neighbouring step from `out`, and is the only writer of its cells.  No workgroup waits on
+ * another: the stream order is the only ordering.  expf / tanhf.  H a multiple of 64 up to 1024, B <= 16, 1 <= T <= 4096. */
+F5E_API int f5e_lstm_f32(f5e_stream st, const float* xg, long long ldxg, const float* w_hh_packed, const int* len, float* out,
+                 float* cell, int B, int T, int H, int ND);
+
+/* frame[b][t] = hid[b T + t][0 .. F) . w2 + b2[0]  (hid f32 [B * T][>= F], row stride ldh; b2 DEVICE f32 [1] or NULL) and
+ * out[b] = scale * mean_{t < n_b} frame[b][t] + offset, n_b = frames[b] clamped to [0, T] (NULL: T; n_b = 0 gives offset).
+ * frame_scores (NULL to skip) f32 [B][T], ZERO at t >= n_b.  One workgroup per row, sums in a fixed order. */
+F5E_API int f5e_score_mean(f5e_stream st, const float* hid, long long ldh, const float* w2, const float* b2, const int* frames,
+                   float* frame_scores, float* out, int B, int T, int F, float scale, float offset);
+
 /* ---------------------------------------------------------------- hipGraph capture --------------------------- */
 F5E_API int f5e_graph_begin(f5e_stream st);
 F5E_API int f5e_graph_end(f5e_stream st, void** graph_exec_out);

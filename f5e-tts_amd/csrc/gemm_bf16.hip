@@ -904,6 +904,7 @@ int f5e_gemm_bf16_bias_pf(hipStream_t st, const void* A, int lda, const void* W,
   if (int e = check_common(a)) return e;
   if (int e = set_consumer(a, ln, bias)) return e;
   F5E_REQUIRE(out && ldo % 4 == 0, "gemm_bf16_bias: bad output");
+  F5E_REQUIRE(M == 1 || ldo >= N, "gemm_bf16_bias: ldo=%d is smaller than N=%d (rows would overlap)", ldo, N);
   if (out_f32) {
     F5E_REQUIRE(act == F5E_ACT_NONE, "gemm_bf16_bias: f32 output supports no activation");
     return dispatch<EPI_F32>(a, st, tile_hint);
@@ -926,9 +927,11 @@ int f5e_gemm_bf16_gate_residual_pf(hipStream_t st, const void* A, int lda, const
   if (int e = check_common(a)) return e;
   F5E_REQUIRE(resid && gate && ldr % 4 == 0 && gate_stride % 4 == 0 && gate_rows > 0 && rows_per_seq > 0,
               "gemm_bf16_gate_residual: bad residual/gate arguments");
+  F5E_REQUIRE(M == 1 || ldr >= N, "gemm_bf16_gate_residual: ldr=%d is smaller than N=%d (rows would overlap)", ldr, N);
   if (ln && ln->stats_out) {
     F5E_REQUIRE(ln->xs_out && ln->next_scale && ln->row_mean && ln->ld_xs % 4 == 0 && N % 64 == 0,
                 "gemm_bf16_gate_residual: AdaLN producer needs xs_out, next_scale, row_mean and N %% 64 == 0");
+    F5E_REQUIRE(M == 1 || ln->ld_xs >= N, "gemm_bf16_gate_residual: ld_xs=%d is smaller than N=%d (rows would overlap)", ln->ld_xs, N);
     a.xs_out = (bf16*)ln->xs_out; a.ld_xs = ln->ld_xs; a.next_scale = ln->next_scale; a.stats_out = ln->stats_out;
     a.row_mean = ln->row_mean;
   }

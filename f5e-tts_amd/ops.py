@@ -70,28 +70,70 @@ def _rows(t: Tensor, dtypes, name: str, cols: int, vec: int = 4, whole_rows: boo
     return C.c_void_p(t.data_ptr()), ld
 
 
+def _err(msg: str):
+    raise _C.F5EError(msg)
+
+
+def _flat(t: Optional[Tensor], dtype, name: str, n: int):
+    """Pointer of a contiguous ``dtype`` GPU tensor that holds at least ``n`` elements (None stays None)."""
+    if t is not None and (t.dtype != dtype or t.numel() < n):
+        _err(f"{name} must be {dtype} with at least {n} elements (got {t.dtype}, {t.numel()})")
+    return _p(t, dtype, name)
+
+
+def _table(t: Tensor, name: str, cols: int):
+    """(pointer, row stride, rows) of an f32 [rows, >= cols] modulation-table view (gate, scale, c, d): unit column stride,
+    16-byte aligned rows."""
+    if t.ndim != 2 or t.dtype != F32 or t.shape[0] < 1 or t.shape[1] < cols or (t.stride(1) != 1 and t.shape[1] > 1):
+        _err(f"{name} must be an f32 [rows, >= {cols}] view with unit column stride (got {t.dtype}, shape {tuple(t.shape)}, "
+             f"strides {tuple(t.stride())})")
+    if not t.is_cuda:
+        _err(f"{name} must live on the GPU (got {t.device}); there is no CPU path")
+    ld = t.stride(0) if t.shape[0] > 1 or t.stride(0) % 4 == 0 else (t.shape[1] + 3) // 4 * 4
+    if ld % 4 or t.data_ptr() % 16:
+        _err(f"{name}: row stride {ld} must be a multiple of 4 and the base 16-byte aligned")
+    return C.c_void_p(t.data_ptr()), ld, t.shape[0]
+
+
+LN_PARTS = (4, 8, 12, 16)
+
+
 def ln_consumer(stats: Tensor, c: Tensor, d: Tensor, rows_per_seq: int, row_mean: Tensor, eval_ptr: Optional[Tensor] = None,
                 cd_eval_stride: int = 0, eps: float = 1e-6) -> "_C.LnFuse":
-    """Consumer side of the fused AdaLN (see f5e_ln_fuse): stats f32 [M, parts, 2] (tile means relative to row_mean);
-    c, d f32 [cd_rows, N] views; row_mean f32 [M]: the rows' centring offsets, moved along by this launch."""
-    if c.stride(0) != d.stride(0) or c.shape != d.shape:
-        raise _C.F5EError("c and d tables must share shape and row stride")
+    """Consumer side of the fused AdaLN (see f5e_ln_fuse): stats f32 [>= M, parts, 2] (tile means relative to row_mean),
+    parts = K / 64 in {4, 8, 12, 16}; c, d f32 [1, >= N] views; row_mean f32 [>= M]: the rows' centring offsets, moved along
+    by this launch.  The GEMM wrapper checks M, N and K against these."""
+    if stats.ndim != 3 or stats.shape[2] != 2 or stats.dtype != F32 or stats.shape[1] not in LN_PARTS:
+        _err(f"ln_consumer: stats must be f32 [rows, parts, 2] with parts in {LN_PARTS} (got {stats.dtype}, shape {tuple(stats.shape)})")
+    if row_mean.dtype != F32 or row_mean.ndim != 1:
+        _err(f"ln_consumer: row_mean must be f32 [rows] (got {row_mean.dtype}, shape {tuple(row_mean.shape)})")
+    if c.ndim != 2 or d.ndim != 2 or c.stride(0) != d.stride(0) or c.shape != d.shape:
+        _err("ln_consumer: c and d tables must be 2-D and share shape and row stride")
+    if eval_ptr is not None and cd_eval_stride <= 0:
+        _err("ln_consumer: eval_ptr needs cd_eval_stride")
     f = _C.LnFuse()
     f.stats, f.parts = _p(stats, F32, "stats").value, stats.shape[1]
-    f.c, f.d, f.cd_stride, f.cd_rows = c.data_ptr(), d.data_ptr(), c.stride(0), c.shape[0]
+    f.c, f.cd_stride, f.cd_rows = _table(c, "ln_consumer: c", 1)
+    f.d = _table(d, "ln_consumer: d", 1)[0]
     f.cd_eval_stride, f.rows_per_seq, f.eps = cd_eval_stride, rows_per_seq, eps
-    f.eval_ptr = eval_ptr.data_ptr() if eval_ptr is not None else None
+    f.eval_ptr = _p(eval_ptr, I32, "eval_ptr").value if eval_ptr is not None else None
     f.row_mean = _p(row_mean, F32, "row_mean").value
     f._keep = (stats, c, d, eval_ptr, row_mean)
     return f
 
 
 def ln_producer(xs_out: Tensor, next_scale: Tensor, stats_out: Tensor, row_mean: Tensor) -> "_C.LnFuse":
-    """Producer side: xs_out bf16 [M, N]; next_scale f32 [gate_rows, N] view with the gate's row stride;
-    stats_out f32 [M, N // 64, 2]; row_mean f32 [M]: the rows' centring offsets (read)."""
+    """Producer side: xs_out bf16 [>= M, >= N] row-strided view; next_scale f32 [gate_rows, >= N] view with the gate's row
+    stride; stats_out f32 [>= M, N // 64, 2]; row_mean f32 [>= M]: the rows' centring offsets (read).  The GEMM wrapper
+    checks M and N against these."""
+    if stats_out.ndim != 3 or stats_out.shape[2] != 2 or stats_out.dtype != F32:
+        _err(f"ln_producer: stats_out must be f32 [rows, N / 64, 2] (got {stats_out.dtype}, shape {tuple(stats_out.shape)})")
+    if row_mean.dtype != F32 or row_mean.ndim != 1:
+        _err(f"ln_producer: row_mean must be f32 [rows] (got {row_mean.dtype}, shape {tuple(row_mean.shape)})")
     f = _C.LnFuse()
-    f.xs_out, f.ld_xs = _p(xs_out, BF, "xs_out").value, xs_out.stride(0)
-    f.next_scale, f.stats_out = next_scale.data_ptr(), _p(stats_out, F32, "stats_out").value
+    f.xs_out, f.ld_xs = _rows(xs_out, (BF,), "xs_out", stats_out.shape[1] * 64)
+    f.next_scale = _table(next_scale, "ln_producer: next_scale", stats_out.shape[1] * 64)[0]
+    f.stats_out = _p(stats_out, F32, "stats_out").value
     f.row_mean = _p(row_mean, F32, "row_mean").value
     f._keep = (xs_out, next_scale, stats_out, row_mean)
     return f
@@ -101,26 +143,86 @@ def _ln_ref(ln):
     return C.byref(ln) if ln is not None else None
 
 
+def _check_consumer(ln, M: int, N: int, K: int, name: str):
+    if ln is None:
+        return
+    if not ln.stats or ln.stats_out:
+        _err(f"{name}: ln must come from ln_consumer")
+    stats, c, _, _, row_mean = ln._keep
+    if stats.shape[0] < M or stats.shape[1] * 64 != K:
+        _err(f"{name}: stats must be [>= {M}, {K // 64}, 2] (got shape {tuple(stats.shape)})")
+    if row_mean.numel() < M:
+        _err(f"{name}: row_mean must hold {M} rows (got {row_mean.numel()})")
+    if c.shape[1] < N:
+        _err(f"{name}: the c / d tables must be at least {N} wide (got {c.shape[1]})")
+
+
+def _check_producer(ln, M: int, N: int, gate: Tensor, name: str):
+    if ln is None:
+        return
+    if not ln.stats_out or ln.stats:
+        _err(f"{name}: ln must come from ln_producer")
+    xs_out, next_scale, stats_out, row_mean = ln._keep
+    if N % 64 or stats_out.shape[0] < M or stats_out.shape[1] != N // 64:
+        _err(f"{name}: stats_out must be [>= {M}, N / 64 = {N / 64:g}, 2] (got shape {tuple(stats_out.shape)})")
+    if row_mean.numel() < M or xs_out.shape[0] < M:
+        _err(f"{name}: row_mean and xs_out must hold {M} rows (got {row_mean.numel()}, {xs_out.shape[0]})")
+    if next_scale.shape[0] != gate.shape[0] or (gate.shape[0] > 1 and next_scale.stride(0) != gate.stride(0)):
+        _err(f"{name}: next_scale must have the gate's rows and row stride")
+
+
 def adaln_pre(x: Tensor, xs: Tensor, scale: Tensor, stats: Tensor, row_mean: Tensor, rows_per_seq: int,
               eval_ptr: Optional[Tensor] = None, eval_stride: int = 0):
     """Head of the fused-AdaLN chain: row_mean[row] = mean(x[row]), xs = bf16((x - mean) (1 + scale[r])), stats[row] =
-    `parts` equal shares of (0, M2) (tile means relative to row_mean)."""
+    `parts` equal shares of (0, M2) (tile means relative to row_mean).  x f32 [rows, D], xs bf16 [>= rows, >= D] row-strided
+    views; scale f32 [mod_rows, >= D]; stats f32 [>= rows, parts, 2]; row_mean f32 [>= rows]."""
     require_device()
+    if x.ndim != 2:
+        _err(f"adaln_pre: x must be [rows, D] (got shape {tuple(x.shape)})")
     rows, D = x.shape
-    check(lib().f5e_adaln_pre(_stream(), _p(x, F32, "x"), x.stride(0), _p(xs, BF, "xs"), xs.stride(0),
-                              C.c_void_p(scale.data_ptr()), scale.stride(0), scale.shape[0], rows_per_seq,
+    px, ldx = _rows(x, (F32,), "x", D)
+    pxs, ld_xs = _rows(xs, (BF,), "xs", D)
+    if xs.shape[0] < rows:
+        _err(f"adaln_pre: xs has {xs.shape[0]} rows, fewer than x's {rows}")
+    if stats.ndim != 3 or stats.shape[2] != 2 or stats.shape[0] < rows:
+        _err(f"adaln_pre: stats must be f32 [>= {rows}, parts, 2] (got shape {tuple(stats.shape)})")
+    if eval_ptr is not None and eval_stride <= 0:
+        _err("adaln_pre: eval_ptr needs eval_stride")
+    ps, mod_stride, mod_rows = _table(scale, "adaln_pre: scale", D)
+    check(lib().f5e_adaln_pre(_stream(), px, ldx, pxs, ld_xs, ps, mod_stride, mod_rows, rows_per_seq,
                               _p(eval_ptr, I32, "eval_ptr"), eval_stride, _p(stats, F32, "stats"), stats.shape[1],
-                              _p(row_mean, F32, "row_mean"), rows, D), "f5e_adaln_pre")
+                              _flat(row_mean, F32, "row_mean", rows), rows, D), "f5e_adaln_pre")
+
+
+def _gemm_operands(a: Tensor, w: Tensor, name: str):
+    """(M, N, K, pa, lda, pw, ldw) of a [M, K] and w [N, K]: bf16 row-strided views (16-byte aligned rows: the LDS-DMA's unit)."""
+    if a.ndim != 2 or w.ndim != 2 or a.shape[0] < 1 or w.shape[0] < 1:
+        _err(f"{name}: a and w must be non-empty 2-D tensors (got shapes {tuple(a.shape)}, {tuple(w.shape)})")
+    (M, K), N = a.shape, w.shape[0]
+    if w.shape[1] != K:
+        _err(f"{name}: w is [{N}, {w.shape[1]}], a is [{M}, {K}]: the K dimensions differ")
+    if K % 64 or N % 4:
+        _err(f"{name}: K = {K} must be a multiple of 64 and N = {N} a multiple of 4")
+    pa, lda = _rows(a, (BF,), "a", K, vec=8)
+    pw, ldw = _rows(w, (BF,), "w", K, vec=8)
+    return M, N, K, pa, lda, pw, ldw
 
 
 def gemm_bf16_bias(a: Tensor, w: Tensor, bias: Optional[Tensor], out: Tensor, act: int = ACT_NONE, tile_hint: int = 0,
                    ln=None):
-    """out[M,N] = act(a[M,K] @ w[N,K].T + bias); out bf16 or f32 (no activation).  ln: ``ln_consumer(...)``."""
+    """out[M,N] = act(a[M,K] @ w[N,K].T + bias); out bf16 or f32 (no activation).  a, w, out: row-strided views with unit
+    column stride (row strides multiples of 8 / 8 / 4 elements); bias f32 [>= N].  ln: ``ln_consumer(...)``.  Everything is
+    refused here, before any launch."""
     require_device()
-    M, K = a.shape
-    N = w.shape[0]
-    check(lib().f5e_gemm_bf16_bias_ln(_stream(), _p(a, BF, "a"), a.stride(0), _p(w, BF, "w"), w.stride(0),
-                                      _p(bias, F32, "bias"), _p(out, None, "out"), out.stride(0), M, N, K, act,
+    M, N, K, pa, lda, pw, ldw = _gemm_operands(a, w, "gemm_bf16_bias")
+    po, ldo = _rows(out, (BF, F32), "out", N)
+    if out.shape[0] < M or out.data_ptr() % 16:
+        _err(f"gemm_bf16_bias: out has {out.shape[0]} rows (a has {M}) at address % 16 = {out.data_ptr() % 16}: needs as many rows "
+             f"as a and a 16-byte aligned base (the ping-pong kernel stores 16-byte pieces)")
+    if act not in (ACT_NONE, ACT_GELU_TANH) or (act != ACT_NONE and out.dtype == F32):
+        _err(f"gemm_bf16_bias: activation {act} with a {out.dtype} out (none or GELU(tanh); an f32 out takes none)")
+    _check_consumer(ln, M, N, K, "gemm_bf16_bias")
+    check(lib().f5e_gemm_bf16_bias_ln(_stream(), pa, lda, pw, ldw, _flat(bias, F32, "bias", N), po, ldo, M, N, K, act,
                                       1 if out.dtype == F32 else 0, tile_hint, _ln_ref(ln)), "f5e_gemm_bf16_bias")
     return out
 
@@ -128,30 +230,49 @@ def gemm_bf16_bias(a: Tensor, w: Tensor, bias: Optional[Tensor], out: Tensor, ac
 def gemm_bf16_gate_residual(a: Tensor, w: Tensor, bias: Optional[Tensor], resid: Tensor, gate: Tensor,
                             rows_per_seq: int, seq_len: Optional[Tensor] = None, eval_ptr: Optional[Tensor] = None,
                             eval_stride: int = 0, tile_hint: int = 0, ln=None):
-    """resid[M,N] += gate[seq % rows] * (a @ w.T + bias), rows past seq_len skipped. gate: [rows, N] f32 view.
-    ln: ``ln_producer(...)`` to also emit the next fused-AdaLN consumer's inputs."""
+    """resid[M,N] += gate[seq % rows] * (a @ w.T + bias), rows past seq_len skipped.  resid f32 [>= M, >= N] row-strided view;
+    gate: [rows, >= N] f32 view; seq_len int32 [>= ceil(M / rows_per_seq)].  ln: ``ln_producer(...)`` to also emit the next
+    fused-AdaLN consumer's inputs.  Everything is refused here, before any launch."""
     require_device()
-    M, K = a.shape
-    N = w.shape[0]
+    M, N, K, pa, lda, pw, ldw = _gemm_operands(a, w, "gemm_bf16_gate_residual")
+    pr, ldr = _rows(resid, (F32,), "resid", N)
+    if resid.shape[0] < M:
+        _err(f"gemm_bf16_gate_residual: resid has {resid.shape[0]} rows, fewer than a's {M}")
+    pg, gate_stride, gate_rows = _table(gate, "gemm_bf16_gate_residual: gate", N)
+    if rows_per_seq < 1:
+        _err(f"gemm_bf16_gate_residual: rows_per_seq = {rows_per_seq}")
+    if eval_ptr is not None and eval_stride <= 0:
+        _err("gemm_bf16_gate_residual: eval_ptr needs eval_stride")
+    _check_producer(ln, M, N, gate, "gemm_bf16_gate_residual")
     check(lib().f5e_gemm_bf16_gate_residual_ln(
-        _stream(), _p(a, BF, "a"), a.stride(0), _p(w, BF, "w"), w.stride(0), _p(bias, F32, "bias"),
-        _p(resid, F32, "resid"), resid.stride(0), C.c_void_p(gate.data_ptr()), gate.stride(0), gate.shape[0],
-        _p(eval_ptr, I32, "eval_ptr"), eval_stride, rows_per_seq, _p(seq_len, I32, "seq_len"), M, N, K, tile_hint,
-        _ln_ref(ln)), "f5e_gemm_bf16_gate_residual")
+        _stream(), pa, lda, pw, ldw, _flat(bias, F32, "bias", N), pr, ldr, pg, gate_stride, gate_rows,
+        _p(eval_ptr, I32, "eval_ptr"), eval_stride, rows_per_seq,
+        _flat(seq_len, I32, "seq_len", -(-M // rows_per_seq)), M, N, K, tile_hint, _ln_ref(ln)), "f5e_gemm_bf16_gate_residual")
     return resid
 
 
-def gemm_bf16_qkv_rope(a: Tensor, w: Tensor, bias: Tensor, q: Tensor, k: Tensor, vt: Tensor, heads: int,
+def gemm_bf16_qkv_rope(a: Tensor, w: Tensor, bias: Optional[Tensor], q: Tensor, k: Tensor, vt: Tensor, heads: int,
                        rope_heads: int, cos_sin: Tensor, rows_per_seq: int, tile_hint: int = 0,
                        q_norm_w: Optional[Tensor] = None, k_norm_w: Optional[Tensor] = None, ln=None):
+    """Fused to_q / to_k / to_v + RoPE (f5e_gemm_bf16_qkv_rope): w [3 * heads * 64, K]; q, k [S, heads, n_pad, 64] and vt
+    [S, heads, 64, n_pad] bf16, contiguous, S >= ceil(M / rows_per_seq); cos_sin f32 [>= rows_per_seq, 32, 2].  Everything is
+    refused here, before any launch."""
     require_device()
-    M, K = a.shape
+    M, N, K, pa, lda, pw, ldw = _gemm_operands(a, w, "gemm_bf16_qkv_rope")
+    if heads < 1 or N != 3 * heads * 64:
+        _err(f"gemm_bf16_qkv_rope: w has {N} rows, not 3 * heads * 64 = {3 * heads * 64}")
+    if q.ndim != 4 or rows_per_seq < 1:
+        _err(f"gemm_bf16_qkv_rope: q must be [S, heads, n_pad, 64] (got shape {tuple(q.shape)}), rows_per_seq >= 1")
     n_pad = q.shape[2]
+    if n_pad % 64 or n_pad < rows_per_seq:
+        _err(f"gemm_bf16_qkv_rope: n_pad = {n_pad} must be a multiple of 64 and >= rows_per_seq = {rows_per_seq}")
+    need = -(-M // rows_per_seq) * heads * n_pad * 64
+    _check_consumer(ln, M, N, K, "gemm_bf16_qkv_rope")
     check(lib().f5e_gemm_bf16_qkv_rope_ln(
-        _stream(), _p(a, BF, "a"), a.stride(0), _p(w, BF, "w"), w.stride(0), _p(bias, F32, "bias"), _p(q, BF, "q"),
-        _p(k, BF, "k"), _p(vt, BF, "vt"), n_pad, heads, rope_heads, _p(cos_sin, F32, "cos_sin"),
-        _p(q_norm_w, F32, "q_norm_w"), _p(k_norm_w, F32, "k_norm_w"), rows_per_seq, M, K, tile_hint, _ln_ref(ln)),
-        "f5e_gemm_bf16_qkv_rope")
+        _stream(), pa, lda, pw, ldw, _flat(bias, F32, "bias", N), _flat(q, BF, "q", need), _flat(k, BF, "k", need),
+        _flat(vt, BF, "vt", need), n_pad, heads, rope_heads, _flat(cos_sin, F32, "cos_sin", rows_per_seq * 64),
+        _flat(q_norm_w, F32, "q_norm_w", 64), _flat(k_norm_w, F32, "k_norm_w", 64), rows_per_seq, M, K, tile_hint,
+        _ln_ref(ln)), "f5e_gemm_bf16_qkv_rope")
 
 
 def qk_frag_index(n_pad: int) -> Tensor:

@@ -48,8 +48,10 @@ F5E_API int f5e_check_device(void);
 /* ---------------------------------------------------------------- bf16 MFMA GEMMs (hot loop) ----------------- */
 
 /* out[M][N] = act(A[M][K] . W[N][K]^T + bias).  A, W bf16; bias f32[N] or NULL; out bf16 (out_f32 = 0) or f32.
- * act: F5E_ACT_NONE or F5E_ACT_GELU_TANH.  K % 64 == 0, N % 4 == 0.  tile_hint: 0 = auto, or force a tile family: 1 = 128x128,
- * 2 = 128x64, 3 = 64x64, 9 = the 256x256 ping-pong kernel (what auto picks from 44 row tiles of 256 on).
+ * act: F5E_ACT_NONE or F5E_ACT_GELU_TANH.  K % 64 == 0, N % 4 == 0; lda, ldw multiples of 8, ldo a multiple of 4 and, with
+ * M > 1, at least N (the same holds for ldr and f5e_ln_fuse.ld_xs below); nothing is written outside [0, M) x [0, N).
+ * tile_hint: 0 = auto, or force a tile family: 1 = 128x128, 2 = 128x64, 3 = 64x64, 9 = the 256x256 ping-pong kernel (what
+ * auto picks from 44 row tiles of 256 on).
  * Replaces: FeedForward project_in + GELU(tanh) (model/modules.py:348-349,625), proj_out (backbones/dit.py:470). */
 F5E_API int f5e_gemm_bf16_bias(f5e_stream st, const void* A, int lda, const void* W, int ldw, const float* bias, void* out,
                        int ldo, int M, int N, int K, int act, int out_f32, int tile_hint);

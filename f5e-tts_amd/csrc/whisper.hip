@@ -1,5 +1,5 @@
 // Whisper on the device (reference infer/utils_infer.py:148-179, eval/utils_eval.py:631-672: openai/whisper-large-v3[-turbo]
-// through transformers, greedy): the three parts that f5e_gemm_f32 / f5e_layernorm / f5e_mha_f32 / f5e_attn_decode_f32 /
+// through transformers, greedy or beam search): the parts that f5e_gemm_f32 / f5e_layernorm / f5e_mha_f32 / f5e_attn_decode_f32 /
 // f5e_text_gather cannot express.  fp32 throughout.
 //
 //   f5e_whisper_logmel          WhisperFeatureExtractor: 400-point centred STFT (direct DFT against a twiddle table in LDS),
@@ -11,6 +11,11 @@
 //                               maximum, sum and context, and the four are merged through LDS with exp(m_w - M).
 //   f5e_greedy_pick             suppression, first-maximum argmax and the token / done bookkeeping of one greedy step, so the
 //                               token loop needs no host round trip per token.
+//
+//   f5e_whisper_beam_step       one step of the pooled beam search (transformers' generate(num_beams=K)): the logits go through
+//                               LDS once, in chunks of 8192 classes that each leave a maximum, a sum of exponentials and their 2K
+//                               largest unsuppressed classes; one workgroup per utterance then folds the chunks, takes the 2K
+//                               largest candidates and applies the rules (open rows, pool of finished hypotheses, flags).
 //
 // Nothing here allocates, synchronises or reads back.  Per-row lengths are DEVICE int32.
 #include "f5e_common.h"
@@ -248,7 +253,282 @@ __global__ __launch_bounds__(256) void alive_count_kernel(const int* __restrict_
   if (threadIdx.x == 0) *alive = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// ---- beam step (transformers' GenerationMixin._beam_search: K open rows, a pool of finished hypotheses) ------------------------
+// Launch 1, one workgroup per (row, chunk of WB_CHUNK classes): the chunk goes from memory to LDS once (float4 when the row
+// allows it); its maximum and sum of exponentials cover ALL its classes, then the suppressed ones become -inf and the 2K largest
+// of what is left are taken by 2K rounds of (argmax over LDS, remove), lowest class first among equals.  Record per (row, chunk)
+// in scratch: max, sum, 2K raw values (-inf: none), 2K classes (-1: none).  A row whose score is not above -inf has no finite
+// candidate: its workgroups leave at once and launch 2 never reads its records.
+// Launch 2, one workgroup per utterance: thread q folds the chunk maxima and sums of row q in ascending chunk order; the
+// K * chunks * 2K survivors become (score + logp, row << 18 | class) in LDS (in the scratch itself beyond WB_LDS_CAND of them) and
+// the 2K largest are taken by the same rounds, lowest (row, class) first among equals; one thread then applies the rules to at
+// most 32 candidates, and all threads gather the tables and move the pool rows.
+constexpr int WB_CHUNK = 8192, WB_MAX_K = 16, WB_MAX_V = 262144, WB_LDS_CAND = 4096, WB_NEW = 100;
+
+__host__ __device__ inline int wb_chunks(int V) { return (V + WB_CHUNK - 1) / WB_CHUNK; }
+__host__ __device__ inline int wb_rec(int K) { return 2 + 4 * K; }   // words of a (row, chunk) record
+
+__global__ __launch_bounds__(256) void beam_chunk_kernel(const float* __restrict__ logits, long long ld,
+                                                         const int* __restrict__ suppress, int n_sup,
+                                                         const int* __restrict__ begin_suppress, int n_beg,
+                                                         const float* __restrict__ score, float* __restrict__ scratch, int V,
+                                                         int K, int vec) {
+  __shared__ __attribute__((aligned(16))) float x[WB_CHUNK];
+  __shared__ float rm[4];
+  __shared__ int ra[4];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = blockIdx.y, r = blockIdx.x;
+  const float NEG = -__builtin_inff();
+  if (!(score[r] > NEG)) return;                                   // uniform over the workgroup
+  const int c0 = c * WB_CHUNK, n = min(V - c0, WB_CHUNK), K2 = 2 * K;
+  const float* row = logits + (size_t)r * ld + c0;
+  float m = NEG;
+  if (vec) {                                                       // ld % 4 == 0 and a 16-byte aligned base: c0 is a multiple of 4
+    const int n4 = n >> 2;
+    for (int i = tid; i < n4; i += 256) {
+      const f32x4 v = *(const f32x4*)(row + 4 * i);
+      *(f32x4*)(x + 4 * i) = v;
+      m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w));
+    }
+    for (int i = 4 * n4 + tid; i < n; i += 256) x[i] = row[i], m = fmaxf(m, x[i]);
+  } else {
+    for (int i = tid; i < n; i += 256) x[i] = row[i], m = fmaxf(m, x[i]);
+  }
+  m = wave_max(m);
+  if (lane == 0) rm[w] = m;
+  __syncthreads();
+  m = fmaxf(fmaxf(rm[0], rm[1]), fmaxf(rm[2], rm[3]));
+  float sum = 0.f;
+  if (m > NEG)
+    for (int i = tid; i < n; i += 256) sum += expf(x[i] - m);
+  sum = wave_sum(sum);
+  __syncthreads();                                                 // rm is reused; every x was read before a class is struck
+  if (lane == 0) rm[w] = sum;
+  for (int i = tid; i < n_sup + n_beg; i += 256) {
+    const int v = (i < n_sup ? suppress[i] : begin_suppress[i - n_sup]) - c0;
+    if (v >= 0 && v < n) x[v] = NEG;
+  }
+  __syncthreads();
+  float* rec = scratch + ((size_t)r * gridDim.y + c) * wb_rec(K);
+  if (tid == 0) rec[0] = m, rec[1] = (rm[0] + rm[1]) + (rm[2] + rm[3]);
+  __syncthreads();
+  for (int t = 0; t < K2; ++t) {
+    float bm = NEG;
+    int ba = WAVE_NONE;
+    for (int i = tid; i < n; i += 256) {                           // ascending per thread: '>' keeps the first maximum
+      const float v = x[i];
+      if (v > bm) bm = v, ba = i;
+    }
+    wave_argmax(bm, ba);
+    if (lane == 0) rm[w] = bm, ra[w] = ba;
+    __syncthreads();
+    bm = rm[0], ba = ra[0];
+#pragma unroll
+    for (int v = 1; v < 4; ++v)
+      if (rm[v] > bm || (rm[v] == bm && ra[v] < ba)) bm = rm[v], ba = ra[v];
+    const bool none = ba == WAVE_NONE || !(bm < __builtin_inff());  // nothing finite is left (uniform)
+    if (tid == 0) {
+      rec[2 + t] = none ? NEG : bm;
+      ((int*)rec)[2 + K2 + t] = none ? -1 : c0 + ba;
+      if (!none) x[ba] = NEG;
+    }
+    __syncthreads();
+    if (none) {
+      for (int u = t + 1 + tid; u < K2; u += 256) rec[2 + u] = NEG, ((int*)rec)[2 + K2 + u] = -1;
+      break;
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void beam_select_kernel(float* score, const int* __restrict__ hyp_in,
+                                                          const int* __restrict__ anc_in, int* __restrict__ hyp_out,
+                                                          int* __restrict__ anc_out, int ld, int* __restrict__ last, int* pool_hyp,
+                                                          int* pool_len, float* pool_score, int* pool_n, int* open_, int* alive,
+                                                          float* scratch, int NCH, int K, int p, int n0, int cap, int eos,
+                                                          float length_penalty) {
+  __shared__ float cv_l[WB_LDS_CAND];
+  __shared__ int ci_l[WB_LDS_CAND];
+  __shared__ float row_sc[WB_MAX_K], row_m[WB_MAX_K], row_ls[WB_MAX_K];
+  __shared__ float top_v[2 * WB_MAX_K], sel_val[WB_MAX_K], ps[WB_MAX_K];
+  __shared__ int top_i[2 * WB_MAX_K], sel_par[WB_MAX_K], sel_cls[WB_MAX_K], pl[WB_MAX_K], pl_old[WB_MAX_K], src[WB_MAX_K];
+  __shared__ float rm[4];
+  __shared__ int ra[4], n_top, dirty;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, b = blockIdx.x;
+  const float NEG = -__builtin_inff();
+  const int K2 = 2 * K, REC = wb_rec(K), per_row = NCH * K2, N = K * per_row;
+  const long long r0 = (long long)b * K;
+  float* sb = scratch + (size_t)r0 * NCH * REC;                    // this utterance's records
+  const bool in_lds = N <= WB_LDS_CAND;
+  // candidate i = (row q, chunk c, rank j): where its value and id live
+  auto slot = [&](int i) { const int rc = i / K2; return in_lds ? i : rc * REC + 2 + (i - rc * K2); };
+  float* cv = in_lds ? cv_l : sb;
+  int* ci = in_lds ? ci_l : (int*)sb + K2;
+  if (tid < K) {
+    const float sc = score[r0 + tid];
+    float M = NEG, S = 0.f;
+    if (sc > NEG) {
+      const float* rr = sb + (size_t)tid * NCH * REC;
+      for (int c = 0; c < NCH; ++c) M = fmaxf(M, rr[(size_t)c * REC]);
+      for (int c = 0; c < NCH; ++c) {                              // ascending chunks: a fixed order
+        const float mc = rr[(size_t)c * REC];
+        if (mc > NEG) S += rr[(size_t)c * REC + 1] * expf(mc - M);
+      }
+    }
+    row_sc[tid] = sc, row_m[tid] = M, row_ls[tid] = logf(S);
+  }
+  __syncthreads();
+  for (int i = tid; i < N; i += 256) {
+    const int q = i / per_row, rc = i / K2, j = i - rc * K2;
+    float v = NEG;
+    int id = WAVE_NONE;
+    if (row_sc[q] > NEG) {
+      const float xr = sb[(size_t)rc * REC + 2 + j];
+      const int cls = ((const int*)sb)[(size_t)rc * REC + 2 + K2 + j];
+      if (cls >= 0) {
+        v = row_sc[q] + ((xr - row_m[q]) - row_ls[q]);
+        id = (q << 18) | cls;
+        if (!(v > NEG && v < __builtin_inff())) v = NEG;           // NaN and +inf are no candidates
+      }
+    }
+    cv[slot(i)] = v, ci[slot(i)] = id;
+  }
+  if (tid == 0) n_top = K2;
+  __syncthreads();
+  for (int t = 0; t < K2; ++t) {
+    float bm = NEG;
+    int ba = WAVE_NONE, bi = -1;
+    for (int i = tid; i < N; i += 256) {
+      const float v = cv[slot(i)];
+      const int id = ci[slot(i)];
+      if (v > bm || (v == bm && v > NEG && id < ba)) bm = v, ba = id, bi = i;
+    }
+    const int mine = ba;
+    wave_argmax(bm, ba);
+    if (lane == 0) rm[w] = bm, ra[w] = ba;
+    __syncthreads();
+    bm = rm[0], ba = ra[0];
+#pragma unroll
+    for (int v = 1; v < 4; ++v)
+      if (rm[v] > bm || (rm[v] == bm && ra[v] < ba)) bm = rm[v], ba = ra[v];
+    const bool none = ba == WAVE_NONE;                              // uniform
+    if (!none && mine == ba && bi >= 0) cv[slot(bi)] = NEG;         // ids are unique: one thread owns the winner
+    if (tid == 0) {
+      if (none) n_top = t;
+      else top_v[t] = bm, top_i[t] = ba;
+    }
+    __syncthreads();
+    if (none) break;
+  }
+  // ---- the rules, on at most 2K candidates in descending order
+  if (tid == 0) {
+    const int nc = n_top;
+    int n = min(max(pool_n[b], 0), K), op = open_[b] != 0, n_run = 0, changed = 0;
+    bool any_open_cand = false;
+    for (int s = 0; s < K; ++s) ps[s] = pool_score[r0 + s], pl[s] = pl_old[s] = pool_len[r0 + s], src[s] = s;
+    const float denom = powf((float)(p + 2 - n0), length_penalty);
+    for (int j = 0; j < nc; ++j) {
+      const int cls = top_i[j] & 0x3ffff;
+      const bool hit = cls == eos || p + 2 >= cap;
+      if (!hit) {
+        any_open_cand = true;
+        if (n_run < K) sel_par[n_run] = top_i[j] >> 18, sel_cls[n_run] = cls, sel_val[n_run] = top_v[j], ++n_run;
+      } else if (op && j < K) {
+        const float sc = top_v[j] / denom;
+        int pos = n;
+        while (pos > 0 && ps[pos - 1] < sc) --pos;                  // after every entry that is not worse
+        if (pos < K) {
+          for (int s = min(n, K - 1); s > pos; --s) ps[s] = ps[s - 1], pl[s] = pl[s - 1], src[s] = src[s - 1];
+          ps[pos] = sc, pl[pos] = p + 2, src[pos] = WB_NEW + j;
+          n = min(n + 1, K);
+          changed = 1;
+        }
+      }
+    }
+    if (n == K) op = op && (n_run > 0 ? sel_val[0] / denom : NEG) > ps[K - 1];
+    for (int q = n_run; q < K; ++q) sel_par[q] = q, sel_cls[q] = eos, sel_val[q] = NEG;
+    for (int q = 0; q < K; ++q) score[r0 + q] = sel_val[q], last[r0 + q] = sel_cls[q];
+    if (changed) {
+      for (int s = 0; s < n; ++s)
+        if (src[s] != s) pool_score[r0 + s] = ps[s], pool_len[r0 + s] = pl[s];
+      pool_n[b] = n;
+    }
+    open_[b] = op;
+    alive[b] = op && any_open_cand;
+    dirty = changed ? n : 0;
+  }
+  __syncthreads();
+  // ---- gather the parents' prefixes, append
+  const int n_h = p + 2, n_a = p + 1;
+  for (int i = tid; i < K * n_h; i += 256) {
+    const int q = i / n_h, c = i % n_h;
+    hyp_out[(r0 + q) * ld + c] = c == p + 1 ? sel_cls[q] : hyp_in[(r0 + sel_par[q]) * ld + c];
+  }
+  for (int i = tid; i < K * n_a; i += 256) {
+    const int q = i / n_a, c = i % n_a;
+    anc_out[(r0 + q) * ld + c] = c == p ? (int)r0 + sel_par[q] : anc_in[(r0 + sel_par[q]) * ld + c];
+  }
+  // ---- the pool's rows, from the last slot down: an old entry only moves to a higher slot, so its source is still whole
+  for (int s = dirty - 1; s >= 0; --s) {
+    const int from = src[s];
+    if (from == s) continue;                                        // uniform
+    int* dst = pool_hyp + (r0 + s) * ld;
+    if (from >= WB_NEW) {
+      const int id = top_i[from - WB_NEW];
+      const int* par = hyp_in + (r0 + (id >> 18)) * ld;
+      for (int c = tid; c < n_h; c += 256) dst[c] = c == p + 1 ? (id & 0x3ffff) : par[c];
+    } else {
+      const int* old = pool_hyp + (r0 + from) * ld;
+      const int n_old = min(max(pl_old[from], 0), ld);               // the caller's lengths: kept inside the row
+      for (int c = tid; c < n_old; c += 256) dst[c] = old[c];
+    }
+    __syncthreads();
+  }
+}
+
 }  // namespace
+
+extern "C" int f5e_whisper_beam_scratch(int B, int K, int V, unsigned long long* bytes_out_host) {
+  F5E_REQUIRE(B > 0 && B <= 65535 && K >= 1 && K <= WB_MAX_K && V >= 2 * K && V <= WB_MAX_V && bytes_out_host,
+              "whisper_beam_scratch: need 0 < B <= 65535, 1 <= K <= %d, 2 K <= V <= %d (B=%d K=%d V=%d)", WB_MAX_K, WB_MAX_V, B, K,
+              V);
+  *bytes_out_host = (unsigned long long)B * K * wb_chunks(V) * wb_rec(K) * sizeof(float);
+  return F5E_OK;
+}
+
+extern "C" int f5e_whisper_beam_step(hipStream_t st, const float* logits, long long ld_logits, const int* suppress, int n_sup,
+                                     const int* begin_suppress, int n_beg, float* score, const int* hyp_in, const int* anc_in,
+                                     int* hyp_out, int* anc_out, int ld, int* last, int* pool_hyp, int* pool_len,
+                                     float* pool_score, int* pool_n, int* open, int* alive, void* scratch,
+                                     unsigned long long scratch_bytes, int B, int K, int V, int p, int n0, int cap, int eos,
+                                     float length_penalty) {
+  F5E_REQUIRE(logits && score && hyp_in && anc_in && hyp_out && anc_out && last && pool_hyp && pool_len && pool_score && pool_n &&
+                  open && alive && scratch,
+              "whisper_beam_step: null operand");
+  F5E_REQUIRE(hyp_in != hyp_out && anc_in != anc_out, "whisper_beam_step: the hyp / anc tables are double-buffered (in != out)");
+  if (K < 1 || K > WB_MAX_K || V > WB_MAX_V) {
+    f5e_set_error("whisper_beam_step: built for 1 <= K <= %d and V <= %d (got K=%d V=%d)", WB_MAX_K, WB_MAX_V, K, V);
+    return F5E_ERR_UNSUPPORTED;
+  }
+  F5E_REQUIRE(B > 0 && B <= 65535 && V >= 2 * K && ld_logits >= V,
+              "whisper_beam_step: need 0 < B <= 65535, V >= 2 K and ld_logits >= V (B=%d K=%d V=%d)", B, K, V);
+  F5E_REQUIRE(n_sup >= 0 && n_beg >= 0 && (n_sup == 0 || suppress) && (n_beg == 0 || begin_suppress),
+              "whisper_beam_step: a suppression list without its pointer");
+  F5E_REQUIRE(eos >= 0 && eos < V, "whisper_beam_step: need 0 <= eos < V");
+  F5E_REQUIRE(n0 >= 1 && p >= n0 - 1 && ld >= p + 2 && cap <= ld,
+              "whisper_beam_step: need n0 >= 1, p >= n0 - 1, tables of at least p + 2 columns and cap <= ld (n0=%d p=%d ld=%d "
+              "cap=%d)", n0, p, ld, cap);
+  const int NCH = wb_chunks(V);
+  const unsigned long long need = (unsigned long long)B * K * NCH * wb_rec(K) * sizeof(float);
+  F5E_REQUIRE(scratch_bytes >= need && ((uintptr_t)scratch & 3) == 0,
+              "whisper_beam_step: scratch of %llu bytes, 4-byte aligned (f5e_whisper_beam_scratch); got %llu", need, scratch_bytes);
+  const int vec = ld_logits % 4 == 0 && ((uintptr_t)logits & 15) == 0;
+  hipLaunchKernelGGL(beam_chunk_kernel, dim3((unsigned)(B * K), (unsigned)NCH), dim3(256), 0, st, logits, ld_logits, suppress,
+                     n_sup, begin_suppress, p + 1 == n0 ? n_beg : 0, score, (float*)scratch, V, K, vec);
+  hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)B), dim3(256), 0, st, score, hyp_in, anc_in, hyp_out, anc_out, ld, last,
+                     pool_hyp, pool_len, pool_score, pool_n, open, alive, (float*)scratch, NCH, K, p, n0, cap, eos,
+                     length_penalty);
+  F5E_LAUNCH_CHECK("whisper_beam_step");
+  return F5E_OK;
+}
 
 extern "C" int f5e_whisper_logmel_partials(int B, int T, unsigned long long* floats_out_host) {
   F5E_REQUIRE(B > 0 && T > 0 && floats_out_host, "whisper_logmel_partials: bad arguments");

@@ -5,10 +5,15 @@
     python -m f5e_tts_amd.eval.eval_wer --gen_wav_dir D --metalst F --lang en|zh --asr_model M --asr_config C --asr_dict T
                                         [--mode ctc_greedy_search|ctc_prefix_beam_search|attention_rescoring]
     python -m f5e_tts_amd.eval.eval_wer --gen_wav_dir D --metalst F --lang en --asr whisper --whisper_dir W [--language english]
+                                        [--whisper_beam 5]
 
 ``--asr whisper`` is the reference's English recogniser of the voice-conversion and LibriSpeech evaluations
 (``run_asr_wer_whisper_large_v3``, eval/utils_eval.py:631-712: whisper-large-v3, greedy, prompt ``english / transcribe``) on the
 device (eval/whisper.py), with that function's own clean-up (``normalize_whisper_en``) in place of ``normalize``.
+``--whisper_beam N`` (default 1 = greedy) searches with N beams instead: the setting of the reference's headline English WER
+(``run_asr_wer``, eval/utils_eval.py:517-526, ``beam_size=5``), here with the semantics of ``transformers``'
+``generate(num_beams=N)`` -- K open rows and a length-normalised pool of finished hypotheses -- not CTranslate2's.
+``--beam_size`` stays the wenet flag; the Whisper recogniser ignores it.
 
 Host code.  Deviations from the reference, parity unpinned (``jiwer``, ``zhon`` and ``zhconv`` are not dependencies here):
   * punctuation is ``string.punctuation`` plus every character of Unicode category P* (the reference: ``zhon.hanzi.punctuation
@@ -167,8 +172,7 @@ def run_asr_wer(items: Iterable[Tuple[str, str, str]], aligner, lang: str, mode:
     return results
 
 
-def main(argv=None, aligner=None) -> float:
-    from .eval_sim import get_test_set
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="WER of generated wavs against their texts on the project's recogniser")
     ap.add_argument("--metalst", required=True, help="utt|prompt_text|prompt_wav|gt_text per line")
     ap.add_argument("--gen_wav_dir", required=True)
@@ -178,6 +182,9 @@ def main(argv=None, aligner=None) -> float:
     ap.add_argument("--whisper_dir", default=None, help="--asr whisper: a local whisper-large-v3 directory (config.json, "
                     "generation_config.json, model.safetensors, vocab.json, added_tokens.json)")
     ap.add_argument("--language", default="english", help="--asr whisper: the language token of the forced prompt")
+    ap.add_argument("--whisper_beam", type=int, default=1,
+                    help="--asr whisper: 1 = greedy (run_asr_wer_whisper_large_v3); N > 1 = the pooled beam search of "
+                         "generate(num_beams=N) (--beam_size is the wenet flag and does not reach Whisper)")
     ap.add_argument("--asr_model", default=None, help="wenet conformer checkpoint (CTC head; decoder for rescoring)")
     ap.add_argument("--asr_config", default=None, help="its train.yaml (input_layer conv2d / conv2d4 / conv2d6 / conv2d8)")
     ap.add_argument("--asr_dict", default=None, help="its `token id` symbol table")
@@ -186,6 +193,12 @@ def main(argv=None, aligner=None) -> float:
     ap.add_argument("--beam_size", type=int, default=10)
     ap.add_argument("--out", default=None, help="per-utterance JSON (default: <gen_wav_dir>/_wer_results.json)")
     ap.add_argument("--device", default="cuda")
+    return ap
+
+
+def main(argv=None, aligner=None) -> float:
+    from .eval_sim import get_test_set
+    ap = build_parser()
     args = ap.parse_args(argv)
     if aligner is None:
         need = ("whisper_dir",) if args.asr == "whisper" else ("asr_model", "asr_config", "asr_dict")
@@ -197,7 +210,7 @@ def main(argv=None, aligner=None) -> float:
         raise SystemExit(f"{args.metalst}: no utterance has a generated wav under {args.gen_wav_dir}")
     if aligner is None and args.asr == "whisper":
         from .whisper import WhisperRecognizer
-        aligner = WhisperRecognizer(args.whisper_dir, args.device, args.language)
+        aligner = WhisperRecognizer(args.whisper_dir, args.device, args.language, beam_size=args.whisper_beam)
     elif aligner is None:
         from ..ppg.ctc_align import CTCAligner
         aligner = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, args.device, asr=True,

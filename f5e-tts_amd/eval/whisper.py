@@ -1,7 +1,9 @@
 """Whisper on the device: the recogniser the reference loads through ``transformers`` -- ``openai/whisper-large-v3-turbo`` to
 transcribe a prompt without text (infer/utils_infer.py:148-179) and ``whisper-large-v3`` with the forced prompt
-``english / transcribe`` for the English WER (eval/utils_eval.py:631-672).  Greedy decoding, fp32, eval mode, no CPU path:
-f5e_whisper_logmel, f5e_cross_attn_decode_f32 and f5e_greedy_pick (csrc/whisper.hip) plus f5e_im2col, f5e_gemm_f32, f5e_layernorm,
+``english / transcribe`` for the English WER (eval/utils_eval.py:631-672).  Greedy decoding, or with ``beam_size > 1`` the pooled
+beam search of ``transformers``' ``generate(num_beams=K)`` (what eval/utils_eval.py:517-526 asks of its recogniser with
+``beam_size=5``); fp32, eval mode, no CPU path: f5e_whisper_logmel, f5e_cross_attn_decode_f32, f5e_greedy_pick and
+f5e_whisper_beam_step (csrc/whisper.hip) plus f5e_im2col, f5e_gemm_f32, f5e_layernorm,
 f5e_mha_f32, f5e_attn_decode_f32 and f5e_text_gather.  The sub-modules only HOLD the weights, under the Hugging Face
 parameter names, so ``load_state_dict`` takes a ``WhisperForConditionalGeneration`` state dict:
 
@@ -13,8 +15,8 @@ parameter names, so ``load_state_dict`` takes a ``WhisperForConditionalGeneratio
     .encoder_attn_layer_norm.*, .fc1.*, .fc2.*, .final_layer_norm.*, model.decoder.layer_norm.*
     (proj_out.weight is tied to model.decoder.embed_tokens.weight: accepted and dropped)
 
-Out of scope: beam search and temperature fallback, timestamps, long-form chunking, language detection (``language`` is
-required), bf16 / fp16 weights (fp16 checkpoints are widened), a graph-captured step.
+Out of scope: temperature fallback, timestamp rules, long-form chunking, language detection (``language`` is required), patience,
+CTranslate2's exact search, bf16 / fp16 weights (fp16 checkpoints are widened), a graph-captured step.
 
 Ragged batches: samples at or beyond ``lens[b]`` count as zero, and the row is zero-padded to the chunk length as the feature
 extractor does; Whisper attends those frames, and so does this.  Row b of a batch equals its own B = 1 run."""
@@ -468,8 +470,10 @@ class Whisper(nn.Module):
         return dict(x=z(R, 1, D), xn=z(R, D), qkv=z(R, 3 * D), ao=z(R, D), q=z(R, D), ff=z(R, cfg.decoder_ffn_dim),
                     logits=z(R, Vp)[:, :V], caches=[(z(R, Umax, D), z(R, Umax, D)) for _ in range(cfg.decoder_layers)])
 
-    def _dec_step(self, st: dict, kv: List[Tuple[Tensor, Tensor]], last: Tensor, p: int, want_logits: bool) -> Optional[Tensor]:
-        """Feeds the tokens ``last`` i32 [R] at position p through the cached decoder; -> logits f32 [R, V] of position p + 1."""
+    def _dec_step(self, st: dict, kv: List[Tuple[Tensor, Tensor]], last: Tensor, p: int, want_logits: bool,
+                  anc: Optional[Tensor] = None) -> Optional[Tensor]:
+        """Feeds the tokens ``last`` i32 [R] at position p through the cached decoder; -> logits f32 [R, V] of position p + 1.
+        ``anc`` i32 [R, >= p]: the beam's ancestry table, followed by every layer (None: a row reads its own cache)."""
         cfg, fd = self.cfg, self._fold()
         D, H = cfg.d_model, cfg.decoder_attention_heads
         scale = (D // H) ** -0.5
@@ -480,7 +484,7 @@ class Whisper(nn.Module):
         for lp, (kc, vc), (K, Vv) in zip(fd["dec"], st["caches"], kv):
             ops.layernorm(x, xn, *lp["ln1"], eps=1e-5)
             ops.gemm_f32(xn, lp["sa"]["w_qkv"], lp["sa"]["b_qkv"], out=qkv)
-            ops.attn_decode_f32(qkv, kc, vc, p, H, scale, out=ao)
+            ops.attn_decode_f32(qkv, kc, vc, p, H, scale, anc=anc, out=ao)
             ops.gemm_f32(ao, lp["sa"]["w_o"], lp["sa"]["b_o"], out=x, addend=x)
             ops.layernorm(x, xn, *lp["ln2"], eps=1e-5)
             ops.gemm_f32(xn, lp["ca"]["w_q"], lp["ca"]["b_q"], out=q)
@@ -526,7 +530,9 @@ class Whisper(nn.Module):
 
     @torch.no_grad()
     def generate_from_kv(self, kv: List[Tuple[Tensor, Tensor]], prompt: Sequence[int], max_new_tokens: Optional[int] = None,
-                         sync_every: int = 8) -> Tuple[Tensor, Tensor]:
+                         sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0, return_beams: bool = False):
+        if int(beam_size) != 1 or return_beams:
+            return self._beam_from_kv(kv, prompt, max_new_tokens, sync_every, int(beam_size), float(length_penalty), return_beams)
         cfg, fd = self.cfg, self._fold()
         B = kv[0][0].shape[0]
         dev = kv[0][0].device
@@ -558,22 +564,84 @@ class Whisper(nn.Module):
         return tokens, (first + n0).to(I32)
 
     @torch.no_grad()
+    def _beam_from_kv(self, kv: List[Tuple[Tensor, Tensor]], prompt: Sequence[int], max_new_tokens: Optional[int], sync_every: int,
+                      K: int, length_penalty: float, return_beams: bool):
+        """The pooled beam search (f5e_whisper_beam_step has the rules): B * K rows, row b K + i = open hypothesis i of utterance
+        b.  Every layer's self-attention follows the ancestry table, the cross-attention reads an utterance's keys once for its
+        K rows, and no cache row ever moves.  The prompt goes through the same step without a pick (the K rows of an utterance
+        are equal until the first pick).  Caches: K x the greedy figure, sized by the prompt + ``max_new_tokens`` when given."""
+        cfg = self.cfg
+        V, eos, n0 = cfg.vocab_size, cfg.eos_token_id, len(prompt)
+        banned = {t for t in tuple(cfg.suppress_tokens) + tuple(cfg.begin_suppress_tokens) if 0 <= t < V}
+        if not 1 <= K <= 16:
+            raise _C.F5EError(f"Whisper.generate: beam_size must lie in 1 .. 16 (got {K})")
+        if V - len(banned) < 2 * K:
+            raise _C.F5EError(f"Whisper.generate: beam_size = {K} needs {2 * K} classes that the first step does not suppress; "
+                              f"{V} - {len(banned)} are left")
+        fd = self._fold()
+        B, dev = kv[0][0].shape[0], kv[0][0].device
+        R = B * K
+        Umax = cfg.max_target_positions if max_new_tokens is None else min(cfg.max_target_positions, n0 + int(max_new_tokens))
+        if n0 < 1 or n0 >= Umax or sync_every < 1 or R > 65535:
+            raise _C.F5EError(f"Whisper.generate: a prompt of {n0} tokens leaves no room below {Umax} positions (or sync_every < 1, "
+                              f"or more than 65535 rows)")
+        hyp = [torch.full((R, Umax), eos, dtype=I32, device=dev) for _ in range(2)]
+        anc = [torch.arange(R, dtype=I32, device=dev)[:, None].repeat(1, Umax) for _ in range(2)]   # prompt: a row's own cache
+        for h in hyp:
+            h[:, :n0] = torch.tensor(list(prompt), dtype=I32, device=dev)
+        last = hyp[0][:, 0].clone()
+        score = torch.full((B, K), -math.inf, dtype=F32, device=dev)
+        score[:, 0] = 0.0
+        score = score.view(R)
+        pool_hyp = torch.full((B, K, Umax), eos, dtype=I32, device=dev)
+        pool_len = torch.zeros(B, K, dtype=I32, device=dev)
+        pool_score = torch.full((B, K), -math.inf, dtype=F32, device=dev)
+        pool_n, open_, alive = (torch.full((B,), v, dtype=I32, device=dev) for v in (0, 1, 1))
+        scratch = torch.empty(max(ops.whisper_beam_scratch(B, K, V), 4), dtype=torch.uint8, device=dev)
+        st = self._dec_state(R, Umax, dev)
+        cur = 0
+        for p in range(Umax - 1):
+            forced = p + 1 < n0
+            logits = self._dec_step(st, kv, last, p, not forced, anc=anc[cur])
+            if forced:
+                last.copy_(hyp[0][:, p + 1])
+                continue
+            ops.whisper_beam_step(logits, score, hyp[cur], anc[cur], hyp[1 - cur], anc[1 - cur], last, pool_hyp, pool_len,
+                                  pool_score, pool_n, open_, alive, p, n0, Umax, eos, K, suppress=fd["suppress"],
+                                  begin_suppress=fd["begin_suppress"], length_penalty=length_penalty, scratch=scratch)
+            cur = 1 - cur
+            if (p + 2 - n0) % sync_every == 0 and int(alive.sum().item()) == 0:
+                break
+        # columns at or beyond an entry's length are not defined by the step: eos there, as in the greedy layout
+        col = torch.arange(Umax, device=dev)
+        beams = torch.where(col[None, None, :] < pool_len[:, :, None], pool_hyp, torch.full_like(pool_hyp, eos))
+        best = (beams[:, 0].contiguous(), pool_len[:, 0].contiguous())
+        return best + ((beams, pool_len, pool_score),) if return_beams else best
+
+    @torch.no_grad()
     def generate(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe",
-                 max_new_tokens: Optional[int] = None, sync_every: int = 8) -> Tuple[Tensor, Tensor]:
-        """Greedy recognition of B utterances, one row each: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row ->
-        (tokens i32 [B, U] starting with the prompt, eos from a row's end on; n i32 [B] = tokens of every row, its closing eos
-        included when it ended by itself).  The host reads the alive count every ``sync_every`` steps; the result does not
-        depend on it.  The bound is ``max_target_positions`` (or the prompt + ``max_new_tokens``)."""
+                 max_new_tokens: Optional[int] = None, sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0,
+                 return_beams: bool = False):
+        """Recognition of B utterances: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> (tokens i32 [B, U] starting
+        with the prompt, eos from a row's end on; n i32 [B] = tokens of every row, its closing eos included when it ended by
+        itself).  The host reads the alive count every ``sync_every`` steps; the result does not depend on it.  The bound is
+        ``max_target_positions`` (or the prompt + ``max_new_tokens``).  ``beam_size`` 1: greedy, one row per utterance.
+        ``beam_size`` K > 1: the pooled beam search of ``transformers``' ``generate(num_beams=K, length_penalty=...)``, K rows
+        per utterance; the best finished hypothesis is returned in the same layout, and with ``return_beams`` a third item
+        (pool tokens i32 [B, K, U], lens i32 [B, K], scores f32 [B, K] = sum of log-probabilities / generated length **
+        length_penalty, best first)."""
         prompt = self.prompt_ids(language, task)
-        return self.generate_from_kv(self.encode(wav, lens), prompt, max_new_tokens, sync_every)
+        return self.generate_from_kv(self.encode(wav, lens), prompt, max_new_tokens, sync_every, beam_size, length_penalty,
+                                     return_beams)
 
 
 class WhisperRecognizer:
     """The duck type ``eval_wer.run_asr_wer`` and ``preprocess_ref_audio_text`` take: ``transcribe(wav_or_path, sr) -> str``."""
 
-    def __init__(self, path: str, device="cuda", language: str = "en"):
+    def __init__(self, path: str, device="cuda", language: str = "en", beam_size: int = 1):
         self.device = torch.device(device)
         self.language = language
+        self.beam_size = int(beam_size)      # the constructor's alone: transcribe() ignores the wenet flag of the same name
         self.model = Whisper.from_pretrained_dir(path).to(self.device)
         self.model.prompt_ids(language)                      # a language the checkpoint does not know fails here, not per file
         self._warned = set()
@@ -600,5 +668,5 @@ class WhisperRecognizer:
                 warnings.warn(f"WhisperRecognizer: {name or 'audio'} is {audio.shape[-1] / SAMPLE_RATE:.1f} s long; only the first "
                               f"{limit / SAMPLE_RATE:.0f} s are transcribed (long-form chunking is out of scope)")
             audio = audio[:, :limit]
-        tokens, n = self.model.generate(audio.contiguous(), None, self.language)
+        tokens, n = self.model.generate(audio.contiguous(), None, self.language, beam_size=self.beam_size)
         return self.model.decode_ids(tokens[0, :int(n[0])].tolist()).strip()

@@ -71,6 +71,7 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--whisper_dir", type=str, help="a local whisper-large-v3(-turbo) directory: a voice whose ref_text is empty "
                                                    "is transcribed with it (without it an empty ref_text is an error)")
     p.add_argument("--ref_language", type=str, default="english", help="--whisper_dir: the language spoken in the reference audio")
+    p.add_argument("--whisper_beam", type=int, default=1, help="--whisper_dir: 1 = greedy; N > 1 = beam search with N beams")
     return p
 
 
@@ -221,7 +222,7 @@ def main(argv=None):
     transcriber = None
     if args.whisper_dir and any(not v["ref_text"].strip() for v in voices.values()):
         from ..eval.whisper import WhisperRecognizer
-        transcriber = WhisperRecognizer(args.whisper_dir, s["device"], args.ref_language)
+        transcriber = WhisperRecognizer(args.whisper_dir, s["device"], args.ref_language, beam_size=args.whisper_beam)
     for v in voices.values():   # reference infer_cli.py:297-303
         v["ref_audio"], v["ref_text"] = U.preprocess_ref_audio_text(v["ref_audio"], v["ref_text"], transcriber=transcriber)
     segments = []

@@ -1625,6 +1625,61 @@ def greedy_pick(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, aliv
     return last
 
 
+def whisper_beam_scratch(B: int, beam: int, V: int) -> int:
+    """Scratch bytes of ``whisper_beam_step`` for B utterances of ``beam`` rows and V classes (host arithmetic)."""
+    n = C.c_ulonglong(0)
+    check(lib().f5e_whisper_beam_scratch(int(B), int(beam), int(V), C.byref(n)), "f5e_whisper_beam_scratch")
+    return int(n.value)
+
+
+def whisper_beam_step(logits: Tensor, score: Tensor, hyp_in: Tensor, anc_in: Tensor, hyp_out: Tensor, anc_out: Tensor, last: Tensor,
+                      pool_hyp: Tensor, pool_len: Tensor, pool_score: Tensor, pool_n: Tensor, open_: Tensor, alive: Tensor,
+                      p: int, n0: int, cap: int, eos: int, beam: int, *, V: Optional[int] = None,
+                      suppress: Optional[Tensor] = None, begin_suppress: Optional[Tensor] = None, length_penalty: float = 1.0,
+                      scratch: Optional[Tensor] = None):
+    """One step of Whisper's pooled beam search (f5e_whisper_beam_step, where the rules are written out): logits f32
+    [B * beam, >= V] (row-strided view, only read), score f32 / last i32 [B * beam], hyp / anc tables contiguous i32 [B * beam, ld]
+    (double-buffered), pool_hyp i32 [B, beam, ld], pool_len i32 / pool_score f32 [B, beam], pool_n / open_ / alive i32 [B],
+    scratch u8 [>= whisper_beam_scratch(B, beam, V)] (allocated when None).  Limits on beam, V, p, n0, cap and eos are the
+    library's."""
+    if logits.ndim != 2 or hyp_in.ndim != 2:
+        raise _C.F5EError("whisper_beam_step: logits [B * beam, >= V] and tables [B * beam, ld]; there is no CPU path")
+    R, beam = logits.shape[0], int(beam)
+    V = logits.shape[1] if V is None else int(V)
+    if beam < 1 or R % beam:
+        raise _C.F5EError(f"whisper_beam_step: beam = {beam} must be at least 1 and divide the {R} rows")
+    B, ld = R // beam, hyp_in.shape[1]
+    if V > logits.shape[1]:
+        raise _C.F5EError(f"whisper_beam_step: V = {V} exceeds the {logits.shape[1]} columns of logits")
+    lp, ldl = _rows(logits, (F32,), "whisper_beam_step: logits", max(V, 1), vec=1)
+    for t, nm in ((hyp_in, "hyp_in"), (anc_in, "anc_in"), (hyp_out, "hyp_out"), (anc_out, "anc_out")):
+        if t.dtype != I32 or tuple(t.shape) != (R, ld) or not t.is_contiguous():
+            raise _C.F5EError(f"whisper_beam_step: {nm} must be a contiguous i32 tensor [{R}, {ld}]")
+    if pool_hyp.dtype != I32 or tuple(pool_hyp.shape) != (B, beam, ld) or not pool_hyp.is_contiguous():
+        raise _C.F5EError(f"whisper_beam_step: pool_hyp must be a contiguous i32 tensor [{B}, {beam}, {ld}]")
+    if hyp_in.data_ptr() == hyp_out.data_ptr() or anc_in.data_ptr() == anc_out.data_ptr():
+        raise _C.F5EError("whisper_beam_step: the tables are double-buffered: in and out must differ")
+    if score.shape != (R,) or last.shape != (R,) or tuple(pool_len.shape) != (B, beam) or tuple(pool_score.shape) != (B, beam) \
+            or pool_n.shape != (B,) or open_.shape != (B,) or alive.shape != (B,) or not pool_len.is_contiguous() \
+            or not pool_score.is_contiguous():
+        raise _C.F5EError(f"whisper_beam_step: score / last [{R}], pool_len / pool_score [{B}, {beam}], pool_n / open / alive [{B}]")
+    require_device()
+    if scratch is None:
+        scratch = torch.empty(max(whisper_beam_scratch(B, beam, V), 4), dtype=torch.uint8, device=logits.device)
+    if scratch.dtype != torch.uint8 or not scratch.is_contiguous():
+        raise _C.F5EError("whisper_beam_step: scratch must be a contiguous uint8 tensor")
+    check(lib().f5e_whisper_beam_step(_stream(), lp, ldl, _p(suppress, I32, "suppress"),
+                                      suppress.numel() if suppress is not None else 0, _p(begin_suppress, I32, "begin_suppress"),
+                                      begin_suppress.numel() if begin_suppress is not None else 0, _p(score, F32, "score"),
+                                      _p(hyp_in, I32, "hyp_in"), _p(anc_in, I32, "anc_in"), _p(hyp_out, I32, "hyp_out"),
+                                      _p(anc_out, I32, "anc_out"), ld, _p(last, I32, "last"), _p(pool_hyp, I32, "pool_hyp"),
+                                      _p(pool_len, I32, "pool_len"), _p(pool_score, F32, "pool_score"), _p(pool_n, I32, "pool_n"),
+                                      _p(open_, I32, "open"), _p(alive, I32, "alive"), C.c_void_p(scratch.data_ptr()),
+                                      scratch.numel(), B, beam, V, int(p), int(n0), int(cap), int(eos), float(length_penalty)),
+          "f5e_whisper_beam_step")
+    return last
+
+
 # ---- UTMOS (csrc/utmos.hip) ----
 
 LSTM_MAX_H, LSTM_MAX_B, LSTM_MAX_T = 1024, 16, 4096

@@ -763,6 +763,49 @@ F5E_API int f5e_greedy_pick(f5e_stream st, const float* logits, long long ld, co
                     const int* begin_suppress, int n_beg, int first_step, int* tokens, int ld_tok, int* last, int* done,
                     int* alive, int R, int V, int p, int eos);
 
+/* One step of Whisper's beam search for B utterances of K rows each (r = b K + i): transformers 5.15.0
+ * GenerationMixin._beam_search with early_stopping = False and do_sample = False, its -1e9 sentinels replaced by flags.  K open
+ * rows per utterance and a separate pool of at most K finished hypotheses ranked by score / length ** length_penalty (the wenet
+ * rule of f5e_beam_step keeps finished rows INSIDE the beam instead).  n0 prompt tokens; step p feeds position p and chooses
+ * column p + 1; cap = the largest total length.
+ *   logits  f32 [B*K][ld_logits >= V], only read, ONCE per step: the raw decoder outputs of position p
+ *   suppress i32 [n_sup], begin_suppress i32 [n_beg]: as f5e_greedy_pick; begin_suppress counts iff p + 1 == n0
+ *   score   f32 [B*K] in/out: accumulated log-probabilities of the open rows.  Start: 0, -inf, ..., -inf per utterance
+ *   hyp_in / anc_in  i32 [B*K][ld] the tables before the step, hyp_out / anc_out after it: DIFFERENT buffers, as f5e_beam_step
+ *   last    i32 [B*K] out: hyp_out column p + 1, contiguous for the next embedding
+ *   pool_hyp i32 [B][K][ld], pool_len i32 [B][K], pool_score f32 [B][K], pool_n i32 [B] (start 0): the pool, in/out, best
+ *           first; entry s < pool_n[b] holds pool_len tokens (columns at or beyond are not defined)
+ *   open    i32 [B] in/out, start 1: the utterance's pool still accepts.  alive i32 [B] out (rule 7)
+ *   scratch f5e_whisper_beam_scratch(B, K, V) bytes, 4-byte aligned (no need to clear it)
+ * Rules, per utterance:
+ *  1. logp = (x - max) - log(sum exp(x - max)) over ALL V classes of the raw row (fp32); only then the classes of suppress (and
+ *     of begin_suppress at the first step) become -inf: the normaliser includes them.
+ *  2. Candidate value = score[r] + logp in fp32.
+ *  3. The 2K largest FINITE candidates of the utterance's K V, in descending order; ties: lower row, then lower class.  A
+ *     candidate is hit iff its class is eos or p + 2 >= cap.
+ *  4. New rows 0..K-1 = the first K candidates that are not hit, in order: the parent's hyp columns 0..p plus the class at
+ *     column p + 1, the parent's anc columns < p plus the parent's GLOBAL row at column p, score = the value, last = the class.
+ *     Rows beyond the candidates there are keep their own prefix, get eos at column p + 1 and score -inf.
+ *  5. If open[b]: every hit candidate AMONG THE FIRST K of the 2K enters the pool with score value / (p + 2 - n0) **
+ *     length_penalty, its p + 2 tokens and length p + 2.  The pool keeps the K best in descending order; an old entry goes
+ *     before a newcomer of equal score, newcomers keep candidate order.  Hit candidates ranked K..2K-1 neither run nor enter.
+ *  6. If the pool holds K entries: open[b] &= score_new[row 0] / (p + 2 - n0) ** length_penalty > pool_score[K-1].
+ *  7. alive[b] = open[b] && not every candidate was hit.
+ * A closed utterance keeps updating its rows; its pool is frozen.  The answer is pool entry 0.
+ * Two launches.  The first, one workgroup per (row, chunk of 8192 classes), stages the chunk in LDS and leaves its maximum, its
+ * sum of exponentials and its 2K largest unsuppressed (value, class) in scratch; the second, one workgroup per utterance, folds
+ * the chunks in ascending order, selects and applies the rules.  No float atomics; the result is deterministic.
+ * Containment: columns > p + 1 of hyp_out, columns > p of anc_out, the input tables, the logits, pool slots that do not change
+ * and scratch beyond the queried size are untouched.
+ * Limits: 1 <= K <= 16 and V <= 262144 (else F5E_ERR_UNSUPPORTED), 2K <= V, 0 <= eos < V, n0 >= 1, n0 - 1 <= p, ld >= p + 2,
+ * cap <= ld, B <= 65535.  No allocation, no synchronisation. */
+F5E_API int f5e_whisper_beam_scratch(int B, int K, int V, unsigned long long* bytes_out_host);
+F5E_API int f5e_whisper_beam_step(f5e_stream st, const float* logits, long long ld_logits, const int* suppress, int n_sup,
+                          const int* begin_suppress, int n_beg, float* score, const int* hyp_in, const int* anc_in, int* hyp_out,
+                          int* anc_out, int ld, int* last, int* pool_hyp, int* pool_len, float* pool_score, int* pool_n,
+                          int* open, int* alive, void* scratch, unsigned long long scratch_bytes, int B, int K, int V, int p,
+                          int n0, int cap, int eos, float length_penalty);
+
 /* ---------------------------------------------------------------- UTMOS (csrc/utmos.hip) ---------------------- */
 /* The UTMOS predictor (utmos22_strong, reference eval/eval_utmos.py): a wav2vec2-base upstream (group-norm feature extractor,
  * post-LayerNorm encoder), a BiLSTM over its frames and a per-frame score averaged per utterance.  The strided convolutions 1-6,

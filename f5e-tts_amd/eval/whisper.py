@@ -15,8 +15,13 @@ parameter names, so ``load_state_dict`` takes a ``WhisperForConditionalGeneratio
     .encoder_attn_layer_norm.*, .fc1.*, .fc2.*, .final_layer_norm.*, model.decoder.layer_norm.*
     (proj_out.weight is tied to model.decoder.embed_tokens.weight: accepted and dropped)
 
-Out of scope: temperature fallback, timestamp rules, long-form chunking, language detection (``language`` is required), patience,
-CTranslate2's exact search, bf16 / fp16 weights (fp16 checkpoints are widened), a graph-captured step.
+Token and word times (``token_timestamps``, ``generate(return_token_timestamps=True)``, ``WhisperRecognizer.transcribe_words`` /
+``align``): the alignment heads' cross-attention, normalised, median-filtered and warped (f5e_cross_attn_probs_f32,
+f5e_dtw_cost_f32, f5e_dtw_path; csrc/whisper_align.hip).
+
+Out of scope: temperature fallback, segment timestamp tokens and their logit rules, long-form chunking, language detection
+(``language`` is required), patience, CTranslate2's exact search, bf16 / fp16 weights (fp16 checkpoints are widened), a
+graph-captured step.
 
 Ragged batches: samples at or beyond ``lens[b]`` count as zero, and the row is zero-padded to the chunk length as the feature
 extractor does; Whisper attends those frames, and so does this.  Row b of a batch equals its own B = 1 run."""
@@ -71,16 +76,23 @@ class WhisperConfig:
     lang_to_id: Dict[str, int] = field(default_factory=dict)
     task_to_id: Dict[str, int] = field(default_factory=dict)
     no_timestamps_token_id: Optional[int] = None
+    alignment_heads: Tuple[Tuple[int, int], ...] = ()       # (decoder layer, head) pairs; empty: no token timestamps
+    median_filter_width: int = 7                            # config.json
 
     @classmethod
     def from_dicts(cls, config: dict, generation: Optional[dict] = None) -> "WhisperConfig":
         names = {f for f in cls.__dataclass_fields__}
         kw = {k: v for k, v in config.items() if k in names and v is not None}
         for k, v in (generation or {}).items():
-            if k in ("suppress_tokens", "begin_suppress_tokens", "lang_to_id", "task_to_id", "no_timestamps_token_id") and v is not None:
+            if k in ("suppress_tokens", "begin_suppress_tokens", "lang_to_id", "task_to_id", "no_timestamps_token_id",
+                     "alignment_heads") and v is not None:
                 kw[k] = v
         for k in ("suppress_tokens", "begin_suppress_tokens"):
             kw[k] = tuple(int(t) for t in kw.get(k) or ())
+        heads = kw.get("alignment_heads") or ()
+        if any(not isinstance(h, (list, tuple)) or len(h) != 2 for h in heads):
+            raise _C.F5EError(f"Whisper: alignment_heads must be [layer, head] pairs (got {heads!r})")
+        kw["alignment_heads"] = tuple((int(l), int(h)) for l, h in heads)
         eos = kw.get("eos_token_id")
         if isinstance(eos, (list, tuple)):
             kw["eos_token_id"] = int(eos[0])
@@ -107,6 +119,12 @@ class WhisperConfig:
             refuse("max_target_positions", "2 .. 4096")
         if not 0 <= self.eos_token_id < self.vocab_size or not 0 <= self.decoder_start_token_id < self.vocab_size:
             refuse("eos_token_id", "eos and decoder_start_token_id must be ids of the vocabulary")
+        if len(self.alignment_heads) > 64 or any(not (0 <= l < self.decoder_layers and 0 <= h < self.decoder_attention_heads)
+                                                 for l, h in self.alignment_heads):
+            refuse("alignment_heads", f"at most 64 (layer, head) pairs with layer < {self.decoder_layers} and head < "
+                                      f"{self.decoder_attention_heads}")
+        if not 1 <= self.median_filter_width <= 15 or self.median_filter_width % 2 == 0:
+            refuse("median_filter_width", "an odd width of 1 .. 15")
 
 
 # ---- host constants of the front-end (float64, rounded once) ------------------------------------------------------------------
@@ -185,6 +203,67 @@ def decode_pieces(id_to_piece: Dict[int, str], first_special: int, ids: Sequence
         raw.extend(_U2B[c] for c in piece if c in _U2B)
     out.append(raw.decode("utf-8", errors="replace"))
     return "".join(out)
+
+
+# ---- tokens -> words (transformers' tokenization_whisper.py: _combine_tokens_into_words) ----------------------------------------
+UNSPACED_LANGUAGES = {"zh", "ja", "th", "lo", "my", "yue", "chinese", "japanese", "thai", "lao", "myanmar", "cantonese"}
+PREPEND_PUNCTUATIONS = "\"'“¡¿([{-"
+APPEND_PUNCTUATIONS = "\"'.。,，!！?？:：”)]}、"
+_ASCII_PUNCTUATION = "!\"#$%&'()*+,-./:;<=>?@[\\]^_`{|}~"
+
+
+def group_tokens(id_to_piece: Dict[int, str], first_special: int, ids: Sequence[int], language: Optional[str] = None,
+                 special_from: Optional[int] = None) -> Tuple[List[str], List[List[int]]]:
+    """-> (words, token indices per word), the reference's grouping rules:
+    1. cut wherever the tokens so far decode to whole unicode characters (specials spelled out): a character split across tokens
+       stays in one piece; a replacement character that the full text has at that place too counts as whole;
+    2. unless the language is written without spaces (zh / ja / th / lo / my / yue), a piece joins the word before it unless it
+       is a special (first id >= ``special_from``, the eos id), starts with a space, is ASCII punctuation, or is the first;
+    3. a word that starts with a space and is otherwise a prepend mark ("'([{- ...) joins the word after it (right to left), then a
+       word that is an append mark (.,!?:)]} ...) joins a word before it that does not end with a space (left to right)."""
+    ids = [int(i) for i in ids]
+    special_from = first_special if special_from is None else special_from
+
+    def dec(tok):
+        return decode_pieces(id_to_piece, first_special, tok, skip_special_tokens=False)
+    full, bad = dec(ids), "�"
+    words, index, cur, offset = [], [], [], 0
+    for k in range(len(ids)):
+        cur.append(k)
+        text = dec([ids[i] for i in cur])
+        at = offset + text.index(bad) if bad in text else -1
+        if at < 0 or at >= len(full) or full[at] == bad:
+            words.append(text)
+            index.append(cur)
+            cur = []
+            offset += len(text)
+    if (language or "en").lower() not in UNSPACED_LANGUAGES:
+        pieces, words, index = list(zip(words, index)), [], []
+        for text, idx in pieces:
+            if ids[idx[0]] >= special_from or text.startswith(" ") or text.strip() in _ASCII_PUNCTUATION or not words:
+                words.append(text)
+                index.append(list(idx))
+            else:
+                words[-1] += text
+                index[-1].extend(idx)
+    i, j = len(words) - 2, len(words) - 1
+    while i >= 0:
+        if words[i].startswith(" ") and words[i].strip() in PREPEND_PUNCTUATIONS:
+            words[j], index[j] = words[i] + words[j], index[i] + index[j]
+            words[i], index[i] = "", []
+        else:
+            j = i
+        i -= 1
+    i, j = 0, 1
+    while j < len(words):
+        if not words[i].endswith(" ") and words[j] in APPEND_PUNCTUATIONS:
+            words[i], index[i] = words[i] + words[j], index[i] + index[j]
+            words[j], index[j] = "", []
+        else:
+            i = j
+        j += 1
+    keep = [k for k in range(len(words)) if words[k]]
+    return [words[k] for k in keep], [index[k] for k in keep]
 
 
 # ---- checkpoint reading (the safetensors container: u64 header length, JSON header, raw little-endian data) ---------------------
@@ -319,6 +398,24 @@ class Whisper(nn.Module):
             raise _C.F5EError("Whisper.decode_ids: no vocabulary is loaded (set_vocab / from_pretrained_dir with vocab.json)")
         return decode_pieces(self.id_to_piece, self.first_special, ids, skip_special_tokens)
 
+    def words_from_tokens(self, ids: Sequence[int], times: Sequence[float], language: Optional[str] = None
+                          ) -> List[Tuple[str, float, float]]:
+        """A hypothesis (prompt and closing eos included) and its token times -> [(word, start_s, end_s)] by ``group_tokens``;
+        specials are skipped.  A word starts at its first token's time and ends at the time of the token after its last one (the
+        next word's start; for the last word the closing token's time), or at its last token's time when nothing follows."""
+        if not self.id_to_piece:
+            raise _C.F5EError("Whisper.words_from_tokens: no vocabulary is loaded (set_vocab / from_pretrained_dir with vocab.json)")
+        ids, times = [int(i) for i in ids], [float(t) for t in times]
+        if len(times) != len(ids):
+            raise _C.F5EError(f"Whisper.words_from_tokens: {len(ids)} tokens need {len(ids)} times (got {len(times)})")
+        words, index = group_tokens(self.id_to_piece, self.first_special, ids, language, self.cfg.eos_token_id)
+        out = []
+        for word, idx in zip(words, index):
+            if ids[idx[0]] >= self.cfg.eos_token_id:
+                continue
+            out.append((word, times[idx[0]], times[min(idx[-1] + 1, len(ids) - 1)]))
+        return out
+
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
         sd = {k: v for k, v in state_dict.items() if k != "proj_out.weight"}       # tied to model.decoder.embed_tokens.weight
         self._folded = None
@@ -374,6 +471,17 @@ class Whisper(nn.Module):
             fd["dec"].append(d)
         fd["suppress"] = torch.tensor(list(cfg.suppress_tokens), dtype=I32, device=dev) if cfg.suppress_tokens else None
         fd["begin_suppress"] = torch.tensor(list(cfg.begin_suppress_tokens), dtype=I32, device=dev) if cfg.begin_suppress_tokens else None
+        # alignment heads, in the order of the list: layer -> [(first slot, heads i32 [k])], one entry per run of consecutive pairs
+        # of that layer (one f5e_cross_attn_probs_f32 launch each)
+        fd["align"] = {}
+        s = 0
+        while s < len(cfg.alignment_heads):
+            e = s
+            while e < len(cfg.alignment_heads) and cfg.alignment_heads[e][0] == cfg.alignment_heads[s][0]:
+                e += 1
+            heads = torch.tensor([h for _, h in cfg.alignment_heads[s:e]], dtype=I32, device=dev)
+            fd["align"].setdefault(cfg.alignment_heads[s][0], []).append((s, heads))
+            s = e
         self._folded = fd
         return fd
 
@@ -471,9 +579,11 @@ class Whisper(nn.Module):
                     logits=z(R, Vp)[:, :V], caches=[(z(R, Umax, D), z(R, Umax, D)) for _ in range(cfg.decoder_layers)])
 
     def _dec_step(self, st: dict, kv: List[Tuple[Tensor, Tensor]], last: Tensor, p: int, want_logits: bool,
-                  anc: Optional[Tensor] = None) -> Optional[Tensor]:
+                  anc: Optional[Tensor] = None, align: Optional[Tuple[Tensor, int, Tensor]] = None) -> Optional[Tensor]:
         """Feeds the tokens ``last`` i32 [R] at position p through the cached decoder; -> logits f32 [R, V] of position p + 1.
-        ``anc`` i32 [R, >= p]: the beam's ancestry table, followed by every layer (None: a row reads its own cache)."""
+        ``anc`` i32 [R, >= p]: the beam's ancestry table, followed by every layer (None: a row reads its own cache).
+        ``align`` = (probs f32 [R, heads, N, ld], t, m_len i32 [B]): the layers that own an alignment head also write those
+        heads' cross-attention probabilities of this position to probs[:, :, t, :m_len] (an extra launch; nothing else changes)."""
         cfg, fd = self.cfg, self._fold()
         D, H = cfg.d_model, cfg.decoder_attention_heads
         scale = (D // H) ** -0.5
@@ -481,7 +591,7 @@ class Whisper(nn.Module):
         x3, xn, qkv, ao, q, ff = st["x"], st["xn"], st["qkv"], st["ao"], st["q"], st["ff"]
         ops.text_gather(last.view(R, 1), fd["emb"], fd["dec_pos"][p:p + 1], None, x3)
         x = x3.view(R, D)
-        for lp, (kc, vc), (K, Vv) in zip(fd["dec"], st["caches"], kv):
+        for li, (lp, (kc, vc), (K, Vv)) in enumerate(zip(fd["dec"], st["caches"], kv)):
             ops.layernorm(x, xn, *lp["ln1"], eps=1e-5)
             ops.gemm_f32(xn, lp["sa"]["w_qkv"], lp["sa"]["b_qkv"], out=qkv)
             ops.attn_decode_f32(qkv, kc, vc, p, H, scale, anc=anc, out=ao)
@@ -489,6 +599,10 @@ class Whisper(nn.Module):
             ops.layernorm(x, xn, *lp["ln2"], eps=1e-5)
             ops.gemm_f32(xn, lp["ca"]["w_q"], lp["ca"]["b_q"], out=q)
             ops.cross_attn_decode_f32(q, K, Vv, H, scale, rows_per_utt=R // K.shape[0], out=ao)
+            if align is not None:
+                for s0, heads in fd["align"].get(li, ()):
+                    ops.cross_attn_probs_f32(q, K, heads, H, scale, align[0][:, s0:s0 + heads.shape[0], align[1]],
+                                             rows_per_utt=R // K.shape[0], m_len=align[2])
             ops.gemm_f32(ao, lp["ca"]["w_o"], lp["ca"]["b_o"], out=x, addend=x)
             ops.layernorm(x, xn, *lp["ln3"], eps=1e-5)
             ops.gemm_f32(xn, lp["w1"], lp["b1"], out=ff, act=ops.ACT_GELU_ERF)
@@ -528,9 +642,92 @@ class Whisper(nn.Module):
             raise _C.F5EError("Whisper: generation_config has no no_timestamps_token_id")
         return [cfg.decoder_start_token_id, cfg.lang_to_id[key], cfg.task_to_id[task], cfg.no_timestamps_token_id]
 
+    # ---- token timestamps (alignment heads and DTW) ------------------------------------------------------------------
+    @torch.no_grad()
+    def alignment_probs(self, kv: List[Tuple[Tensor, Tensor]], tokens: Tensor, n, frames, n0: int,
+                        include_last: bool = False) -> Tuple[Optional[Tensor], Tensor, Tensor]:
+        """The teacher-forced pass of ``token_timestamps``: -> (probs f32 [B, heads, N_cap, ld] or None when no row has a fed
+        position, n_rows i32 [B], m_len i32 [B]).  probs[b, s, t, :m_len[b]] for t < n_rows[b] is the cross-attention of alignment
+        head s for the token at position n0 + t, softmax over all encoder keys; everything else of the buffer is zero or
+        belongs to positions beyond the row's own.  One host read (n), to size the buffer by the longest hypothesis."""
+        cfg = self.cfg
+        if not cfg.alignment_heads:
+            raise _C.F5EError("Whisper.token_timestamps: this model has no alignment_heads (generation_config.json); token "
+                              "timestamps are not available for it")
+        if not isinstance(tokens, Tensor) or tokens.ndim != 2 or not tokens.is_cuda:
+            raise _C.F5EError("Whisper.token_timestamps: tokens must be an integer tensor [B, U] on the GPU; there is no CPU path")
+        B, U = tokens.shape
+        dev, Tp = tokens.device, cfg.max_source_positions
+        n_host = [int(v) for v in (n.tolist() if isinstance(n, Tensor) else n)]
+        fr = frames.tolist() if isinstance(frames, Tensor) else frames
+        fr_host = [int(fr)] * B if isinstance(fr, (int, float)) else [int(v) for v in fr]
+        n0 = int(n0)
+        if kv[0][0].shape[0] != B or len(n_host) != B or len(fr_host) != B or n0 < 1 or min(n_host) < n0 or max(n_host) > U:
+            raise _C.F5EError(f"Whisper.token_timestamps: {B} rows need {B} lengths in [{n0}, {U}] and {B} frame counts "
+                              f"(got n = {n_host}, frames = {fr_host}, {kv[0][0].shape[0]} utterances of keys)")
+        rows = [max(v - n0 - (0 if include_last else 1), 0) for v in n_host]
+        N_cap, cols = max(rows), [min(max(f // 2, 1), Tp) for f in fr_host]
+        n_rows = torch.tensor(rows, dtype=I32).to(dev)
+        m_len = torch.tensor(cols, dtype=I32).to(dev)
+        if N_cap == 0:
+            return None, n_rows, m_len
+        if n0 + N_cap > cfg.max_target_positions or N_cap > ops.DTW_MAX_N:
+            raise _C.F5EError(f"Whisper.token_timestamps: {n0} + {N_cap} positions exceed max_target_positions = "
+                              f"{cfg.max_target_positions} (or the {ops.DTW_MAX_N} rows of the DTW kernel)")
+        probs = torch.zeros(B, len(cfg.alignment_heads), N_cap, (max(cols) + 3) // 4 * 4, dtype=F32, device=dev)
+        ids = tokens.to(I32)
+        st = self._dec_state(B, n0 + N_cap, dev)
+        for p in range(n0 + N_cap):
+            self._dec_step(st, kv, ids[:, p].contiguous(), p, False, align=(probs, p - n0, m_len) if p >= n0 else None)
+        return probs, n_rows, m_len
+
+    @torch.no_grad()
+    def token_timestamps(self, kv: List[Tuple[Tensor, Tensor]], tokens: Tensor, n, frames, n0: int,
+                         include_last: bool = False) -> Tensor:
+        """Teacher-forced token times: tokens i32 [B, U] on the device (row b holds n[b] tokens, n0 of them the prompt), ``frames``
+        mel frames per utterance (samples // 160; an int, a list or a tensor) -> times f32 [B, U] in seconds: zeros for the
+        prompt, 0.02 x the encoder position at which the DTW path over the alignment heads' cross-attention enters the token's
+        row for positions n0 .. n[b] - 2, position n[b] - 1 repeating n[b] - 2 (the last token is never fed, as in
+        ``transformers``), zeros beyond.  ``include_last``: the last token is fed too and takes its own row (OpenAI's rule).
+        The given tokens go through the cached step; the layers that own an alignment head write those heads' probabilities
+        (f5e_cross_attn_probs_f32), then f5e_dtw_cost_f32 and f5e_dtw_path.  Row b of a ragged batch equals its own B = 1 run."""
+        probs, n_rows, m_len = self.alignment_probs(kv, tokens, n, frames, n0, include_last)
+        B, U = tokens.shape
+        times = torch.zeros(B, U, dtype=F32, device=tokens.device)
+        if probs is None:
+            return times
+        N_cap, n0 = probs.shape[2], int(n0)
+        cost = ops.dtw_cost_f32(probs, n_rows, m_len, self.cfg.median_filter_width)
+        first = ops.dtw_path(cost, n_rows, m_len)
+        # float32(frame * 0.02 in float64): the reference's own rounding
+        sec = (first.clamp(min=0).to(torch.float64) * 0.02).to(F32)
+        fed = torch.arange(N_cap, device=tokens.device)[None, :] < n_rows[:, None]
+        times[:, n0:n0 + N_cap] = torch.where(fed, sec, torch.zeros_like(sec))
+        if not include_last:
+            bi = torch.nonzero(n_rows > 0)[:, 0]
+            last = n0 + n_rows[bi].to(torch.int64)
+            times[bi, last] = times[bi, last - 1]
+        return times
+
+    def _frames_of(self, wav: Tensor, lens) -> List[int]:
+        """Mel frames of every row of a batch: samples // hop, at most the chunk."""
+        B, S = wav.shape
+        host = [S] * B if lens is None else [int(v) for v in (lens.tolist() if isinstance(lens, Tensor) else lens)]
+        return [min(min(v, S) // HOP, self.n_frames) for v in host]
+
     @torch.no_grad()
     def generate_from_kv(self, kv: List[Tuple[Tensor, Tensor]], prompt: Sequence[int], max_new_tokens: Optional[int] = None,
-                         sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0, return_beams: bool = False):
+                         sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0, return_beams: bool = False,
+                         return_token_timestamps: bool = False, frames=None):
+        """``generate`` from the cross keys / values.  ``return_token_timestamps``: one more item at the end, the times f32
+        [B, U] of the returned best hypothesis = ``token_timestamps`` on the returned tokens (a teacher-forced pass after the
+        search, greedy or beam); ``frames``: mel frames per utterance (None: the whole chunk)."""
+        if return_token_timestamps:
+            if not self.cfg.alignment_heads:
+                raise _C.F5EError("Whisper.generate: return_token_timestamps needs alignment_heads in generation_config.json")
+            res = self.generate_from_kv(kv, prompt, max_new_tokens, sync_every, beam_size, length_penalty, return_beams)
+            times = self.token_timestamps(kv, res[0], res[1], self.n_frames if frames is None else frames, len(prompt))
+            return tuple(res) + (times,)
         if int(beam_size) != 1 or return_beams:
             return self._beam_from_kv(kv, prompt, max_new_tokens, sync_every, int(beam_size), float(length_penalty), return_beams)
         cfg, fd = self.cfg, self._fold()
@@ -621,7 +818,7 @@ class Whisper(nn.Module):
     @torch.no_grad()
     def generate(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe",
                  max_new_tokens: Optional[int] = None, sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0,
-                 return_beams: bool = False):
+                 return_beams: bool = False, return_token_timestamps: bool = False):
         """Recognition of B utterances: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> (tokens i32 [B, U] starting
         with the prompt, eos from a row's end on; n i32 [B] = tokens of every row, its closing eos included when it ended by
         itself).  The host reads the alive count every ``sync_every`` steps; the result does not depend on it.  The bound is
@@ -629,10 +826,14 @@ class Whisper(nn.Module):
         ``beam_size`` K > 1: the pooled beam search of ``transformers``' ``generate(num_beams=K, length_penalty=...)``, K rows
         per utterance; the best finished hypothesis is returned in the same layout, and with ``return_beams`` a third item
         (pool tokens i32 [B, K, U], lens i32 [B, K], scores f32 [B, K] = sum of log-probabilities / generated length **
-        length_penalty, best first)."""
+        length_penalty, best first).  ``return_token_timestamps``: one more item at the end, times f32 [B, U] in seconds of the
+        returned tokens (``token_timestamps``; needs ``alignment_heads`` in the generation config)."""
         prompt = self.prompt_ids(language, task)
+        if not return_token_timestamps:
+            return self.generate_from_kv(self.encode(wav, lens), prompt, max_new_tokens, sync_every, beam_size, length_penalty,
+                                         return_beams)
         return self.generate_from_kv(self.encode(wav, lens), prompt, max_new_tokens, sync_every, beam_size, length_penalty,
-                                     return_beams)
+                                     return_beams, True, self._frames_of(wav, lens))
 
 
 class WhisperRecognizer:
@@ -646,8 +847,8 @@ class WhisperRecognizer:
         self.model.prompt_ids(language)                      # a language the checkpoint does not know fails here, not per file
         self._warned = set()
 
-    @torch.no_grad()
-    def transcribe(self, audio, sr: Optional[int] = None, mode=None, **ignored) -> str:
+    def _audio(self, audio, sr: Optional[int]) -> Tensor:
+        """A wav path or a wave at ``sr`` -> mono f32 [1, S] at 16 kHz on the device, cut to the chunk (with a warning)."""
         from ..infer import audio as A
         from ..infer.utils_infer import load_wav
         name = audio if isinstance(audio, str) else None
@@ -668,5 +869,55 @@ class WhisperRecognizer:
                 warnings.warn(f"WhisperRecognizer: {name or 'audio'} is {audio.shape[-1] / SAMPLE_RATE:.1f} s long; only the first "
                               f"{limit / SAMPLE_RATE:.0f} s are transcribed (long-form chunking is out of scope)")
             audio = audio[:, :limit]
-        tokens, n = self.model.generate(audio.contiguous(), None, self.language, beam_size=self.beam_size)
+        return audio.contiguous()
+
+    @torch.no_grad()
+    def transcribe(self, audio, sr: Optional[int] = None, mode=None, **ignored) -> str:
+        tokens, n = self.model.generate(self._audio(audio, sr), None, self.language, beam_size=self.beam_size)
         return self.model.decode_ids(tokens[0, :int(n[0])].tolist()).strip()
+
+    @torch.no_grad()
+    def transcribe_words(self, audio, sr: Optional[int] = None) -> list:
+        """-> [WordSpan(word, start_s, end_s)] of the transcript (``ppg.ctc_align.WordSpan``): the decoded hypothesis goes through
+        ``token_timestamps(include_last=True)``, so the closing token's time ends the last word.  Words are stripped of the
+        punctuation merged into them and of surrounding space; a word of punctuation alone is dropped."""
+        from ..ppg.ctc_align import WordSpan
+        model, wav = self.model, self._audio(audio, sr)
+        kv = model.encode(wav)
+        prompt = model.prompt_ids(self.language)
+        tokens, n = model.generate_from_kv(kv, prompt, beam_size=self.beam_size)[:2]
+        times = model.token_timestamps(kv, tokens, n, model._frames_of(wav, None), len(prompt), include_last=True)
+        k = int(n[0])
+        spans = []
+        for word, start, end in model.words_from_tokens(tokens[0, :k].tolist(), times[0, :k].tolist(), self.language):
+            word = word.strip().strip(PREPEND_PUNCTUATIONS + APPEND_PUNCTUATIONS).strip()
+            if word:
+                spans.append(WordSpan(word, start, end))
+        return spans
+
+    def align(self, audio, sr: Optional[int], text: str) -> list:
+        """``CTCAligner.align``'s signature: the word spans of the recording, carrying the words of ``text``.  The recording is
+        transcribed with word times; ``split_words(text)`` must agree with the transcript's words (case and punctuation
+        aside), else ValueError names the first pair that differs: correct the text or give the parts by hand."""
+        from ..ppg.ctc_align import WordSpan, split_words
+
+        def key(w):
+            return "".join(ch for ch in w.lower() if ch.isalnum())
+        spans = [s for span in self.transcribe_words(audio, sr) for s in _per_word(span, split_words) if key(s.word)]
+        want = [w for w in split_words(text) if key(w)]
+        for i in range(max(len(want), len(spans))):
+            a = want[i] if i < len(want) else None
+            b = spans[i].word if i < len(spans) else None
+            if a is None or b is None or key(a) != key(b):
+                raise ValueError(f"WhisperRecognizer.align: the text and the transcript differ at word {i}: {a!r} vs {b!r} "
+                                 f"(transcript: {' '.join(s.word for s in spans)!r}); correct the text or give the parts by hand")
+        return [WordSpan(w, s.start_s, s.end_s) for w, s in zip(want, spans)]
+
+
+def _per_word(span, split_words) -> list:
+    """A transcript word that ``split_words`` cuts further (every CJK character is a word of its own) shares its span evenly."""
+    parts = [w for w in split_words(span.word) if any(ch.isalnum() for ch in w)]
+    if len(parts) <= 1:
+        return [span]
+    step = (span.end_s - span.start_s) / len(parts)
+    return [type(span)(w, span.start_s + k * step, span.start_s + (k + 1) * step) for k, w in enumerate(parts)]

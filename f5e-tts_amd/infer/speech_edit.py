@@ -140,6 +140,10 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--asr_model", type=str, help="ASR checkpoint with a CTC head (the PPG extractor's model)")
     p.add_argument("--asr_config", type=str, help="Its train.yaml")
     p.add_argument("--asr_dict", type=str, help="Its symbol table (`token id` lines)")
+    p.add_argument("--whisper_dir", type=str, help="A local Whisper model directory: find the spans from its word timestamps "
+                                                   "instead (needs alignment_heads in its generation_config.json)")
+    p.add_argument("--whisper_language", type=str, default="en", help="The recording's language, for --whisper_dir")
+    p.add_argument("--whisper_beam", type=int, default=1, help="Beam size of the --whisper_dir transcription (1: greedy)")
     p.add_argument("-m", "--model", type=str, default="F5TTS_v1_Base", help="The model name")
     p.add_argument("-mc", "--model_cfg", type=str, default="", help="The path to the model config file .yaml")
     p.add_argument("-p", "--ckpt_file", type=str, required=True, help="The path to model checkpoint .pt/.safetensors")
@@ -162,8 +166,11 @@ def main(argv=None):
     if parts is not None and any(len(p) != 2 for p in parts):
         raise SystemExit('--parts: "start-end,start-end" in seconds')
     fix = [float(v) for v in args.fix_duration.split(",") if v.strip()] if args.fix_duration else None
-    if parts is None and not (args.asr_model and args.asr_config and args.asr_dict):
-        raise SystemExit("give --parts, or --asr_model / --asr_config / --asr_dict to find them")
+    wenet = bool(args.asr_model and args.asr_config and args.asr_dict)
+    if wenet and args.whisper_dir:
+        raise SystemExit("give one aligner: --asr_model / --asr_config / --asr_dict, or --whisper_dir")
+    if parts is None and not wenet and not args.whisper_dir:
+        raise SystemExit("give --parts, or --asr_model / --asr_config / --asr_dict (or --whisper_dir) to find them")
     from ..model import DiT
     from .infer_cli import DEFAULT_VOCODER_PATH, load_arch
     vocoder = U.load_vocoder(args.vocoder_name, is_local=True,
@@ -172,9 +179,12 @@ def main(argv=None):
     model = U.load_model(DiT, load_arch(args.model, args.model_cfg), args.ckpt_file, mel_spec_type=args.vocoder_name,
                          vocab_file=args.vocab_file, device=args.device)
     aligner = None
-    if parts is None:
+    if parts is None and wenet:
         from ..ppg.ctc_align import CTCAligner
         aligner = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, args.device, asr=True)
+    elif parts is None:
+        from ..eval.whisper import WhisperRecognizer
+        aligner = WhisperRecognizer(args.whisper_dir, args.device, args.whisper_language, args.whisper_beam)
     wave, sr, _mel = speech_edit_process(args.audio, args.origin_text, args.target_text, model, vocoder,
                                          parts_to_edit=parts, fix_duration=fix, aligner=aligner,
                                          mel_spec_type=args.vocoder_name, nfe_step=args.nfe_step,

@@ -1680,6 +1680,90 @@ def whisper_beam_step(logits: Tensor, score: Tensor, hyp_in: Tensor, anc_in: Ten
     return last
 
 
+# ---- Whisper word timestamps (csrc/whisper_align.hip) ----
+
+DTW_MAX_N, DTW_MAX_M = 448, 4096
+
+
+def cross_attn_probs_f32(q: Tensor, k: Tensor, heads_sel: Tensor, heads: int, scale: float, out: Tensor, rows_per_utt: int = 1,
+                         m_len: Optional[Tensor] = None) -> Tensor:
+    """f5e_cross_attn_probs_f32: q f32 [R, D] (row-strided view), k f32 [B, Tk, D] with B = R / rows_per_utt, heads_sel i32
+    [n_sel] on the device (heads of this layer) -> out f32 [R, n_sel, >= m] (a view with unit column stride; a token position and
+    the heads' place among all alignment heads are the caller's slicing): out[r, s, :m] = the softmax over all Tk keys of
+    head heads_sel[s], m = min(m_len[u], out.shape[2], Tk) (m_len i32 [B] on the device; None: Tk); columns at or beyond m are not
+    written."""
+    if q.ndim != 2 or k.ndim != 3 or out.ndim != 3 or heads_sel.ndim != 1:
+        raise _C.F5EError("cross_attn_probs_f32: q [R, D], k [B, Tk, D], heads_sel [n_sel], out [R, n_sel, >= m]; there is no CPU "
+                          "path")
+    R, D = q.shape
+    kp, ldk, B, Tk, Dk = _btc(k, "cross_attn_probs_f32: k")
+    n_sel = heads_sel.shape[0]
+    if Dk != D or D % heads or rows_per_utt < 1 or R != B * rows_per_utt or n_sel < 1 or out.shape[0] != R or out.shape[1] != n_sel:
+        raise _C.F5EError(f"cross_attn_probs_f32: inconsistent shapes q {tuple(q.shape)} k {tuple(k.shape)} out {tuple(out.shape)} "
+                          f"heads={heads} n_sel={n_sel} rows_per_utt={rows_per_utt}")
+    cols = out.shape[2]
+    if not out.is_cuda or out.dtype != F32 or cols < 1 or (cols > 1 and out.stride(2) != 1):
+        raise _C.F5EError(f"cross_attn_probs_f32: out must be an f32 GPU view with unit column stride "
+                          f"(got {out.dtype}, shape {tuple(out.shape)}, strides {tuple(out.stride())})")
+    s_row = out.stride(0) if R > 1 else 0
+    s_sel = out.stride(1) if n_sel > 1 else 0
+    have = out.untyped_storage().nbytes() // 4 - out.storage_offset()
+    if s_row < 0 or s_sel < 0 or have < (R - 1) * s_row + (n_sel - 1) * s_sel + min(cols, Tk):
+        raise _C.F5EError("cross_attn_probs_f32: out does not fit its storage")
+    qp, ldq = _rows(q, (F32,), "cross_attn_probs_f32: q", D)
+    require_device()
+    check(lib().f5e_cross_attn_probs_f32(_stream(), qp, ldq, kp, ldk, _p(heads_sel, I32, "heads_sel"), n_sel,
+                                         _len(m_len, B, "cross_attn_probs_f32"), cols, C.c_void_p(out.data_ptr()), s_row, s_sel, R,
+                                         rows_per_utt, Tk, heads, D // heads, float(scale)), "f5e_cross_attn_probs_f32")
+    return out
+
+
+def dtw_cost_f32(probs: Tensor, n_rows: Tensor, m_len: Tensor, width: int = 7, M: Optional[int] = None,
+                 out: Optional[Tensor] = None) -> Tensor:
+    """f5e_dtw_cost_f32: probs f32 [B, n_sel, N_cap, ld] (contiguous), n_rows / m_len i32 [B] on the device -> C f32
+    [B, N_cap, M] (M: the column capacity, ld when None): per-column normalisation over the rows, median of ``width`` along the
+    columns, minus the mean over the heads.  Cells outside (n_rows, m_len) are not written."""
+    if probs.ndim != 4:
+        raise _C.F5EError(f"dtw_cost_f32: probs must be [B, n_sel, N_cap, ld] (got {tuple(probs.shape)}); there is no CPU path")
+    B, n_sel, N_cap, ld = probs.shape
+    M = ld if M is None else int(M)
+    if not 1 <= M <= ld:
+        raise _C.F5EError(f"dtw_cost_f32: M = {M} must lie in 1 .. {ld}")
+    out = torch.zeros(B, N_cap, M, dtype=F32, device=probs.device) if out is None else out
+    if out.shape != (B, N_cap, M):
+        raise _C.F5EError(f"dtw_cost_f32: out must be [{B}, {N_cap}, {M}] (got {tuple(out.shape)})")
+    require_device()
+    check(lib().f5e_dtw_cost_f32(_stream(), _p(probs, F32, "probs"), ld, _len(n_rows, B, "dtw_cost_f32"),
+                                 _len(m_len, B, "dtw_cost_f32"), _p(out, F32, "out"), M, B, n_sel, N_cap, M, int(width)),
+          "f5e_dtw_cost_f32")
+    return out
+
+
+def dtw_workspace_bytes(B: int, N_cap: int, M_cap: int) -> int:
+    """Scratch bytes of ``dtw_path`` for B lattices of up to N_cap x M_cap cells (host arithmetic)."""
+    n = C.c_ulonglong(0)
+    check(lib().f5e_dtw_workspace_bytes(int(B), int(N_cap), int(M_cap), C.byref(n)), "f5e_dtw_workspace_bytes")
+    return int(n.value)
+
+
+def dtw_path(cost: Tensor, n_rows: Tensor, m_len: Tensor, first: Optional[Tensor] = None,
+             workspace: Optional[Tensor] = None) -> Tensor:
+    """f5e_dtw_path: cost f32 [B, N_cap, M_cap] (contiguous, only read), n_rows / m_len i32 [B] on the device -> first i32
+    [B, N_cap]: the column at which the warping path enters row t, -1 at and beyond n_rows.  workspace: a device tensor of at
+    least ``dtw_workspace_bytes`` bytes (allocated here when None)."""
+    if cost.ndim != 3:
+        raise _C.F5EError(f"dtw_path: cost must be [B, N_cap, M_cap] (got {tuple(cost.shape)}); there is no CPU path")
+    B, N_cap, M_cap = cost.shape
+    first = torch.empty(B, N_cap, dtype=I32, device=cost.device) if first is None else first
+    if first.shape != (B, N_cap):
+        raise _C.F5EError(f"dtw_path: first must be [{B}, {N_cap}] (got {tuple(first.shape)})")
+    require_device()
+    workspace, nbytes = _workspace(workspace, dtw_workspace_bytes(B, N_cap, M_cap), I32, cost.device)
+    check(lib().f5e_dtw_path(_stream(), _p(cost, F32, "cost"), M_cap, _len(n_rows, B, "dtw_path"), _len(m_len, B, "dtw_path"),
+                             _p(first, I32, "first"), _p(workspace, None, "workspace"), nbytes, B, N_cap, M_cap), "f5e_dtw_path")
+    return first
+
+
 # ---- UTMOS (csrc/utmos.hip) ----
 
 LSTM_MAX_H, LSTM_MAX_B, LSTM_MAX_T = 1024, 16, 4096

@@ -806,6 +806,58 @@ F5E_API int f5e_whisper_beam_step(f5e_stream st, const float* logits, long long 
                           int* open, int* alive, void* scratch, unsigned long long scratch_bytes, int B, int K, int V, int p,
                           int n0, int cap, int eos, float length_penalty);
 
+/* ---------------------------------------------------------------- Whisper word timestamps (csrc/whisper_align.hip) */
+/* Token times from the cross-attention of a few "alignment heads" (transformers 5.15.0 generation_whisper.py:
+ * _extract_token_timestamps, _median_filter, _dynamic_time_warping with num_frames given), for one utterance with the
+ * hypothesis tokens[0..n), n0 of them the prompt, `frames` mel frames, M = frames / 2 encoder positions clamped to 1 .. 1500,
+ * alignment heads (decoder layer, head) and an odd filter width w (7):
+ *  1. Row t of a head = softmax over ALL Tk encoder keys of the scaled scores of the query produced when the token at position
+ *     n0 + t is fed; only its first M columns are kept.  t = 0 .. N - 1 with N = n - n0 - 1: the last token is never fed (with
+ *     "include_last", OpenAI's rule, N = n - n0).
+ *  2. Per head and column j: mean and POPULATION standard deviation over the N rows; z = (p - mean) / std.
+ *  3. Median of width w along j, reflect padding of w / 2 (no edge repeat); rows stay unfiltered when M <= w / 2.
+ *  4. C[t][j] = -(mean over the heads of the filtered z), fp32.
+ *  5. cost fp32 [N + 1][M + 1] = +inf except cost[0][0] = 0.  With c0 = cost[i-1][j-1], c1 = cost[i-1][j], c2 = cost[i][j-1]:
+ *     diagonal if c0 < c1 && c0 < c2, else up if c1 < c0 && c1 < c2, else left (STRICT comparisons: every tie goes left);
+ *     cost[i][j] = C[i-1][j-1] + the chosen cost, ONE fp32 addition (the reference adds a float64 that holds an fp32 value to an
+ *     fp32 and rounds to fp32: the same number).
+ *  6. Backtrace from (N, M); row 0 forces left, column 0 forces up.  first[t] = the column at which the path enters row t (the
+ *     smallest j - 1 over its cells (t + 1, j)); the time of token n0 + t is first[t] * 0.02 s.
+ *  7. N = 0: no row, every time 0.  N = 1: time 0 (the reference gets there through NaNs; here nothing is NaN).  A column whose
+ *     standard deviation is 0 (every column when N = 1) gives NaN in the reference; HERE ITS z IS 0, a defined result.
+ * fp32, no allocation, no synchronisation, nothing read back, no atomics; lengths are DEVICE int32; all of it is capturable. */
+
+/* Rule 1 for the heads of ONE layer: for row r < R, u = r / rows_per_utt and s < n_sel with h = heads[s] (DEVICE int [n_sel]),
+ *   probs[r * stride_row + s * stride_sel + j] = softmax_{all Tk keys}(scale * q[r][h*dk + :] . k[u][:][h*dk + :])[j]
+ * for j < min(m_len[u], M_cap, Tk) (m_len: DEVICE int [R / rows_per_utt], NULL: Tk; M_cap >= 1: the columns the caller has room
+ * for).  Strides in floats; the caller puts a token
+ * position and a head's place among all alignment heads into the `probs` pointer.  Columns at or beyond that bound, and everything
+ * of a head index outside [0, H), are NOT written.  q [R][ldq >= H*dk]; k [R / rows_per_utt][Tk][ldk >= H*dk].  One workgroup
+ * of four waves per (row, selected head); maximum and sum are folded over the waves in a fixed order.  A launch of its own:
+ * f5e_cross_attn_decode_f32 is unchanged.  dk = 16, 32, 64, 128 (else F5E_ERR_UNSUPPORTED); Tk <= 4096; R, H, n_sel <= 65535;
+ * ldq, ldk multiples of 4 floats, q and k 16-byte aligned (else F5E_ERR_BAD_SHAPE). */
+F5E_API int f5e_cross_attn_probs_f32(f5e_stream st, const float* q, int ldq, const float* k, int ldk, const int* heads,
+                             int n_sel, const int* m_len, int M_cap, float* probs, long long stride_row, long long stride_sel,
+                             int R, int rows_per_utt, int Tk, int H, int dk, float scale);
+
+/* Rules 2-4.  probs f32 [B][n_sel][N_cap][ld >= M_cap] (only read), n_rows / m_len DEVICE int [B] (clamped to [0, N_cap] /
+ * [0, M_cap]) -> C f32 [B][N_cap][ldc >= M_cap].  Cells outside (n_rows[b], m_len[b]) are NOT written.  One launch: a workgroup
+ * owns 64 columns (+ w / 2 on each side) of an utterance, keeps mean and std of every (head, column) in LDS, and takes the
+ * median by rank counting.  1 <= n_sel <= 64 and width odd in 1 .. 15 (else F5E_ERR_UNSUPPORTED); 1 <= N_cap <= 448,
+ * 1 <= M_cap <= 4096, B <= 65535 (else F5E_ERR_BAD_SHAPE). */
+F5E_API int f5e_dtw_cost_f32(f5e_stream st, const float* probs, int ld, const int* n_rows, const int* m_len, float* C, int ldc,
+                     int B, int n_sel, int N_cap, int M_cap, int width);
+
+/* Rules 5-7.  C f32 [B][N_cap][ldc >= M_cap] (only read), n_rows / m_len DEVICE int [B] -> first i32 [B][N_cap]: first[b][t]
+ * for t < n_rows[b], -1 beyond.  An utterance whose lengths are not in 1 .. N_cap / 1 .. M_cap gets a whole row of -1.  One
+ * workgroup per utterance walks the anti-diagonals i + j with one barrier each: thread i owns row i, keeps cost[i][j-1] and
+ * cost[i-1][j-1] in registers and reads cost[i-1][j] from a double-buffered LDS row; two trace bits per cell go to `workspace`
+ * (f5e_dtw_workspace_bytes(B, N_cap, M_cap) bytes, 4-byte aligned, no need to clear it; nothing beyond that size is touched);
+ * one thread walks the backtrace.  1 <= N_cap <= 448 and 1 <= M_cap <= 4096 (else F5E_ERR_UNSUPPORTED); B <= 65535. */
+F5E_API int f5e_dtw_workspace_bytes(int B, int N_cap, int M_cap, unsigned long long* bytes_out_host);
+F5E_API int f5e_dtw_path(f5e_stream st, const float* C, int ldc, const int* n_rows, const int* m_len, int* first,
+                 void* workspace, unsigned long long workspace_bytes, int B, int N_cap, int M_cap);
+
 /* ---------------------------------------------------------------- UTMOS (csrc/utmos.hip) ---------------------- */
 /* The UTMOS predictor (utmos22_strong, reference eval/eval_utmos.py): a wav2vec2-base upstream (group-norm feature extractor,
  * post-LayerNorm encoder), a BiLSTM over its frames and a per-frame score averaged per utterance.  The strided convolutions 1-6,

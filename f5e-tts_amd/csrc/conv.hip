@@ -446,11 +446,20 @@ static int convpos_launch(hipStream_t st, const void* x, int ldx, const void* w_
   F5E_REQUIRE(S > 0 && N > 0 && D > 0 && groups > 0 && D % groups == 0, "convpos: bad D=%d / groups=%d", D, groups);
   const int cpg = D / groups;
   F5E_REQUIRE(cpg % 16 == 0 && cpg <= 64, "convpos: channels per group = %d must be 16, 32, 48 or 64", cpg);
-  F5E_REQUIRE(ldx % 8 == 0, "convpos: ldx must be a multiple of 8");
-  if (mode == 0) F5E_REQUIRE(out_bf16 && ldo % 4 == 0, "convpos: mode 0 needs a bf16 output");
-  else {
+  // the row strides count only between rows: a single row may come with any (torch gives a size-1 dimension any stride)
+  const bool many = (long long)S * N > 1;
+  const auto al = [](const void* p, unsigned n) { return (uintptr_t)p % n == 0; };
+  F5E_REQUIRE(ldx % 8 == 0 && (!many || ldx >= D), "convpos: ldx=%d must be a multiple of 8 and >= D=%d", ldx, D);
+  F5E_REQUIRE(al(x, 16) && al(w_packed, 16) && al(bias, 16),
+              "convpos: x, w_packed and bias must be 16-byte aligned (16-byte LDS-DMA chunks, float4 bias reads)");
+  if (mode == 0) {
+    F5E_REQUIRE(out_bf16 && ldo % 4 == 0 && (!many || ldo >= D), "convpos: mode 0 needs a bf16 output, ldo=%d a multiple of 4 and >= D=%d", ldo, D);
+    F5E_REQUIRE(al(out_bf16, 8), "convpos: out_bf16 must be 8-byte aligned (4 x bf16 stores)");
+  } else {
     F5E_REQUIRE(mode == 1, "convpos: mode must be 0 or 1");
     F5E_REQUIRE(out_f32 && resid && ldo32 % 4 == 0 && ldr % 4 == 0, "convpos: mode 1 needs f32 output + residual");
+    F5E_REQUIRE(!many || (ldo32 >= D && ldr >= D), "convpos: ldo32=%d and ldr=%d must be >= D=%d", ldo32, ldr, D);
+    F5E_REQUIRE(al(out_f32, 16) && al(resid, 16), "convpos: out_f32 and resid must be 16-byte aligned (float4 accesses)");
   }
   ConvPosArgs a{};
   a.x = (const bf16*)x; a.ldx = ldx; a.w = (const bf16*)w_packed; a.bias = bias;

@@ -41,6 +41,11 @@ __device__ __forceinline__ void fft1024(float2* x, const float2* tw, int tid) {
   __syncthreads();
 }
 
+// log(max(acc, 1e-5)).  The floor is a constant of the front-end and is stored correctly rounded: log(1e-5f) =
+// -11.51292549..., nearest fp32 -11.512925148 (0xC13834F1, what torch's log gives on the host); the device's logf (good
+// to one ulp) returns a neighbour of it, so silent frames used to differ from the reference in the last bit.
+__device__ __forceinline__ float log_floored(float acc) { return acc > 1e-5f ? logf(acc) : -11.512925148f; }
+
 __global__ __launch_bounds__(256) void stft_logmel_kernel(const float* wav, int nw, int ldw, const float* window,
                                                            const float2* tw, const float* fb, float* out, int T,
                                                            int hop, int n_mels) {
@@ -61,7 +66,7 @@ __global__ __launch_bounds__(256) void stft_logmel_kernel(const float* wav, int 
   if (tid < n_mels) {
     float acc = 0.f;
     for (int k = 0; k < NBIN; ++k) acc += mag[k] * fb[(size_t)k * n_mels + tid];
-    out[((size_t)b * T + f) * n_mels + tid] = logf(fmaxf(acc, 1e-5f));
+    out[((size_t)b * T + f) * n_mels + tid] = log_floored(acc);
   }
 }
 
@@ -100,7 +105,7 @@ __global__ __launch_bounds__(256) void stft_logmel_banded_kernel(const float* wa
   if (tid < n_mels) {
     float acc = 0.f;
     for (int k = 0; k < cnt; ++k) acc += mag[lo + k] * wts[off + k];
-    out[((size_t)b * T + f) * n_mels + tid] = logf(fmaxf(acc, 1e-5f));
+    out[((size_t)b * T + f) * n_mels + tid] = log_floored(acc);
   }
 }
 
@@ -153,6 +158,7 @@ int f5e_stft_logmel(hipStream_t st, const float* wav, int nw, int ldw, const flo
                     const float* fb, float* out, int B, int n_fft, int hop, int n_mels) {
   F5E_REQUIRE(wav && window && twiddle && fb && out, "stft_logmel: null operand");
   F5E_REQUIRE(n_fft == NFFT, "stft_logmel: only n_fft = win_length = 1024 is built (got %d)", n_fft);
+  F5E_REQUIRE(B == 1 || ldw >= nw, "stft_logmel: ldw=%d must be >= nw=%d", ldw, nw);
   F5E_REQUIRE(B > 0 && hop > 0 && n_mels > 0 && n_mels <= 256, "stft_logmel: bad shape");
   F5E_REQUIRE(nw > NFFT / 2, "stft_logmel: reflect padding needs nw > %d samples (got %d)", NFFT / 2, nw);
   const int T = 1 + nw / hop;
@@ -167,6 +173,7 @@ int f5e_stft_logmel_banded(hipStream_t st, const float* wav, int nw, int ldw, co
                            int n_mels) {
   F5E_REQUIRE(wav && window && twiddle && fb_compact && fb_band && out, "stft_logmel_banded: null operand");
   F5E_REQUIRE(n_fft == NFFT, "stft_logmel_banded: only n_fft = win_length = 1024 is built (got %d)", n_fft);
+  F5E_REQUIRE(B == 1 || ldw >= nw, "stft_logmel_banded: ldw=%d must be >= nw=%d", ldw, nw);
   F5E_REQUIRE(B > 0 && hop > 0 && n_mels > 0 && n_mels <= 256 && nnz > 0 && nnz <= FB_MAX_NNZ,
               "stft_logmel_banded: bad shape (n_mels <= 256, 0 < nnz=%d <= %d)", nnz, FB_MAX_NNZ);
   F5E_REQUIRE(nw > NFFT / 2, "stft_logmel_banded: reflect padding needs nw > %d samples (got %d)", NFFT / 2, nw);
@@ -182,6 +189,7 @@ int f5e_stft_logmel_banded_ex(hipStream_t st, const float* wav, int nw, int ldw,
                               int n_fft, int hop, int n_mels, int pad_left, int T, float mag_eps) {
   F5E_REQUIRE(wav && window && twiddle && fb_compact && fb_band && out, "stft_logmel_banded_ex: null operand");
   F5E_REQUIRE(n_fft == NFFT, "stft_logmel_banded_ex: only n_fft = win_length = 1024 is built (got %d)", n_fft);
+  F5E_REQUIRE(B == 1 || ldw >= nw, "stft_logmel_banded_ex: ldw=%d must be >= nw=%d", ldw, nw);
   F5E_REQUIRE(B > 0 && hop > 0 && T > 0 && n_mels > 0 && n_mels <= 256 && nnz > 0 && nnz <= FB_MAX_NNZ,
               "stft_logmel_banded_ex: bad shape (T=%d, n_mels <= 256, 0 < nnz=%d <= %d)", T, nnz, FB_MAX_NNZ);
   F5E_REQUIRE(pad_left >= 0 && pad_left < nw, "stft_logmel_banded_ex: reflect padding needs 0 <= pad_left=%d < nw=%d",
@@ -200,6 +208,10 @@ int f5e_istft_head(hipStream_t st, const float* z, int ldz, const float* window,
   F5E_REQUIRE(z && window && twiddle && frames_ws && out, "istft_head: null operand");
   F5E_REQUIRE(n_fft == NFFT, "istft_head: only n_fft = 1024 is built (got %d)", n_fft);
   F5E_REQUIRE(B > 0 && T > 1 && hop > 0 && NFFT % hop == 0, "istft_head: bad shape B=%d T=%d hop=%d", B, T, hop);
+  // hop = 1024: the frames only touch, and the Hann window is 0 at j = 0, so the window envelope under out[b][512 + 1024 f]
+  // is 0 and the sample 0 / 0 (torch.istft refuses the case: its NOLA check)
+  F5E_REQUIRE(hop <= NFFT / 2, "istft_head: hop=%d above n_fft / 2 = %d leaves samples with a zero window envelope "
+              "(torch.istft's NOLA condition)", hop, NFFT / 2);
   F5E_REQUIRE(ldz >= 2 * NBIN, "istft_head: ldz=%d < %d", ldz, 2 * NBIN);
   hipLaunchKernelGGL(istft_frames_kernel, dim3(B * T), dim3(256), 0, st, z, ldz, window, (const float2*)twiddle,
                      frames_ws);

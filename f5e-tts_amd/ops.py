@@ -474,17 +474,54 @@ def pack_convpos_weight(w: Tensor, groups: int = 16) -> Tensor:
     return out.to(BF).contiguous()
 
 
+def _vec(t: Tensor, dtype, name: str, shape, align: int = 4):
+    """Pointer of a contiguous ``dtype`` GPU tensor of exactly ``shape`` whose base is ``align``-byte aligned."""
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape):
+        _err(f"{name} must be {dtype} {list(shape)} (got {t.dtype}, shape {tuple(t.shape)})")
+    ptr = _p(t, dtype, name)
+    if t.data_ptr() % align:
+        _err(f"{name}: base address must be {align}-byte aligned")
+    return ptr
+
+
 def convpos(x: Tensor, w_packed: Tensor, bias: Tensor, S: int, N: int, *, out_bf16: Optional[Tensor] = None,
             out_f32: Optional[Tensor] = None, resid: Optional[Tensor] = None):
-    require_device()
+    """Grouped Conv1d(D, D, 31, padding 15) + Mish over S sequences of N rows (f5e_convpos).  x bf16 [S * N, D] view (unit
+    column stride, row stride a multiple of 8, 16-byte aligned base); w_packed bf16 [G, 31, 64, 64] (``pack_convpos_weight``),
+    D / G in {16, 32, 48, 64}; bias f32 [D].  Exactly one output: out_bf16 = mish(conv + bias) bf16 [S * N, D], or out_f32 =
+    mish(conv + bias) + resid, both f32 [S * N, D]; outputs and resid are views with unit column stride and a row stride
+    that is a multiple of 4, and need not be contiguous.  Everything is refused here or by the library, before any launch."""
+    S, N = int(S), int(N)
+    if S < 1 or N < 1:
+        _err(f"convpos: needs S >= 1 and N >= 1 (got {S}, {N})")
+    if x.ndim != 2 or x.shape[0] != S * N:
+        _err(f"convpos: x must be [S * N, D] = [{S * N}, D] (got shape {tuple(x.shape)})")
     D = x.shape[1]
-    mode = 0 if out_f32 is None else 1
-    check(lib().f5e_convpos(_stream(), _p(x, BF, "x"), x.stride(0), _p(w_packed, BF, "w_packed"), _p(bias, F32, "bias"),
-                            mode, _p(out_bf16, BF, "out_bf16"), out_bf16.stride(0) if out_bf16 is not None else 0,
-                            _p(out_f32, F32, "out_f32"), out_f32.stride(0) if out_f32 is not None else 0,
-                            _p(resid, F32, "resid"), resid.stride(0) if resid is not None else 0, S, N, D,
-                            w_packed.shape[0]),
+    if w_packed.ndim != 4 or tuple(w_packed.shape[1:]) != (31, 64, 64) or w_packed.shape[0] < 1:
+        _err(f"convpos: w_packed must be bf16 [G, 31, 64, 64] (got shape {tuple(w_packed.shape)})")
+    G = w_packed.shape[0]
+    if D % G or D // G not in (16, 32, 48, 64):
+        _err(f"convpos: D / G = {D} / {G} must be 16, 32, 48 or 64")
+    if (out_bf16 is None) == (out_f32 is None):
+        _err("convpos: exactly one of out_bf16 and out_f32 must be given")
+    if (resid is None) != (out_f32 is None):
+        _err("convpos: resid goes with out_f32, and only with it")
+    require_device()
+    xp, ldx = _rows(x, (BF,), "convpos: x", D, vec=8)
+    wp = _vec(w_packed, BF, "convpos: w_packed", (G, 31, 64, 64), 16)
+    bp = _vec(bias, F32, "convpos: bias", (D,), 16)
+    op, ldo, o32p, ldo32, rp, ldr = None, 0, None, 0, None, 0
+    if out_bf16 is not None:
+        _shaped(out_bf16, (S * N, D), "convpos: out_bf16")
+        op, ldo = _rows(out_bf16, (BF,), "convpos: out_bf16", D)
+    else:
+        _shaped(out_f32, (S * N, D), "convpos: out_f32")
+        _shaped(resid, (S * N, D), "convpos: resid")
+        o32p, ldo32 = _rows(out_f32, (F32,), "convpos: out_f32", D)
+        rp, ldr = _rows(resid, (F32,), "convpos: resid", D)
+    check(lib().f5e_convpos(_stream(), xp, ldx, wp, bp, 0 if out_f32 is None else 1, op, ldo, o32p, ldo32, rp, ldr, S, N, D, G),
           "f5e_convpos")
+    return out_bf16 if out_f32 is None else out_f32
 
 
 def dwconv7(x: Tensor, w_t: Tensor, bias: Tensor, out: Tensor):
@@ -545,17 +582,26 @@ def conv2d_sub(x: Tensor, w_packed: Tensor, bias: Optional[Tensor], stride: int,
 
 
 def sinus_embed(t: Tensor, freqs: Tensor, out: Tensor, scale: float = 1000.0):
-    require_device()
+    """out[e] = cat(sin(a), cos(a)), a = (scale t[e]) freqs[k]: t f32 [E], freqs f32 [dim / 2], out f32 [E, dim], all contiguous
+    on the GPU.  Everything is refused here or by the library (dim even and >= 4), before any launch."""
+    if out.ndim != 2 or out.shape[0] < 1 or out.shape[1] % 2:
+        _err(f"sinus_embed: out must be f32 [E, dim] with dim even (got shape {tuple(out.shape)})")
     E, dim = out.shape
-    check(lib().f5e_sinus_embed(_stream(), _p(t, F32, "t"), _p(freqs, F32, "freqs"), _p(out, F32, "out"), E, dim, scale),
-          "f5e_sinus_embed")
+    require_device()
+    check(lib().f5e_sinus_embed(_stream(), _vec(t, F32, "sinus_embed: t", (E,)), _vec(freqs, F32, "sinus_embed: freqs", (dim // 2,)),
+                                _p(out, F32, "sinus_embed: out"), E, dim, scale), "f5e_sinus_embed")
     return out
 
 
 def rope_table(inv_freq: Tensor, out: Tensor):
-    require_device()
+    """out[n, i] = (cos, sin)(n inv_freq[i]): inv_freq f32 [half], out f32 [N, half, 2], both contiguous on the GPU.
+    Everything is refused here, before any launch."""
+    if out.ndim != 3 or out.shape[2] != 2 or min(out.shape) < 1:
+        _err(f"rope_table: out must be f32 [N, half, 2] (got shape {tuple(out.shape)})")
     N, half, _ = out.shape
-    check(lib().f5e_rope_table(_stream(), _p(inv_freq, F32, "inv_freq"), _p(out, F32, "out"), N, half), "f5e_rope_table")
+    require_device()
+    check(lib().f5e_rope_table(_stream(), _vec(inv_freq, F32, "rope_table: inv_freq", (half,)), _p(out, F32, "rope_table: out"),
+                               N, half), "f5e_rope_table")
     return out
 
 
@@ -1067,11 +1113,42 @@ def resample(x: Tensor, orig_freq: int, new_freq: int, out: Optional[Tensor] = N
     return out if x.ndim == 2 else o2[0]
 
 
-def stft_logmel(wav: Tensor, window: Tensor, twiddle: Tensor, fb: Tensor, out: Tensor, n_fft: int, hop: int):
-    require_device()
+def _stft_operands(wav: Tensor, window: Tensor, twiddle: Tensor, out: Tensor, hop: int, n_mels: int, T: Optional[int],
+                   name: str):
+    """(wav pointer, nw, ldw, window pointer, twiddle pointer, out pointer, B) of the STFT log-mel entry points: wav f32
+    [B, nw] with unit sample stride (any row stride), window f32 [1024], twiddle f32 [512, 2], out f32 contiguous and exactly
+    [B, T, n_mels] (T = 1 + nw // hop unless given): the kernels write all of it and nothing else."""
+    if wav.ndim != 2 or wav.dtype != F32 or not wav.is_cuda or min(wav.shape) < 1 or (wav.stride(1) != 1 and wav.shape[1] > 1):
+        _err(f"{name}: wav must be an f32 [B, nw] GPU tensor with unit sample stride (got {wav.dtype}, {wav.device}, shape "
+             f"{tuple(wav.shape)}, strides {tuple(wav.stride())})")
     B, nw = wav.shape
-    check(lib().f5e_stft_logmel(_stream(), _p(wav, F32, "wav"), nw, wav.stride(0), _p(window, F32, "window"),
-                                _p(twiddle, F32, "twiddle"), _p(fb, F32, "fb"), _p(out, F32, "out"), B, n_fft, hop,
+    hop = int(hop)
+    if hop < 1:
+        _err(f"{name}: hop must be positive (got {hop})")
+    if B > 1 and wav.stride(0) < nw:
+        _err(f"{name}: wav's row stride {wav.stride(0)} is smaller than its {nw} samples")
+    T = 1 + nw // hop if T is None else int(T)
+    wp, tp = _vec(window, F32, f"{name}: window", (1024,)), _vec(twiddle, F32, f"{name}: twiddle", (512, 2))
+    op = _vec(out, F32, f"{name}: out", (B, T, n_mels))
+    return C.c_void_p(wav.data_ptr()), nw, wav.stride(0) if B > 1 else nw, wp, tp, op, B
+
+
+def _band_operands(fb_compact: Tensor, fb_band: Tensor, name: str):
+    if fb_band.ndim != 2 or fb_band.shape[1] != 3 or fb_band.shape[0] < 1:
+        _err(f"{name}: fb_band must be i32 [n_mels, 3] (got shape {tuple(fb_band.shape)})")
+    if fb_compact.ndim != 1:
+        _err(f"{name}: fb_compact must be f32 [nnz] (got shape {tuple(fb_compact.shape)})")
+    return _p(fb_compact, F32, f"{name}: fb_compact"), _p(fb_band, I32, f"{name}: fb_band"), fb_compact.numel(), fb_band.shape[0]
+
+
+def stft_logmel(wav: Tensor, window: Tensor, twiddle: Tensor, fb: Tensor, out: Tensor, n_fft: int, hop: int):
+    """out f32 [B, 1 + nw // hop, n_mels] = log(clamp(|STFT(wav)| fb, 1e-5)), centred and reflect-padded; fb f32 [513, n_mels]
+    contiguous.  Operands as ``_stft_operands``; everything is refused here or by the library, before any launch."""
+    if fb.ndim != 2 or fb.shape[0] != 513 or fb.shape[1] < 1:
+        _err(f"stft_logmel: fb must be f32 [513, n_mels] (got shape {tuple(fb.shape)})")
+    require_device()
+    wavp, nw, ldw, wp, tp, op, B = _stft_operands(wav, window, twiddle, out, hop, fb.shape[1], None, "stft_logmel")
+    check(lib().f5e_stft_logmel(_stream(), wavp, nw, ldw, wp, tp, _p(fb, F32, "stft_logmel: fb"), op, B, n_fft, hop,
                                 fb.shape[1]), "f5e_stft_logmel")
     return out
 
@@ -1098,36 +1175,45 @@ def band_filterbank(fb: Tensor):
 
 def stft_logmel_banded(wav: Tensor, window: Tensor, twiddle: Tensor, fb_compact: Tensor, fb_band: Tensor, out: Tensor,
                        n_fft: int, hop: int):
+    """``stft_logmel`` with the filterbank in ``band_filterbank``'s form (fb_compact f32 [nnz <= 2048], fb_band i32
+    [n_mels, 3]): the same result bit for bit."""
+    fcp, fbp, nnz, n_mels = _band_operands(fb_compact, fb_band, "stft_logmel_banded")
     require_device()
-    B, nw = wav.shape
-    check(lib().f5e_stft_logmel_banded(_stream(), _p(wav, F32, "wav"), nw, wav.stride(0), _p(window, F32, "window"),
-                                       _p(twiddle, F32, "twiddle"), _p(fb_compact, F32, "fb_compact"),
-                                       _p(fb_band, I32, "fb_band"), fb_compact.numel(), _p(out, F32, "out"), B, n_fft, hop,
-                                       fb_band.shape[0]), "f5e_stft_logmel_banded")
+    wavp, nw, ldw, wp, tp, op, B = _stft_operands(wav, window, twiddle, out, hop, n_mels, None, "stft_logmel_banded")
+    check(lib().f5e_stft_logmel_banded(_stream(), wavp, nw, ldw, wp, tp, fcp, fbp, nnz, op, B, n_fft, hop, n_mels),
+          "f5e_stft_logmel_banded")
     return out
 
 
 def stft_logmel_banded_ex(wav: Tensor, window: Tensor, twiddle: Tensor, fb_compact: Tensor, fb_band: Tensor, out: Tensor,
                           n_fft: int, hop: int, pad_left: int, mag_eps: float):
     """out f32 [B, T, n_mels]: frames start pad_left samples before f * hop (reflect-padded); T = out.shape[1]."""
+    fcp, fbp, nnz, n_mels = _band_operands(fb_compact, fb_band, "stft_logmel_banded_ex")
+    if out.ndim != 3:
+        _err(f"stft_logmel_banded_ex: out must be [B, T, n_mels] (got shape {tuple(out.shape)})")
     require_device()
-    B, nw = wav.shape
     T = out.shape[1]
-    if out.shape != (B, T, fb_band.shape[0]):
-        raise _C.F5EError(f"out must be [B, T, n_mels] = [{B}, T, {fb_band.shape[0]}] (got {tuple(out.shape)})")
-    check(lib().f5e_stft_logmel_banded_ex(_stream(), _p(wav, F32, "wav"), nw, wav.stride(0), _p(window, F32, "window"),
-                                          _p(twiddle, F32, "twiddle"), _p(fb_compact, F32, "fb_compact"),
-                                          _p(fb_band, I32, "fb_band"), fb_compact.numel(), _p(out, F32, "out"), B, n_fft,
-                                          hop, fb_band.shape[0], pad_left, T, mag_eps), "f5e_stft_logmel_banded_ex")
+    wavp, nw, ldw, wp, tp, op, B = _stft_operands(wav, window, twiddle, out, hop, n_mels, T, "stft_logmel_banded_ex")
+    check(lib().f5e_stft_logmel_banded_ex(_stream(), wavp, nw, ldw, wp, tp, fcp, fbp, nnz, op, B, n_fft, hop, n_mels,
+                                          int(pad_left), T, mag_eps), "f5e_stft_logmel_banded_ex")
     return out
 
 
 def istft_head(z: Tensor, window: Tensor, twiddle: Tensor, frames_ws: Tensor, out: Tensor, B: int, T: int, n_fft: int,
                hop: int):
+    """Vocos ISTFTHead tail: z f32 [B * T, >= 1026] view (513 log-magnitudes | 513 phases; unit column stride, any row stride
+    >= 1026), frames_ws f32 scratch of at least B * T * 1024 elements, out f32 [B, hop (T - 1)] contiguous.  Everything is
+    refused here or by the library (hop must divide 1024 and be at most 512), before any launch."""
+    B, T, hop = int(B), int(T), int(hop)
+    if B < 1 or T < 2 or hop < 1:
+        _err(f"istft_head: needs B >= 1, T >= 2 and hop >= 1 (got {B}, {T}, {hop})")
+    if z.ndim != 2 or z.shape[0] != B * T:
+        _err(f"istft_head: z must have B * T = {B * T} rows (got shape {tuple(z.shape)})")
     require_device()
-    check(lib().f5e_istft_head(_stream(), _p(z, F32, "z"), z.stride(0), _p(window, F32, "window"),
-                               _p(twiddle, F32, "twiddle"), _p(frames_ws, F32, "frames_ws"), _p(out, F32, "out"), B, T,
-                               n_fft, hop), "f5e_istft_head")
+    zp, ldz = _rows(z, (F32,), "istft_head: z", 1026, vec=1)
+    wp, tp = _vec(window, F32, "istft_head: window", (1024,)), _vec(twiddle, F32, "istft_head: twiddle", (512, 2))
+    check(lib().f5e_istft_head(_stream(), zp, ldz, wp, tp, _flat(frames_ws, F32, "istft_head: frames_ws", B * T * 1024),
+                               _vec(out, F32, "istft_head: out", (B, hop * (T - 1))), B, T, n_fft, hop), "f5e_istft_head")
     return out
 
 

@@ -177,7 +177,12 @@ F5E_API int f5e_gemm_f32(f5e_stream st, const float* A, int lda, int a_rows, int
 
 /* One grouped Conv1d(D, D, 31, groups, padding = 15) + Mish of ConvPositionEmbedding (modules.py:167-190, called with
  * mask=None at backbones/dit.py:176).  x bf16 [S*N][ldx]; w_packed bf16 [groups][31][64 oc][64 ic], zero padded when
- * D/groups (16, 32, 48 or 64) is below 64.  mode 0: out_bf16 = mish(conv + bias); mode 1: out_f32 = mish(..) + resid. */
+ * D/groups (16, 32, 48 or 64) is below 64.  mode 0: out_bf16 = mish(conv + bias); mode 1: out_f32 = mish(..) + resid.
+ * Refused before any launch: D % groups != 0 or D/groups outside {16, 32, 48, 64}; ldx not a multiple of 8; ldo, ldo32 or
+ * ldr not a multiple of 4; with more than one row (S * N > 1) any of ldx and the mode's ldo / ldo32, ldr below D; x,
+ * w_packed, bias, out_f32 or resid not 16-byte aligned, out_bf16 not 8-byte aligned; a mode without its output (mode 1:
+ * and its residual).  Only columns [0, D) of the S * N rows of x / resid are read and of the output written; bias holds D
+ * floats. */
 F5E_API int f5e_convpos(f5e_stream st, const void* x, int ldx, const void* w_packed, const float* bias, int mode,
                 void* out_bf16, int ldo, float* out_f32, int ldo32, const float* resid, int ldr, int S, int N, int D,
                 int groups);
@@ -200,7 +205,9 @@ F5E_API int f5e_conv2d_sub_f32(f5e_stream st, const float* x, const float* w, co
 
 /* ---------------------------------------------------------------- sampler elementwise ------------------------ */
 
-/* out[e] = cat(sin(a), cos(a)), a = (scale * t[e]) * freqs[k]   (modules.py:154-161; freqs = host constant [dim/2]) */
+/* out[e] = cat(sin(a), cos(a)), a = (scale * t[e]) * freqs[k]   (modules.py:154-161; freqs = host constant [dim/2]).
+ * t f32 [E], out f32 [E][dim], dim even and >= 4; a is one fp32 product of a product (no add: nothing to contract) and
+ * goes through sincosf, as n * inv_freq[i] does in f5e_rope_table (inv_freq f32 [half], out f32 [N][half][2]). */
 F5E_API int f5e_sinus_embed(f5e_stream st, const float* t, const float* freqs, float* out, int E, int dim, float scale);
 /* out[n][i] = (cos, sin)(n * inv_freq[i])   (x_transformers RotaryEmbedding.forward_from_seq_len) */
 F5E_API int f5e_rope_table(f5e_stream st, const float* inv_freq, float* out, int N, int half);
@@ -371,7 +378,10 @@ F5E_API int f5e_log_softmax_rows(f5e_stream st, const float* x, long long ldx, f
 /* ---------------------------------------------------------------- mel / vocoder ------------------------------ */
 
 /* out[B][T][n_mels] = log(clamp(|STFT(wav)| . fb, 1e-5)), T = 1 + nw / hop, reflect-padded, centred (modules.py:75-101).
- * window f32 [1024]; twiddle f32 [512][2] = (cos, -sin)(2 pi k / 1024); fb f32 [513][n_mels]. */
+ * window f32 [1024]; twiddle f32 [512][2] = (cos, -sin)(2 pi k / 1024); fb f32 [513][n_mels].  wav f32 [B][ldw], nw
+ * samples of each row read.  Refused: n_fft != 1024, nw <= 512 (the reflection), n_mels > 256, ldw < nw with B > 1.  out is
+ * written in full and must hold B * T * n_mels floats: the caller sizes it by T = 1 + nw / hop.  A clamped output is the
+ * correctly rounded log(1e-5f) = 0xC13834F1 (a stored constant, not the device's logf of 1e-5). */
 F5E_API int f5e_stft_logmel(f5e_stream st, const float* wav, int nw, int ldw, const float* window, const float* twiddle,
                     const float* fb, float* out, int B, int n_fft, int hop, int n_mels);
 /* The same, bit for bit, with the filterbank handed over banded: filter m is non-zero on FFT bins [lo, lo + cnt) only
@@ -388,7 +398,9 @@ F5E_API int f5e_stft_logmel_banded_ex(f5e_stream st, const float* wav, int nw, i
                               const float* twiddle, const float* fb_compact, const int* fb_band, int nnz, float* out, int B,
                               int n_fft, int hop, int n_mels, int pad_left, int T, float mag_eps);
 /* Vocos ISTFTHead tail: z f32 [B*T][ldz] (513 log-magnitudes | 513 phases) -> out f32 [B][hop * (T - 1)];
- * frames_ws f32 [B*T][1024] scratch. */
+ * frames_ws f32 [B*T][1024] scratch (written in full).  Refused: n_fft != 1024, T < 2, ldz < 1026, a hop that does not
+ * divide 1024, and hop > 512: at hop = 1024 the Hann envelope under out[b][512 + 1024 f] is zero (0 / 0; torch.istft
+ * refuses the same case as a NOLA violation). */
 F5E_API int f5e_istft_head(f5e_stream st, const float* z, int ldz, const float* window, const float* twiddle, float* frames_ws,
                    float* out, int B, int T, int n_fft, int hop);
 

@@ -98,6 +98,10 @@ SIGNATURES = {
     "f5e_whisper_beam_scratch": [_I, _I, _I, C.POINTER(C.c_ulonglong)],
     "f5e_whisper_beam_step": [_P, _P, _LL, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, C.c_ulonglong,
                               _I, _I, _I, _I, _I, _I, _I, _F],
+    "f5e_whisper_ts_pick": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
+    "f5e_whisper_ts_rule": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I],
+    "f5e_whisper_beam_step_ts": [_P, _P, _LL, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
+                                 C.c_ulonglong, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],
     "f5e_cross_attn_probs_f32": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _LL, _LL, _I, _I, _I, _I, _I, _F],
     "f5e_dtw_cost_f32": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I],
     "f5e_dtw_workspace_bytes": [_I, _I, _I, C.POINTER(C.c_ulonglong)],

@@ -16,6 +16,11 @@
 //                               LDS once, in chunks of 8192 classes that each leave a maximum, a sum of exponentials and their 2K
 //                               largest unsuppressed classes; one workgroup per utterance then folds the chunks, takes the 2K
 //                               largest candidates and applies the rules (open rows, pool of finished hypotheses, flags).
+//   f5e_whisper_ts_pick         the greedy step under Whisper's timestamp rules (transformers' WhisperTimeStampLogitsProcessor):
+//   f5e_whisper_ts_rule         one launch per step reads a row once, keeps a running log-sum-exp and argmax for the allowed
+//   f5e_whisper_beam_step_ts    timestamps and for the allowed text apart, decides, picks and accumulates the pick's
+//                               log-probability; the same pass without the pick leaves a rule descriptor per row that the beam
+//                               step's chunk launch applies as one more mask.
 //
 // Nothing here allocates, synchronises or reads back.  Per-row lengths are DEVICE int32.
 #include "f5e_common.h"
@@ -253,6 +258,160 @@ __global__ __launch_bounds__(256) void alive_count_kernel(const int* __restrict_
   if (threadIdx.x == 0) *alive = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
+// ---- timestamp rules (transformers' WhisperTimeStampLogitsProcessor, after the two suppress processors) ---------------------------
+// Everything the processor bans is an interval: the text classes [0, eos) or [0, ts_begin), and the timestamps outside [lo, hi].
+// One workgroup per row reads the logits once; a lane keeps, for the allowed timestamps and for the allowed text classes
+// apart, a running maximum with its first index and the sum of exp(x - maximum).  The groups are folded across the wave by
+// shuffles and across the waves through LDS in wave order, so the result does not depend on timing.  log-sum-exp(timestamps) >
+// max(text) bans all text: the log-softmax normaliser of the processor is common to both sides and drops out.
+struct TsRule {
+  int kind, lo, hi;   // text ban: 0 none, 1 [0, eos), 2 [0, ts_begin); allowed timestamps [lo, hi] (lo > hi: none)
+};
+
+struct TsGroup {
+  float m, s;         // maximum (-inf: no class), sum of exp(x - m)
+  int a;              // lowest index of the maximum
+};
+
+// Four classes of a lane at once, v0 + 256 k (ascending): x[k] counts iff in[k].  One rescale of the sum per call, then four
+// independent exponentials: the dependent chain of a lane is a quarter of the one-class-at-a-time form.
+__device__ __forceinline__ void ts_group_add4(TsGroup& g, const float (&x)[4], const bool (&in)[4], int v0) {
+  const float NEG = -__builtin_inff();
+  float m4 = NEG;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) m4 = in[k] ? fmaxf(m4, x[k]) : m4;
+  if (!(m4 > NEG)) return;
+  if (m4 > g.m) {                                 // '>' keeps the first maximum; the first class: 0 * exp(-inf) = 0
+    g.s *= expf(g.m - m4);
+    g.m = m4;
+#pragma unroll
+    for (int k = 3; k >= 0; --k)
+      if (in[k] && x[k] == m4) g.a = v0 + 256 * k;
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) g.s += in[k] ? expf(x[k] - g.m) : 0.f;
+}
+
+__device__ __forceinline__ void ts_group_merge(TsGroup& g, float om, float os, int oa) {
+  const float M = fmaxf(g.m, om);
+  const float fa = g.m == M ? 1.f : expf(g.m - M), fb = om == M ? 1.f : expf(om - M);   // -inf == -inf: no exp(NaN)
+  g.s = g.s * fa + os * fb;
+  if (om > g.m || (om == g.m && oa < g.a)) g.a = oa;
+  g.m = M;
+}
+
+__device__ __forceinline__ void ts_group_wave(TsGroup& g) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(g.m, o, 64), os = __shfl_xor(g.s, o, 64);
+    const int oa = __shfl_xor(g.a, o, 64);
+    ts_group_merge(g, om, os, oa);
+  }
+}
+
+// The state of a row from its generated tokens hist[0 .. len) (uniform over the workgroup; `slot` is one LDS word).
+__device__ TsRule ts_rule_of(const int* __restrict__ hist, int len, int V, int ts_begin, int max_initial, int* slot) {
+  const int tid = threadIdx.x;
+  if (tid == 0) *slot = -1;
+  __syncthreads();
+  int li = -1;
+  for (int i = tid; i < len; i += 256)
+    if (hist[i] >= ts_begin) li = i;
+  if (li >= 0) atomicMax(slot, li);
+  __syncthreads();
+  li = *slot;
+  TsRule d = {0, ts_begin, V - 1};
+  const bool last_ts = len >= 1 && hist[len - 1] >= ts_begin;
+  const bool pen_ts = len < 2 || hist[len - 2] >= ts_begin;
+  if (last_ts) {
+    if (pen_ts) d.lo = V;                         // a closed pair, or the opening timestamp: text has to follow
+    else d.kind = 1;                              // text, timestamp: only [eos, ts_begin) and timestamps may follow
+  }
+  if (li >= 0) {                                  // timestamps do not decrease; only the one that closes a segment may repeat
+    const int tl = min(hist[li], V - 1);
+    d.lo = max(d.lo, last_ts && !pen_ts ? tl : tl + 1);
+  }
+  if (len == 0) {
+    d.kind = 2;
+    if (max_initial >= 0) d.hi = min(d.hi, ts_begin + min(max_initial, V));
+  }
+  return d;
+}
+
+// PICK: the greedy step (tokens, last, done, sum_logp).  Otherwise the rule descriptor of the row goes to desc[r][0..4) for the
+// beam's chunk kernel: kind, lo, hi, 0.  The generated tokens of row r are tokens[r][n0 .. p].
+template <bool PICK>
+__global__ __launch_bounds__(256) void ts_rule_kernel(const float* __restrict__ logits, long long ld,
+                                                      const int* __restrict__ suppress, int n_sup,
+                                                      const int* __restrict__ begin_suppress, int n_beg, int* tokens, int ld_tok,
+                                                      int* last, int* done, float* sum_logp, int* __restrict__ desc, int V, int p,
+                                                      int n0, int eos, int no_ts, int max_initial) {
+  __shared__ unsigned bits[GP_MAX_V / 32];
+  __shared__ float rm[2][4], rs[2][4];
+  __shared__ int ra[2][4], slot;
+  const int tid = threadIdx.x, r = blockIdx.x;
+  if (PICK && done[r]) {                          // uniform over the workgroup
+    if (tid == 0) tokens[(size_t)r * ld_tok + p + 1] = eos, last[r] = eos;
+    return;
+  }
+  const int words = (V + 31) / 32, ts_begin = no_ts + 1;
+  for (int i = tid; i < words; i += 256) bits[i] = 0u;
+  const TsRule d = ts_rule_of(tokens + (size_t)r * ld_tok + n0, p + 1 - n0, V, ts_begin, max_initial, &slot);   // syncs twice
+  for (int i = tid; i < n_sup + n_beg; i += 256) {
+    const int v = i < n_sup ? suppress[i] : begin_suppress[i - n_sup];
+    if (v >= 0 && v < V) atomicOr(&bits[v >> 5], 1u << (v & 31));
+  }
+  __syncthreads();
+  const float NEG = -__builtin_inff();
+  const float* row = logits + (size_t)r * ld;
+  TsGroup ts = {NEG, 0.f, WAVE_NONE}, tx = {NEG, 0.f, WAVE_NONE};
+  const int text_from = d.kind == 2 ? ts_begin : d.kind == 1 ? eos : 0;
+  for (int v0 = tid; v0 < V; v0 += 1024) {        // ascending per thread: '>' keeps the first maximum
+    float x[4];
+    bool is_ts[4], is_tx[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int v = v0 + 256 * k;
+      x[k] = v < V ? row[v] : NEG;
+      const bool ok = v < V && !((bits[(v >> 5) & (GP_MAX_V / 32 - 1)] >> (v & 31)) & 1u) && v != no_ts && x[k] > NEG &&
+                      x[k] < __builtin_inff();    // NaN, +-inf: no class
+      is_ts[k] = ok && v >= ts_begin && v >= d.lo && v <= d.hi;
+      is_tx[k] = ok && v < ts_begin && v >= text_from;
+    }
+    ts_group_add4(ts, x, is_ts, v0);
+    ts_group_add4(tx, x, is_tx, v0);
+  }
+  ts_group_wave(ts);
+  ts_group_wave(tx);
+  if ((tid & 63) == 0) {
+    const int w = tid >> 6;
+    rm[0][w] = ts.m, rs[0][w] = ts.s, ra[0][w] = ts.a;
+    rm[1][w] = tx.m, rs[1][w] = tx.s, ra[1][w] = tx.a;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    ts = {rm[0][0], rs[0][0], ra[0][0]}, tx = {rm[1][0], rs[1][0], ra[1][0]};
+    for (int w = 1; w < 4; ++w) ts_group_merge(ts, rm[0][w], rs[0][w], ra[0][w]), ts_group_merge(tx, rm[1][w], rs[1][w], ra[1][w]);
+    const float lse_ts = ts.m > NEG ? ts.m + logf(ts.s) : NEG;
+    const bool only_ts = lse_ts > tx.m;           // the sum of the timestamps' probabilities beats every text class
+    if (!PICK) {
+      int* dr = desc + (size_t)r * 4;
+      dr[0] = only_ts ? 2 : d.kind, dr[1] = d.lo, dr[2] = d.hi, dr[3] = 0;
+      return;
+    }
+    if (only_ts) tx = {NEG, 0.f, WAVE_NONE};
+    const bool text_wins = tx.m >= ts.m && tx.a != WAVE_NONE;   // text ids lie below the timestamps: the lower index at a tie
+    int arg = text_wins ? tx.a : ts.a;
+    const float xm = text_wins ? tx.m : ts.m;
+    ts_group_merge(tx, ts.m, ts.s, ts.a);         // all allowed classes: tx.m = xm
+    if (arg == WAVE_NONE) arg = 0;                // nothing is allowed
+    else sum_logp[r] += (xm - tx.m) - logf(tx.s);
+    tokens[(size_t)r * ld_tok + p + 1] = arg;
+    last[r] = arg;
+    if (arg == eos) done[r] = 1;
+  }
+}
+
 // ---- beam step (transformers' GenerationMixin._beam_search: K open rows, a pool of finished hypotheses) ------------------------
 // Launch 1, one workgroup per (row, chunk of WB_CHUNK classes): the chunk goes from memory to LDS once (float4 when the row
 // allows it); its maximum and sum of exponentials cover ALL its classes, then the suppressed ones become -inf and the 2K largest
@@ -272,7 +431,7 @@ __global__ __launch_bounds__(256) void beam_chunk_kernel(const float* __restrict
                                                          const int* __restrict__ suppress, int n_sup,
                                                          const int* __restrict__ begin_suppress, int n_beg,
                                                          const float* __restrict__ score, float* __restrict__ scratch, int V,
-                                                         int K, int vec) {
+                                                         int K, int vec, const int* __restrict__ desc, int eos, int no_ts) {
   __shared__ __attribute__((aligned(16))) float x[WB_CHUNK];
   __shared__ float rm[4];
   __shared__ int ra[4];
@@ -306,6 +465,14 @@ __global__ __launch_bounds__(256) void beam_chunk_kernel(const float* __restrict
   for (int i = tid; i < n_sup + n_beg; i += 256) {
     const int v = (i < n_sup ? suppress[i] : begin_suppress[i - n_sup]) - c0;
     if (v >= 0 && v < n) x[v] = NEG;
+  }
+  if (desc) {                                                      // the row's timestamp rules (ts_rule_kernel): one more mask
+    const int kind = desc[4 * r], lo = desc[4 * r + 1], hi = desc[4 * r + 2], ts_begin = no_ts + 1;
+    const int text_from = kind == 2 ? ts_begin : kind == 1 ? eos : 0;
+    for (int i = tid; i < n; i += 256) {
+      const int v = c0 + i;
+      if (v == no_ts || (v >= ts_begin ? (v < lo || v > hi) : v < text_from)) x[i] = NEG;
+    }
   }
   __syncthreads();
   float* rec = scratch + ((size_t)r * gridDim.y + c) * wb_rec(K);
@@ -494,12 +661,12 @@ extern "C" int f5e_whisper_beam_scratch(int B, int K, int V, unsigned long long*
   return F5E_OK;
 }
 
-extern "C" int f5e_whisper_beam_step(hipStream_t st, const float* logits, long long ld_logits, const int* suppress, int n_sup,
-                                     const int* begin_suppress, int n_beg, float* score, const int* hyp_in, const int* anc_in,
-                                     int* hyp_out, int* anc_out, int ld, int* last, int* pool_hyp, int* pool_len,
-                                     float* pool_score, int* pool_n, int* open, int* alive, void* scratch,
-                                     unsigned long long scratch_bytes, int B, int K, int V, int p, int n0, int cap, int eos,
-                                     float length_penalty) {
+// desc == nullptr: the step without the timestamp rules.  Otherwise i32 [B*K][4], filled here by ts_rule_kernel from hyp_in.
+static int beam_step_impl(hipStream_t st, const float* logits, long long ld_logits, const int* suppress, int n_sup,
+                          const int* begin_suppress, int n_beg, float* score, const int* hyp_in, const int* anc_in, int* hyp_out,
+                          int* anc_out, int ld, int* last, int* pool_hyp, int* pool_len, float* pool_score, int* pool_n, int* open,
+                          int* alive, void* scratch, unsigned long long scratch_bytes, int B, int K, int V, int p, int n0, int cap,
+                          int eos, float length_penalty, int* desc, int no_ts, int max_initial) {
   F5E_REQUIRE(logits && score && hyp_in && anc_in && hyp_out && anc_out && last && pool_hyp && pool_len && pool_score && pool_n &&
                   open && alive && scratch,
               "whisper_beam_step: null operand");
@@ -521,13 +688,47 @@ extern "C" int f5e_whisper_beam_step(hipStream_t st, const float* logits, long l
   F5E_REQUIRE(scratch_bytes >= need && ((uintptr_t)scratch & 3) == 0,
               "whisper_beam_step: scratch of %llu bytes, 4-byte aligned (f5e_whisper_beam_scratch); got %llu", need, scratch_bytes);
   const int vec = ld_logits % 4 == 0 && ((uintptr_t)logits & 15) == 0;
+  if (desc)
+    hipLaunchKernelGGL(ts_rule_kernel<false>, dim3((unsigned)(B * K)), dim3(256), 0, st, logits, ld_logits, suppress, n_sup,
+                       begin_suppress, p + 1 == n0 ? n_beg : 0, const_cast<int*>(hyp_in), ld, nullptr, nullptr, nullptr, desc, V, p,
+                       n0, eos, no_ts, max_initial);
   hipLaunchKernelGGL(beam_chunk_kernel, dim3((unsigned)(B * K), (unsigned)NCH), dim3(256), 0, st, logits, ld_logits, suppress,
-                     n_sup, begin_suppress, p + 1 == n0 ? n_beg : 0, score, (float*)scratch, V, K, vec);
+                     n_sup, begin_suppress, p + 1 == n0 ? n_beg : 0, score, (float*)scratch, V, K, vec, desc, eos, no_ts);
   hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)B), dim3(256), 0, st, score, hyp_in, anc_in, hyp_out, anc_out, ld, last,
                      pool_hyp, pool_len, pool_score, pool_n, open, alive, (float*)scratch, NCH, K, p, n0, cap, eos,
                      length_penalty);
   F5E_LAUNCH_CHECK("whisper_beam_step");
   return F5E_OK;
+}
+
+extern "C" int f5e_whisper_beam_step(hipStream_t st, const float* logits, long long ld_logits, const int* suppress, int n_sup,
+                                     const int* begin_suppress, int n_beg, float* score, const int* hyp_in, const int* anc_in,
+                                     int* hyp_out, int* anc_out, int ld, int* last, int* pool_hyp, int* pool_len,
+                                     float* pool_score, int* pool_n, int* open, int* alive, void* scratch,
+                                     unsigned long long scratch_bytes, int B, int K, int V, int p, int n0, int cap, int eos,
+                                     float length_penalty) {
+  return beam_step_impl(st, logits, ld_logits, suppress, n_sup, begin_suppress, n_beg, score, hyp_in, anc_in, hyp_out, anc_out, ld,
+                        last, pool_hyp, pool_len, pool_score, pool_n, open, alive, scratch, scratch_bytes, B, K, V, p, n0, cap, eos,
+                        length_penalty, nullptr, 0, -1);
+}
+
+// The arguments every ruled entry shares: <|notimestamps|> is a class with at least one timestamp above it.
+#define F5E_TS_REQUIRE(name)                                                                                                  \
+  F5E_REQUIRE(no_timestamps >= 0 && no_timestamps + 1 < V && eos <= no_timestamps && max_initial >= -1,                        \
+              name ": need 0 <= eos <= no_timestamps < V - 1 and max_initial >= -1 (eos=%d no_timestamps=%d V=%d "              \
+                   "max_initial=%d)", eos, no_timestamps, V, max_initial)
+
+extern "C" int f5e_whisper_beam_step_ts(hipStream_t st, const float* logits, long long ld_logits, const int* suppress, int n_sup,
+                                        const int* begin_suppress, int n_beg, float* score, const int* hyp_in, const int* anc_in,
+                                        int* hyp_out, int* anc_out, int ld, int* last, int* pool_hyp, int* pool_len,
+                                        float* pool_score, int* pool_n, int* open, int* alive, void* scratch,
+                                        unsigned long long scratch_bytes, int B, int K, int V, int p, int n0, int cap, int eos,
+                                        float length_penalty, int no_timestamps, int max_initial, int* desc) {
+  F5E_REQUIRE(desc, "whisper_beam_step_ts: null operand");
+  F5E_TS_REQUIRE("whisper_beam_step_ts");
+  return beam_step_impl(st, logits, ld_logits, suppress, n_sup, begin_suppress, n_beg, score, hyp_in, anc_in, hyp_out, anc_out, ld,
+                        last, pool_hyp, pool_len, pool_score, pool_n, open, alive, scratch, scratch_bytes, B, K, V, p, n0, cap, eos,
+                        length_penalty, desc, no_timestamps, max_initial);
 }
 
 extern "C" int f5e_whisper_logmel_partials(int B, int T, unsigned long long* floats_out_host) {
@@ -600,5 +801,47 @@ extern "C" int f5e_greedy_pick(hipStream_t st, const float* logits, long long ld
                      first_step ? n_beg : 0, tokens, ld_tok, last, done, V, p, eos);
   hipLaunchKernelGGL(alive_count_kernel, dim3(1), dim3(256), 0, st, done, alive, R);
   F5E_LAUNCH_CHECK("greedy_pick");
+  return F5E_OK;
+}
+
+static int ts_check(const char* name, const float* logits, long long ld, const int* suppress, int n_sup, const int* begin_suppress,
+                    int n_beg, const int* tokens, int ld_tok, int R, int V, int p, int n0, int eos) {
+  F5E_REQUIRE(logits && tokens, "%s: null operand", name);
+  F5E_REQUIRE(R > 0 && R <= 0x7fffffff / 2 && V >= 2 && V <= GP_MAX_V && ld >= V,
+              "%s: need R > 0, 2 <= V <= %d and ld >= V (R=%d V=%d)", name, GP_MAX_V, R, V);
+  F5E_REQUIRE(n_sup >= 0 && n_beg >= 0 && (n_sup == 0 || suppress) && (n_beg == 0 || begin_suppress),
+              "%s: a suppression list without its pointer", name);
+  F5E_REQUIRE(n0 >= 1 && p >= n0 - 1 && ld_tok >= p + 2,
+              "%s: need n0 >= 1, p >= n0 - 1 and token rows of at least p + 2 columns (n0=%d p=%d ld_tok=%d)", name, n0, p, ld_tok);
+  F5E_REQUIRE(eos >= 0 && eos < V, "%s: need 0 <= eos < V", name);
+  return F5E_OK;
+}
+
+extern "C" int f5e_whisper_ts_pick(hipStream_t st, const float* logits, long long ld, const int* suppress, int n_sup,
+                                   const int* begin_suppress, int n_beg, int* tokens, int ld_tok, int* last, int* done, int* alive,
+                                   float* sum_logp, int R, int V, int p, int n0, int eos, int no_timestamps, int max_initial) {
+  F5E_REQUIRE(last && done && alive && sum_logp, "whisper_ts_pick: null operand");
+  const int rc = ts_check("whisper_ts_pick", logits, ld, suppress, n_sup, begin_suppress, n_beg, tokens, ld_tok, R, V, p, n0, eos);
+  if (rc != F5E_OK) return rc;
+  F5E_TS_REQUIRE("whisper_ts_pick");
+  hipLaunchKernelGGL(ts_rule_kernel<true>, dim3((unsigned)R), dim3(256), 0, st, logits, ld, suppress, n_sup, begin_suppress,
+                     p + 1 == n0 ? n_beg : 0, tokens, ld_tok, last, done, sum_logp, nullptr, V, p, n0, eos, no_timestamps,
+                     max_initial);
+  hipLaunchKernelGGL(alive_count_kernel, dim3(1), dim3(256), 0, st, done, alive, R);
+  F5E_LAUNCH_CHECK("whisper_ts_pick");
+  return F5E_OK;
+}
+
+extern "C" int f5e_whisper_ts_rule(hipStream_t st, const float* logits, long long ld, const int* suppress, int n_sup,
+                                   const int* begin_suppress, int n_beg, const int* tokens, int ld_tok, int* desc, int R, int V,
+                                   int p, int n0, int eos, int no_timestamps, int max_initial) {
+  F5E_REQUIRE(desc, "whisper_ts_rule: null operand");
+  const int rc = ts_check("whisper_ts_rule", logits, ld, suppress, n_sup, begin_suppress, n_beg, tokens, ld_tok, R, V, p, n0, eos);
+  if (rc != F5E_OK) return rc;
+  F5E_TS_REQUIRE("whisper_ts_rule");
+  hipLaunchKernelGGL(ts_rule_kernel<false>, dim3((unsigned)R), dim3(256), 0, st, logits, ld, suppress, n_sup, begin_suppress,
+                     p + 1 == n0 ? n_beg : 0, const_cast<int*>(tokens), ld_tok, nullptr, nullptr, nullptr, desc, V, p, n0, eos,
+                     no_timestamps, max_initial);
+  F5E_LAUNCH_CHECK("whisper_ts_rule");
   return F5E_OK;
 }

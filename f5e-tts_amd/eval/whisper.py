@@ -19,9 +19,13 @@ Token and word times (``token_timestamps``, ``generate(return_token_timestamps=T
 ``align``): the alignment heads' cross-attention, normalised, median-filtered and warped (f5e_cross_attn_probs_f32,
 f5e_dtw_cost_f32, f5e_dtw_path; csrc/whisper_align.hip).
 
-Out of scope: temperature fallback, segment timestamp tokens and their logit rules, long-form chunking, language detection
-(``language`` is required), patience, CTranslate2's exact search, bf16 / fp16 weights (fp16 checkpoints are widened), a
-graph-captured step.
+Timestamp tokens and long recordings (``generate(return_timestamps=True)``, ``transcribe_long``, ``detect_language``): the rules
+of ``WhisperTimeStampLogitsProcessor`` on the device (f5e_whisper_ts_pick, f5e_whisper_beam_step_ts) and the sequential seek loop
+of ``transformers``' long-form ``generate`` with ``condition_on_prev_tokens=False`` at temperature 0.
+
+Out of scope: temperature fallback and sampling, conditioning on previous windows and ``prompt_ids``, the pipeline's strided
+``chunk_length_s`` merging, word timestamps across windows, patience, CTranslate2's exact search, bf16 / fp16 weights (fp16
+checkpoints are widened), a graph-captured step.
 
 Ragged batches: samples at or beyond ``lens[b]`` count as zero, and the row is zero-padded to the chunk length as the feature
 extractor does; Whisper attends those frames, and so does this.  Row b of a batch equals its own B = 1 run."""
@@ -77,6 +81,8 @@ class WhisperConfig:
     task_to_id: Dict[str, int] = field(default_factory=dict)
     no_timestamps_token_id: Optional[int] = None
     alignment_heads: Tuple[Tuple[int, int], ...] = ()       # (decoder layer, head) pairs; empty: no token timestamps
+    max_initial_timestamp_index: Optional[int] = None       # the first timestamp of a window is at most this many steps of 0.02 s
+    prev_sot_token_id: Optional[int] = None                 # <|startofprev|>: read, never fed (conditioning is out of scope)
     median_filter_width: int = 7                            # config.json
 
     @classmethod
@@ -85,7 +91,7 @@ class WhisperConfig:
         kw = {k: v for k, v in config.items() if k in names and v is not None}
         for k, v in (generation or {}).items():
             if k in ("suppress_tokens", "begin_suppress_tokens", "lang_to_id", "task_to_id", "no_timestamps_token_id",
-                     "alignment_heads") and v is not None:
+                     "alignment_heads", "max_initial_timestamp_index", "prev_sot_token_id") and v is not None:
                 kw[k] = v
         for k in ("suppress_tokens", "begin_suppress_tokens"):
             kw[k] = tuple(int(t) for t in kw.get(k) or ())
@@ -97,6 +103,21 @@ class WhisperConfig:
         if isinstance(eos, (list, tuple)):
             kw["eos_token_id"] = int(eos[0])
         return cls(**kw)
+
+    @property
+    def timestamp_begin(self) -> int:
+        """The id of <|0.00|>: the class after <|notimestamps|>.  Refused by name when the generation config lacks it."""
+        if self.no_timestamps_token_id is None:
+            raise _C.F5EError("Whisper: generation_config has no no_timestamps_token_id; timestamp decoding needs it")
+        if not self.eos_token_id <= self.no_timestamps_token_id < self.vocab_size - 1:
+            raise _C.F5EError(f"Whisper: no_timestamps_token_id = {self.no_timestamps_token_id} leaves no timestamp classes "
+                              f"(eos {self.eos_token_id}, vocab_size {self.vocab_size})")
+        return self.no_timestamps_token_id + 1
+
+    @property
+    def no_speech_token_id(self) -> int:
+        """<|nospeech|> = no_timestamps_token_id - 1, the way ``transformers`` derives it for its no-speech detector."""
+        return self.timestamp_begin - 2
 
     def check(self) -> None:
         def refuse(name, why):
@@ -266,6 +287,65 @@ def group_tokens(id_to_piece: Dict[int, str], first_special: int, ids: Sequence[
     return [words[k] for k in keep], [index[k] for k in keep]
 
 
+# ---- long-form: a window's tokens -> segments (transformers' generation_whisper.py: _retrieve_segment) ----------------------------
+TIME_PRECISION, INPUT_STRIDE = 0.02, 2      # seconds per timestamp step; mel frames per encoder position
+
+
+@dataclass
+class Segment:
+    """One segment of ``transcribe_long``: times in seconds from the start of the recording, the tokens of the slice (its
+    timestamp tokens included), the window's first frame, and the window's figures (shared by the segments of a window)."""
+    start_s: float
+    end_s: float
+    tokens: List[int]
+    seek: int
+    avg_logprob: float
+    no_speech_prob: float
+    compression_ratio: float
+
+
+def split_segments(seq: Sequence[int], ts_begin: int, seek_frames: int, num_frames: int
+                   ) -> Tuple[List[Tuple[float, float, List[int]]], int]:
+    """The generated tokens of one window (prompt and closing eos removed) -> ([(start_s, end_s, tokens)], mel frames by which
+    the window advances).  ``seek_frames``: the window's first frame, ``num_frames``: the frames of the recording it covers.
+      * consecutive timestamp pairs cut the sequence; a segment runs from its first token's time to its closing timestamp's;
+      * the sequence ends ``text, timestamp`` (single timestamp ending): the rest is the last segment, and the whole window is
+        consumed; otherwise what follows the last pair is dropped and the next window starts at that pair's time;
+      * no pair at all: one segment over the window, ending at the last timestamp if there is one other than <|0.00|>, else
+        at the window's end (``int(num_frames * 0.01 / 0.02)`` steps, in float32 as the reference evaluates it).
+    Times are float64: seek_frames * 0.02 / 2 + steps * 0.02."""
+    seq = [int(t) for t in seq]
+    is_ts = [t >= ts_begin for t in seq]
+    offset = float(seek_frames) * TIME_PRECISION / INPUT_STRIDE
+    single = is_ts[-2:] == [False, True]
+    cuts = [i + 1 for i in range(len(seq) - 1) if is_ts[i] and is_ts[i + 1]]
+    if not cuts:
+        stamps = [t for t in seq if t >= ts_begin]
+        last_pos = int(np.float32(num_frames) * np.float32(0.01) / np.float32(TIME_PRECISION))
+        if stamps and stamps[-1] != ts_begin:
+            last_pos = float(stamps[-1] - ts_begin)
+        return [(offset, offset + last_pos * TIME_PRECISION, seq)], int(num_frames)
+    if single:
+        cuts.append(len(seq))
+    else:
+        cuts[-1] += 1                          # the last segment keeps the pair's second timestamp
+    out, lo = [], 0
+    for k, hi in enumerate(cuts):
+        piece = seq[lo:hi]
+        end_tok = piece[-1] if (k < len(cuts) - 1 or single) else piece[-2]
+        out.append((offset + float(piece[0] - ts_begin) * TIME_PRECISION, offset + float(end_tok - ts_begin) * TIME_PRECISION, piece))
+        lo = hi
+    return out, int(num_frames) if single else (seq[lo - 2] - ts_begin) * INPUT_STRIDE
+
+
+def compression_ratio(tokens: Sequence[int], vocab_size: int) -> float:
+    """zlib on the tokens' little-endian bytes, as ``_retrieve_compression_ratio``: reported, never acted on."""
+    import zlib
+    width = int(math.log2(vocab_size) / 8) + 1
+    raw = b"".join(int(t).to_bytes(width, "little") for t in tokens)
+    return len(raw) / len(zlib.compress(raw)) if raw else 0.0
+
+
 # ---- checkpoint reading (the safetensors container: u64 header length, JSON header, raw little-endian data) ---------------------
 _ST_DTYPES = {"F32": np.dtype("<f4"), "F16": np.dtype("<f2"), "BF16": np.dtype("<u2"), "F64": np.dtype("<f8")}
 
@@ -337,6 +417,13 @@ class _Model(nn.Module):
     def __init__(self, cfg: WhisperConfig):
         super().__init__()
         self.encoder, self.decoder = _Encoder(cfg), _Decoder(cfg)
+
+
+def _prompt_len(prompt) -> int:
+    """Tokens of a prompt given as ids for all rows or as [B, n0] ids."""
+    if isinstance(prompt, Tensor):
+        return prompt.shape[-1]
+    return len(prompt[0]) if len(prompt) and isinstance(prompt[0], (list, tuple)) else len(prompt)
 
 
 def _f(t: Tensor, dev) -> Tensor:
@@ -471,6 +558,9 @@ class Whisper(nn.Module):
             fd["dec"].append(d)
         fd["suppress"] = torch.tensor(list(cfg.suppress_tokens), dtype=I32, device=dev) if cfg.suppress_tokens else None
         fd["begin_suppress"] = torch.tensor(list(cfg.begin_suppress_tokens), dtype=I32, device=dev) if cfg.begin_suppress_tokens else None
+        # language detection = a greedy pick that suppresses every class but the language ids
+        langs = {int(v) for v in cfg.lang_to_id.values()}
+        fd["not_lang"] = torch.tensor([v for v in range(cfg.vocab_size) if v not in langs], dtype=I32, device=dev) if langs else None
         # alignment heads, in the order of the list: layer -> [(first slot, heads i32 [k])], one entry per run of consecutive pairs
         # of that layer (one f5e_cross_attn_probs_f32 launch each)
         fd["align"] = {}
@@ -626,8 +716,9 @@ class Whisper(nn.Module):
             out[:, p] = self._dec_step(st, kv, ids[:, p].contiguous(), p, True)
         return out
 
-    def prompt_ids(self, language: str, task: str = "transcribe") -> List[int]:
-        """``<|startoftranscript|> <|lang|> <|task|> <|notimestamps|>``: what the reference's forced_decoder_ids produce."""
+    def prompt_ids(self, language: str, task: str = "transcribe", timestamps: bool = False) -> List[int]:
+        """``<|startoftranscript|> <|lang|> <|task|> <|notimestamps|>``: what the reference's forced_decoder_ids produce.
+        ``timestamps``: without the last token (the model then emits timestamp tokens)."""
         cfg = self.cfg
         if not language:
             raise _C.F5EError("Whisper: language is required (language detection is out of scope)")
@@ -640,7 +731,44 @@ class Whisper(nn.Module):
             raise _C.F5EError(f"Whisper: task {task!r} is not in generation_config.task_to_id ({sorted(cfg.task_to_id)})")
         if cfg.no_timestamps_token_id is None:
             raise _C.F5EError("Whisper: generation_config has no no_timestamps_token_id")
-        return [cfg.decoder_start_token_id, cfg.lang_to_id[key], cfg.task_to_id[task], cfg.no_timestamps_token_id]
+        ids = [cfg.decoder_start_token_id, cfg.lang_to_id[key], cfg.task_to_id[task], cfg.no_timestamps_token_id]
+        return ids[:3] if timestamps else ids
+
+    def _prompt_rows(self, prompt, B: int, dev) -> Tensor:
+        """One prompt for all rows (a sequence of ids) or one per row ([B, n0], equal lengths) -> i32 [B, n0] on the device."""
+        t = prompt if isinstance(prompt, Tensor) else torch.tensor(np.asarray(prompt, dtype=np.int64))
+        t = t.to(device=dev, dtype=I32)
+        if t.ndim == 1:
+            t = t[None, :].expand(B, -1)
+        if t.ndim != 2 or t.shape[0] != B:
+            raise _C.F5EError(f"Whisper.generate: the prompt must be n0 ids or [{B}, n0] ids (got shape {tuple(t.shape)})")
+        return t.contiguous()
+
+    @torch.no_grad()
+    def detect_language(self, kv: List[Tuple[Tensor, Tensor]]) -> Tensor:
+        """-> i32 [B]: the language id of every utterance, ``transformers``' ``detect_language``: one cached step on
+        ``<|startoftranscript|>``, then the first maximum over the ids of ``lang_to_id`` (f5e_greedy_pick with every other class
+        suppressed)."""
+        cfg, fd = self.cfg, self._fold()
+        if fd["not_lang"] is None:
+            raise _C.F5EError("Whisper.detect_language: generation_config has no lang_to_id")
+        B, dev = kv[0][0].shape[0], kv[0][0].device
+        tokens = torch.full((B, 2), cfg.decoder_start_token_id, dtype=I32, device=dev)
+        last, done = tokens[:, 0].clone(), torch.zeros(B, dtype=I32, device=dev)
+        logits = self._dec_step(self._dec_state(B, 1, dev), kv, last, 0, True)
+        ops.greedy_pick(logits, tokens, last, done, torch.zeros(1, dtype=I32, device=dev), 0, cfg.eos_token_id, suppress=fd["not_lang"])
+        return last
+
+    def _prompts(self, kv, language, task: str, timestamps: bool):
+        """The prompt of ``generate``: a list of ids for a named language, i32 [B, n0] with the detected ids for None."""
+        if language is not None:
+            return self.prompt_ids(language, task, timestamps)
+        if not self.cfg.lang_to_id:
+            raise _C.F5EError("Whisper: language = None asks for detection, but generation_config has no lang_to_id")
+        ids = self.prompt_ids(sorted(self.cfg.lang_to_id)[0], task, timestamps)      # checks task and no_timestamps_token_id
+        rows = torch.tensor(ids, dtype=I32, device=kv[0][0].device)[None, :].repeat(kv[0][0].shape[0], 1)
+        rows[:, 1] = self.detect_language(kv)
+        return rows
 
     # ---- token timestamps (DESIGN 4o: alignment heads and DTW) ------------------------------------------------------------------
     @torch.no_grad()
@@ -718,57 +846,84 @@ class Whisper(nn.Module):
     @torch.no_grad()
     def generate_from_kv(self, kv: List[Tuple[Tensor, Tensor]], prompt: Sequence[int], max_new_tokens: Optional[int] = None,
                          sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0, return_beams: bool = False,
-                         return_token_timestamps: bool = False, frames=None):
-        """``generate`` from the cross keys / values.  ``return_token_timestamps``: one more item at the end, the times f32
-        [B, U] of the returned best hypothesis = ``token_timestamps`` on the returned tokens (a teacher-forced pass after the
-        search, greedy or beam); ``frames``: mel frames per utterance (None: the whole chunk)."""
+                         return_token_timestamps: bool = False, frames=None, return_timestamps: bool = False,
+                         stats: Optional[dict] = None):
+        """``generate`` from the cross keys / values.  ``prompt``: ids for all rows, or [B, n0] ids.  ``return_token_timestamps``:
+        one more item at the end, the times f32 [B, U] of the returned best hypothesis = ``token_timestamps`` on the returned
+        tokens (a teacher-forced pass after the search, greedy or beam); ``frames``: mel frames per utterance (None: the whole
+        chunk).  ``return_timestamps``: the picks follow Whisper's timestamp rules (f5e_whisper_ts_pick /
+        f5e_whisper_beam_step_ts; the prompt must not end in <|notimestamps|>).  ``stats``: a dict that receives
+        ``no_speech_logp`` f32 [B] (the log-probability of <|nospeech|> after <|startoftranscript|>) and ``sum_logp`` f32 [B]
+        (ruled greedy: the sum of the picks' log-probabilities among the allowed classes; beam: the best hypothesis' score times
+        its generated length)."""
+        n0 = _prompt_len(prompt)
         if return_token_timestamps:
             if not self.cfg.alignment_heads:
                 raise _C.F5EError("Whisper.generate: return_token_timestamps needs alignment_heads in generation_config.json")
-            res = self.generate_from_kv(kv, prompt, max_new_tokens, sync_every, beam_size, length_penalty, return_beams)
-            times = self.token_timestamps(kv, res[0], res[1], self.n_frames if frames is None else frames, len(prompt))
+            res = self.generate_from_kv(kv, prompt, max_new_tokens, sync_every, beam_size, length_penalty, return_beams,
+                                        return_timestamps=return_timestamps, stats=stats)
+            times = self.token_timestamps(kv, res[0], res[1], self.n_frames if frames is None else frames, n0)
             return tuple(res) + (times,)
         if int(beam_size) != 1 or return_beams:
-            return self._beam_from_kv(kv, prompt, max_new_tokens, sync_every, int(beam_size), float(length_penalty), return_beams)
+            if not return_timestamps and stats is None:
+                return self._beam_from_kv(kv, prompt, max_new_tokens, sync_every, int(beam_size), float(length_penalty), return_beams)
+            return self._beam_from_kv(kv, prompt, max_new_tokens, sync_every, int(beam_size), float(length_penalty), return_beams,
+                                      bool(return_timestamps), stats)
         cfg, fd = self.cfg, self._fold()
         B = kv[0][0].shape[0]
         dev = kv[0][0].device
-        n0 = len(prompt)
+        ts_begin = cfg.timestamp_begin if return_timestamps else None
         Umax = cfg.max_target_positions if max_new_tokens is None else min(cfg.max_target_positions, n0 + int(max_new_tokens))
         if n0 < 1 or n0 >= Umax or sync_every < 1:
             raise _C.F5EError(f"Whisper.generate: a prompt of {n0} tokens leaves no room below {Umax} positions (or sync_every < 1)")
         eos = cfg.eos_token_id
         tokens = torch.full((B, Umax), eos, dtype=I32, device=dev)
-        tokens[:, :n0] = torch.tensor(list(prompt), dtype=I32, device=dev)
+        tokens[:, :n0] = self._prompt_rows(prompt, B, dev)
         last = tokens[:, 0].clone()
         done = torch.zeros(B, dtype=I32, device=dev)
         alive = torch.full((1,), B, dtype=I32, device=dev)
+        sum_logp = torch.zeros(B, dtype=F32, device=dev) if return_timestamps else None
         st = self._dec_state(B, Umax, dev)
         for p in range(Umax - 1):
             forced = p + 1 < n0
-            logits = self._dec_step(st, kv, last, p, not forced)
+            logits = self._dec_step(st, kv, last, p, not forced or (p == 0 and stats is not None))
+            if p == 0 and stats is not None:
+                stats["no_speech_logp"] = self._no_speech_logp(logits)
             if forced:                       # all prompt tokens but the last go through the same cached step; nothing is picked
                 last.copy_(tokens[:, p + 1])
                 continue
-            ops.greedy_pick(logits, tokens, last, done, alive, p, eos, suppress=fd["suppress"], begin_suppress=fd["begin_suppress"],
-                            first_step=p + 1 == n0)
+            if return_timestamps:
+                ops.whisper_ts_pick(logits, tokens, last, done, alive, sum_logp, p, n0, eos, ts_begin - 1, suppress=fd["suppress"],
+                                    begin_suppress=fd["begin_suppress"], max_initial=cfg.max_initial_timestamp_index)
+            else:
+                ops.greedy_pick(logits, tokens, last, done, alive, p, eos, suppress=fd["suppress"],
+                                begin_suppress=fd["begin_suppress"], first_step=p + 1 == n0)
             if (p + 2 - n0) % sync_every == 0 and int(alive.item()) == 0:
                 break
         # a finished row holds eos from its end on (done rows keep getting eos; untouched columns were eos from the start)
         gen = tokens[:, n0:]
         is_eos = gen == eos
         first = torch.where(is_eos.any(1), is_eos.to(torch.int64).argmax(1) + 1, torch.full((B,), Umax - n0, dtype=torch.int64, device=dev))
+        if stats is not None:
+            stats["sum_logp"] = sum_logp
         return tokens, (first + n0).to(I32)
+
+    def _no_speech_logp(self, logits: Tensor) -> Tensor:
+        """log softmax(logits)[<|nospeech|>] per row (f5e_token_logp), from the step that fed <|startoftranscript|>."""
+        target = torch.full((logits.shape[0],), self.cfg.no_speech_token_id, dtype=I32, device=logits.device)
+        return ops.token_logp(logits, target)
 
     @torch.no_grad()
     def _beam_from_kv(self, kv: List[Tuple[Tensor, Tensor]], prompt: Sequence[int], max_new_tokens: Optional[int], sync_every: int,
-                      K: int, length_penalty: float, return_beams: bool):
+                      K: int, length_penalty: float, return_beams: bool, ts: bool = False, stats: Optional[dict] = None):
         """The pooled beam search (f5e_whisper_beam_step has the rules): B * K rows, row b K + i = open hypothesis i of utterance
         b.  Every layer's self-attention follows the ancestry table, the cross-attention reads an utterance's keys once for its
         K rows, and no cache row ever moves.  The prompt goes through the same step without a pick (the K rows of an utterance
         are equal until the first pick).  Caches: K x the greedy figure, sized by the prompt + ``max_new_tokens`` when given."""
         cfg = self.cfg
-        V, eos, n0 = cfg.vocab_size, cfg.eos_token_id, len(prompt)
+        V, eos = cfg.vocab_size, cfg.eos_token_id
+        n0 = _prompt_len(prompt)
+        ts_begin = cfg.timestamp_begin if ts else None
         banned = {t for t in tuple(cfg.suppress_tokens) + tuple(cfg.begin_suppress_tokens) if 0 <= t < V}
         if not 1 <= K <= 16:
             raise _C.F5EError(f"Whisper.generate: beam_size must lie in 1 .. 16 (got {K})")
@@ -784,8 +939,10 @@ class Whisper(nn.Module):
                               f"or more than 65535 rows)")
         hyp = [torch.full((R, Umax), eos, dtype=I32, device=dev) for _ in range(2)]
         anc = [torch.arange(R, dtype=I32, device=dev)[:, None].repeat(1, Umax) for _ in range(2)]   # prompt: a row's own cache
+        rows = self._prompt_rows(prompt, B, dev).repeat_interleave(K, 0)
         for h in hyp:
-            h[:, :n0] = torch.tensor(list(prompt), dtype=I32, device=dev)
+            h[:, :n0] = rows
+        desc = torch.zeros(R, 4, dtype=I32, device=dev) if ts else None
         last = hyp[0][:, 0].clone()
         score = torch.full((B, K), -math.inf, dtype=F32, device=dev)
         score[:, 0] = 0.0
@@ -799,13 +956,21 @@ class Whisper(nn.Module):
         cur = 0
         for p in range(Umax - 1):
             forced = p + 1 < n0
-            logits = self._dec_step(st, kv, last, p, not forced, anc=anc[cur])
+            logits = self._dec_step(st, kv, last, p, not forced or (p == 0 and stats is not None), anc=anc[cur])
+            if p == 0 and stats is not None:
+                stats["no_speech_logp"] = self._no_speech_logp(logits)[::K].contiguous()
             if forced:
                 last.copy_(hyp[0][:, p + 1])
                 continue
-            ops.whisper_beam_step(logits, score, hyp[cur], anc[cur], hyp[1 - cur], anc[1 - cur], last, pool_hyp, pool_len,
-                                  pool_score, pool_n, open_, alive, p, n0, Umax, eos, K, suppress=fd["suppress"],
-                                  begin_suppress=fd["begin_suppress"], length_penalty=length_penalty, scratch=scratch)
+            if ts:
+                ops.whisper_beam_step_ts(logits, score, hyp[cur], anc[cur], hyp[1 - cur], anc[1 - cur], last, pool_hyp, pool_len,
+                                         pool_score, pool_n, open_, alive, p, n0, Umax, eos, K, ts_begin - 1, desc,
+                                         max_initial=cfg.max_initial_timestamp_index, suppress=fd["suppress"],
+                                         begin_suppress=fd["begin_suppress"], length_penalty=length_penalty, scratch=scratch)
+            else:
+                ops.whisper_beam_step(logits, score, hyp[cur], anc[cur], hyp[1 - cur], anc[1 - cur], last, pool_hyp, pool_len,
+                                      pool_score, pool_n, open_, alive, p, n0, Umax, eos, K, suppress=fd["suppress"],
+                                      begin_suppress=fd["begin_suppress"], length_penalty=length_penalty, scratch=scratch)
             cur = 1 - cur
             if (p + 2 - n0) % sync_every == 0 and int(alive.sum().item()) == 0:
                 break
@@ -813,12 +978,14 @@ class Whisper(nn.Module):
         col = torch.arange(Umax, device=dev)
         beams = torch.where(col[None, None, :] < pool_len[:, :, None], pool_hyp, torch.full_like(pool_hyp, eos))
         best = (beams[:, 0].contiguous(), pool_len[:, 0].contiguous())
+        if stats is not None:
+            stats["sum_logp"] = pool_score[:, 0] * (pool_len[:, 0] - n0).clamp(min=1).to(F32) ** length_penalty
         return best + ((beams, pool_len, pool_score),) if return_beams else best
 
     @torch.no_grad()
     def generate(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe",
                  max_new_tokens: Optional[int] = None, sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0,
-                 return_beams: bool = False, return_token_timestamps: bool = False):
+                 return_beams: bool = False, return_token_timestamps: bool = False, return_timestamps: bool = False):
         """Recognition of B utterances: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> (tokens i32 [B, U] starting
         with the prompt, eos from a row's end on; n i32 [B] = tokens of every row, its closing eos included when it ended by
         itself).  The host reads the alive count every ``sync_every`` steps; the result does not depend on it.  The bound is
@@ -827,28 +994,130 @@ class Whisper(nn.Module):
         per utterance; the best finished hypothesis is returned in the same layout, and with ``return_beams`` a third item
         (pool tokens i32 [B, K, U], lens i32 [B, K], scores f32 [B, K] = sum of log-probabilities / generated length **
         length_penalty, best first).  ``return_token_timestamps``: one more item at the end, times f32 [B, U] in seconds of the
-        returned tokens (``token_timestamps``; needs ``alignment_heads`` in the generation config)."""
-        prompt = self.prompt_ids(language, task)
-        if not return_token_timestamps:
+        returned tokens (``token_timestamps``; needs ``alignment_heads`` in the generation config).  ``language`` None: detected
+        per row (``detect_language``); "" is refused as before.  ``return_timestamps``: the prompt has no <|notimestamps|> and
+        the picks follow the timestamp rules, so the tokens carry <|t|> ids (``cfg.timestamp_begin`` + t / 0.02)."""
+        if language is not None and not return_timestamps:
+            prompt = self.prompt_ids(language, task)
+            if not return_token_timestamps:
+                return self.generate_from_kv(self.encode(wav, lens), prompt, max_new_tokens, sync_every, beam_size, length_penalty,
+                                             return_beams)
             return self.generate_from_kv(self.encode(wav, lens), prompt, max_new_tokens, sync_every, beam_size, length_penalty,
-                                         return_beams)
-        return self.generate_from_kv(self.encode(wav, lens), prompt, max_new_tokens, sync_every, beam_size, length_penalty,
-                                     return_beams, True, self._frames_of(wav, lens))
+                                         return_beams, True, self._frames_of(wav, lens))
+        if return_timestamps:
+            self.cfg.timestamp_begin                                    # refused by name before any launch
+        kv = self.encode(wav, lens)
+        return self.generate_from_kv(kv, self._prompts(kv, language, task, return_timestamps), max_new_tokens, sync_every, beam_size,
+                                     length_penalty, return_beams, return_token_timestamps,
+                                     self._frames_of(wav, lens) if return_token_timestamps else None, return_timestamps)
+
+    # ---- long recordings: the sequential seek loop (DESIGN 4o) -------------------------------------------------------------------
+    @torch.no_grad()
+    def transcribe_long(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe", beam_size: int = 1,
+                        no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = None,
+                        sync_every: int = 8, **unbuilt) -> List[List[Segment]]:
+        """Recordings of any length: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> the segments of every row.
+        The seek loop of ``transformers``' long-form ``generate`` (``return_timestamps=True``, ``condition_on_prev_tokens=False``,
+        temperature 0): every window of ``n_frames`` mel frames is decoded with timestamp tokens, cut into segments at the
+        timestamp pairs (``split_segments``), and the row's next window starts where the last complete segment ended.
+          * features: once per row over its own samples, 160 * (len // 160) of them, so the clamp at the maximum - 8 is per
+            recording; a window is a slice of them, zero-padded in the feature domain.  A row shorter than one window is framed
+            as ``generate`` frames it, its samples zero-padded to the window (what the feature extractor does with a short
+            recording), and equals ``generate(return_timestamps=True)``;
+          * every iteration batches the current windows of the rows that are not finished; a row's result does not depend on
+            its batch-mates;
+          * ``language`` None: detected per row on the first window;
+          * windows decode up to ``max_target_positions`` tokens;
+          * ``no_speech_threshold`` and ``logprob_threshold`` (both or neither): a window whose <|nospeech|> probability exceeds
+            the first and whose average log-probability falls below the second is skipped whole.
+        ``avg_logprob``: greedy, the mean log-probability of the picks among the classes the rules allow (the closing eos
+        counts), as ``_retrieve_avg_logprobs`` at temperature 0; beam search, the best hypothesis' own score.  One host read per
+        window besides the alive counts."""
+        for name, value in unbuilt.items():
+            off = {"temperature": (None, 0, 0.0, (0.0,), [0.0]), "condition_on_prev_tokens": (None, False), "prompt_ids": (None,),
+                   "chunk_length_s": (None,), "stride_length_s": (None,), "return_token_timestamps": (None, False),
+                   "graph": (None, False), "compression_ratio_threshold": (None,)}
+            if name not in off:
+                raise TypeError(f"Whisper.transcribe_long: unknown argument {name!r}")
+            if not any(value is v or (not isinstance(value, Tensor) and value == v) for v in off[name]):
+                raise _C.F5EError(f"Whisper.transcribe_long: {name} = {value!r} is out of scope (temperature fallback and sampling, "
+                                  "conditioning on previous tokens, prompt_ids, strided chunk merging, word timestamps across "
+                                  "windows and a graph-captured step are not built)")
+        if (no_speech_threshold is None) != (logprob_threshold is None):
+            raise _C.F5EError("Whisper.transcribe_long: the no-speech skip needs no_speech_threshold and logprob_threshold together")
+        if sync_every < 1:
+            raise _C.F5EError("Whisper.transcribe_long: sync_every < 1")
+        cfg = self.cfg
+        ts_begin, eos, W, M = cfg.timestamp_begin, cfg.eos_token_id, self.n_frames, cfg.num_mel_bins
+        wav, lens = self._check_audio(wav, lens, "transcribe_long")
+        fd = self._fold()
+        B, S = wav.shape
+        dev = wav.device
+        samples = [S] * B if lens is None else [min(int(v), S) for v in lens.tolist()]
+        frames = [max(v // HOP, W) for v in samples]
+        if min(samples) < 1:
+            raise _C.F5EError(f"Whisper.transcribe_long: an empty recording (lens = {samples})")
+        lens_dev = torch.tensor([min(v, f * HOP) for v, f in zip(samples, frames)], dtype=I32).to(dev)
+        feats = [ops.whisper_logmel(wav[b:b + 1], lens_dev[b:b + 1], fd["window"], fd["twiddle"], fd["fb"], frames[b])[0]
+                 for b in range(B)]
+        prompts = None if language is None else self.prompt_ids(language, task, True)
+        seek, out = [0] * B, [[] for _ in range(B)]
+        while True:
+            act = [b for b in range(B) if seek[b] < frames[b]]
+            if not act:
+                return out
+            nf = [min(W, frames[b] - seek[b]) for b in act]
+            win = torch.zeros(len(act), W, M, dtype=F32, device=dev)
+            for i, b in enumerate(act):
+                win[i, :nf[i]] = feats[b][seek[b]:seek[b] + nf[i]]
+            kv = self.cross_kv(self.encode_features(win))
+            if prompts is None:                                        # the first iteration: every row is in it, at seek 0
+                prompts = self._prompts(kv, None, task, True)
+            prompt = prompts[torch.tensor(act, device=dev)] if isinstance(prompts, Tensor) else prompts
+            n0, stats = _prompt_len(prompt), {}
+            tokens, n = self.generate_from_kv(kv, prompt, None, sync_every, beam_size, 1.0, return_timestamps=True, stats=stats)[:2]
+            tokens, n = tokens.tolist(), n.tolist()
+            sum_logp, ns_logp = stats["sum_logp"].tolist(), stats["no_speech_logp"].tolist()
+            for i, b in enumerate(act):
+                full = tokens[i][n0:n[i]]
+                seq = full[:-1] if full and full[-1] == eos else full
+                avg, ns = sum_logp[i] / max(len(full), 1), math.exp(ns_logp[i])
+                if not seq or (no_speech_threshold is not None and avg < logprob_threshold and ns > no_speech_threshold):
+                    seek[b] += nf[i]
+                    continue
+                parts, step = split_segments(seq, ts_begin, seek[b], nf[i])
+                if step <= 0:
+                    raise _C.F5EError(f"Whisper.transcribe_long: the window at frame {seek[b]} of row {b} does not advance")
+                cr = compression_ratio(full, cfg.vocab_size)
+                out[b].extend(Segment(s0, s1, tok, seek[b], avg, ns, cr) for s0, s1, tok in parts)
+                seek[b] += step
 
 
 class WhisperRecognizer:
     """The duck type ``eval_wer.run_asr_wer`` and ``preprocess_ref_audio_text`` take: ``transcribe(wav_or_path, sr) -> str``."""
 
-    def __init__(self, path: str, device="cuda", language: str = "en", beam_size: int = 1):
+    def __init__(self, path: str, device="cuda", language: Optional[str] = "en", beam_size: int = 1, long_form: bool = False):
+        """``language``: a name or code, or None / "auto" to detect it per recording.  ``long_form``: ``transcribe`` runs the
+        seek loop over the whole recording (``Whisper.transcribe_long``) instead of cutting it to the first chunk."""
         self.device = torch.device(device)
         self.language = language
         self.beam_size = int(beam_size)      # the constructor's alone: transcribe() ignores the wenet flag of the same name
+        self.long_form = bool(long_form)
         self.model = Whisper.from_pretrained_dir(path).to(self.device)
-        self.model.prompt_ids(language)                      # a language the checkpoint does not know fails here, not per file
+        if self._lang() is not None:
+            self.model.prompt_ids(language)                  # a language the checkpoint does not know fails here, not per file
+        elif not self.model.cfg.lang_to_id:
+            raise _C.F5EError("WhisperRecognizer: language detection needs lang_to_id in generation_config.json")
+        if self.long_form:
+            self.model.cfg.timestamp_begin                   # refused by name here, not per file
         self._warned = set()
 
-    def _audio(self, audio, sr: Optional[int]) -> Tensor:
-        """A wav path or a wave at ``sr`` -> mono f32 [1, S] at 16 kHz on the device, cut to the chunk (with a warning)."""
+    def _lang(self) -> Optional[str]:
+        return None if self.language is None or str(self.language).lower() == "auto" else self.language
+
+    def _audio(self, audio, sr: Optional[int], cut: bool = True) -> Tensor:
+        """A wav path or a wave at ``sr`` -> mono f32 [1, S] at 16 kHz on the device, cut to the chunk (with a warning) unless
+        ``cut`` is False."""
         from ..infer import audio as A
         from ..infer.utils_infer import load_wav
         name = audio if isinstance(audio, str) else None
@@ -863,7 +1132,7 @@ class WhisperRecognizer:
             audio = audio.mean(0, keepdim=True)
         audio = A.resample_device(audio.to(self.device, F32), int(sr), SAMPLE_RATE)
         limit = HOP * self.model.n_frames
-        if audio.shape[-1] > limit:
+        if cut and audio.shape[-1] > limit:
             if name not in self._warned:
                 self._warned.add(name)
                 warnings.warn(f"WhisperRecognizer: {name or 'audio'} is {audio.shape[-1] / SAMPLE_RATE:.1f} s long; only the first "
@@ -873,8 +1142,16 @@ class WhisperRecognizer:
 
     @torch.no_grad()
     def transcribe(self, audio, sr: Optional[int] = None, mode=None, **ignored) -> str:
-        tokens, n = self.model.generate(self._audio(audio, sr), None, self.language, beam_size=self.beam_size)
+        if getattr(self, "long_form", False):
+            return "".join(text for _, _, text in self.transcribe_segments(audio, sr)).strip()
+        tokens, n = self.model.generate(self._audio(audio, sr), None, self._lang(), beam_size=self.beam_size)
         return self.model.decode_ids(tokens[0, :int(n[0])].tolist()).strip()
+
+    @torch.no_grad()
+    def transcribe_segments(self, audio, sr: Optional[int] = None) -> List[Tuple[float, float, str]]:
+        """-> [(start_s, end_s, text)] over the whole recording, however long (``Whisper.transcribe_long``)."""
+        segs = self.model.transcribe_long(self._audio(audio, sr, cut=False), None, self._lang(), beam_size=self.beam_size)[0]
+        return [(s.start_s, s.end_s, self.model.decode_ids(s.tokens)) for s in segs]
 
     @torch.no_grad()
     def transcribe_words(self, audio, sr: Optional[int] = None) -> list:
@@ -882,6 +1159,8 @@ class WhisperRecognizer:
         ``token_timestamps(include_last=True)``, so the closing token's time ends the last word.  Words are stripped of the
         punctuation merged into them and of surrounding space; a word of punctuation alone is dropped."""
         from ..ppg.ctc_align import WordSpan
+        if self._lang() is None:
+            raise _C.F5EError("WhisperRecognizer.transcribe_words: word timestamps need a named language (not 'auto')")
         model, wav = self.model, self._audio(audio, sr)
         kv = model.encode(wav)
         prompt = model.prompt_ids(self.language)

@@ -70,7 +70,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--asr_dict", type=str, help="best_of: the ASR model's symbol table (`token id` lines)")
     p.add_argument("--whisper_dir", type=str, help="a local whisper-large-v3(-turbo) directory: a voice whose ref_text is empty "
                                                    "is transcribed with it (without it an empty ref_text is an error)")
-    p.add_argument("--ref_language", type=str, default="english", help="--whisper_dir: the language spoken in the reference audio")
+    p.add_argument("--ref_language", type=str, default="english", help="--whisper_dir: the language spoken in the reference audio; auto: detected "
+                   "from the audio")
     p.add_argument("--whisper_beam", type=int, default=1, help="--whisper_dir: 1 = greedy; N > 1 = beam search with N beams")
     return p
 

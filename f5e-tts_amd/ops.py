@@ -1722,7 +1722,7 @@ def whisper_beam_step(logits: Tensor, score: Tensor, hyp_in: Tensor, anc_in: Ten
                       pool_hyp: Tensor, pool_len: Tensor, pool_score: Tensor, pool_n: Tensor, open_: Tensor, alive: Tensor,
                       p: int, n0: int, cap: int, eos: int, beam: int, *, V: Optional[int] = None,
                       suppress: Optional[Tensor] = None, begin_suppress: Optional[Tensor] = None, length_penalty: float = 1.0,
-                      scratch: Optional[Tensor] = None):
+                      scratch: Optional[Tensor] = None, _ts: Optional[tuple] = None):
     """One step of Whisper's pooled beam search (f5e_whisper_beam_step, where the rules are written out): logits f32
     [B * beam, >= V] (row-strided view, only read), score f32 / last i32 [B * beam], hyp / anc tables contiguous i32 [B * beam, ld]
     (double-buffered), pool_hyp i32 [B, beam, ld], pool_len i32 / pool_score f32 [B, beam], pool_n / open_ / alive i32 [B],
@@ -1754,16 +1754,77 @@ def whisper_beam_step(logits: Tensor, score: Tensor, hyp_in: Tensor, anc_in: Ten
         scratch = torch.empty(max(whisper_beam_scratch(B, beam, V), 4), dtype=torch.uint8, device=logits.device)
     if scratch.dtype != torch.uint8 or not scratch.is_contiguous():
         raise _C.F5EError("whisper_beam_step: scratch must be a contiguous uint8 tensor")
-    check(lib().f5e_whisper_beam_step(_stream(), lp, ldl, _p(suppress, I32, "suppress"),
-                                      suppress.numel() if suppress is not None else 0, _p(begin_suppress, I32, "begin_suppress"),
-                                      begin_suppress.numel() if begin_suppress is not None else 0, _p(score, F32, "score"),
-                                      _p(hyp_in, I32, "hyp_in"), _p(anc_in, I32, "anc_in"), _p(hyp_out, I32, "hyp_out"),
-                                      _p(anc_out, I32, "anc_out"), ld, _p(last, I32, "last"), _p(pool_hyp, I32, "pool_hyp"),
-                                      _p(pool_len, I32, "pool_len"), _p(pool_score, F32, "pool_score"), _p(pool_n, I32, "pool_n"),
-                                      _p(open_, I32, "open"), _p(alive, I32, "alive"), C.c_void_p(scratch.data_ptr()),
-                                      scratch.numel(), B, beam, V, int(p), int(n0), int(cap), int(eos), float(length_penalty)),
-          "f5e_whisper_beam_step")
+    args = (_stream(), lp, ldl, _p(suppress, I32, "suppress"), suppress.numel() if suppress is not None else 0,
+            _p(begin_suppress, I32, "begin_suppress"), begin_suppress.numel() if begin_suppress is not None else 0,
+            _p(score, F32, "score"), _p(hyp_in, I32, "hyp_in"), _p(anc_in, I32, "anc_in"), _p(hyp_out, I32, "hyp_out"),
+            _p(anc_out, I32, "anc_out"), ld, _p(last, I32, "last"), _p(pool_hyp, I32, "pool_hyp"), _p(pool_len, I32, "pool_len"),
+            _p(pool_score, F32, "pool_score"), _p(pool_n, I32, "pool_n"), _p(open_, I32, "open"), _p(alive, I32, "alive"),
+            C.c_void_p(scratch.data_ptr()), scratch.numel(), B, beam, V, int(p), int(n0), int(cap), int(eos), float(length_penalty))
+    if _ts is None:
+        check(lib().f5e_whisper_beam_step(*args), "f5e_whisper_beam_step")
+    else:
+        no_timestamps, max_initial, desc = _ts
+        if desc.dtype != I32 or tuple(desc.shape) != (R, 4) or not desc.is_contiguous():
+            raise _C.F5EError(f"whisper_beam_step_ts: desc must be a contiguous i32 tensor [{R}, 4]")
+        check(lib().f5e_whisper_beam_step_ts(*args, int(no_timestamps), -1 if max_initial is None else int(max_initial),
+                                             _p(desc, I32, "desc")), "f5e_whisper_beam_step_ts")
     return last
+
+
+def whisper_beam_step_ts(logits: Tensor, score: Tensor, hyp_in: Tensor, anc_in: Tensor, hyp_out: Tensor, anc_out: Tensor,
+                         last: Tensor, pool_hyp: Tensor, pool_len: Tensor, pool_score: Tensor, pool_n: Tensor, open_: Tensor,
+                         alive: Tensor, p: int, n0: int, cap: int, eos: int, beam: int, no_timestamps: int, desc: Tensor, *,
+                         max_initial: Optional[int] = None, **kw):
+    """``whisper_beam_step`` under Whisper's timestamp rules (f5e_whisper_beam_step_ts): ``desc`` i32 [B * beam, 4] receives the
+    rows' rule descriptors (``whisper_ts_rule``), which the chunk launch applies as one more mask."""
+    return whisper_beam_step(logits, score, hyp_in, anc_in, hyp_out, anc_out, last, pool_hyp, pool_len, pool_score, pool_n, open_,
+                             alive, p, n0, cap, eos, beam, _ts=(no_timestamps, max_initial, desc), **kw)
+
+
+def _ts_common(name: str, logits: Tensor, tokens: Tensor, V: Optional[int], p: int, suppress, begin_suppress):
+    if logits.ndim != 2 or tokens.ndim != 2 or tokens.shape[0] != logits.shape[0]:
+        raise _C.F5EError(f"{name}: logits [R, >= V] and tokens [R, >= p + 2]; there is no CPU path")
+    V = logits.shape[1] if V is None else int(V)
+    if V > logits.shape[1]:
+        raise _C.F5EError(f"{name}: V = {V} exceeds the {logits.shape[1]} columns of logits")
+    lp, ld = _rows(logits, (F32,), f"{name}: logits", max(V, 1), vec=1)
+    tp, ld_tok = _rows(tokens, (I32,), f"{name}: tokens", int(p) + 2, vec=1)
+    return (_stream(), lp, ld, _p(suppress, I32, "suppress"), suppress.numel() if suppress is not None else 0,
+            _p(begin_suppress, I32, "begin_suppress"), begin_suppress.numel() if begin_suppress is not None else 0, tp, ld_tok), V
+
+
+def whisper_ts_pick(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, sum_logp: Tensor, p: int, n0: int,
+                    eos: int, no_timestamps: int, *, V: Optional[int] = None, suppress: Optional[Tensor] = None,
+                    begin_suppress: Optional[Tensor] = None, max_initial: Optional[int] = None):
+    """f5e_whisper_ts_pick: ``greedy_pick`` under Whisper's timestamp rules.  The generated tokens of a row are tokens[r, n0:p + 1];
+    begin_suppress counts at the first step (p + 1 == n0); sum_logp f32 [R] gains the log-probability of the pick among the
+    allowed classes.  Writes tokens[:, p + 1], last, done (0 -> 1), alive and sum_logp."""
+    head, V = _ts_common("whisper_ts_pick", logits, tokens, V, p, suppress, begin_suppress)
+    R = logits.shape[0]
+    if last.shape != (R,) or done.shape != (R,) or alive.numel() != 1 or sum_logp.shape != (R,):
+        raise _C.F5EError(f"whisper_ts_pick: last [{R}], done [{R}], alive [1], sum_logp [{R}]")
+    require_device()
+    check(lib().f5e_whisper_ts_pick(*head, _p(last, I32, "last"), _p(done, I32, "done"), _p(alive, I32, "alive"),
+                                    _p(sum_logp, F32, "sum_logp"), R, V, int(p), int(n0), int(eos), int(no_timestamps),
+                                    -1 if max_initial is None else int(max_initial)), "f5e_whisper_ts_pick")
+    return last
+
+
+def whisper_ts_rule(logits: Tensor, tokens: Tensor, p: int, n0: int, eos: int, no_timestamps: int, *, V: Optional[int] = None,
+                    suppress: Optional[Tensor] = None, begin_suppress: Optional[Tensor] = None, max_initial: Optional[int] = None,
+                    out: Optional[Tensor] = None) -> Tensor:
+    """f5e_whisper_ts_rule: -> desc i32 [R, 4] = (text ban: 0 none / 1 [0, eos) / 2 all text, lo, hi, 0) per row: what
+    Whisper's timestamp rules ban for the histories tokens[r, n0:p + 1] and these logits, besides the suppressed classes and
+    <|notimestamps|> itself; the timestamps allowed are [lo, hi]."""
+    head, V = _ts_common("whisper_ts_rule", logits, tokens, V, p, suppress, begin_suppress)
+    R = logits.shape[0]
+    out = torch.empty(R, 4, dtype=I32, device=logits.device) if out is None else out
+    if out.dtype != I32 or tuple(out.shape) != (R, 4) or not out.is_contiguous():
+        raise _C.F5EError(f"whisper_ts_rule: out must be a contiguous i32 tensor [{R}, 4]")
+    require_device()
+    check(lib().f5e_whisper_ts_rule(*head, _p(out, I32, "out"), R, V, int(p), int(n0), int(eos), int(no_timestamps),
+                                    -1 if max_initial is None else int(max_initial)), "f5e_whisper_ts_rule")
+    return out
 
 
 # ---- Whisper word timestamps (csrc/whisper_align.hip) ----

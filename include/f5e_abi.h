@@ -818,6 +818,43 @@ F5E_API int f5e_whisper_beam_step(f5e_stream st, const float* logits, long long 
                           int* open, int* alive, void* scratch, unsigned long long scratch_bytes, int B, int K, int V, int p,
                           int n0, int cap, int eos, float length_penalty);
 
+/* Whisper's timestamp rules (transformers 5.15.0 WhisperTimeStampLogitsProcessor, run after the two suppress processors) for
+ * decoding WITH timestamp tokens.  ts_begin = no_timestamps + 1; a class >= ts_begin is a timestamp, every other one is text.
+ * The generated tokens of row r are h = tokens[r][n0 .. p] (none at the first step p = n0 - 1).  Banned, besides the classes of
+ * suppress (and of begin_suppress iff p + 1 == n0):
+ *  1. <|notimestamps|> itself.
+ *  2. h ends with a timestamp and the token before it is a timestamp or absent: every timestamp.
+ *  3. h ends with a timestamp after a text token: the classes [0, eos) -- [eos, ts_begin) stay, as in the processor.
+ *  4. With T the last timestamp of h: the timestamps below T in state 3, the timestamps up to and including T otherwise.
+ *  5. First step: all text; with max_initial >= 0 also the timestamps above ts_begin + max_initial (-1: no such limit).
+ *  6. If log-sum-exp over the timestamps still allowed > the maximum over the text still allowed: all text.  (The processor
+ *     compares log-probabilities; their normaliser is common to both sides.)  NaN and infinite logits count as banned.
+ * f5e_whisper_ts_pick: one greedy step under these rules, as f5e_greedy_pick otherwise (lowest index among equal maxima, 0 if
+ *   nothing is allowed; done rows get eos; tokens[r][p + 1], last[r], done[r] 0 -> 1, *alive), and for a row that was not done
+ *   sum_logp[r] += (x[pick] - M) - log(sum over the allowed classes of exp(x - M)), M their maximum: the log-softmax of the
+ *   processed scores at the pick (the closing eos counts).  One workgroup per row reads the logits once: per lane a running
+ *   maximum / first index / sum of exponentials for the timestamps and for the text, folded by shuffles and through LDS in a
+ *   fixed order.  Writes nothing else; the logits are only read.
+ * f5e_whisper_ts_rule: the same pass, leaving only the row's rule descriptor desc[r][0..4) = {text ban: 0 none, 1 [0, eos),
+ *   2 [0, ts_begin); lo; hi (the timestamps allowed are [lo, hi], none if lo > hi); 0}.
+ * f5e_whisper_beam_step_ts: f5e_whisper_beam_step with the rules: f5e_whisper_ts_rule on hyp_in into desc i32 [B*K][4] (the
+ *   caller's buffer), then the chunk launch strikes the banned classes after the suppressed ones (rule 1 of the beam step is
+ *   unchanged: the normaliser covers all V raw classes).  Three launches.
+ * Limits: 2 <= V <= 262144, 0 <= eos <= no_timestamps < V - 1, n0 >= 1, p >= n0 - 1, ld_tok >= p + 2, max_initial >= -1; the
+ * beam's own limits as above. */
+F5E_API int f5e_whisper_ts_pick(f5e_stream st, const float* logits, long long ld, const int* suppress, int n_sup,
+                        const int* begin_suppress, int n_beg, int* tokens, int ld_tok, int* last, int* done, int* alive,
+                        float* sum_logp, int R, int V, int p, int n0, int eos, int no_timestamps, int max_initial);
+F5E_API int f5e_whisper_ts_rule(f5e_stream st, const float* logits, long long ld, const int* suppress, int n_sup,
+                        const int* begin_suppress, int n_beg, const int* tokens, int ld_tok, int* desc, int R, int V, int p,
+                        int n0, int eos, int no_timestamps, int max_initial);
+F5E_API int f5e_whisper_beam_step_ts(f5e_stream st, const float* logits, long long ld_logits, const int* suppress, int n_sup,
+                             const int* begin_suppress, int n_beg, float* score, const int* hyp_in, const int* anc_in,
+                             int* hyp_out, int* anc_out, int ld, int* last, int* pool_hyp, int* pool_len, float* pool_score,
+                             int* pool_n, int* open, int* alive, void* scratch, unsigned long long scratch_bytes, int B, int K,
+                             int V, int p, int n0, int cap, int eos, float length_penalty, int no_timestamps, int max_initial,
+                             int* desc);
+
 /* ---------------------------------------------------------------- Whisper word timestamps (csrc/whisper_align.hip) */
 /* Token times from the cross-attention of a few "alignment heads" (transformers 5.15.0 generation_whisper.py:
  * _extract_token_timestamps, _median_filter, _dynamic_time_warping with num_frames given), for one utterance with the

@@ -19,13 +19,13 @@ Ragged batches: row b of a padded batch equals its own B = 1 run (the upstream's
 backward direction from the row's last frame; the mean runs over the row's frames)."""
 from __future__ import annotations
 
-import math
 from typing import Dict, Optional
 
 import torch
 import torch.nn as nn
 
 from .. import _C, ops
+from ..xfmr_f32 import plan, take, view
 from .wav2vec2 import Wav2Vec2, Wav2Vec2Config, convert_hf_state_dict
 from .wavlm import _f
 
@@ -121,13 +121,9 @@ class UTMOS22Strong(nn.Module):
         T = max(self.wav2vec2.frame_count(S), 1)
         D, Hp, P = self.wav2vec2.cfg.encoder_embed_dim, (self.blstm.hidden_size + 63) // 64 * 64, self.projection[0].out_features
         M = B * T
-        shapes = dict(hid=(B, T, D), xg=(M, 8 * Hp), lstm=(B, T, 2 * Hp), cell=(2, B, Hp), p1=(M, P))
-        plan, off = {}, 0
-        for name, shape in shapes.items():
-            plan[name] = (off, shape)
-            off += (math.prod(shape) + 63) // 64 * 64
-        plan["_up"] = (off, ())
-        return plan, off + self.wav2vec2.workspace_bytes(B, S) // 4
+        pl = plan(dict(hid=(B, T, D), xg=(M, 8 * Hp), lstm=(B, T, 2 * Hp), cell=(2, B, Hp), p1=(M, P)))
+        pl["_up"] = pl.pop("_total")
+        return pl, pl["_up"][0] + self.wav2vec2.workspace_bytes(B, S) // 4
 
     def workspace_bytes(self, B: int, S: int) -> int:
         """Scratch bytes of ``predict`` for B rows of S samples, the upstream's included (host arithmetic)."""
@@ -146,16 +142,8 @@ class UTMOS22Strong(nn.Module):
                               f"{self.wav2vec2.min_samples()} samples)")
         dev = wav16k.device
         hd = self._fold()
-        plan, total = self._plan(B, S)
-        if workspace is None:
-            ws = torch.empty(total, dtype=F32, device=dev)
-        else:
-            if not workspace.is_cuda or workspace.dtype not in (F32, torch.uint8) or not workspace.is_contiguous() or \
-                    workspace.data_ptr() % 16 or workspace.numel() * workspace.element_size() < total * 4:
-                raise _C.F5EError(f"UTMOS22Strong.predict: workspace must be a contiguous 16-byte aligned f32 / uint8 GPU tensor "
-                                  f"of at least {total * 4} bytes (workspace_bytes)")
-            ws = workspace.view(-1)
-            ws = ws[: ws.numel() // 4 * 4].view(F32) if ws.dtype == torch.uint8 else ws
+        pl, total = self._plan(B, S)
+        ws = take(workspace, total, dev, "UTMOS22Strong.predict")
         if out is None:
             out = torch.empty(B, dtype=F32, device=dev)
         elif out.shape != (B,) or out.dtype != F32 or not out.is_cuda:
@@ -163,12 +151,8 @@ class UTMOS22Strong(nn.Module):
         if frame_scores is not None and (frame_scores.shape != (B, T) or frame_scores.dtype != F32 or not frame_scores.is_cuda):
             raise _C.F5EError(f"UTMOS22Strong.predict: frame_scores must be an f32 GPU tensor [{B}, {T}]")
 
-        def buf(name):
-            off, shape = plan[name]
-            return ws[off:off + math.prod(shape)].view(shape)
-
-        hid, xg, lstm, cell, p1 = buf("hid"), buf("xg"), buf("lstm"), buf("cell"), buf("p1")
-        _, frames = self.wav2vec2.extract(wav16k, lengths, out=hid, workspace=ws[plan["_up"][0]:total])
+        hid, xg, lstm, cell, p1 = (view(ws, pl, name) for name in ("hid", "xg", "lstm", "cell", "p1"))
+        _, frames = self.wav2vec2.extract(wav16k, lengths, out=hid, workspace=ws[pl["_up"][0]:total])
         M, D = B * T, hid.shape[2]
         ops.gemm_f32(hid.view(M, D), hd["w_ih"], hd["b_ih"], out=xg)          # both directions, every frame, constants folded
         ops.lstm_f32(xg, hd["w_hh"], frames, lstm, cell)

@@ -1,6 +1,7 @@
 """wav2vec2-base, the upstream of the UTMOS predictor (``eval/utmos.py``; the reference fetches ``utmos22_strong`` through
 ``torch.hub``, eval/eval_utmos.py:18): from 16 kHz audio to the last hidden state of the encoder.  fp32, eval mode, on the device:
-f5e_w2v_conv0_gn (csrc/utmos.hip), f5e_gemm_f32, f5e_layernorm, f5e_wavlm_posconv and f5e_mha_f32.  The sub-modules
+f5e_w2v_conv0_gn (csrc/utmos.hip), f5e_gemm_f32, f5e_layernorm, f5e_wavlm_posconv and f5e_mha_f32; the encoder layer
+is ``xfmr_f32.layer``, post-norm, and everything shared with WavLM is ``eval/wavlm.py::WaveEncoder``.  The sub-modules
 only HOLD the weights.
 
 Only the base family's structure is built -- the fairseq "default" feature extractor (GroupNorm over time after conv 0, no norm
@@ -27,7 +28,8 @@ import torch
 import torch.nn as nn
 
 from .. import _C, ops
-from .wavlm import WavLM, _Holder, _WeightNormConv, _f, fold_weight_norm, frame_counts
+from ..xfmr_f32 import fold, layer
+from .wavlm import WaveEncoder, _Holder, _WeightNormConv, frame_counts
 
 Tensor = torch.Tensor
 F32, I32 = torch.float32, torch.int32
@@ -158,7 +160,9 @@ class _FeatureExtractor(nn.Module):
         self.conv_layers = nn.ModuleList(layers)
 
 
-class Wav2Vec2(nn.Module):
+class Wav2Vec2(WaveEncoder):
+    _conv_act = ops.ACT_GELU_ERF                # no norm after convs 1..: the GELU rides on the GEMM
+
     def __init__(self, cfg: Optional[Wav2Vec2Config] = None):
         super().__init__()
         self.cfg = cfg = cfg or Wav2Vec2Config()
@@ -168,91 +172,27 @@ class Wav2Vec2(nn.Module):
         self.layer_norm = nn.LayerNorm(C, eps=cfg.layer_norm_eps)
         self.post_extract_proj = nn.Linear(C, D)
         self.encoder = _Encoder(cfg)
-        self._folded = None
-        super().train(False)
-        for p in self.parameters():
-            p.requires_grad_(False)
+        self._freeze()
 
-    # ---- eval mode only; weights as the kernels take them, once per load ------------------------------------------------
-    def train(self, mode: bool = True):
-        if mode:
-            raise _C.F5EError("Wav2Vec2: training is out of scope (eval mode only)")
-        return super().train(False)
-
-    def _apply(self, fn, *a, **kw):
-        self._folded = None
-        return super()._apply(fn, *a, **kw)
-
-    def load_state_dict(self, *a, **kw):
-        self._folded = None
-        return super().load_state_dict(*a, **kw)
-
-    def _fold(self) -> dict:
-        dev = self.layer_norm.weight.device
-        if self._folded is not None and self._folded["device"] == dev:
-            return self._folded
-        if dev.type != "cuda":
-            raise _C.F5EError(f"Wav2Vec2 lives on {dev}: move it to the GPU (there is no CPU path)")
-        cfg, enc = self.cfg, self.encoder
-        fd = dict(device=dev, conv=[], layers=[])
-        for i, seq in enumerate(self.feature_extractor.conv_layers):
-            w = seq[0].weight.detach()
-            w = w[:, 0] if i == 0 else w.permute(0, 2, 1).reshape(w.shape[0], -1)     # tap-major: k = tap * C + ic
-            fd["conv"].append(dict(w=_f(w, dev), b=_f(seq[0].bias, dev) if seq[0].bias is not None else None))
-        gn = self.feature_extractor.conv_layers[0][2]
-        fd["gn_g"], fd["gn_b"] = _f(gn.weight, dev), _f(gn.bias, dev)
-        fd["ln_g"], fd["ln_b"] = _f(self.layer_norm.weight, dev), _f(self.layer_norm.bias, dev)
-        fd["proj_w"], fd["proj_b"] = _f(self.post_extract_proj.weight, dev), _f(self.post_extract_proj.bias, dev)
-        pc = enc.pos_conv[0]
-        fd["pos_w"] = ops.pack_wavlm_posconv_weight(fold_weight_norm(pc.weight_g, pc.weight_v), cfg.conv_pos_groups).to(dev)
-        fd["pos_b"] = _f(pc.bias, dev)
-        for lyr in enc.layers:
-            sa = lyr.self_attn
-            fd["layers"].append(dict(
-                w_qkv=_f(torch.cat([sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight], 0), dev),
-                b_qkv=_f(torch.cat([sa.q_proj.bias, sa.k_proj.bias, sa.v_proj.bias], 0), dev),
-                w_out=_f(sa.out_proj.weight, dev), b_out=_f(sa.out_proj.bias, dev),
-                ln1_g=_f(lyr.self_attn_layer_norm.weight, dev), ln1_b=_f(lyr.self_attn_layer_norm.bias, dev),
-                w1=_f(lyr.fc1.weight, dev), b1=_f(lyr.fc1.bias, dev), w2=_f(lyr.fc2.weight, dev), b2=_f(lyr.fc2.bias, dev),
-                ln2_g=_f(lyr.final_layer_norm.weight, dev), ln2_b=_f(lyr.final_layer_norm.bias, dev)))
-        fd["enc_g"], fd["enc_b"] = _f(enc.layer_norm.weight, dev), _f(enc.layer_norm.bias, dev)
-        self._folded = fd
-        return fd
+    def _fold_more(self, fd: dict, dev) -> None:
+        fd["gn_g"], fd["gn_b"] = fold(dev, self.feature_extractor.conv_layers[0][2])
 
     # ---- geometry and workspace ---------------------------------------------------------------------------------------------
-    frame_count = WavLM.frame_count
-    min_samples = WavLM.min_samples
-
     def _geometry(self, S: int) -> Tuple[int, List[int], List[int]]:
-        """``WavLM._geometry`` (T, need, pitch), with the batch pitch of layer 0 raised to hold ALL (S - 10) // 5 + 1 frames of
-        conv 0: the group norm runs over every one of them, also over those that no later layer reads."""
+        """``WaveEncoder._geometry`` (T, need, pitch), with the batch pitch of layer 0 raised to hold ALL (S - 10) // 5 + 1 frames
+        of conv 0: the group norm runs over every one of them, also over those that no later layer reads."""
         cfg = self.cfg
-        T, need, pitch = WavLM._geometry(self, S)
+        T, need, pitch = super()._geometry(S)
         T0 = frame_counts(S, cfg)[0]
         while pitch[0] < T0:
             pitch = [p + math.prod(cfg.conv_stride[l + 1:]) for l, p in enumerate(pitch)]
         return T, need, pitch
 
-    def _plan(self, B: int, S: int) -> Dict[str, tuple]:
-        """name -> (offset in floats, shape) of every intermediate; offsets are multiples of 64 floats."""
+    def _shapes(self, B: int, S: int, T: int, **conv) -> Dict[str, tuple]:
         cfg = self.cfg
-        T, _need, pitch = self._geometry(S)
-        T = max(T, 1)
-        C, D, FF = cfg.conv_dim[-1], cfg.encoder_embed_dim, cfg.encoder_ffn_embed_dim
-        M, slack = B * T, max(cfg.conv_kernel) * C
-        shapes = dict(frames=(B,), partials=(ops.w2v_conv0_gn_partials(B, max(S, 10), C),), mask=(M,),
-                      ca=(B * pitch[0] * C + slack,), cb=(B * (pitch[1] if len(pitch) > 1 else 1) * C + slack,),
-                      xnc=(M, C), proj=(M, D), qkv=(M, 3 * D), ao=(M, D), ff=(M, FF))
-        plan, off = {}, 0
-        for name, shape in shapes.items():
-            plan[name] = (off, shape)
-            off += (math.prod(shape) + 63) // 64 * 64
-        plan["_total"] = (off, ())
-        return plan
-
-    def workspace_bytes(self, B: int, S: int) -> int:
-        """Scratch bytes of ``extract`` for B rows of S samples (host arithmetic)."""
-        return self._plan(int(B), int(S))["_total"][0] * 4
+        C, D, M = cfg.conv_dim[-1], cfg.encoder_embed_dim, B * T
+        return dict(frames=(B,), partials=(ops.w2v_conv0_gn_partials(B, max(S, 10), C),), mask=(M,), **conv, xnc=(M, C),
+                    proj=(M, D), qkv=(M, 3 * D), ao=(M, D), ff=(M, cfg.encoder_ffn_embed_dim))
 
     # ---- forward -------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -263,75 +203,27 @@ class Wav2Vec2(nn.Module):
         (``workspace_bytes(B, S)`` bytes, f32 or uint8) and device lengths it allocates nothing once the weights are folded (a
         first call does that), so it can be captured into a graph."""
         cfg = self.cfg
-        if not isinstance(wav, Tensor) or wav.ndim != 2 or wav.dtype != F32:
-            raise _C.F5EError("Wav2Vec2.extract: wav must be a float32 tensor [B, S]")
-        if not wav.is_cuda:
-            raise _C.F5EError(f"Wav2Vec2.extract: wav lives on {wav.device}; there is no CPU path")
-        B, S = wav.shape
-        T, _need, pitch = self._geometry(S)
-        if B < 1 or T < 1:
-            raise _C.F5EError(f"Wav2Vec2.extract: {S} samples give no frame (a row needs {self.min_samples()})")
-        dev = wav.device
-        if lengths is not None and not (isinstance(lengths, Tensor) and lengths.is_cuda):
-            host = [int(v) for v in (lengths.tolist() if isinstance(lengths, Tensor) else lengths)]
-            if len(host) != B or min(host) < self.min_samples() or max(host) > S:
-                raise _C.F5EError(f"Wav2Vec2.extract: lengths must be {B} values in [{self.min_samples()}, {S}]; got {host}")
-            lengths = torch.tensor(host, dtype=I32).to(dev, non_blocking=True)
-        elif lengths is not None and (lengths.dtype != I32 or lengths.shape != (B,)):
-            raise _C.F5EError(f"Wav2Vec2.extract: lengths must be i32 [{B}] (got {lengths.dtype} {tuple(lengths.shape)})")
-        fd = self._fold()
-        wav = wav.contiguous()
+        wav, lengths, fd, buf = self._enter(wav, lengths, workspace)
+        (B, S), (T, _need, pitch) = wav.shape, self._geometry(wav.shape[1])
         C, D, H = cfg.conv_dim[-1], cfg.encoder_embed_dim, cfg.encoder_attention_heads
-        plan = self._plan(B, S)
-        total = plan["_total"][0]
-        if workspace is None:
-            ws = torch.empty(total, dtype=F32, device=dev)
-        else:
-            if not workspace.is_cuda or workspace.dtype not in (F32, torch.uint8) or not workspace.is_contiguous() or \
-                    workspace.data_ptr() % 16 or workspace.numel() * workspace.element_size() < total * 4:
-                raise _C.F5EError(f"Wav2Vec2.extract: workspace must be a contiguous 16-byte aligned f32 / uint8 GPU tensor of "
-                                  f"at least {total * 4} bytes (workspace_bytes)")
-            ws = workspace.view(-1)
-            ws = ws[: ws.numel() // 4 * 4].view(F32) if ws.dtype == torch.uint8 else ws
         if out is None:
-            out = torch.empty(B, T, D, dtype=F32, device=dev)
+            out = torch.empty(B, T, D, dtype=F32, device=wav.device)
         elif out.shape != (B, T, D) or out.dtype != F32 or not out.is_cuda or not out.is_contiguous() or out.data_ptr() % 16:
             raise _C.F5EError(f"Wav2Vec2.extract: out must be a contiguous 16-byte aligned f32 GPU tensor [{B}, {T}, {D}]")
-
-        def buf(name):
-            off, shape = plan[name]
-            return ws[off:off + math.prod(shape)].view(shape)
-
         M, eps = B * T, cfg.layer_norm_eps
-        frames, mask = buf("frames").view(I32), buf("mask")
-        # the conv front-end: layer 0 in two launches (statistics over time, apply), layers 1.. one GEMM + GELU each on an
-        # overlapping strided view of the layer below
-        cur, nxt = buf("ca"), buf("cb")
-        c0 = fd["conv"][0]
+        frames = buf("frames").view(I32)
+        cur, c0 = buf("ca"), fd["conv"][0]      # the conv front-end: layer 0 in two launches (statistics over time, apply)
         ops.w2v_conv0_gn(wav, c0["w"], c0["b"], fd["gn_g"], fd["gn_b"], lengths, cur[:B * pitch[0] * C].view(B, pitch[0], C),
-                         buf("partials"), frames, mask.view(B, T), cfg.conv_kernel, cfg.conv_stride, eps)
-        for l in range(1, len(cfg.conv_dim)):
-            k, s, p = cfg.conv_kernel[l], cfg.conv_stride[l], fd["conv"][l]
-            rows = B * pitch[l]
-            ops.gemm_f32(torch.as_strided(cur, (rows, k * C), (s * C, 1)), p["w"], p["b"], out=nxt[:rows * C].view(rows, C),
-                         act=ops.ACT_GELU_ERF)
-            cur, nxt = nxt, cur
-        feat, xnc = cur[:B * pitch[-1] * C].view(B, pitch[-1], C), buf("xnc")
-        for b in range(B):
-            ops.layernorm(feat[b, :T], xnc[b * T:(b + 1) * T], fd["ln_g"], fd["ln_b"], eps=eps)
-        proj = buf("proj")
-        ops.gemm_f32(xnc, fd["proj_w"], fd["proj_b"], out=proj, row_scale=mask)       # x[padding_mask] = 0
+                         buf("partials"), frames, buf("mask").view(B, T), cfg.conv_kernel, cfg.conv_stride, eps)
+        proj = self._project(fd, buf, cur, buf("cb"), B, T, pitch)
         ops.wavlm_posconv(proj.view(B, T, D), fd["pos_w"], fd["pos_b"], frames, out)
         x = out.view(M, D)
         ops.layernorm(x, x, fd["enc_g"], fd["enc_b"], eps=eps)
-        qkv, ao, ff = buf("qkv"), buf("ao"), buf("ff")
-        scale = (D // H) ** -0.5
-        for p in fd["layers"]:                                                          # post-LN: x = LN(x + f(x))
-            ops.gemm_f32(x, p["w_qkv"], p["b_qkv"], out=qkv)
+        bufs, scale = (None, buf("qkv"), buf("ao"), None, buf("ff")), (D // H) ** -0.5
+
+        def self_attn(_W, _x, qkv, ao):
             ops.mha_f32(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], H, scale, B=B, kv_len=frames, out=ao)
-            ops.gemm_f32(ao, p["w_out"], p["b_out"], out=x, addend=x)
-            ops.layernorm(x, x, p["ln1_g"], p["ln1_b"], eps=eps)
-            ops.gemm_f32(x, p["w1"], p["b1"], out=ff, act=ops.ACT_GELU_ERF)
-            ops.gemm_f32(ff, p["w2"], p["b2"], out=x, addend=x)
-            ops.layernorm(x, x, p["ln2_g"], p["ln2_b"], eps=eps)
+
+        for W in fd["layers"]:                                                          # post-LN: x = LN(x + f(x))
+            layer(x, x, W, bufs, pre_norm=False, act=ops.ACT_GELU_ERF, eps=eps, self_attn=self_attn)
         return out, frames

@@ -1,7 +1,8 @@
 """WavLM-large, the upstream of the SIM metric (the reference fetches it through ``torch.hub`` / s3prl, eval/ecapa_tdnn.py:171-199):
 from 16 kHz audio to the stack of hidden states that ``ECAPA_TDNN.forward`` takes -- the input of every encoder layer plus the
 encoder output, s3prl's ``hidden_states`` list.  fp32, eval mode, on the device: csrc/wavlm.hip, f5e_relbias_attn_f32,
-f5e_gemm_f32 and f5e_layernorm.  The sub-modules only HOLD the weights.
+f5e_gemm_f32 and f5e_layernorm; the encoder layer is ``xfmr_f32.layer``, pre-norm, each layer writing the
+next entry of the stack.  The sub-modules only HOLD the weights.  ``WaveEncoder``: what is shared with ``eval/wav2vec2.py``.
 
 Only the large family's structure is built (layer-norm feature extractor, ``layer_norm_first``, ``normalize=True``); anything
 else is refused by field name.  Parameter names are fairseq's / s3prl's, so ``load_state_dict`` works on the
@@ -29,6 +30,7 @@ import torch
 import torch.nn as nn
 
 from .. import _C, ops
+from ..xfmr_f32 import fold, fold_layer, layer, plan, take, view
 
 Tensor = torch.Tensor
 F32, I32 = torch.float32, torch.int32
@@ -221,38 +223,22 @@ def _f(t: Tensor, dev) -> Tensor:
     return t.detach().to(dev, F32).contiguous()
 
 
-class WavLM(nn.Module):
-    def __init__(self, cfg: Optional[WavLMConfig] = None):
-        super().__init__()
-        self.cfg = cfg = cfg or WavLMConfig()
-        cfg.check()
-        C, D = cfg.conv_dim[-1], cfg.encoder_embed_dim
-        self.feature_extractor = _FeatureExtractor(cfg)
-        self.layer_norm = nn.LayerNorm(C, eps=cfg.layer_norm_eps)
-        self.post_extract_proj = nn.Linear(C, D)
-        self.mask_emb = nn.Parameter(torch.zeros(D))
-        self.encoder = _Encoder(cfg)
+class WaveEncoder(nn.Module):
+    """What WavLM and Wav2Vec2 share: eval mode only, the weights folded once per load, the conv front-end's geometry, the
+    scratch plan, the checks of ``extract`` and its launches up to the masked projection.  A model adds its parameter holders
+    (``feature_extractor``, ``layer_norm``, ``post_extract_proj``, ``encoder``), ``_shapes``, ``_fold_more`` and ``extract``."""
+    _conv_act = ops.ACT_NONE                    # the activation fused into the GEMMs of conv layers 1..
+
+    def _freeze(self) -> None:
         self._folded, self._tables = None, {}
-        super().train(False)
+        nn.Module.train(self, False)
         for p in self.parameters():
             p.requires_grad_(False)
-
-    @classmethod
-    def from_sim_checkpoint(cls, state: Dict[str, Tensor], cfg: Optional[WavLMConfig] = None) -> "WavLM":
-        """``state``: the ``"model"`` entry of a reference SIM checkpoint; its ``feature_extract.model.*`` slice is loaded."""
-        sd = {k[len(SIM_PREFIX):]: v for k, v in state.items() if k.startswith(SIM_PREFIX)}
-        if not sd:
-            raise _C.F5EError(f"WavLM.from_sim_checkpoint: the state dict has no {SIM_PREFIX}* keys")
-        model = cls(cfg)
-        missing, unexpected = model.load_state_dict(sd, strict=False)
-        if missing:
-            raise _C.F5EError(f"WavLM.from_sim_checkpoint: the checkpoint lacks {len(missing)} keys, e.g. {missing[:3]}")
-        return model
 
     # ---- eval mode only; weights as the kernels take them, once per load ------------------------------------------------
     def train(self, mode: bool = True):
         if mode:
-            raise _C.F5EError("WavLM: training is out of scope (eval mode only)")
+            raise _C.F5EError(f"{type(self).__name__}: training is out of scope (eval mode only)")
         return super().train(False)
 
     def _apply(self, fn, *a, **kw):
@@ -264,50 +250,41 @@ class WavLM(nn.Module):
         return super().load_state_dict(*a, **kw)
 
     def _fold(self) -> dict:
-        dev = self.mask_emb.device
+        dev = self.layer_norm.weight.device
         if self._folded is not None and self._folded["device"] == dev:
             return self._folded
         if dev.type != "cuda":
-            raise _C.F5EError(f"WavLM lives on {dev}: move it to the GPU (there is no CPU path)")
+            raise _C.F5EError(f"{type(self).__name__} lives on {dev}: move it to the GPU (there is no CPU path)")
         cfg, enc = self.cfg, self.encoder
         fd = dict(device=dev, conv=[], layers=[])
         for i, seq in enumerate(self.feature_extractor.conv_layers):
             w = seq[0].weight.detach()
             w = w[:, 0] if i == 0 else w.permute(0, 2, 1).reshape(w.shape[0], -1)     # tap-major: k = tap * C + ic
-            fd["conv"].append(dict(w=_f(w, dev), b=_f(seq[0].bias, dev) if seq[0].bias is not None else None,
-                                   g=_f(seq[2][1].weight, dev), beta=_f(seq[2][1].bias, dev)))
-        fd["ln_g"], fd["ln_b"] = _f(self.layer_norm.weight, dev), _f(self.layer_norm.bias, dev)
-        fd["proj_w"], fd["proj_b"] = _f(self.post_extract_proj.weight, dev), _f(self.post_extract_proj.bias, dev)
+            fd["conv"].append(dict(w=_f(w, dev), b=_f(seq[0].bias, dev) if seq[0].bias is not None else None))
+        fd["ln_g"], fd["ln_b"] = fold(dev, self.layer_norm)
+        fd["proj_w"], fd["proj_b"] = fold(dev, self.post_extract_proj)
         pc = enc.pos_conv[0]
         fd["pos_w"] = ops.pack_wavlm_posconv_weight(fold_weight_norm(pc.weight_g, pc.weight_v), cfg.conv_pos_groups).to(dev)
         fd["pos_b"] = _f(pc.bias, dev)
         for lyr in enc.layers:
             sa = lyr.self_attn
-            fd["layers"].append(dict(
-                ln1_g=_f(lyr.self_attn_layer_norm.weight, dev), ln1_b=_f(lyr.self_attn_layer_norm.bias, dev),
-                w_qkv=_f(torch.cat([sa.q_proj.weight, sa.k_proj.weight, sa.v_proj.weight], 0), dev),
-                b_qkv=_f(torch.cat([sa.q_proj.bias, sa.k_proj.bias, sa.v_proj.bias], 0), dev),
-                w_gate=_f(sa.grep_linear.weight, dev), b_gate=_f(sa.grep_linear.bias, dev), const=_f(sa.grep_a.reshape(-1), dev),
-                w_out=_f(sa.out_proj.weight, dev), b_out=_f(sa.out_proj.bias, dev),
-                ln2_g=_f(lyr.final_layer_norm.weight, dev), ln2_b=_f(lyr.final_layer_norm.bias, dev),
-                w1=_f(lyr.fc1.weight, dev), b1=_f(lyr.fc1.bias, dev), w2=_f(lyr.fc2.weight, dev), b2=_f(lyr.fc2.bias, dev)))
-        fd["enc_g"], fd["enc_b"] = _f(enc.layer_norm.weight, dev), _f(enc.layer_norm.bias, dev)
+            fd["layers"].append(fold_layer(dev, lyr.self_attn_layer_norm, sa.q_proj, sa.k_proj, sa.v_proj, sa.out_proj,
+                                           lyr.final_layer_norm, lyr.fc1, lyr.fc2))
+        fd["enc_g"], fd["enc_b"] = fold(dev, enc.layer_norm)
+        self._fold_more(fd, dev)
         self._folded = fd
         return fd
-
-    def _table(self, T: int) -> Tensor:
-        """The bias table for Tt = T, built on the host once per (load, T)."""
-        dev = self.mask_emb.device
-        t = self._tables.get(T)
-        if t is None or t.device != dev:
-            cfg = self.cfg
-            emb = self.encoder.layers[0].self_attn.relative_attention_bias.weight
-            t = self._tables[T] = bias_table(emb, T, cfg.num_buckets, cfg.max_distance).to(dev, F32).contiguous()
-        return t
 
     # ---- geometry and workspace ---------------------------------------------------------------------------------------------
     def frame_count(self, n_samples: int) -> int:
         return frame_counts(n_samples, self.cfg)[-1]
+
+    def min_samples(self) -> int:
+        """The shortest row that yields one frame."""
+        n = 1
+        for k, s in zip(reversed(self.cfg.conv_kernel), reversed(self.cfg.conv_stride)):
+            n = (n - 1) * s + k
+        return n
 
     def _geometry(self, S: int) -> Tuple[int, List[int], List[int]]:
         """(T, need, pitch): frames of the longest row, the frames of layer l that layer l + 1 .. reads (need[l]) and the frame
@@ -329,22 +306,107 @@ class WavLM(nn.Module):
         """name -> (offset in floats, shape) of every intermediate; offsets are multiples of 64 floats."""
         cfg = self.cfg
         T, _need, pitch = self._geometry(S)
-        T = max(T, 1)
-        C, D, H, FF = cfg.conv_dim[-1], cfg.encoder_embed_dim, cfg.encoder_attention_heads, cfg.encoder_ffn_embed_dim
-        M, slack = B * T, max(cfg.conv_kernel) * C
-        shapes = dict(frames=(B,), wn=(B, S), partials=(ops.wav_norm_partials(B, S),), mask=(M,),
-                      ca=(B * pitch[0] * C + slack,), cb=(B * (pitch[1] if len(pitch) > 1 else 1) * C + slack,),
-                      xnc=(M, C), proj=(M, D), xn=(M, D), qkv=(M, 3 * D), gate=(B, H, T), ao=(M, D), ff=(M, FF))
-        plan, off = {}, 0
-        for name, shape in shapes.items():
-            plan[name] = (off, shape)
-            off += (math.prod(shape) + 63) // 64 * 64
-        plan["_total"] = (off, ())
-        return plan
+        C, slack = cfg.conv_dim[-1], max(cfg.conv_kernel) * cfg.conv_dim[-1]
+        return plan(self._shapes(B, S, max(T, 1), ca=(B * pitch[0] * C + slack,),
+                                 cb=(B * (pitch[1] if len(pitch) > 1 else 1) * C + slack,)))
 
     def workspace_bytes(self, B: int, S: int) -> int:
         """Scratch bytes of ``extract`` for B rows of S samples (host arithmetic)."""
         return self._plan(int(B), int(S))["_total"][0] * 4
+
+    # ---- forward: the part of ``extract`` that both models run -----------------------------------------------------------
+    def _enter(self, wav: Tensor, lengths, workspace: Optional[Tensor]):
+        """The checks of ``extract`` -> (wav, lengths on the device, the folded weights, buf(name): a view of the scratch)."""
+        who = f"{type(self).__name__}.extract"
+        if not isinstance(wav, Tensor) or wav.ndim != 2 or wav.dtype != F32:
+            raise _C.F5EError(f"{who}: wav must be a float32 tensor [B, S]")
+        if not wav.is_cuda:
+            raise _C.F5EError(f"{who}: wav lives on {wav.device}; there is no CPU path")
+        B, S = wav.shape
+        if B < 1 or self._geometry(S)[0] < 1:
+            raise _C.F5EError(f"{who}: {S} samples give no frame (a row needs {self.min_samples()})")
+        if lengths is not None and not (isinstance(lengths, Tensor) and lengths.is_cuda):
+            host = [int(v) for v in (lengths.tolist() if isinstance(lengths, Tensor) else lengths)]
+            if len(host) != B or min(host) < self.min_samples() or max(host) > S:
+                raise _C.F5EError(f"{who}: lengths must be {B} values in [{self.min_samples()}, {S}]; got {host}")
+            lengths = torch.tensor(host, dtype=I32).to(wav.device, non_blocking=True)
+        elif lengths is not None and (lengths.dtype != I32 or lengths.shape != (B,)):
+            raise _C.F5EError(f"{who}: lengths must be i32 [{B}] (got {lengths.dtype} {tuple(lengths.shape)})")
+        fd, pl = self._fold(), self._plan(B, S)
+        ws = take(workspace, pl["_total"][0], wav.device, who)
+        return wav.contiguous(), lengths, fd, lambda name: view(ws, pl, name)
+
+    def _after_conv(self, y: Tensor, p: dict, eps: float) -> None:
+        """What follows the GEMM of a conv layer 1.. (nothing when ``_conv_act`` is all)."""
+
+    def _project(self, fd: dict, buf, cur: Tensor, nxt: Tensor, B: int, T: int, pitch: List[int]) -> Tensor:
+        """Conv layers 1.. (one GEMM each on an overlapping strided view of the layer below, ``cur``, ping-pong with ``nxt``),
+        the LayerNorm of every row's own T frames and the masked projection -> proj [B * T, D]."""
+        cfg = self.cfg
+        C, eps = cfg.conv_dim[-1], cfg.layer_norm_eps
+        for l in range(1, len(cfg.conv_dim)):
+            k, s, p = cfg.conv_kernel[l], cfg.conv_stride[l], fd["conv"][l]
+            rows = B * pitch[l]
+            y = nxt[:rows * C].view(rows, C)
+            ops.gemm_f32(torch.as_strided(cur, (rows, k * C), (s * C, 1)), p["w"], p["b"], out=y, act=self._conv_act)
+            self._after_conv(y, p, eps)
+            cur, nxt = nxt, cur
+        feat, xnc = cur[:B * pitch[-1] * C].view(B, pitch[-1], C), buf("xnc")
+        for b in range(B):
+            ops.layernorm(feat[b, :T], xnc[b * T:(b + 1) * T], fd["ln_g"], fd["ln_b"], eps=eps)
+        return ops.gemm_f32(xnc, fd["proj_w"], fd["proj_b"], out=buf("proj"), row_scale=buf("mask"))     # x[padding_mask] = 0
+
+
+class WavLM(WaveEncoder):
+    def __init__(self, cfg: Optional[WavLMConfig] = None):
+        super().__init__()
+        self.cfg = cfg = cfg or WavLMConfig()
+        cfg.check()
+        C, D = cfg.conv_dim[-1], cfg.encoder_embed_dim
+        self.feature_extractor = _FeatureExtractor(cfg)
+        self.layer_norm = nn.LayerNorm(C, eps=cfg.layer_norm_eps)
+        self.post_extract_proj = nn.Linear(C, D)
+        self.mask_emb = nn.Parameter(torch.zeros(D))
+        self.encoder = _Encoder(cfg)
+        self._freeze()
+
+    @classmethod
+    def from_sim_checkpoint(cls, state: Dict[str, Tensor], cfg: Optional[WavLMConfig] = None) -> "WavLM":
+        """``state``: the ``"model"`` entry of a reference SIM checkpoint; its ``feature_extract.model.*`` slice is loaded."""
+        sd = {k[len(SIM_PREFIX):]: v for k, v in state.items() if k.startswith(SIM_PREFIX)}
+        if not sd:
+            raise _C.F5EError(f"WavLM.from_sim_checkpoint: the state dict has no {SIM_PREFIX}* keys")
+        model = cls(cfg)
+        missing, unexpected = model.load_state_dict(sd, strict=False)
+        if missing:
+            raise _C.F5EError(f"WavLM.from_sim_checkpoint: the checkpoint lacks {len(missing)} keys, e.g. {missing[:3]}")
+        return model
+
+    def _fold_more(self, fd: dict, dev) -> None:
+        for p, seq in zip(fd["conv"], self.feature_extractor.conv_layers):
+            p["g"], p["beta"] = fold(dev, seq[2][1])
+        gates = [(lyr.self_attn.grep_linear, lyr.self_attn.grep_a) for lyr in self.encoder.layers]
+        fd["layers"] = [W._replace(extra=(*fold(dev, lin), _f(a.reshape(-1), dev)))                 # w_gate, b_gate, const
+                        for W, (lin, a) in zip(fd["layers"], gates)]
+
+    def _table(self, T: int) -> Tensor:
+        """The bias table for Tt = T, built on the host once per (load, T)."""
+        dev = self.mask_emb.device
+        t = self._tables.get(T)
+        if t is None or t.device != dev:
+            cfg = self.cfg
+            emb = self.encoder.layers[0].self_attn.relative_attention_bias.weight
+            t = self._tables[T] = bias_table(emb, T, cfg.num_buckets, cfg.max_distance).to(dev, F32).contiguous()
+        return t
+
+    def _shapes(self, B: int, S: int, T: int, **conv) -> Dict[str, tuple]:
+        cfg = self.cfg
+        C, D, H, M = cfg.conv_dim[-1], cfg.encoder_embed_dim, cfg.encoder_attention_heads, B * T
+        return dict(frames=(B,), wn=(B, S), partials=(ops.wav_norm_partials(B, S),), mask=(M,), **conv, xnc=(M, C), proj=(M, D),
+                    xn=(M, D), qkv=(M, 3 * D), gate=(B, H, T), ao=(M, D), ff=(M, cfg.encoder_ffn_embed_dim))
+
+    def _after_conv(self, y: Tensor, p: dict, eps: float) -> None:
+        ops.layernorm_gelu(y, y, p["g"], p["beta"], eps)
 
     # ---- forward -------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -355,88 +417,33 @@ class WavLM(nn.Module):
         (``workspace_bytes(B, S)`` bytes, f32 or uint8) and device lengths it allocates nothing once the weights are folded and
         the bias table of this T exists (a first call does both), so it can be captured into a graph."""
         cfg = self.cfg
-        if not isinstance(wav, Tensor) or wav.ndim != 2 or wav.dtype != F32:
-            raise _C.F5EError("WavLM.extract: wav must be a float32 tensor [B, S]")
-        if not wav.is_cuda:
-            raise _C.F5EError(f"WavLM.extract: wav lives on {wav.device}; there is no CPU path")
-        B, S = wav.shape
-        T, need, pitch = self._geometry(S)
-        if B < 1 or T < 1:
-            raise _C.F5EError(f"WavLM.extract: {S} samples give no frame (a row needs {self.min_samples()})")
-        dev = wav.device
-        if lengths is not None and not (isinstance(lengths, Tensor) and lengths.is_cuda):
-            host = [int(v) for v in (lengths.tolist() if isinstance(lengths, Tensor) else lengths)]
-            if len(host) != B or min(host) < self.min_samples() or max(host) > S:
-                raise _C.F5EError(f"WavLM.extract: lengths must be {B} values in [{self.min_samples()}, {S}]; got {host}")
-            lengths = torch.tensor(host, dtype=I32).to(dev, non_blocking=True)
-        elif lengths is not None and (lengths.dtype != I32 or lengths.shape != (B,)):
-            raise _C.F5EError(f"WavLM.extract: lengths must be i32 [{B}] (got {lengths.dtype} {tuple(lengths.shape)})")
-        fd, table = self._fold(), self._table(T)
-        wav = wav.contiguous()
-        C, D, H, FF, L = cfg.conv_dim[-1], cfg.encoder_embed_dim, cfg.encoder_attention_heads, cfg.encoder_ffn_embed_dim, \
-            cfg.encoder_layers
-        plan = self._plan(B, S)
-        total = plan["_total"][0]
-        if workspace is None:
-            ws = torch.empty(total, dtype=F32, device=dev)
-        else:
-            if not workspace.is_cuda or workspace.dtype not in (F32, torch.uint8) or not workspace.is_contiguous() or \
-                    workspace.data_ptr() % 16 or workspace.numel() * workspace.element_size() < total * 4:
-                raise _C.F5EError(f"WavLM.extract: workspace must be a contiguous 16-byte aligned f32 / uint8 GPU tensor of at "
-                                  f"least {total * 4} bytes (workspace_bytes)")
-            ws = workspace.view(-1)
-            ws = ws[: ws.numel() // 4 * 4].view(F32) if ws.dtype == torch.uint8 else ws
+        wav, lengths, fd, buf = self._enter(wav, lengths, workspace)
+        (B, S), (T, need, pitch) = wav.shape, self._geometry(wav.shape[1])
+        table = self._table(T)
+        C, D, H, L = cfg.conv_dim[-1], cfg.encoder_embed_dim, cfg.encoder_attention_heads, cfg.encoder_layers
         if out is None:
-            out = torch.empty(L + 1, B, T, D, dtype=F32, device=dev)
+            out = torch.empty(L + 1, B, T, D, dtype=F32, device=wav.device)
         elif out.shape != (L + 1, B, T, D) or out.dtype != F32 or not out.is_cuda or not out.is_contiguous():
             raise _C.F5EError(f"WavLM.extract: out must be a contiguous f32 GPU tensor [{L + 1}, {B}, {T}, {D}]")
-
-        def buf(name):
-            off, shape = plan[name]
-            return ws[off:off + math.prod(shape)].view(shape)
-
         M, eps = B * T, cfg.layer_norm_eps
-        frames, wn, mask = buf("frames").view(I32), buf("wn"), buf("mask")
-        ops.wav_norm(wav, lengths, wn, buf("partials"), frames, mask.view(B, T), cfg.conv_kernel, cfg.conv_stride)
-        # the conv front-end: layer 0 fused, layers 1.. one GEMM each on an overlapping strided view of the layer below
-        cur, nxt = buf("ca"), buf("cb")
-        c0 = fd["conv"][0]
+        frames, wn = buf("frames").view(I32), buf("wn")
+        ops.wav_norm(wav, lengths, wn, buf("partials"), frames, buf("mask").view(B, T), cfg.conv_kernel, cfg.conv_stride)
+        cur, c0 = buf("ca"), fd["conv"][0]                      # the conv front-end: layer 0 fused
         ops.wavlm_conv0(wn, c0["w"], c0["b"], c0["g"], c0["beta"], cur[:B * pitch[0] * C].view(B, pitch[0], C), T0=need[0])
-        for l in range(1, len(cfg.conv_dim)):
-            k, s, p = cfg.conv_kernel[l], cfg.conv_stride[l], fd["conv"][l]
-            rows = B * pitch[l]
-            y = nxt[:rows * C].view(rows, C)
-            ops.gemm_f32(torch.as_strided(cur, (rows, k * C), (s * C, 1)), p["w"], p["b"], out=y)
-            ops.layernorm_gelu(y, y, p["g"], p["beta"], eps)
-            cur, nxt = nxt, cur
-        feat, xnc = cur[:B * pitch[-1] * C].view(B, pitch[-1], C), buf("xnc")
-        for b in range(B):
-            ops.layernorm(feat[b, :T], xnc[b * T:(b + 1) * T], fd["ln_g"], fd["ln_b"], eps=eps)
-        proj = buf("proj")
-        ops.gemm_f32(xnc, fd["proj_w"], fd["proj_b"], out=proj, row_scale=mask)       # x[padding_mask] = 0
+        proj = self._project(fd, buf, cur, buf("cb"), B, T, pitch)
         ops.wavlm_posconv(proj.view(B, T, D), fd["pos_w"], fd["pos_b"], frames, out[0])
-        xn, qkv, gate, ao, ff = buf("xn"), buf("qkv"), buf("gate"), buf("ao"), buf("ff")
-        scale = (D // H) ** -0.5
-        for l, p in enumerate(fd["layers"]):
-            x, y = out[l].view(M, D), out[l + 1].view(M, D)
-            ops.layernorm(x, xn, p["ln1_g"], p["ln1_b"], eps=eps)
-            ops.gemm_f32(xn, p["w_qkv"], p["b_qkv"], out=qkv)
-            ops.wavlm_gate(xn, p["w_gate"], p["b_gate"], p["const"], gate)
+        bufs, gate, scale = (buf("xn"), buf("qkv"), buf("ao"), None, buf("ff")), buf("gate"), (D // H) ** -0.5
+
+        def self_attn(W, xn, qkv, ao):                          # the gated relative-position bias: two launches
+            ops.wavlm_gate(xn, *W.extra, gate)
             ops.relbias_attn(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], gate, table, H, scale, kv_len=frames, out=ao)
-            ops.gemm_f32(ao, p["w_out"], p["b_out"], out=y, addend=x)
-            ops.layernorm(y, xn, p["ln2_g"], p["ln2_b"], eps=eps)
-            ops.gemm_f32(xn, p["w1"], p["b1"], out=ff, act=ops.ACT_GELU_ERF)
-            ops.gemm_f32(ff, p["w2"], p["b2"], out=y, addend=y)
+
+        for l, W in enumerate(fd["layers"]):                    # pre-LN; layer l reads out[l] and writes out[l + 1]
+            layer(out[l].view(M, D), out[l + 1].view(M, D), W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=eps,
+                  self_attn=self_attn)
         last = out[L].view(M, D)
         ops.layernorm(last, last, fd["enc_g"], fd["enc_b"], eps=eps)
         return out, frames
-
-    def min_samples(self) -> int:
-        """The shortest row that yields one frame."""
-        n = 1
-        for k, s in zip(reversed(self.cfg.conv_kernel), reversed(self.cfg.conv_stride)):
-            n = (n - 1) * s + k
-        return n
 
     def forward(self, wavs: Sequence[Tensor]) -> dict:
         """s3prl's call: a list of 1-D 16 kHz waveforms on the GPU -> {"hidden_states": [L + 1 tensors [B, T, D]], "lengths":

@@ -4,7 +4,8 @@ transcribe a prompt without text (infer/utils_infer.py:148-179) and ``whisper-la
 beam search of ``transformers``' ``generate(num_beams=K)`` (what eval/utils_eval.py:517-526 asks of its recogniser with
 ``beam_size=5``); fp32, eval mode, no CPU path: f5e_whisper_logmel, f5e_cross_attn_decode_f32, f5e_greedy_pick and
 f5e_whisper_beam_step (csrc/whisper.hip) plus f5e_im2col, f5e_gemm_f32, f5e_layernorm,
-f5e_mha_f32, f5e_attn_decode_f32 and f5e_text_gather.  The sub-modules only HOLD the weights, under the Hugging Face
+f5e_mha_f32, f5e_attn_decode_f32 and f5e_text_gather; every layer is ``xfmr_f32.layer``, which is handed
+the attention launches.  The sub-modules only HOLD the weights, under the Hugging Face
 parameter names, so ``load_state_dict`` takes a ``WhisperForConditionalGeneration`` state dict:
 
     model.encoder.conv1.{weight,bias}, model.encoder.conv2.*, model.encoder.embed_positions.weight,
@@ -37,6 +38,7 @@ import os
 import struct
 import warnings
 from dataclasses import dataclass, field
+from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -44,6 +46,7 @@ import torch
 import torch.nn as nn
 
 from .. import _C, ops
+from ..xfmr_f32 import fold, fold_layer, layer
 
 Tensor = torch.Tensor
 F32, I32 = torch.float32, torch.int32
@@ -518,18 +521,6 @@ class Whisper(nn.Module):
         return super()._apply(fn, *a, **kw)
 
     # ---- weights as the kernels take them, once per load -----------------------------------------------------------------------
-    @staticmethod
-    def _attn_weights(a: _Attn, dev, cross: bool) -> dict:
-        D = a.q_proj.weight.shape[0]
-        zero = torch.zeros(D, dtype=F32, device=a.q_proj.bias.device)
-        if cross:      # q alone per step; k | v once per utterance
-            return dict(w_q=_f(a.q_proj.weight, dev), b_q=_f(a.q_proj.bias, dev),
-                        w_kv=_f(torch.cat([a.k_proj.weight, a.v_proj.weight], 0), dev), b_kv=_f(torch.cat([zero, a.v_proj.bias]), dev),
-                        w_o=_f(a.out_proj.weight, dev), b_o=_f(a.out_proj.bias, dev))
-        return dict(w_qkv=_f(torch.cat([a.q_proj.weight, a.k_proj.weight, a.v_proj.weight], 0), dev),
-                    b_qkv=_f(torch.cat([a.q_proj.bias, zero, a.v_proj.bias]), dev),      # k_proj has no bias: zeros in the k third
-                    w_o=_f(a.out_proj.weight, dev), b_o=_f(a.out_proj.bias, dev))
-
     def _fold(self) -> dict:
         dev = self.model.decoder.embed_tokens.weight.device
         if self._folded is not None and self._folded["device"] == dev:
@@ -538,24 +529,20 @@ class Whisper(nn.Module):
             raise _C.F5EError(f"Whisper lives on {dev}: move it to the GPU (there is no CPU path)")
         cfg, enc, dec = self.cfg, self.model.encoder, self.model.decoder
 
-        def ln(m):
-            return _f(m.weight, dev), _f(m.bias, dev)
-
-        def common(lyr):
-            return dict(ln1=ln(lyr.self_attn_layer_norm), sa=self._attn_weights(lyr.self_attn, dev, False), ln3=ln(lyr.final_layer_norm),
-                        w1=_f(lyr.fc1.weight, dev), b1=_f(lyr.fc1.bias, dev), w2=_f(lyr.fc2.weight, dev), b2=_f(lyr.fc2.bias, dev))
+        def rec(lyr, ca=None):        # k_proj has no bias: fold_layer leaves zeros in the k third of qkv[1], the k half of xkv[1]
+            sa = lyr.self_attn
+            x = dict(ln_x=lyr.encoder_attn_layer_norm, xq=ca.q_proj, xk=ca.k_proj, xv=ca.v_proj, xout=ca.out_proj) if ca else {}
+            return fold_layer(dev, lyr.self_attn_layer_norm, sa.q_proj, sa.k_proj, sa.v_proj, sa.out_proj, lyr.final_layer_norm,
+                              lyr.fc1, lyr.fc2, **x)
         fd = dict(device=dev,
                   window=torch.from_numpy(hann_window()).to(dev, F32), twiddle=torch.from_numpy(dft_twiddle()).to(dev, F32).contiguous(),
                   fb=torch.from_numpy(mel_filters(cfg.num_mel_bins)).to(dev, F32).contiguous(),
                   # tap-major conv weights: k = tap * C_in + ic, the column order of f5e_im2col
                   c1_w=_f(enc.conv1.weight.permute(0, 2, 1).reshape(cfg.d_model, -1), dev), c1_b=_f(enc.conv1.bias, dev),
                   c2_w=_f(enc.conv2.weight.permute(0, 2, 1).reshape(cfg.d_model, -1), dev), c2_b=_f(enc.conv2.bias, dev),
-                  enc_pos=_f(enc.embed_positions.weight, dev), enc_ln=ln(enc.layer_norm), enc=[common(l) for l in enc.layers],
-                  emb=_f(dec.embed_tokens.weight, dev), dec_pos=_f(dec.embed_positions.weight, dev), dec_ln=ln(dec.layer_norm), dec=[])
-        for lyr in dec.layers:
-            d = common(lyr)
-            d.update(ln2=ln(lyr.encoder_attn_layer_norm), ca=self._attn_weights(lyr.encoder_attn, dev, True))
-            fd["dec"].append(d)
+                  enc_pos=_f(enc.embed_positions.weight, dev), enc_ln=fold(dev, enc.layer_norm), enc=[rec(l) for l in enc.layers],
+                  emb=_f(dec.embed_tokens.weight, dev), dec_pos=_f(dec.embed_positions.weight, dev), dec_ln=fold(dev, dec.layer_norm),
+                  dec=[rec(l, l.encoder_attn) for l in dec.layers])
         fd["suppress"] = torch.tensor(list(cfg.suppress_tokens), dtype=I32, device=dev) if cfg.suppress_tokens else None
         fd["begin_suppress"] = torch.tensor(list(cfg.begin_suppress_tokens), dtype=I32, device=dev) if cfg.begin_suppress_tokens else None
         # language detection = a greedy pick that suppresses every class but the language ids
@@ -603,17 +590,6 @@ class Whisper(nn.Module):
         fd = self._fold()
         return ops.whisper_logmel(wav, lens, fd["window"], fd["twiddle"], fd["fb"], self.n_frames)
 
-    def _enc_layer(self, x: Tensor, p: dict, B: int, H: int, bufs: dict) -> None:
-        D = x.shape[1]
-        xn, qkv, ao, ff = bufs["xn"], bufs["qkv"], bufs["ao"], bufs["ff"]
-        ops.layernorm(x, xn, *p["ln1"], eps=1e-5)
-        ops.gemm_f32(xn, p["sa"]["w_qkv"], p["sa"]["b_qkv"], out=qkv)
-        ops.mha_f32(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], H, (D // H) ** -0.5, B=B, out=ao)
-        ops.gemm_f32(ao, p["sa"]["w_o"], p["sa"]["b_o"], out=x, addend=x)
-        ops.layernorm(x, xn, *p["ln3"], eps=1e-5)
-        ops.gemm_f32(xn, p["w1"], p["b1"], out=ff, act=ops.ACT_GELU_ERF)
-        ops.gemm_f32(ff, p["w2"], p["b2"], out=x, addend=x)
-
     @torch.no_grad()
     def encode_features(self, feats: Tensor) -> Tensor:
         """feats f32 [B, T, num_mel_bins] (channels-last, T = 2 * max_source_positions) -> the encoder's last hidden state f32
@@ -634,10 +610,14 @@ class Whisper(nn.Module):
                      addend=fd["enc_pos"])
         del col1, h1, col2
         M_ = B * Tp
-        bufs = dict(xn=torch.empty(M_, D, dtype=F32, device=dev), qkv=torch.empty(M_, 3 * D, dtype=F32, device=dev),
-                    ao=torch.empty(M_, D, dtype=F32, device=dev), ff=torch.empty(M_, cfg.encoder_ffn_dim, dtype=F32, device=dev))
-        for p in fd["enc"]:
-            self._enc_layer(x, p, B, cfg.encoder_attention_heads, bufs)
+        z = lambda n: torch.empty(M_, n, dtype=F32, device=dev)   # noqa: E731
+        bufs, H = (z(D), z(3 * D), z(D), None, z(cfg.encoder_ffn_dim)), cfg.encoder_attention_heads
+
+        def self_attn(_W, _xn, qkv, ao):
+            ops.mha_f32(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], H, (D // H) ** -0.5, B=B, out=ao)
+
+        for W in fd["enc"]:
+            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn)
         ops.layernorm(x, x, *fd["enc_ln"], eps=1e-5)
         return x.view(B, Tp, D)
 
@@ -649,7 +629,7 @@ class Whisper(nn.Module):
         out = []
         for p in fd["dec"]:
             kv = torch.empty(B * Tp, 2 * D, dtype=F32, device=enc_out.device)
-            ops.gemm_f32(enc_out.view(B * Tp, D), p["ca"]["w_kv"], p["ca"]["b_kv"], out=kv)
+            ops.gemm_f32(enc_out.view(B * Tp, D), *p.xkv, out=kv)
             kv = kv.view(B, Tp, 2 * D)
             out.append((kv[..., :D], kv[..., D:]))
         return out
@@ -665,8 +645,26 @@ class Whisper(nn.Module):
         D, V = cfg.d_model, cfg.vocab_size
         Vp = (V + 3) // 4 * 4
         z = lambda *s: torch.empty(*s, dtype=F32, device=dev)   # noqa: E731
-        return dict(x=z(R, 1, D), xn=z(R, D), qkv=z(R, 3 * D), ao=z(R, D), q=z(R, D), ff=z(R, cfg.decoder_ffn_dim),
-                    logits=z(R, Vp)[:, :V], caches=[(z(R, Umax, D), z(R, Umax, D)) for _ in range(cfg.decoder_layers)])
+        st = dict(x=z(R, 1, D), xn=z(R, D), qkv=z(R, 3 * D), ao=z(R, D), q=z(R, D), ff=z(R, cfg.decoder_ffn_dim),
+                  logits=z(R, Vp)[:, :V], caches=[(z(R, Umax, D), z(R, Umax, D)) for _ in range(cfg.decoder_layers)])
+        # the attention launches of ``layer``, built once per state; ``_dec_step`` sets in ``at`` what a step (p, anc, kv, align)
+        # and a layer (i) change
+        H, caches, align_of = cfg.decoder_attention_heads, st["caches"], self._fold()["align"]
+        scale, at = (D // H) ** -0.5, SimpleNamespace(i=0, p=0, anc=None, kv=None, align=None)
+
+        def self_attn(_W, _xn, qkv, ao):
+            kc, vc = caches[at.i]
+            ops.attn_decode_f32(qkv, kc, vc, at.p, H, scale, anc=at.anc, out=ao)
+
+        def cross_attn(_W, q, ao):
+            (K, Vv), align = at.kv[at.i], at.align
+            ops.cross_attn_decode_f32(q, K, Vv, H, scale, rows_per_utt=R // K.shape[0], out=ao)
+            if align is not None:
+                for s0, heads in align_of.get(at.i, ()):
+                    ops.cross_attn_probs_f32(q, K, heads, H, scale, align[0][:, s0:s0 + heads.shape[0], align[1]],
+                                             rows_per_utt=R // K.shape[0], m_len=align[2])
+        st["layer"] = (at, (st["xn"], st["qkv"], st["ao"], st["q"], st["ff"]), self_attn, cross_attn)
+        return st
 
     def _dec_step(self, st: dict, kv: List[Tuple[Tensor, Tensor]], last: Tensor, p: int, want_logits: bool,
                   anc: Optional[Tensor] = None, align: Optional[Tuple[Tensor, int, Tensor]] = None) -> Optional[Tensor]:
@@ -675,28 +673,14 @@ class Whisper(nn.Module):
         ``align`` = (probs f32 [R, heads, N, ld], t, m_len i32 [B]): the layers that own an alignment head also write those
         heads' cross-attention probabilities of this position to probs[:, :, t, :m_len] (an extra launch; nothing else changes)."""
         cfg, fd = self.cfg, self._fold()
-        D, H = cfg.d_model, cfg.decoder_attention_heads
-        scale = (D // H) ** -0.5
-        R = last.shape[0]
-        x3, xn, qkv, ao, q, ff = st["x"], st["xn"], st["qkv"], st["ao"], st["q"], st["ff"]
+        R, D = last.shape[0], cfg.d_model
+        x3, xn, (at, bufs, self_attn, cross_attn) = st["x"], st["xn"], st["layer"]
+        at.p, at.anc, at.kv, at.align = p, anc, kv, align
         ops.text_gather(last.view(R, 1), fd["emb"], fd["dec_pos"][p:p + 1], None, x3)
         x = x3.view(R, D)
-        for li, (lp, (kc, vc), (K, Vv)) in enumerate(zip(fd["dec"], st["caches"], kv)):
-            ops.layernorm(x, xn, *lp["ln1"], eps=1e-5)
-            ops.gemm_f32(xn, lp["sa"]["w_qkv"], lp["sa"]["b_qkv"], out=qkv)
-            ops.attn_decode_f32(qkv, kc, vc, p, H, scale, anc=anc, out=ao)
-            ops.gemm_f32(ao, lp["sa"]["w_o"], lp["sa"]["b_o"], out=x, addend=x)
-            ops.layernorm(x, xn, *lp["ln2"], eps=1e-5)
-            ops.gemm_f32(xn, lp["ca"]["w_q"], lp["ca"]["b_q"], out=q)
-            ops.cross_attn_decode_f32(q, K, Vv, H, scale, rows_per_utt=R // K.shape[0], out=ao)
-            if align is not None:
-                for s0, heads in fd["align"].get(li, ()):
-                    ops.cross_attn_probs_f32(q, K, heads, H, scale, align[0][:, s0:s0 + heads.shape[0], align[1]],
-                                             rows_per_utt=R // K.shape[0], m_len=align[2])
-            ops.gemm_f32(ao, lp["ca"]["w_o"], lp["ca"]["b_o"], out=x, addend=x)
-            ops.layernorm(x, xn, *lp["ln3"], eps=1e-5)
-            ops.gemm_f32(xn, lp["w1"], lp["b1"], out=ff, act=ops.ACT_GELU_ERF)
-            ops.gemm_f32(ff, lp["w2"], lp["b2"], out=x, addend=x)
+        for i, W in enumerate(fd["dec"]):
+            at.i = i
+            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn, cross_attn=cross_attn)
         if not want_logits:
             return None
         ops.layernorm(x, xn, *fd["dec_ln"], eps=1e-5)

@@ -35,6 +35,7 @@ import torch
 from torch import nn
 
 from .. import _C, ops
+from ..xfmr_f32 import fold_layer, layer
 
 F32, I32 = torch.float32, torch.int32
 Tensor = torch.Tensor
@@ -899,17 +900,15 @@ class ConformerEngine:
 
     def _decoder_weights(self, f, sd, pre: str) -> dict:
         """One TransformerDecoder's weights, repacked once: the embedding pre-scaled by sqrt(D) (embedding.py:62), q | k | v
-        of the self-attention and k | v of the source attention stacked into one GEMM each."""
-        att = lambda p, names: (torch.cat([f(p + f"linear_{n}.weight") for n in names], 0).contiguous(),   # noqa: E731
-                                torch.cat([f(p + f"linear_{n}.bias") for n in names], 0).contiguous())
+        of the self-attention and k | v of the source attention stacked into one GEMM each (``xfmr_f32.fold_layer``)."""
+        wb = lambda n: (sd[n + ".weight"], sd[n + ".bias"])   # noqa: E731
         layers, i = [], 0
         while f"{pre}decoders.{i}.norm1.weight" in sd:
             p = f"{pre}decoders.{i}."
-            layers.append(dict(
-                ln=[(f(p + f"norm{k}.weight"), f(p + f"norm{k}.bias")) for k in (1, 2, 3)],
-                self_qkv=att(p + "self_attn.", "qkv"), self_out=att(p + "self_attn.", ["out"]),
-                src_q=att(p + "src_attn.", "q"), src_kv=att(p + "src_attn.", "kv"), src_out=att(p + "src_attn.", ["out"]),
-                ff=tuple(f(p + "feed_forward." + n_) for n_ in ("w_1.weight", "w_1.bias", "w_2.weight", "w_2.bias"))))
+            sa, xa = p + "self_attn.linear_", p + "src_attn.linear_"
+            layers.append(fold_layer(self.device, wb(p + "norm1"), wb(sa + "q"), wb(sa + "k"), wb(sa + "v"), wb(sa + "out"),
+                                     wb(p + "norm3"), wb(p + "feed_forward.w_1"), wb(p + "feed_forward.w_2"), ln_x=wb(p + "norm2"),
+                                     xq=wb(xa + "q"), xk=wb(xa + "k"), xv=wb(xa + "v"), xout=wb(xa + "out")))
             i += 1
         return dict(embed=(f(pre + "embed.0.weight") * math.sqrt(self.dim)).contiguous(), layers=layers,
                     after=(f(pre + "after_norm.weight"), f(pre + "after_norm.bias")),
@@ -935,21 +934,18 @@ class ConformerEngine:
         x = x.view(R, D)
         hn, ctx, q = torch.empty(R, D, device=dv), torch.empty(R, D, device=dv), torch.empty(R, D, device=dv)
         qkv, kv = torch.empty(R, 3 * D, device=dv), torch.empty(B * T2, 2 * D, device=dv)
-        units = W["layers"][0]["ff"][0].shape[0] if W["layers"] else D
-        mid = torch.empty(R, units, device=dv)
-        for L in W["layers"]:
-            _ln(x, hn, L["ln"][0])
-            ops.gemm_f32(hn, *L["self_qkv"], out=qkv)
+        units = W["layers"][0].ff[0].shape[0] if W["layers"] else D
+        bufs = (hn, qkv, ctx, q, torch.empty(R, units, device=dv))
+
+        def self_attn(_L, _hn, qkv, ctx):
             ops.mha_f32(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], H, scale, B=NB, kv_len=ys_len, causal=True, out=ctx)
-            ops.gemm_f32(ctx, *L["self_out"], out=x, addend=x)
-            _ln(x, hn, L["ln"][1])
-            ops.gemm_f32(hn, *L["src_q"], out=q)
-            ops.gemm_f32(mem, *L["src_kv"], out=kv)
+
+        def src_attn(L, q, ctx):                # the memory's keys and values, projected per layer into one buffer
+            ops.gemm_f32(mem, *L.xkv, out=kv)
             ops.mha_f32(q, kv[:, :D], kv[:, D:], H, scale, B=B, kv_len=mem_len, causal=False, out=ctx)
-            ops.gemm_f32(ctx, *L["src_out"], out=x, addend=x)
-            _ln(x, hn, L["ln"][2])
-            ops.gemm_f32(hn, L["ff"][0], L["ff"][1], out=mid, act=ops.ACT_RELU)
-            ops.gemm_f32(mid, L["ff"][2], L["ff"][3], out=x, addend=x)
+
+        for L in W["layers"]:
+            layer(x, x, L, bufs, pre_norm=True, act=ops.ACT_RELU, eps=1e-5, self_attn=self_attn, cross_attn=src_attn)
         _ln(x, hn, W["after"])
         logits = torch.empty(R, W["out"][0].shape[0], device=dv)
         ops.gemm_f32(hn, *W["out"], out=logits)
@@ -971,7 +967,7 @@ class ConformerEngine:
         if not 1 <= umax <= 4096:
             raise _C.F5EError(f"decode_state: the search runs at most 4096 steps (got {umax})")
         R, nl = B * beam, len(W["layers"])
-        units = W["layers"][0]["ff"][0].shape[0] if nl else D
+        units = W["layers"][0].ff[0].shape[0] if nl else D
         V = W["out"][0].shape[0]
         S = SimpleNamespace(W=W, B=B, beam=beam, R=R, umax=umax, eos=eos, mem_len=mem_len, p=0,
                             scale=1.0 / math.sqrt(D // H),
@@ -988,13 +984,25 @@ class ConformerEngine:
             h[:, 0] = sos
         mem = memory.reshape(B * T2, D)
         for L in W["layers"]:
-            S.kv.append(ops.gemm_f32(mem, *L["src_kv"], out=torch.empty(B * T2, 2 * D, device=dv)))
+            S.kv.append(ops.gemm_f32(mem, *L.xkv, out=torch.empty(B * T2, 2 * D, device=dv)))
+        # the attention launches of ``layer``, built once; ``decode_step`` sets in ``at`` what a step (p, anc, every = reorder_cache)
+        # and a layer (i) change
+        S.at = at = SimpleNamespace(i=0, p=0, anc=None, every=False)
+        kc, vc, kv, scale = S.kc, S.vc, S.kv, S.scale
+
+        def self_attn(_L, _hn, qkv, ctx):
+            ops.attn_decode_f32(qkv, kc[at.i], vc[at.i], at.p, H, scale, anc=at.anc if (at.i == 0 or at.every) else None, out=ctx)
+
+        def src_attn(_L, q, ctx):
+            ops.mha_f32(q, kv[at.i][:, :D], kv[at.i][:, D:], H, scale, B=B, kv_len=mem_len, causal=False, out=ctx)
+        S.layer = ((S.hn, S.qkv, S.ctx, S.q, S.mid), self_attn, src_attn)
         return S
 
     def decode_step(self, S: SimpleNamespace, reorder_cache: bool = False, prune: bool = True) -> Tensor:
         """TransformerDecoder.forward_one_step (decoder.py:137-181) for position ``S.p`` of all R rows plus, with ``prune``,
         the beam update of asr_model.py:374-403 -> the step's raw logits [R, V] (a buffer of ``S``).  11 launches per layer
-        + 4: embedding of the last tokens at position p; per layer LayerNorm, q | k | v, f5e_attn_decode_f32 on the layer's
+        (``xfmr_f32.layer`` with the two attention launches of ``decode_state``) + 4:
+        embedding of the last tokens at position p; per layer LayerNorm, q | k | v, f5e_attn_decode_f32 on the layer's
         cache, out-projection, LayerNorm, q, f5e_mha_f32 of B items x beam queries against the memory, out-projection,
         LayerNorm, two feed-forward GEMMs; after_norm, output layer, f5e_beam_step.  The ancestry table goes to layer 0 alone
         (the reference: its caches of the layers above stay with the row index) or, ``reorder_cache``, to every layer."""
@@ -1004,19 +1012,11 @@ class ConformerEngine:
         cur, nxt = p & 1, (p & 1) ^ 1
         ops.text_gather(S.last.view(S.R, 1), W["embed"], self.pos_table(1, offset=p), None, S.x)
         x = S.x.view(S.R, D)
+        at, (bufs, self_attn, src_attn) = S.at, S.layer
+        at.p, at.anc, at.every = p, S.anc[cur], reorder_cache
         for i, L in enumerate(W["layers"]):
-            _ln(x, S.hn, L["ln"][0])
-            ops.gemm_f32(S.hn, *L["self_qkv"], out=S.qkv)
-            ops.attn_decode_f32(S.qkv, S.kc[i], S.vc[i], p, H, S.scale, anc=S.anc[cur] if (i == 0 or reorder_cache) else None,
-                                out=S.ctx)
-            ops.gemm_f32(S.ctx, *L["self_out"], out=x, addend=x)
-            _ln(x, S.hn, L["ln"][1])
-            ops.gemm_f32(S.hn, *L["src_q"], out=S.q)
-            ops.mha_f32(S.q, S.kv[i][:, :D], S.kv[i][:, D:], H, S.scale, B=S.B, kv_len=S.mem_len, causal=False, out=S.ctx)
-            ops.gemm_f32(S.ctx, *L["src_out"], out=x, addend=x)
-            _ln(x, S.hn, L["ln"][2])
-            ops.gemm_f32(S.hn, L["ff"][0], L["ff"][1], out=S.mid, act=ops.ACT_RELU)
-            ops.gemm_f32(S.mid, L["ff"][2], L["ff"][3], out=x, addend=x)
+            at.i = i
+            layer(x, x, L, bufs, pre_norm=True, act=ops.ACT_RELU, eps=1e-5, self_attn=self_attn, cross_attn=src_attn)
         _ln(x, S.hn, W["after"])
         ops.gemm_f32(S.hn, *W["out"], out=S.logits)
         if prune:

@@ -99,6 +99,8 @@ SIGNATURES = {
     "f5e_whisper_beam_step": [_P, _P, _LL, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, C.c_ulonglong,
                               _I, _I, _I, _I, _I, _I, _I, _F],
     "f5e_whisper_ts_pick": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
+    "f5e_whisper_sample_pick": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, C.c_ulonglong,
+                                _P, _P],
     "f5e_whisper_ts_rule": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I],
     "f5e_whisper_beam_step_ts": [_P, _P, _LL, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P,
                                  C.c_ulonglong, _I, _I, _I, _I, _I, _I, _I, _F, _I, _I, _P],

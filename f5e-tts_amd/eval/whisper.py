@@ -22,9 +22,14 @@ f5e_dtw_cost_f32, f5e_dtw_path; csrc/whisper_align.hip).
 
 Timestamp tokens and long recordings (``generate(return_timestamps=True)``, ``transcribe_long``, ``detect_language``): the rules
 of ``WhisperTimeStampLogitsProcessor`` on the device (f5e_whisper_ts_pick, f5e_whisper_beam_step_ts) and the sequential seek loop
-of ``transformers``' long-form ``generate`` with ``condition_on_prev_tokens=False`` at temperature 0.
+of ``transformers``' long-form ``generate`` with ``condition_on_prev_tokens=False``.
 
-Out of scope: temperature fallback and sampling, conditioning on previous windows and ``prompt_ids``, the pipeline's strided
+Temperature fallback and sampling (``transcribe_long(fallback=Fallback(...))``, ``generate(temperature=, seed=)``): a window whose
+compression ratio or average log-probability misses its threshold is decoded again at the next temperature, sampled on the
+device under the same rules (f5e_whisper_sample_pick: Gumbel-max with counter-based Philox noise, so a draw depends on the seed,
+the utterance, the decode and the position alone).
+
+Out of scope: beam-sample, top-k / top-p, conditioning on previous windows and ``prompt_ids``, the pipeline's strided
 ``chunk_length_s`` merging, word timestamps across windows, patience, CTranslate2's exact search, bf16 / fp16 weights (fp16
 checkpoints are widened), a graph-captured step.
 
@@ -305,6 +310,36 @@ class Segment:
     avg_logprob: float
     no_speech_prob: float
     compression_ratio: float
+    temperature: float = 0.0      # of the attempt that was kept for the window (``Fallback``)
+
+
+@dataclass(frozen=True)
+class Fallback:
+    """Temperature fallback of ``transcribe_long`` (``transformers``' ``generate_with_fallback`` / ``_need_fallback``): a window is
+    decoded at ``temperatures[0]`` and again at the next entry while its compression ratio exceeds
+    ``compression_ratio_threshold`` or its average log-probability falls below ``logprob_threshold`` (None: that test is off);
+    the last attempt is kept.  0 decodes greedily (or with the beams asked for), a positive entry samples one row per utterance
+    with f5e_whisper_sample_pick and ``seed``.  ``logprob_threshold`` is also the one the no-speech skip uses."""
+    temperatures: Tuple[float, ...] = (0.0, 0.2, 0.4, 0.6, 0.8, 1.0)
+    compression_ratio_threshold: Optional[float] = None
+    logprob_threshold: Optional[float] = None
+    seed: int = 0
+
+    def __post_init__(self):
+        t = self.temperatures
+        try:
+            t = tuple(float(v) for v in ((t,) if isinstance(t, (int, float)) else t))
+        except (TypeError, ValueError):
+            raise _C.F5EError(f"Fallback: temperatures = {self.temperatures!r} is not a sequence of numbers") from None
+        if not t or not all(math.isfinite(v) and v >= 0.0 for v in t):
+            raise _C.F5EError(f"Fallback: temperatures = {self.temperatures!r} must be a non-empty sequence of finite values >= 0")
+        for name in ("compression_ratio_threshold", "logprob_threshold"):
+            v = getattr(self, name)
+            if v is not None and not (isinstance(v, (int, float)) and not isinstance(v, bool) and math.isfinite(v)):
+                raise _C.F5EError(f"Fallback: {name} = {v!r} must be None or a finite number")
+        if isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < 1 << 64:
+            raise _C.F5EError(f"Fallback: seed = {self.seed!r} must be an integer in 0 .. 2^64 - 1")
+        object.__setattr__(self, "temperatures", t)
 
 
 def split_segments(seq: Sequence[int], ts_begin: int, seek_frames: int, num_frames: int
@@ -342,7 +377,7 @@ def split_segments(seq: Sequence[int], ts_begin: int, seek_frames: int, num_fram
 
 
 def compression_ratio(tokens: Sequence[int], vocab_size: int) -> float:
-    """zlib on the tokens' little-endian bytes, as ``_retrieve_compression_ratio``: reported, never acted on."""
+    """zlib on the tokens' little-endian bytes, as ``_retrieve_compression_ratio``: reported, and acted on by ``Fallback``."""
     import zlib
     width = int(math.log2(vocab_size) / 8) + 1
     raw = b"".join(int(t).to_bytes(width, "little") for t in tokens)
@@ -831,7 +866,8 @@ class Whisper(nn.Module):
     def generate_from_kv(self, kv: List[Tuple[Tensor, Tensor]], prompt: Sequence[int], max_new_tokens: Optional[int] = None,
                          sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0, return_beams: bool = False,
                          return_token_timestamps: bool = False, frames=None, return_timestamps: bool = False,
-                         stats: Optional[dict] = None):
+                         stats: Optional[dict] = None, temperature: float = 0.0, seed: int = 0, row_key: Optional[Tensor] = None,
+                         serial: Optional[Tensor] = None):
         """``generate`` from the cross keys / values.  ``prompt``: ids for all rows, or [B, n0] ids.  ``return_token_timestamps``:
         one more item at the end, the times f32 [B, U] of the returned best hypothesis = ``token_timestamps`` on the returned
         tokens (a teacher-forced pass after the search, greedy or beam); ``frames``: mel frames per utterance (None: the whole
@@ -839,13 +875,18 @@ class Whisper(nn.Module):
         f5e_whisper_beam_step_ts; the prompt must not end in <|notimestamps|>).  ``stats``: a dict that receives
         ``no_speech_logp`` f32 [B] (the log-probability of <|nospeech|> after <|startoftranscript|>) and ``sum_logp`` f32 [B]
         (ruled greedy: the sum of the picks' log-probabilities among the allowed classes; beam: the best hypothesis' score times
-        its generated length)."""
+        its generated length).  ``temperature`` > 0: every pick is a draw from softmax(logits / temperature) over the allowed
+        classes (f5e_whisper_sample_pick, with or without the timestamp rules; ``sum_logp`` is then the sum of the picks' T = 1
+        log-probabilities); the noise is a function of ``seed``, the position and per row ``row_key`` (None: the row's index)
+        and ``serial`` (None: 0), i32 [B] on the device, so a row's draws do not depend on its batch."""
         n0 = _prompt_len(prompt)
+        sample = self._check_sampling(temperature, seed, beam_size, return_beams)
         if return_token_timestamps:
             if not self.cfg.alignment_heads:
                 raise _C.F5EError("Whisper.generate: return_token_timestamps needs alignment_heads in generation_config.json")
             res = self.generate_from_kv(kv, prompt, max_new_tokens, sync_every, beam_size, length_penalty, return_beams,
-                                        return_timestamps=return_timestamps, stats=stats)
+                                        return_timestamps=return_timestamps, stats=stats, temperature=temperature, seed=seed,
+                                        row_key=row_key, serial=serial)
             times = self.token_timestamps(kv, res[0], res[1], self.n_frames if frames is None else frames, n0)
             return tuple(res) + (times,)
         if int(beam_size) != 1 or return_beams:
@@ -866,7 +907,10 @@ class Whisper(nn.Module):
         last = tokens[:, 0].clone()
         done = torch.zeros(B, dtype=I32, device=dev)
         alive = torch.full((1,), B, dtype=I32, device=dev)
-        sum_logp = torch.zeros(B, dtype=F32, device=dev) if return_timestamps else None
+        sum_logp = torch.zeros(B, dtype=F32, device=dev) if return_timestamps or sample else None
+        if sample:
+            row_key = torch.arange(B, dtype=I32, device=dev) if row_key is None else row_key.to(dev, I32).contiguous()
+            serial = torch.zeros(B, dtype=I32, device=dev) if serial is None else serial.to(dev, I32).contiguous()
         st = self._dec_state(B, Umax, dev)
         for p in range(Umax - 1):
             forced = p + 1 < n0
@@ -876,7 +920,12 @@ class Whisper(nn.Module):
             if forced:                       # all prompt tokens but the last go through the same cached step; nothing is picked
                 last.copy_(tokens[:, p + 1])
                 continue
-            if return_timestamps:
+            if sample:
+                ops.whisper_sample_pick(logits, tokens, last, done, alive, sum_logp, p, n0, eos,
+                                        ts_begin - 1 if return_timestamps else None, float(temperature), int(seed), row_key, serial,
+                                        suppress=fd["suppress"], begin_suppress=fd["begin_suppress"],
+                                        max_initial=cfg.max_initial_timestamp_index if return_timestamps else None)
+            elif return_timestamps:
                 ops.whisper_ts_pick(logits, tokens, last, done, alive, sum_logp, p, n0, eos, ts_begin - 1, suppress=fd["suppress"],
                                     begin_suppress=fd["begin_suppress"], max_initial=cfg.max_initial_timestamp_index)
             else:
@@ -891,6 +940,21 @@ class Whisper(nn.Module):
         if stats is not None:
             stats["sum_logp"] = sum_logp
         return tokens, (first + n0).to(I32)
+
+    @staticmethod
+    def _check_sampling(temperature, seed, beam_size, return_beams) -> bool:
+        """-> whether the decode samples; refusals by name, before any launch."""
+        if isinstance(temperature, bool) or not isinstance(temperature, (int, float)) or not math.isfinite(temperature) or \
+                temperature < 0:
+            raise _C.F5EError(f"Whisper.generate: temperature = {temperature!r} must be a finite number >= 0")
+        if temperature == 0:
+            return False
+        if int(beam_size) != 1 or return_beams:
+            raise _C.F5EError(f"Whisper.generate: temperature = {temperature!r} with beam_size = {beam_size} is out of scope "
+                              "(beam-sample is not built; sampling decodes one row per utterance)")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 1 << 64:
+            raise _C.F5EError(f"Whisper.generate: seed = {seed!r} must be an integer in 0 .. 2^64 - 1")
+        return True
 
     def _no_speech_logp(self, logits: Tensor) -> Tensor:
         """log softmax(logits)[<|nospeech|>] per row (f5e_token_logp), from the step that fed <|startoftranscript|>."""
@@ -969,7 +1033,8 @@ class Whisper(nn.Module):
     @torch.no_grad()
     def generate(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe",
                  max_new_tokens: Optional[int] = None, sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0,
-                 return_beams: bool = False, return_token_timestamps: bool = False, return_timestamps: bool = False):
+                 return_beams: bool = False, return_token_timestamps: bool = False, return_timestamps: bool = False,
+                 temperature: float = 0.0, seed: int = 0):
         """Recognition of B utterances: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> (tokens i32 [B, U] starting
         with the prompt, eos from a row's end on; n i32 [B] = tokens of every row, its closing eos included when it ended by
         itself).  The host reads the alive count every ``sync_every`` steps; the result does not depend on it.  The bound is
@@ -980,7 +1045,17 @@ class Whisper(nn.Module):
         length_penalty, best first).  ``return_token_timestamps``: one more item at the end, times f32 [B, U] in seconds of the
         returned tokens (``token_timestamps``; needs ``alignment_heads`` in the generation config).  ``language`` None: detected
         per row (``detect_language``); "" is refused as before.  ``return_timestamps``: the prompt has no <|notimestamps|> and
-        the picks follow the timestamp rules, so the tokens carry <|t|> ids (``cfg.timestamp_begin`` + t / 0.02)."""
+        the picks follow the timestamp rules, so the tokens carry <|t|> ids (``cfg.timestamp_begin`` + t / 0.02).
+        ``temperature`` > 0: the picks are draws from softmax(logits / temperature) over the allowed classes, a function of
+        ``seed``, the row's index and the position (``generate_from_kv``); with ``beam_size`` > 1 that is refused."""
+        if self._check_sampling(temperature, seed, beam_size, return_beams):
+            if return_timestamps:
+                self.cfg.timestamp_begin                                    # refused by name before any launch
+            kv = self.encode(wav, lens)
+            return self.generate_from_kv(kv, self._prompts(kv, language, task, return_timestamps), max_new_tokens, sync_every, 1,
+                                         length_penalty, False, return_token_timestamps,
+                                         self._frames_of(wav, lens) if return_token_timestamps else None, return_timestamps,
+                                         temperature=temperature, seed=seed)
         if language is not None and not return_timestamps:
             prompt = self.prompt_ids(language, task)
             if not return_token_timestamps:
@@ -999,7 +1074,8 @@ class Whisper(nn.Module):
     @torch.no_grad()
     def transcribe_long(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe", beam_size: int = 1,
                         no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = None,
-                        sync_every: int = 8, **unbuilt) -> List[List[Segment]]:
+                        sync_every: int = 8, fallback: Optional[Fallback] = None, row_keys: Optional[Sequence[int]] = None,
+                        trace: Optional[list] = None, **unbuilt) -> List[List[Segment]]:
         """Recordings of any length: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> the segments of every row.
         The seek loop of ``transformers``' long-form ``generate`` (``return_timestamps=True``, ``condition_on_prev_tokens=False``,
         temperature 0): every window of ``n_frames`` mel frames is decoded with timestamp tokens, cut into segments at the
@@ -1016,7 +1092,19 @@ class Whisper(nn.Module):
             the first and whose average log-probability falls below the second is skipped whole.
         ``avg_logprob``: greedy, the mean log-probability of the picks among the classes the rules allow (the closing eos
         counts), as ``_retrieve_avg_logprobs`` at temperature 0; beam search, the best hypothesis' own score.  One host read per
-        window besides the alive counts."""
+        window besides the alive counts.
+        ``fallback`` (a ``Fallback``; None: every window is decoded once, as above): ``generate_with_fallback``.  The active
+        windows are decoded at ``temperatures[0]``; a row whose compression ratio (of its tokens with the closing eos) exceeds
+        ``compression_ratio_threshold`` or whose average log-probability lies below ``logprob_threshold`` is decoded again at the
+        next temperature, and only such rows: their cross keys / values are gathered, nothing is encoded again.  A row for which
+        the no-speech condition holds is skipped instead (``_need_fallback``).  After the last temperature the last attempt is
+        kept.  0 is the greedy or beam decode; a positive temperature samples ONE row per utterance whatever ``beam_size`` is
+        (f5e_whisper_sample_pick; ``avg_logprob`` is then the mean T = 1 log-probability of the draws), with the noise keyed by
+        ``fallback.seed``, the position, the utterance's key (``row_keys``; None: its index in the call) and the number of sampled
+        decodes the utterance has started before, so a row's result does not depend on its batch-mates.  ``logprob_threshold``
+        and ``fallback.logprob_threshold`` are one threshold: two different values are refused.  ``Segment.temperature`` is the
+        temperature of the attempt that was kept.  One host read per attempt.  ``trace``: a list that receives one dict per
+        attempt (row, seek, temperature, compression_ratio, avg_logprob, no_speech_prob, needs_fallback, should_skip)."""
         for name, value in unbuilt.items():
             off = {"temperature": (None, 0, 0.0, (0.0,), [0.0]), "condition_on_prev_tokens": (None, False), "prompt_ids": (None,),
                    "chunk_length_s": (None,), "stride_length_s": (None,), "return_token_timestamps": (None, False),
@@ -1024,13 +1112,25 @@ class Whisper(nn.Module):
             if name not in off:
                 raise TypeError(f"Whisper.transcribe_long: unknown argument {name!r}")
             if not any(value is v or (not isinstance(value, Tensor) and value == v) for v in off[name]):
-                raise _C.F5EError(f"Whisper.transcribe_long: {name} = {value!r} is out of scope (temperature fallback and sampling, "
-                                  "conditioning on previous tokens, prompt_ids, strided chunk merging, word timestamps across "
-                                  "windows and a graph-captured step are not built)")
-        if (no_speech_threshold is None) != (logprob_threshold is None):
+                raise _C.F5EError(f"Whisper.transcribe_long: {name} = {value!r} is out of scope (conditioning on previous tokens, "
+                                  "prompt_ids, strided chunk merging, word timestamps across windows and a graph-captured step "
+                                  "are not built; temperature fallback goes through fallback=Fallback(...))")
+        if fallback is not None and not isinstance(fallback, Fallback):
+            raise _C.F5EError(f"Whisper.transcribe_long: fallback = {fallback!r} must be a Fallback or None")
+        lp_thr = logprob_threshold                                     # one threshold for the fallback and for the no-speech skip
+        if fallback is not None and fallback.logprob_threshold is not None:
+            if logprob_threshold is not None and float(logprob_threshold) != float(fallback.logprob_threshold):
+                raise _C.F5EError(f"Whisper.transcribe_long: logprob_threshold = {logprob_threshold!r} and "
+                                  f"fallback.logprob_threshold = {fallback.logprob_threshold!r} are one threshold; give one value")
+            lp_thr = fallback.logprob_threshold
+        elif (no_speech_threshold is None) != (logprob_threshold is None):
             raise _C.F5EError("Whisper.transcribe_long: the no-speech skip needs no_speech_threshold and logprob_threshold together")
+        cr_thr = None if fallback is None else fallback.compression_ratio_threshold
+        temps = (0.0,) if fallback is None else fallback.temperatures
         if sync_every < 1:
             raise _C.F5EError("Whisper.transcribe_long: sync_every < 1")
+        if row_keys is not None and isinstance(wav, Tensor) and wav.ndim == 2 and len(row_keys) != wav.shape[0]:
+            raise _C.F5EError(f"Whisper.transcribe_long: row_keys has {len(row_keys)} entries for {wav.shape[0]} recordings")
         cfg = self.cfg
         ts_begin, eos, W, M = cfg.timestamp_begin, cfg.eos_token_id, self.n_frames, cfg.num_mel_bins
         wav, lens = self._check_audio(wav, lens, "transcribe_long")
@@ -1045,7 +1145,8 @@ class Whisper(nn.Module):
         feats = [ops.whisper_logmel(wav[b:b + 1], lens_dev[b:b + 1], fd["window"], fd["twiddle"], fd["fb"], frames[b])[0]
                  for b in range(B)]
         prompts = None if language is None else self.prompt_ids(language, task, True)
-        seek, out = [0] * B, [[] for _ in range(B)]
+        keys = list(range(B)) if row_keys is None else [int(v) for v in row_keys]
+        seek, out, serial = [0] * B, [[] for _ in range(B)], [0] * B
         while True:
             act = [b for b in range(B) if seek[b] < frames[b]]
             if not act:
@@ -1058,31 +1159,69 @@ class Whisper(nn.Module):
             if prompts is None:                                        # the first iteration: every row is in it, at seek 0
                 prompts = self._prompts(kv, None, task, True)
             prompt = prompts[torch.tensor(act, device=dev)] if isinstance(prompts, Tensor) else prompts
-            n0, stats = _prompt_len(prompt), {}
-            tokens, n = self.generate_from_kv(kv, prompt, None, sync_every, beam_size, 1.0, return_timestamps=True, stats=stats)[:2]
-            tokens, n = tokens.tolist(), n.tolist()
-            sum_logp, ns_logp = stats["sum_logp"].tolist(), stats["no_speech_logp"].tolist()
+            n0 = _prompt_len(prompt)
+            kept, pend = [None] * len(act), list(range(len(act)))      # per active row: (full, avg, ns, cr, temperature, skip)
+            for temp in temps:
+                sub, sub_prompt = kv, prompt
+                if len(pend) < len(act):                               # only the rows that fall back: gathered, not re-encoded
+                    idx = torch.tensor(pend, device=dev)
+                    sub = [(k[idx], v[idx]) for k, v in kv]
+                    sub_prompt = prompt[idx] if isinstance(prompt, Tensor) else prompt
+                stats = {}
+                if temp > 0:
+                    rows = [act[i] for i in pend]
+                    tokens, n = self.generate_from_kv(
+                        sub, sub_prompt, None, sync_every, 1, 1.0, return_timestamps=True, stats=stats, temperature=temp,
+                        seed=fallback.seed, row_key=torch.tensor([keys[b] for b in rows], dtype=I32).to(dev),
+                        serial=torch.tensor([serial[b] for b in rows], dtype=I32).to(dev))[:2]
+                    for b in rows:
+                        serial[b] += 1
+                else:
+                    tokens, n = self.generate_from_kv(sub, sub_prompt, None, sync_every, beam_size, 1.0, return_timestamps=True,
+                                                      stats=stats)[:2]
+                tokens, n = tokens.tolist(), n.tolist()
+                sum_logp, ns_logp = stats["sum_logp"].tolist(), stats["no_speech_logp"].tolist()
+                again = []
+                for j, i in enumerate(pend):
+                    full = tokens[j][n0:n[j]]
+                    avg, ns = sum_logp[j] / max(len(full), 1), math.exp(ns_logp[j])
+                    cr = compression_ratio(full, cfg.vocab_size)
+                    skip = no_speech_threshold is not None and avg < lp_thr and ns > no_speech_threshold
+                    need = not skip and fallback is not None and ((cr_thr is not None and cr > cr_thr) or
+                                                                  (lp_thr is not None and avg < lp_thr))
+                    kept[i] = (full, avg, ns, cr, temp, skip)
+                    if need:
+                        again.append(i)
+                    if trace is not None:
+                        trace.append(dict(row=act[i], seek=seek[act[i]], temperature=temp, compression_ratio=cr, avg_logprob=avg,
+                                          no_speech_prob=ns, needs_fallback=need, should_skip=skip))
+                pend = again
+                if not pend:
+                    break
             for i, b in enumerate(act):
-                full = tokens[i][n0:n[i]]
+                full, avg, ns, cr, temp, skip = kept[i]
                 seq = full[:-1] if full and full[-1] == eos else full
-                avg, ns = sum_logp[i] / max(len(full), 1), math.exp(ns_logp[i])
-                if not seq or (no_speech_threshold is not None and avg < logprob_threshold and ns > no_speech_threshold):
+                if not seq or skip:
                     seek[b] += nf[i]
                     continue
                 parts, step = split_segments(seq, ts_begin, seek[b], nf[i])
                 if step <= 0:
                     raise _C.F5EError(f"Whisper.transcribe_long: the window at frame {seek[b]} of row {b} does not advance")
-                cr = compression_ratio(full, cfg.vocab_size)
-                out[b].extend(Segment(s0, s1, tok, seek[b], avg, ns, cr) for s0, s1, tok in parts)
+                out[b].extend(Segment(s0, s1, tok, seek[b], avg, ns, cr, temp) for s0, s1, tok in parts)
                 seek[b] += step
 
 
 class WhisperRecognizer:
     """The duck type ``eval_wer.run_asr_wer`` and ``preprocess_ref_audio_text`` take: ``transcribe(wav_or_path, sr) -> str``."""
 
-    def __init__(self, path: str, device="cuda", language: Optional[str] = "en", beam_size: int = 1, long_form: bool = False):
+    def __init__(self, path: str, device="cuda", language: Optional[str] = "en", beam_size: int = 1, long_form: bool = False,
+                 fallback: Optional[Fallback] = None):
         """``language``: a name or code, or None / "auto" to detect it per recording.  ``long_form``: ``transcribe`` runs the
-        seek loop over the whole recording (``Whisper.transcribe_long``) instead of cutting it to the first chunk."""
+        seek loop over the whole recording (``Whisper.transcribe_long``) instead of cutting it to the first chunk.  ``fallback``:
+        the temperature fallback of that loop (needs ``long_form``)."""
+        if fallback is not None and not (long_form and isinstance(fallback, Fallback)):
+            raise _C.F5EError("WhisperRecognizer: fallback needs long_form=True and a Fallback record")
+        self.fallback = fallback
         self.device = torch.device(device)
         self.language = language
         self.beam_size = int(beam_size)      # the constructor's alone: transcribe() ignores the wenet flag of the same name
@@ -1134,7 +1273,8 @@ class WhisperRecognizer:
     @torch.no_grad()
     def transcribe_segments(self, audio, sr: Optional[int] = None) -> List[Tuple[float, float, str]]:
         """-> [(start_s, end_s, text)] over the whole recording, however long (``Whisper.transcribe_long``)."""
-        segs = self.model.transcribe_long(self._audio(audio, sr, cut=False), None, self._lang(), beam_size=self.beam_size)[0]
+        kw = {} if getattr(self, "fallback", None) is None else dict(fallback=self.fallback)
+        segs = self.model.transcribe_long(self._audio(audio, sr, cut=False), None, self._lang(), beam_size=self.beam_size, **kw)[0]
         return [(s.start_s, s.end_s, self.model.decode_ids(s.tokens)) for s in segs]
 
     @torch.no_grad()

@@ -1810,6 +1810,30 @@ def whisper_ts_pick(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, 
     return last
 
 
+def whisper_sample_pick(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, sum_logp: Tensor, p: int, n0: int,
+                        eos: int, no_timestamps: Optional[int], temperature: float, seed: int, row_key: Tensor, serial: Tensor, *,
+                        V: Optional[int] = None, suppress: Optional[Tensor] = None, begin_suppress: Optional[Tensor] = None,
+                        max_initial: Optional[int] = None):
+    """f5e_whisper_sample_pick: ``whisper_ts_pick`` with a draw from softmax(x / temperature) over the allowed classes in place of
+    the argmax.  The noise is a function of (class, p, serial[r], row_key[r], seed) only (i32 [R] device tensors and a 64-bit
+    seed), so a row's draw does not depend on its batch.  ``no_timestamps`` None: without the timestamp rules.  sum_logp gains the
+    T = 1 log-probability of the pick among the allowed classes.  Writes tokens[:, p + 1], last, done (0 -> 1), alive, sum_logp."""
+    R = logits.shape[0]
+    if last.shape != (R,) or done.shape != (R,) or alive.numel() != 1 or sum_logp.shape != (R,) or row_key.shape != (R,) or \
+            serial.shape != (R,):
+        raise _C.F5EError(f"whisper_sample_pick: last [{R}], done [{R}], alive [1], sum_logp [{R}], row_key [{R}], serial [{R}]")
+    if not 0 <= int(seed) < 1 << 64:
+        raise _C.F5EError(f"whisper_sample_pick: the seed must lie in 0 .. 2^64 - 1 (got {seed})")
+    head, V = _ts_common("whisper_sample_pick", logits, tokens, V, p, suppress, begin_suppress)
+    require_device()
+    check(lib().f5e_whisper_sample_pick(*head, _p(last, I32, "last"), _p(done, I32, "done"), _p(alive, I32, "alive"),
+                                        _p(sum_logp, F32, "sum_logp"), R, V, int(p), int(n0), int(eos),
+                                        -1 if no_timestamps is None else int(no_timestamps),
+                                        -1 if max_initial is None else int(max_initial), float(temperature), int(seed),
+                                        _p(row_key, I32, "row_key"), _p(serial, I32, "serial")), "f5e_whisper_sample_pick")
+    return last
+
+
 def whisper_ts_rule(logits: Tensor, tokens: Tensor, p: int, n0: int, eos: int, no_timestamps: int, *, V: Optional[int] = None,
                     suppress: Optional[Tensor] = None, begin_suppress: Optional[Tensor] = None, max_initial: Optional[int] = None,
                     out: Optional[Tensor] = None) -> Tensor:

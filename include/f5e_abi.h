@@ -855,6 +855,25 @@ F5E_API int f5e_whisper_beam_step_ts(f5e_stream st, const float* logits, long lo
                              int V, int p, int n0, int cap, int eos, float length_penalty, int no_timestamps, int max_initial,
                              int* desc);
 
+/* f5e_whisper_sample_pick: f5e_whisper_ts_pick with a draw in place of the argmax (temperature fallback).  The noise
+ * is a pure function of counters:
+ *   w   = Philox4x32-10(counter = (i >> 2, p, serial[r], row_key[r]), key = (seed & 0xffffffff, seed >> 32)), class i uses word
+ *         i & 3 (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl increments 0x9E3779B9 / 0xBB67AE85);
+ *   u_i = ((w >> 8) + 0.5) * 2^-24, strictly inside (0, 1);   g_i = -log(-log(u_i));
+ *   pick = the lowest index among the maxima of x_i / temperature + g_i over the allowed classes (Gumbel-max: a draw from
+ *         softmax(x / temperature) over them), 0 if nothing is allowed.
+ * Rules 1-6 are decided on the raw logits (the temperature warper runs after the Whisper processors), and sum_logp gains the
+ * T = 1 log-softmax of the processed scores at the pick, (x[pick] - M) - log(sum over the allowed classes of exp(x - M)), as in
+ * f5e_whisper_ts_pick.  fp32: x / temperature is one division, g uses the accurate logf / log1pf (the upper half of u goes
+ * through 1 - u, which fp32 holds exactly there), the sum is one addition.  no_timestamps = -1: no timestamp rules (every class
+ * is text; max_initial is ignored).  row_key, serial: DEVICE i32 [R].  One workgroup per row, one pass, the logits are read once;
+ * writes tokens[r][p + 1], last, done (0 -> 1), *alive and sum_logp, nothing else.
+ * Limits: those of f5e_whisper_ts_pick (or no_timestamps = -1), and a finite temperature > 0. */
+F5E_API int f5e_whisper_sample_pick(f5e_stream st, const float* logits, long long ld, const int* suppress, int n_sup,
+                            const int* begin_suppress, int n_beg, int* tokens, int ld_tok, int* last, int* done, int* alive,
+                            float* sum_logp, int R, int V, int p, int n0, int eos, int no_timestamps, int max_initial,
+                            float temperature, unsigned long long seed, const int* row_key, const int* serial);
+
 /* ---------------------------------------------------------------- Whisper word timestamps (csrc/whisper_align.hip) */
 /* Token times from the cross-attention of a few "alignment heads" (transformers 5.15.0 generation_whisper.py:
  * _extract_token_timestamps, _median_filter, _dynamic_time_warping with num_frames given), for one utterance with the

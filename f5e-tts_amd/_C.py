@@ -77,6 +77,9 @@ SIGNATURES = {
     "f5e_relpos_attn": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _F],
     "f5e_mha_f32": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F],
     "f5e_attn_decode_f32": [_P, _P, _I, _P, _P, _LL, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _F],
+    "f5e_attn_prefill_f32": [_P, _P, _I, _P, _P, _LL, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F],
+    "f5e_attn_decode_from_f32": [_P, _P, _I, _P, _P, _LL, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F],
+    "f5e_whisper_embed": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],
     "f5e_beam_step": [_P, _P, _LL, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I],
     "f5e_layer_mix_inorm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
     "f5e_res2_dconv": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],

@@ -13,6 +13,8 @@
 // from row r itself when anc is null; position p comes from the registers.  A search therefore never moves cache rows when the
 // second prune reshuffles the beam: following the table gives the corrected search (every layer sees its real ancestors),
 // passing null reproduces the reference, whose per-layer caches stay with the row index.
+// FROM (f5e_attn_decode_from_f32): a row left-padded by begin[r] positions reads positions begin[r] .. p only; the other
+// instantiation is the code as it was (lo is the constant 0).
 // The K/V read is the traffic: (p + 1) * 2 * dk floats per wave, straight to registers (cdna_hip_programming App. B,
 // "attention decode").
 //
@@ -33,11 +35,11 @@ namespace {
 constexpr int DEC_MAX_U = 4096;    // cached positions per row (the LDS score row of the attention wave)
 constexpr int STEP_MAX_K = 16;
 
-template <int DK>
+template <int DK, bool FROM>
 __global__ __launch_bounds__(64) void attn_decode_kernel(const float* __restrict__ qkv, int ld_qkv, float* kc, float* vc,
                                                           long long row_stride, int pos_stride, const int* __restrict__ anc,
                                                           int ld_anc, float* __restrict__ out, int ldo, int R, int H, int p,
-                                                          float scale) {
+                                                          float scale, const int* __restrict__ begin) {
   __shared__ float s[DEC_MAX_U];
   constexpr int G = DK >= 64 ? 1 : 64 / DK;     // key groups of the context pass
   constexpr int DPL = DK > 64 ? DK / 64 : 1;    // channels per lane of the context pass
@@ -45,6 +47,7 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(const float* __restrict
   const int HD = H * DK;
   const float* me = qkv + (long long)r * ld_qkv + h * DK;   // q; k at + HD, v at + 2 HD
   const long long head = (long long)h * DK;
+  const int lo = FROM ? min(max(begin[r], 0), p) : 0;       // the first visible position
 
   // the new key / value into slot [r][p]
   for (int d = lane; d < DK; d += 64) {
@@ -59,7 +62,7 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(const float* __restrict
 
   // ---- 1. scores
   float m = -__builtin_inff();
-  for (int j = lane; j <= p; j += 64) {
+  for (int j = lo + lane; j <= p; j += 64) {
     const float* kr;
     if (j == p) {
       kr = me + HD;
@@ -80,7 +83,7 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(const float* __restrict
   m = wave_max(m);
   // ---- 2. weights (a lane rewrites only the entries it wrote)
   float sum = 0.f;
-  for (int j = lane; j <= p; j += 64) {
+  for (int j = lo + lane; j <= p; j += 64) {
     const float e = expf(s[j] - m);
     s[j] = e;
     sum += e;
@@ -92,7 +95,7 @@ __global__ __launch_bounds__(64) void attn_decode_kernel(const float* __restrict
   float acc[DPL];
 #pragma unroll
   for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
-  for (int j = g; j <= p; j += G) {
+  for (int j = lo + g; j <= p; j += G) {
     const float* vr;
     if (j == p) {
       vr = me + 2 * HD;
@@ -205,9 +208,9 @@ __global__ __launch_bounds__(1024) void beam_step_kernel(const float* __restrict
 
 }  // namespace
 
-int f5e_attn_decode_f32(hipStream_t st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
-                        int pos_stride, const int* anc, int ld_anc, float* out, int ldo, int R, int Umax, int H, int dk, int p,
-                        float scale) {
+static int attn_decode_launch(hipStream_t st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                              int pos_stride, const int* anc, int ld_anc, const int* begin, float* out, int ldo, int R, int Umax,
+                              int H, int dk, int p, float scale) {
   F5E_REQUIRE(qkv && kc && vc && out, "attn_decode_f32: null operand");
   F5E_REQUIRE(R > 0 && R <= 65535 && H > 0 && H <= 65535, "attn_decode_f32: need 0 < R, H <= 65535");
   F5E_REQUIRE(dk == 16 || dk == 32 || dk == 64 || dk == 128, "attn_decode_f32: head dim must be 16, 32, 64 or 128");
@@ -220,9 +223,13 @@ int f5e_attn_decode_f32(hipStream_t st, const float* qkv, int ld_qkv, float* kc,
               "attn_decode_f32: qkv / cache strides must be multiples of 4 floats, qkv and kc 16-byte aligned");
   F5E_REQUIRE(!anc || ld_anc >= p, "attn_decode_f32: the ancestry table has fewer than p columns");
   const dim3 grid((unsigned)H, (unsigned)R), block(64);
-#define F5E_DEC_LAUNCH(DK)                                                                                                  \
-  hipLaunchKernelGGL(attn_decode_kernel<DK>, grid, block, 0, st, qkv, ld_qkv, kc, vc, row_stride, pos_stride, anc, ld_anc, \
-                     out, ldo, R, H, p, scale)
+#define F5E_DEC_LAUNCH(DK)                                                                                                   \
+  if (begin)                                                                                                                 \
+    hipLaunchKernelGGL((attn_decode_kernel<DK, true>), grid, block, 0, st, qkv, ld_qkv, kc, vc, row_stride, pos_stride, anc, \
+                       ld_anc, out, ldo, R, H, p, scale, begin);                                                             \
+  else                                                                                                                       \
+    hipLaunchKernelGGL((attn_decode_kernel<DK, false>), grid, block, 0, st, qkv, ld_qkv, kc, vc, row_stride, pos_stride,     \
+                       anc, ld_anc, out, ldo, R, H, p, scale, begin)
   switch (dk) {
     case 16: F5E_DEC_LAUNCH(16); break;
     case 32: F5E_DEC_LAUNCH(32); break;
@@ -232,6 +239,20 @@ int f5e_attn_decode_f32(hipStream_t st, const float* qkv, int ld_qkv, float* kc,
 #undef F5E_DEC_LAUNCH
   F5E_LAUNCH_CHECK("attn_decode_f32");
   return F5E_OK;
+}
+
+int f5e_attn_decode_f32(hipStream_t st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                        int pos_stride, const int* anc, int ld_anc, float* out, int ldo, int R, int Umax, int H, int dk, int p,
+                        float scale) {
+  return attn_decode_launch(st, qkv, ld_qkv, kc, vc, row_stride, pos_stride, anc, ld_anc, nullptr, out, ldo, R, Umax, H, dk, p,
+                            scale);
+}
+
+int f5e_attn_decode_from_f32(hipStream_t st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                             int pos_stride, const int* anc, int ld_anc, const int* begin, float* out, int ldo, int R, int Umax,
+                             int H, int dk, int p, float scale) {
+  return attn_decode_launch(st, qkv, ld_qkv, kc, vc, row_stride, pos_stride, anc, ld_anc, begin, out, ldo, R, Umax, H, dk, p,
+                            scale);
 }
 
 int f5e_beam_step(hipStream_t st, const float* logits, long long ld_logits, float* score, const int* hyp_in, const int* anc_in,

@@ -5,7 +5,8 @@
     python -m f5e_tts_amd.eval.eval_wer --gen_wav_dir D --metalst F --lang en|zh --asr_model M --asr_config C --asr_dict T
                                         [--mode ctc_greedy_search|ctc_prefix_beam_search|attention_rescoring]
     python -m f5e_tts_amd.eval.eval_wer --gen_wav_dir D --metalst F --lang en --asr whisper --whisper_dir W [--language english]
-                                        [--whisper_beam 5] [--whisper_long [--whisper_fallback [--whisper_seed S]]]
+                                        [--whisper_beam 5] [--whisper_long [--whisper_fallback [--whisper_seed S]]
+                                        [--whisper_prompt TEXT] [--whisper_condition]]
 
 ``--asr whisper`` is the reference's English recogniser of the voice-conversion and LibriSpeech evaluations
 (``run_asr_wer_whisper_large_v3``, eval/utils_eval.py:631-712: whisper-large-v3, greedy, prompt ``english / transcribe``) on the
@@ -189,6 +190,11 @@ def build_parser() -> argparse.ArgumentParser:
                     help="--whisper_long: temperature fallback (0.0, 0.2, ... 1.0) with compression_ratio_threshold 1.35 and "
                          "logprob_threshold -1.0: a window that loops or is very unlikely is decoded again, sampled")
     ap.add_argument("--whisper_seed", type=int, default=0, help="--whisper_fallback: the seed of the sampled decodes")
+    ap.add_argument("--whisper_prompt", default=None, metavar="TEXT",
+                    help="--whisper_long: an initial prompt (a name, a domain word). Without --whisper_condition it leads EVERY window of a "
+                         "recording; with it, it leads the first window's previous text and then scrolls out of it")
+    ap.add_argument("--whisper_condition", action="store_true",
+                    help="--whisper_long: condition every window on the text of the windows before it")
     ap.add_argument("--whisper_beam", type=int, default=1,
                     help="--asr whisper: 1 = greedy (run_asr_wer_whisper_large_v3); N > 1 = the pooled beam search of "
                          "generate(num_beams=N) (--beam_size is the wenet flag and does not reach Whisper)")
@@ -221,8 +227,13 @@ def main(argv=None, aligner=None) -> float:
             ap.error("--whisper_fallback needs --whisper_long")
         fb = Fallback(compression_ratio_threshold=1.35, logprob_threshold=-1.0, seed=args.whisper_seed) if args.whisper_fallback \
             else None
+        if (args.whisper_prompt is not None or args.whisper_condition) and not args.whisper_long:
+            ap.error("--whisper_prompt and --whisper_condition need --whisper_long")
+        ctx = {}
+        if args.whisper_prompt is not None or args.whisper_condition:
+            ctx = dict(initial_prompt=args.whisper_prompt, condition_on_previous_text=args.whisper_condition)
         aligner = WhisperRecognizer(args.whisper_dir, args.device, args.language, beam_size=args.whisper_beam,
-                                    long_form=args.whisper_long, **({} if fb is None else dict(fallback=fb)))
+                                    long_form=args.whisper_long, **({} if fb is None else dict(fallback=fb)), **ctx)
     elif aligner is None:
         from ..ppg.ctc_align import CTCAligner
         aligner = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, args.device, asr=True,

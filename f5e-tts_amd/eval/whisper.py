@@ -29,8 +29,13 @@ compression ratio or average log-probability misses its threshold is decoded aga
 device under the same rules (f5e_whisper_sample_pick: Gumbel-max with counter-based Philox noise, so a draw depends on the seed,
 the utterance, the decode and the position alone).
 
-Out of scope: beam-sample, top-k / top-p, conditioning on previous windows and ``prompt_ids``, the pipeline's strided
-``chunk_length_s`` merging, word timestamps across windows, patience, CTranslate2's exact search, bf16 / fp16 weights (fp16
+Conditioning and prompts (``transcribe_long(context=Context(...))``, ``get_prompt_ids`` / ``encode_text``): a window starts with
+<|startofprev|>, the previous windows' text and / or an initial prompt; that prefix goes through the decoder in one pass
+(``decoder_prefill``: f5e_whisper_embed, f5e_attn_prefill_f32, f5e_mha_f32 with U queries per row; csrc/whisper_prefill.hip), and
+ragged prefixes of a batch are left-padded (f5e_attn_decode_from_f32 for the steps that follow).
+
+Out of scope: beam-sample, top-k / top-p, the pipeline's strided ``chunk_length_s`` merging, word timestamps across windows,
+the prefill inside ``alignment_probs`` / ``token_timestamps``, patience, CTranslate2's exact search, bf16 / fp16 weights (fp16
 checkpoints are widened), a graph-captured step.
 
 Ragged batches: samples at or beyond ``lens[b]`` count as zero, and the row is zero-padded to the chunk length as the feature
@@ -90,7 +95,7 @@ class WhisperConfig:
     no_timestamps_token_id: Optional[int] = None
     alignment_heads: Tuple[Tuple[int, int], ...] = ()       # (decoder layer, head) pairs; empty: no token timestamps
     max_initial_timestamp_index: Optional[int] = None       # the first timestamp of a window is at most this many steps of 0.02 s
-    prev_sot_token_id: Optional[int] = None                 # <|startofprev|>: read, never fed (conditioning is out of scope)
+    prev_sot_token_id: Optional[int] = None                 # <|startofprev|>: leads the previous text / an initial prompt
     median_filter_width: int = 7                            # config.json
 
     @classmethod
@@ -234,6 +239,31 @@ def decode_pieces(id_to_piece: Dict[int, str], first_special: int, ids: Sequence
     return "".join(out)
 
 
+# ---- byte-level tokenisation (GPT-2's BPE, what WhisperTokenizer applies to plain text) ------------------------------------------------
+GPT2_PATTERN = r"'s|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+"
+
+
+def bpe_merge(word: Sequence[str], ranks: Dict[Tuple[str, str], int]) -> List[str]:
+    """The symbols of one pre-token merged greedily by rank: the lowest-ranked adjacent pair, every occurrence left to right,
+    until no pair has a rank."""
+    word = list(word)
+    while len(word) > 1:
+        best = min(((ranks.get(pair, math.inf), pair) for pair in zip(word[:-1], word[1:])), key=lambda t: t[0])
+        if best[0] == math.inf:
+            break
+        a, b = best[1]
+        out, i = [], 0
+        while i < len(word):
+            if i + 1 < len(word) and word[i] == a and word[i + 1] == b:
+                out.append(a + b)
+                i += 2
+            else:
+                out.append(word[i])
+                i += 1
+        word = out
+    return word
+
+
 # ---- tokens -> words (transformers' tokenization_whisper.py: _combine_tokens_into_words) ----------------------------------------
 UNSPACED_LANGUAGES = {"zh", "ja", "th", "lo", "my", "yue", "chinese", "japanese", "thai", "lao", "myanmar", "cantonese"}
 PREPEND_PUNCTUATIONS = "\"'“¡¿([{-"
@@ -340,6 +370,74 @@ class Fallback:
         if isinstance(self.seed, bool) or not isinstance(self.seed, int) or not 0 <= self.seed < 1 << 64:
             raise _C.F5EError(f"Fallback: seed = {self.seed!r} must be an integer in 0 .. 2^64 - 1")
         object.__setattr__(self, "temperatures", t)
+
+
+@dataclass(frozen=True)
+class Context:
+    """What a window of ``transcribe_long`` is given in front of its forced tokens (``transformers``' long-form ``generate``):
+    ``condition_on_prev_tokens``: <|startofprev|> and the row's previous text (``previous_text``); ``prompt_ids``: an initial
+    prompt, ``[<|startofprev|>, ids ...]`` as ``Whisper.get_prompt_ids`` makes it.  ``prompt_condition_type``:
+      * "first-segment": the prompt (without its <|startofprev|>) counts as the row's first previous segment, so under
+        conditioning it leads the first window's previous text and then scrolls out of the last ``max_target_positions // 2 -
+        1`` tokens; a window that is NOT conditioned gets the whole prompt in front of its forced tokens, every such window, as
+        ``_prepare_decoder_input_ids`` does.  The returned segments never contain it;
+      * "all-segments": the prompt takes the place of <|startofprev|> in front of the previous text of every window; it needs
+        conditioning (refused otherwise, as ``transformers`` refuses it)."""
+    condition_on_prev_tokens: bool = False
+    prompt_ids: Optional[Tuple[int, ...]] = None
+    prompt_condition_type: str = "first-segment"
+
+    def __post_init__(self):
+        if not isinstance(self.condition_on_prev_tokens, bool):
+            raise _C.F5EError(f"Context: condition_on_prev_tokens = {self.condition_on_prev_tokens!r} must be a bool")
+        if self.prompt_condition_type not in ("first-segment", "all-segments"):
+            raise _C.F5EError(f"Context: prompt_condition_type = {self.prompt_condition_type!r} must be 'first-segment' or "
+                              "'all-segments'")
+        if self.prompt_condition_type == "all-segments" and not self.condition_on_prev_tokens:
+            raise _C.F5EError("Context: prompt_condition_type = 'all-segments' needs condition_on_prev_tokens = True")
+        ids = self.prompt_ids
+        if ids is not None:
+            try:
+                ids = tuple(int(t) for t in (ids.tolist() if hasattr(ids, "tolist") else ids))
+            except (TypeError, ValueError):
+                raise _C.F5EError(f"Context: prompt_ids = {self.prompt_ids!r} is not a sequence of token ids") from None
+            if not ids:
+                raise _C.F5EError("Context: prompt_ids is empty (None switches the prompt off)")
+            object.__setattr__(self, "prompt_ids", ids)
+
+
+def conditions_next_window(temperature: Optional[float]) -> bool:
+    """``is_low_temperature`` of ``generate_with_fallback``: a window kept at a temperature of 0.5 or more does not condition
+    the next one."""
+    return temperature is None or temperature < 0.5
+
+
+def previous_text(history: Sequence[Sequence[int]], ts_begin: int, cut: int) -> List[int]:
+    """The tokens of a row's segments so far (timestamps included) as ``_pad_to_max_length(skip_ending_double_timestamps=True,
+    cut_off_length=cut)`` joins them: a segment of more than two tokens whose last but one is a timestamp loses its last token
+    (the closing pair's second timestamp), and the whole is cut to its LAST ``cut`` tokens."""
+    seq: List[int] = []
+    for seg in history:
+        seg = [int(t) for t in seg]
+        seq.extend(seg[:-1] if len(seg) > 2 and seg[-2] >= ts_begin else seg)
+    return seq[-cut:] if cut > 0 else []
+
+
+def window_prompt(ctx: Optional[Context], forced: Sequence[int], history: Sequence[Sequence[int]], conditioned: bool,
+                  prev_sot: Optional[int], ts_begin: int, cut: int) -> List[int]:
+    """The decoder input of one row's window (``_prepare_decoder_input_ids`` for that row alone): ``forced`` = <|startof
+    transcript|> <|lang|> <|task|>; ``history``: the row's segments so far (with the "first-segment" prompt as the first of
+    them); ``conditioned``: the context conditions and the row's last window was kept at a low temperature.  A row is
+    conditioned iff it has history of its own."""
+    forced = [int(t) for t in forced]
+    if ctx is None:
+        return forced
+    if conditioned and ctx.condition_on_prev_tokens and len(history) > 0:
+        lead = list(ctx.prompt_ids) if ctx.prompt_ids is not None and ctx.prompt_condition_type == "all-segments" else [prev_sot]
+        return lead + previous_text(history, ts_begin, cut) + forced
+    if ctx.prompt_ids is not None:
+        return list(ctx.prompt_ids) + forced
+    return forced
 
 
 def split_segments(seq: Sequence[int], ts_begin: int, seek_frames: int, num_frames: int
@@ -476,6 +574,8 @@ class Whisper(nn.Module):
         self.model = _Model(cfg)
         self.id_to_piece: Dict[int, str] = {}
         self.first_special = cfg.eos_token_id
+        self.bpe_ranks: Dict[Tuple[str, str], int] = {}
+        self._piece_to_id: Optional[Dict[str, int]] = None
         self._folded = None
         super().train(False)
         for p in self.parameters():
@@ -507,16 +607,66 @@ class Whisper(nn.Module):
         vocab = js("vocab.json", False)
         if vocab is not None:
             model.set_vocab(vocab, js("added_tokens.json", False))
+        merges = os.path.join(path, "merges.txt")
+        if os.path.exists(merges):
+            with open(merges, encoding="utf-8") as f:
+                model.set_merges(f.read().split("\n"))
         return model
 
     def set_vocab(self, vocab: Dict[str, int], added: Optional[Dict[str, int]] = None) -> None:
         """``vocab.json`` (piece -> id) and ``added_tokens.json`` (special -> id); the first special id is the lowest added id
         (the eos id when there is no such file)."""
         self.id_to_piece = {int(i): p for p, i in vocab.items()}
+        self._piece_to_id = None
         self.first_special = self.cfg.eos_token_id
         if added:
             self.id_to_piece.update({int(i): p for p, i in added.items()})
             self.first_special = min(min(int(i) for i in added.values()), self.cfg.eos_token_id)
+
+    def set_merges(self, merges: Sequence) -> None:
+        """``merges.txt``: its lines ("a b"; a "#version" header and empty lines are skipped) or (a, b) pairs, best first."""
+        pairs = []
+        for m in merges:
+            if isinstance(m, str):
+                if not m.strip() or m.startswith("#version"):
+                    continue
+                m = m.split(" ")
+            if len(m) != 2:
+                raise _C.F5EError(f"Whisper.set_merges: {m!r} is not a pair of symbols")
+            pairs.append((str(m[0]), str(m[1])))
+        self.bpe_ranks = {pair: i for i, pair in enumerate(pairs)}
+
+    def encode_text(self, text: str) -> List[int]:
+        """Plain text -> ids: the GPT-2 pre-tokeniser pattern, the pieces' UTF-8 bytes as printable characters, merged by the
+        ranks of ``merges.txt`` (what ``WhisperTokenizer`` does with text that holds no special token).  ``decode_ids`` undoes it."""
+        if not self.id_to_piece or not self.bpe_ranks:
+            raise _C.F5EError("Whisper.encode_text: needs vocab.json and merges.txt (set_vocab and set_merges, or a checkpoint "
+                              "directory that holds both)")
+        try:
+            import regex
+        except ImportError:
+            raise _C.F5EError("Whisper.encode_text: the 'regex' module is not installed (the GPT-2 pre-tokeniser pattern needs "
+                              "\\p{L} / \\p{N})") from None
+        if self._piece_to_id is None:                                   # reset by set_vocab
+            self._piece_to_id = {p: i for i, p in self.id_to_piece.items()}
+        piece_to_id = self._piece_to_id
+        b2u, ids = bytes_to_unicode(), []
+        for tok in regex.findall(GPT2_PATTERN, text):
+            for piece in bpe_merge([b2u[b] for b in tok.encode("utf-8")], self.bpe_ranks):
+                if piece not in piece_to_id:
+                    raise _C.F5EError(f"Whisper.encode_text: piece {piece!r} of {tok!r} is not in the vocabulary")
+                ids.append(piece_to_id[piece])
+        return ids
+
+    def get_prompt_ids(self, text: str) -> List[int]:
+        """``WhisperTokenizer.get_prompt_ids``: [<|startofprev|>] + the ids of " " + text.strip(); for ``Context(prompt_ids=)``.
+        Text that spells a special token is refused."""
+        if self.cfg.prev_sot_token_id is None:
+            raise _C.F5EError("Whisper.get_prompt_ids: generation_config has no prev_sot_token_id (<|startofprev|>)")
+        for i, piece in self.id_to_piece.items():
+            if i >= self.first_special and piece and piece in text:
+                raise _C.F5EError(f"Whisper.get_prompt_ids: the text contains the special token {piece}, which a prompt must not")
+        return [self.cfg.prev_sot_token_id] + self.encode_text(" " + text.strip())
 
     def decode_ids(self, ids: Sequence[int], skip_special_tokens: bool = True) -> str:
         if not self.id_to_piece:
@@ -685,11 +835,11 @@ class Whisper(nn.Module):
         # the attention launches of ``layer``, built once per state; ``_dec_step`` sets in ``at`` what a step (p, anc, kv, align)
         # and a layer (i) change
         H, caches, align_of = cfg.decoder_attention_heads, st["caches"], self._fold()["align"]
-        scale, at = (D // H) ** -0.5, SimpleNamespace(i=0, p=0, anc=None, kv=None, align=None)
+        scale, at = (D // H) ** -0.5, SimpleNamespace(i=0, p=0, anc=None, kv=None, align=None, begin=None)
 
         def self_attn(_W, _xn, qkv, ao):
             kc, vc = caches[at.i]
-            ops.attn_decode_f32(qkv, kc, vc, at.p, H, scale, anc=at.anc, out=ao)
+            ops.attn_decode_f32(qkv, kc, vc, at.p, H, scale, anc=at.anc, out=ao, begin=at.begin)
 
         def cross_attn(_W, q, ao):
             (K, Vv), align = at.kv[at.i], at.align
@@ -702,16 +852,22 @@ class Whisper(nn.Module):
         return st
 
     def _dec_step(self, st: dict, kv: List[Tuple[Tensor, Tensor]], last: Tensor, p: int, want_logits: bool,
-                  anc: Optional[Tensor] = None, align: Optional[Tuple[Tensor, int, Tensor]] = None) -> Optional[Tensor]:
+                  anc: Optional[Tensor] = None, align: Optional[Tuple[Tensor, int, Tensor]] = None,
+                  begin: Optional[Tensor] = None) -> Optional[Tensor]:
         """Feeds the tokens ``last`` i32 [R] at position p through the cached decoder; -> logits f32 [R, V] of position p + 1.
         ``anc`` i32 [R, >= p]: the beam's ancestry table, followed by every layer (None: a row reads its own cache).
         ``align`` = (probs f32 [R, heads, N, ld], t, m_len i32 [B]): the layers that own an alignment head also write those
-        heads' cross-attention probabilities of this position to probs[:, :, t, :m_len] (an extra launch; nothing else changes)."""
+        heads' cross-attention probabilities of this position to probs[:, :, t, :m_len] (an extra launch; nothing else changes).
+        ``begin`` i32 [R] (None: the launches as they always were): row r is left-padded by begin[r] positions, so it stands at
+        position p - begin[r] of the position table and reads the cached positions begin[r] .. p."""
         cfg, fd = self.cfg, self._fold()
         R, D = last.shape[0], cfg.d_model
         x3, xn, (at, bufs, self_attn, cross_attn) = st["x"], st["xn"], st["layer"]
-        at.p, at.anc, at.kv, at.align = p, anc, kv, align
-        ops.text_gather(last.view(R, 1), fd["emb"], fd["dec_pos"][p:p + 1], None, x3)
+        at.p, at.anc, at.kv, at.align, at.begin = p, anc, kv, align, begin
+        if begin is None:
+            ops.text_gather(last.view(R, 1), fd["emb"], fd["dec_pos"][p:p + 1], None, x3)
+        else:
+            ops.whisper_embed(last.view(R, 1), fd["emb"], fd["dec_pos"], x3, p, begin)
         x = x3.view(R, D)
         for i, W in enumerate(fd["dec"]):
             at.i = i
@@ -722,13 +878,71 @@ class Whisper(nn.Module):
         return ops.gemm_f32(xn, fd["emb"], None, out=st["logits"])
 
     @torch.no_grad()
-    def decoder_logits(self, kv: List[Tuple[Tensor, Tensor]], ids: Tensor) -> Tensor:
+    def decoder_prefill(self, st: dict, kv: List[Tuple[Tensor, Tensor]], ids, begin: Optional[Tensor] = None,
+                        want: Sequence[int] = ()) -> Optional[Tensor]:
+        """Feeds positions 0 .. U0 - 1 of ``ids`` i32 [R, U0] through the decoder in ONE pass per layer: the
+        embedding is f5e_whisper_embed, every projection one f5e_gemm_f32 over the R * U0 rows, the self-attention
+        f5e_attn_prefill_f32 (which files the keys and values in slots 0 .. U0 - 1 of the caches of ``st``, as U0 single steps
+        would have), the cross-attention f5e_mha_f32 with U0 queries per row.  -> logits f32 [R, len(want), V] of the positions
+        listed in ``want`` (the vocabulary GEMM runs for those rows alone), or None when none is wanted.
+        ``begin`` i32 [R] on the device: row r is left-padded by begin[r] positions (they are fed, filed and never read).
+        A state of R * K rows (beam search) takes the R prompts into the FIRST row of each group of K; the caller points the
+        ancestry table there.  ``ids`` given as a list is checked against the vocabulary here; a device tensor is clamped."""
+        cfg, fd = self.cfg, self._fold()
+        if not isinstance(ids, Tensor):
+            host = np.asarray(ids, dtype=np.int64)
+            if host.ndim != 2 or host.size == 0 or host.min() < 0 or host.max() >= cfg.vocab_size:
+                raise _C.F5EError(f"Whisper.decoder_prefill: ids must be [R, U0] ids in [0, {cfg.vocab_size}) "
+                                  f"(got shape {host.shape}, range {host.min() if host.size else 0} .. {host.max() if host.size else 0})")
+            ids = torch.from_numpy(host)
+        if ids.ndim != 2 or ids.shape[0] < 1 or ids.shape[1] < 1:
+            raise _C.F5EError(f"Whisper.decoder_prefill: ids must be [R, U0] with U0 >= 1 (got shape {tuple(ids.shape)})")
+        R, U0 = ids.shape
+        kc0 = st["caches"][0][0]
+        Rs, Umax, D = kc0.shape
+        B, dev = kv[0][0].shape[0], kc0.device
+        want = [int(w) for w in want]
+        if Rs % R or R % B or U0 > Umax or any(not 0 <= w < U0 for w in want):
+            raise _C.F5EError(f"Whisper.decoder_prefill: {R} prompts of {U0} tokens do not fit a state of {Rs} rows and {Umax} "
+                              f"positions over {B} utterances (or a wanted position of {want} lies outside the prompt)")
+        if begin is not None and (not isinstance(begin, Tensor) or begin.shape != (R,) or begin.dtype != I32 or not begin.is_cuda):
+            raise _C.F5EError(f"Whisper.decoder_prefill: begin must be i32 [{R}] on the device")
+        ids = ids.to(device=dev, dtype=I32).contiguous()
+        K, H, M = Rs // R, cfg.decoder_attention_heads, R * U0
+        scale, at = (D // H) ** -0.5, SimpleNamespace(i=0)
+        z = lambda n: torch.empty(M, n, dtype=F32, device=dev)   # noqa: E731
+        x = ops.whisper_embed(ids, fd["emb"], fd["dec_pos"], torch.empty(R, U0, D, dtype=F32, device=dev), 0, begin).view(M, D)
+        bufs = (z(D), z(3 * D), z(D), z(D), z(cfg.decoder_ffn_dim))
+
+        def self_attn(_W, _xn, qkv, ao):
+            kc, vc = st["caches"][at.i]
+            ops.attn_prefill_f32(qkv, kc[::K], vc[::K], U0, H, scale, begin=begin, out=ao)
+
+        def cross_attn(_W, q, ao):                       # the R / B rows of an utterance are (R / B) * U0 queries on its keys
+            Kx, Vx = kv[at.i]
+            ops.mha_f32(q, Kx.view(-1, D), Vx.view(-1, D), H, scale, B=B, out=ao)
+
+        for i, W in enumerate(fd["dec"]):
+            at.i = i
+            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn, cross_attn=cross_attn)
+        if not want:
+            return None
+        V = cfg.vocab_size
+        rows = x.view(R, U0, D)[:, want].reshape(R * len(want), D)
+        ops.layernorm(rows, rows, *fd["dec_ln"], eps=1e-5)
+        logits = torch.empty(R * len(want), (V + 3) // 4 * 4, dtype=F32, device=dev)[:, :V]
+        return ops.gemm_f32(rows, fd["emb"], None, out=logits).view(R, len(want), V)
+
+    @torch.no_grad()
+    def decoder_logits(self, kv: List[Tuple[Tensor, Tensor]], ids: Tensor, one_pass: bool = False) -> Tensor:
         """Teacher forcing through the cached step: ids i32 [B, U] on the device -> logits f32 [B, U, V] (position u predicts
-        token u + 1)."""
+        token u + 1).  ``one_pass``: through ``decoder_prefill`` instead (the same numbers up to fp32 summation order)."""
         B, U = ids.shape
         if U > self.cfg.max_target_positions:
             raise _C.F5EError(f"Whisper.decoder_logits: {U} tokens exceed max_target_positions = {self.cfg.max_target_positions}")
         st = self._dec_state(B, U, ids.device)
+        if one_pass:
+            return self.decoder_prefill(st, kv, ids, want=range(U)).contiguous()
         out = torch.empty(B, U, self.cfg.vocab_size, dtype=F32, device=ids.device)
         ids = ids.to(I32)
         for p in range(U):
@@ -867,7 +1081,7 @@ class Whisper(nn.Module):
                          sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0, return_beams: bool = False,
                          return_token_timestamps: bool = False, frames=None, return_timestamps: bool = False,
                          stats: Optional[dict] = None, temperature: float = 0.0, seed: int = 0, row_key: Optional[Tensor] = None,
-                         serial: Optional[Tensor] = None):
+                         serial: Optional[Tensor] = None, begin: Optional[Tensor] = None, prefill: bool = False):
         """``generate`` from the cross keys / values.  ``prompt``: ids for all rows, or [B, n0] ids.  ``return_token_timestamps``:
         one more item at the end, the times f32 [B, U] of the returned best hypothesis = ``token_timestamps`` on the returned
         tokens (a teacher-forced pass after the search, greedy or beam); ``frames``: mel frames per utterance (None: the whole
@@ -878,9 +1092,27 @@ class Whisper(nn.Module):
         its generated length).  ``temperature`` > 0: every pick is a draw from softmax(logits / temperature) over the allowed
         classes (f5e_whisper_sample_pick, with or without the timestamp rules; ``sum_logp`` is then the sum of the picks' T = 1
         log-probabilities); the noise is a function of ``seed``, the position and per row ``row_key`` (None: the row's index)
-        and ``serial`` (None: 0), i32 [B] on the device, so a row's draws do not depend on its batch."""
+        and ``serial`` (None: 0), i32 [B] on the device, so a row's draws do not depend on its batch.
+        ``prefill``: the prompt's tokens but the last go through ``decoder_prefill`` in one pass instead of one cached step
+        each; the picks start at n0 as before.  ``begin`` i32 [B] on the device (or a list): row b of the [B, n0] prompt is
+        left-padded by begin[b] tokens (any valid id), which it neither attends nor counts as positions, so ragged prompts
+        share one n0 and a row equals its own B = 1 run.  With either, ``no_speech_logp`` is read at the prompt's
+        <|startoftranscript|> (the last one of row 0; left-padding puts it in the same column for every row).  The bound
+        ``max_target_positions`` counts the padded columns, so a padded row has begin[b] fewer picks than alone: with ``begin``,
+        ``stats`` also receives ``at_bound`` i32 [B], non-zero for a row that was still open when the last step of the bound ran
+        (only such a row can differ from its own unpadded run; ``transcribe_long`` decodes it again alone).  The defaults take
+        the launches they always took."""
         n0 = _prompt_len(prompt)
         sample = self._check_sampling(temperature, seed, beam_size, return_beams)
+        sot_pos = 0
+        if begin is not None or prefill:
+            if return_token_timestamps:
+                raise _C.F5EError("Whisper.generate: return_token_timestamps with begin / prefill is out of scope (the "
+                                  "teacher-forced pass of token_timestamps feeds unpadded rows)")
+            begin, sot_pos = self._check_begin(begin, prompt, kv[0][0].shape[0], n0, stats is not None)
+            if int(beam_size) != 1 or return_beams:
+                return self._beam_from_kv(kv, prompt, max_new_tokens, sync_every, int(beam_size), float(length_penalty),
+                                          return_beams, bool(return_timestamps), stats, begin, bool(prefill), sot_pos)
         if return_token_timestamps:
             if not self.cfg.alignment_heads:
                 raise _C.F5EError("Whisper.generate: return_token_timestamps needs alignment_heads in generation_config.json")
@@ -912,10 +1144,21 @@ class Whisper(nn.Module):
             row_key = torch.arange(B, dtype=I32, device=dev) if row_key is None else row_key.to(dev, I32).contiguous()
             serial = torch.zeros(B, dtype=I32, device=dev) if serial is None else serial.to(dev, I32).contiguous()
         st = self._dec_state(B, Umax, dev)
-        for p in range(Umax - 1):
+        first_p = 0
+        if prefill and n0 > 1:
+            first_p = n0 - 1
+            logits = self.decoder_prefill(st, kv, tokens[:, :first_p].contiguous(), begin,
+                                          (sot_pos,) if stats is not None and sot_pos < first_p else ())
+            if logits is not None:
+                stats["no_speech_logp"] = self._no_speech_logp(logits[:, 0])
+            last.copy_(tokens[:, first_p])
+        at_bound = None
+        for p in range(first_p, Umax - 1):
             forced = p + 1 < n0
-            logits = self._dec_step(st, kv, last, p, not forced or (p == 0 and stats is not None))
-            if p == 0 and stats is not None:
+            if p == Umax - 2 and begin is not None and stats is not None:
+                at_bound = 1 - done                          # rows still open when the last step of the shared bound runs
+            logits = self._dec_step(st, kv, last, p, not forced or (p == sot_pos and stats is not None), begin=begin)
+            if p == sot_pos and stats is not None:
                 stats["no_speech_logp"] = self._no_speech_logp(logits)
             if forced:                       # all prompt tokens but the last go through the same cached step; nothing is picked
                 last.copy_(tokens[:, p + 1])
@@ -939,6 +1182,8 @@ class Whisper(nn.Module):
         first = torch.where(is_eos.any(1), is_eos.to(torch.int64).argmax(1) + 1, torch.full((B,), Umax - n0, dtype=torch.int64, device=dev))
         if stats is not None:
             stats["sum_logp"] = sum_logp
+            if begin is not None:
+                stats["at_bound"] = torch.zeros(B, dtype=I32, device=dev) if at_bound is None else at_bound
         return tokens, (first + n0).to(I32)
 
     @staticmethod
@@ -956,6 +1201,24 @@ class Whisper(nn.Module):
             raise _C.F5EError(f"Whisper.generate: seed = {seed!r} must be an integer in 0 .. 2^64 - 1")
         return True
 
+    def _check_begin(self, begin, prompt, B: int, n0: int, want_sot: bool) -> Tuple[Optional[Tensor], int]:
+        """-> (begin as i32 [B] on the device or None, the column of <|startoftranscript|>); refusals before any launch."""
+        dev = self._fold()["device"]
+        if begin is not None:
+            host = [int(v) for v in (begin.tolist() if isinstance(begin, Tensor) else begin)]
+            if len(host) != B or min(host) < 0 or max(host) >= n0:
+                raise _C.F5EError(f"Whisper.generate: begin must be {B} pad counts in [0, {n0}) (got {host})")
+            begin = torch.tensor(host, dtype=I32).to(dev)
+        sot_pos = 0
+        if want_sot:
+            row = prompt[0] if isinstance(prompt, Tensor) and prompt.ndim == 2 else prompt
+            row = row.tolist() if isinstance(row, Tensor) else (row[0] if len(row) and isinstance(row[0], (list, tuple)) else row)
+            at = [i for i, t in enumerate(row) if int(t) == self.cfg.decoder_start_token_id]
+            if not at:
+                raise _C.F5EError("Whisper.generate: the prompt has no <|startoftranscript|> to read the no-speech probability at")
+            sot_pos = at[-1]
+        return begin, sot_pos
+
     def _no_speech_logp(self, logits: Tensor) -> Tensor:
         """log softmax(logits)[<|nospeech|>] per row (f5e_token_logp), from the step that fed <|startoftranscript|>."""
         target = torch.full((logits.shape[0],), self.cfg.no_speech_token_id, dtype=I32, device=logits.device)
@@ -963,11 +1226,15 @@ class Whisper(nn.Module):
 
     @torch.no_grad()
     def _beam_from_kv(self, kv: List[Tuple[Tensor, Tensor]], prompt: Sequence[int], max_new_tokens: Optional[int], sync_every: int,
-                      K: int, length_penalty: float, return_beams: bool, ts: bool = False, stats: Optional[dict] = None):
+                      K: int, length_penalty: float, return_beams: bool, ts: bool = False, stats: Optional[dict] = None,
+                      begin: Optional[Tensor] = None, prefill: bool = False, sot_pos: int = 0):
         """The pooled beam search (f5e_whisper_beam_step has the rules): B * K rows, row b K + i = open hypothesis i of utterance
         b.  Every layer's self-attention follows the ancestry table, the cross-attention reads an utterance's keys once for its
         K rows, and no cache row ever moves.  The prompt goes through the same step without a pick (the K rows of an utterance
-        are equal until the first pick).  Caches: K x the greedy figure, sized by the prompt + ``max_new_tokens`` when given."""
+        are equal until the first pick).  Caches: K x the greedy figure, sized by the prompt + ``max_new_tokens`` when given.
+        ``prefill``: the prompt but its last token is prefilled ONCE per utterance, into the cache row of its first beam, and the
+        ancestry table sends every beam there for those positions (the rows are equal until the first pick, so this is what
+        K equal prefills would leave).  ``begin`` i32 [B]: left-padding per utterance, shared by its K rows."""
         cfg = self.cfg
         V, eos = cfg.vocab_size, cfg.eos_token_id
         n0 = _prompt_len(prompt)
@@ -1001,11 +1268,25 @@ class Whisper(nn.Module):
         pool_n, open_, alive = (torch.full((B,), v, dtype=I32, device=dev) for v in (0, 1, 1))
         scratch = torch.empty(max(ops.whisper_beam_scratch(B, K, V), 4), dtype=torch.uint8, device=dev)
         st = self._dec_state(R, Umax, dev)
-        cur = 0
-        for p in range(Umax - 1):
+        cur, first_p = 0, 0
+        begin_rows = None if begin is None else begin.repeat_interleave(K).contiguous()
+        if prefill and n0 > 1:
+            first_p = n0 - 1
+            logits = self.decoder_prefill(st, kv, hyp[0][::K, :first_p].contiguous(), begin,
+                                          (sot_pos,) if stats is not None and sot_pos < first_p else ())
+            if logits is not None:
+                stats["no_speech_logp"] = self._no_speech_logp(logits[:, 0])
+            for a in anc:                                  # prompt positions live in the row of the utterance's first beam
+                a[:, :first_p] = (torch.arange(R, dtype=I32, device=dev) // K * K)[:, None]
+            last.copy_(hyp[0][:, first_p])
+        at_bound = None
+        for p in range(first_p, Umax - 1):
             forced = p + 1 < n0
-            logits = self._dec_step(st, kv, last, p, not forced or (p == 0 and stats is not None), anc=anc[cur])
-            if p == 0 and stats is not None:
+            if p == Umax - 2 and begin is not None and stats is not None:
+                at_bound = alive.clone()                     # utterances still searching when the last step of the bound runs
+            logits = self._dec_step(st, kv, last, p, not forced or (p == sot_pos and stats is not None), anc=anc[cur],
+                                    begin=begin_rows)
+            if p == sot_pos and stats is not None:
                 stats["no_speech_logp"] = self._no_speech_logp(logits)[::K].contiguous()
             if forced:
                 last.copy_(hyp[0][:, p + 1])
@@ -1028,6 +1309,8 @@ class Whisper(nn.Module):
         best = (beams[:, 0].contiguous(), pool_len[:, 0].contiguous())
         if stats is not None:
             stats["sum_logp"] = pool_score[:, 0] * (pool_len[:, 0] - n0).clamp(min=1).to(F32) ** length_penalty
+            if begin is not None:
+                stats["at_bound"] = torch.zeros(B, dtype=I32, device=dev) if at_bound is None else at_bound
         return best + ((beams, pool_len, pool_score),) if return_beams else best
 
     @torch.no_grad()
@@ -1075,7 +1358,7 @@ class Whisper(nn.Module):
     def transcribe_long(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe", beam_size: int = 1,
                         no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = None,
                         sync_every: int = 8, fallback: Optional[Fallback] = None, row_keys: Optional[Sequence[int]] = None,
-                        trace: Optional[list] = None, **unbuilt) -> List[List[Segment]]:
+                        trace: Optional[list] = None, context: Optional[Context] = None, **unbuilt) -> List[List[Segment]]:
         """Recordings of any length: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> the segments of every row.
         The seek loop of ``transformers``' long-form ``generate`` (``return_timestamps=True``, ``condition_on_prev_tokens=False``,
         temperature 0): every window of ``n_frames`` mel frames is decoded with timestamp tokens, cut into segments at the
@@ -1104,7 +1387,20 @@ class Whisper(nn.Module):
         decodes the utterance has started before, so a row's result does not depend on its batch-mates.  ``logprob_threshold``
         and ``fallback.logprob_threshold`` are one threshold: two different values are refused.  ``Segment.temperature`` is the
         temperature of the attempt that was kept.  One host read per attempt.  ``trace``: a list that receives one dict per
-        attempt (row, seek, temperature, compression_ratio, avg_logprob, no_speech_prob, needs_fallback, should_skip)."""
+        attempt (row, seek, temperature, compression_ratio, avg_logprob, no_speech_prob, needs_fallback, should_skip; with a
+        ``context`` also prompt, the window's decoder input).
+        ``context`` (a ``Context``; None: every window starts with its three forced tokens, as above): conditioning on the
+        previous windows' text and an initial prompt.  Every window's decoder input is ``window_prompt`` of its row; the rows of
+        an iteration are left-padded to a common length (``generate_from_kv(begin=)``) and the prompt goes through
+        ``decoder_prefill`` in one pass.  The token bound stays ``max_target_positions`` for prompt and picks together
+        (``_set_max_new_tokens_and_length`` grows ``max_length`` by the prompt and caps it there), so a fully conditioned window
+        has ``max_target_positions - (max_target_positions // 2 - 1) - 4`` picks left.  With a ``fallback``, a window kept at a
+        temperature of 0.5 or more does not condition the next one (``conditions_next_window``).  ``no_speech_prob`` is read
+        at <|startoftranscript|>, wherever the prompt puts it.  Deliberately unlike ``transformers``, which decides from row
+        0's history whether ANY row of a batch is conditioned, a row is conditioned iff it has previous segments of its own:
+        a row equals its own B = 1 run.  Two things keep that true under padding (``_decode_with_context``): a padded row that
+        runs into the batch's token bound, which counts its pad columns, is decoded again alone with its own bound, and a
+        sampled attempt batches a row only with rows of its own prompt length, since the noise is keyed by the position."""
         for name, value in unbuilt.items():
             off = {"temperature": (None, 0, 0.0, (0.0,), [0.0]), "condition_on_prev_tokens": (None, False), "prompt_ids": (None,),
                    "chunk_length_s": (None,), "stride_length_s": (None,), "return_token_timestamps": (None, False),
@@ -1114,7 +1410,8 @@ class Whisper(nn.Module):
             if not any(value is v or (not isinstance(value, Tensor) and value == v) for v in off[name]):
                 raise _C.F5EError(f"Whisper.transcribe_long: {name} = {value!r} is out of scope (conditioning on previous tokens, "
                                   "prompt_ids, strided chunk merging, word timestamps across windows and a graph-captured step "
-                                  "are not built; temperature fallback goes through fallback=Fallback(...))")
+                                  "are not built under these names; temperature fallback goes through fallback=Fallback(...), "
+                                  "conditioning and prompts through context=Context(...))")
         if fallback is not None and not isinstance(fallback, Fallback):
             raise _C.F5EError(f"Whisper.transcribe_long: fallback = {fallback!r} must be a Fallback or None")
         lp_thr = logprob_threshold                                     # one threshold for the fallback and for the no-speech skip
@@ -1125,6 +1422,8 @@ class Whisper(nn.Module):
             lp_thr = fallback.logprob_threshold
         elif (no_speech_threshold is None) != (logprob_threshold is None):
             raise _C.F5EError("Whisper.transcribe_long: the no-speech skip needs no_speech_threshold and logprob_threshold together")
+        if context is not None:
+            self._check_context(context)
         cr_thr = None if fallback is None else fallback.compression_ratio_threshold
         temps = (0.0,) if fallback is None else fallback.temperatures
         if sync_every < 1:
@@ -1147,6 +1446,14 @@ class Whisper(nn.Module):
         prompts = None if language is None else self.prompt_ids(language, task, True)
         keys = list(range(B)) if row_keys is None else [int(v) for v in row_keys]
         seek, out, serial = [0] * B, [[] for _ in range(B)], [0] * B
+        if context is not None:
+            lead = context.prompt_ids
+            if lead is not None and context.prompt_condition_type == "first-segment":     # ``_prepare_segments``
+                lead = lead[1:] if lead[0] == cfg.prev_sot_token_id else lead
+                history = [[list(lead)] for _ in range(B)]
+            else:
+                history = [[] for _ in range(B)]
+            cond, cut = [context.condition_on_prev_tokens] * B, cfg.max_target_positions // 2 - 1
         while True:
             act = [b for b in range(B) if seek[b] < frames[b]]
             if not act:
@@ -1159,31 +1466,47 @@ class Whisper(nn.Module):
             if prompts is None:                                        # the first iteration: every row is in it, at seek 0
                 prompts = self._prompts(kv, None, task, True)
             prompt = prompts[torch.tensor(act, device=dev)] if isinstance(prompts, Tensor) else prompts
+            plist = None
+            if context is not None:                                    # per row: previous text / prompt + the forced tokens
+                if isinstance(prompts, Tensor):
+                    prompts = prompts.tolist()                         # the detected languages: one host read per call
+                plist = [window_prompt(context, prompts[b] if isinstance(prompts[0], list) else prompts, history[b], cond[b],
+                                      cfg.prev_sot_token_id, ts_begin, cut) for b in act]
             n0 = _prompt_len(prompt)
             kept, pend = [None] * len(act), list(range(len(act)))      # per active row: (full, avg, ns, cr, temperature, skip)
             for temp in temps:
-                sub, sub_prompt = kv, prompt
-                if len(pend) < len(act):                               # only the rows that fall back: gathered, not re-encoded
-                    idx = torch.tensor(pend, device=dev)
-                    sub = [(k[idx], v[idx]) for k, v in kv]
-                    sub_prompt = prompt[idx] if isinstance(prompt, Tensor) else prompt
-                stats = {}
-                if temp > 0:
+                if context is not None:
                     rows = [act[i] for i in pend]
-                    tokens, n = self.generate_from_kv(
-                        sub, sub_prompt, None, sync_every, 1, 1.0, return_timestamps=True, stats=stats, temperature=temp,
-                        seed=fallback.seed, row_key=torch.tensor([keys[b] for b in rows], dtype=I32).to(dev),
-                        serial=torch.tensor([serial[b] for b in rows], dtype=I32).to(dev))[:2]
-                    for b in rows:
-                        serial[b] += 1
+                    fulls, sum_logp, ns_logp = self._decode_with_context(
+                        kv, plist, pend, temp, beam_size, sync_every, 0 if fallback is None else fallback.seed,
+                        [keys[b] for b in rows], [serial[b] for b in rows])
+                    if temp > 0:
+                        for b in rows:
+                            serial[b] += 1
                 else:
-                    tokens, n = self.generate_from_kv(sub, sub_prompt, None, sync_every, beam_size, 1.0, return_timestamps=True,
-                                                      stats=stats)[:2]
-                tokens, n = tokens.tolist(), n.tolist()
-                sum_logp, ns_logp = stats["sum_logp"].tolist(), stats["no_speech_logp"].tolist()
+                    sub, sub_prompt = kv, prompt
+                    if len(pend) < len(act):                           # only the rows that fall back: gathered, not re-encoded
+                        idx = torch.tensor(pend, device=dev)
+                        sub = [(k[idx], v[idx]) for k, v in kv]
+                        sub_prompt = prompt[idx] if isinstance(prompt, Tensor) else prompt
+                    stats = {}
+                    if temp > 0:
+                        rows = [act[i] for i in pend]
+                        tokens, n = self.generate_from_kv(
+                            sub, sub_prompt, None, sync_every, 1, 1.0, return_timestamps=True, stats=stats, temperature=temp,
+                            seed=fallback.seed, row_key=torch.tensor([keys[b] for b in rows], dtype=I32).to(dev),
+                            serial=torch.tensor([serial[b] for b in rows], dtype=I32).to(dev))[:2]
+                        for b in rows:
+                            serial[b] += 1
+                    else:
+                        tokens, n = self.generate_from_kv(sub, sub_prompt, None, sync_every, beam_size, 1.0, return_timestamps=True,
+                                                          stats=stats)[:2]
+                    tokens, n = tokens.tolist(), n.tolist()
+                    fulls = [tokens[j][n0:n[j]] for j in range(len(pend))]
+                    sum_logp, ns_logp = stats["sum_logp"].tolist(), stats["no_speech_logp"].tolist()
                 again = []
                 for j, i in enumerate(pend):
-                    full = tokens[j][n0:n[j]]
+                    full = fulls[j]
                     avg, ns = sum_logp[j] / max(len(full), 1), math.exp(ns_logp[j])
                     cr = compression_ratio(full, cfg.vocab_size)
                     skip = no_speech_threshold is not None and avg < lp_thr and ns > no_speech_threshold
@@ -1195,12 +1518,16 @@ class Whisper(nn.Module):
                     if trace is not None:
                         trace.append(dict(row=act[i], seek=seek[act[i]], temperature=temp, compression_ratio=cr, avg_logprob=avg,
                                           no_speech_prob=ns, needs_fallback=need, should_skip=skip))
+                        if context is not None:
+                            trace[-1]["prompt"] = plist[i]
                 pend = again
                 if not pend:
                     break
             for i, b in enumerate(act):
                 full, avg, ns, cr, temp, skip = kept[i]
                 seq = full[:-1] if full and full[-1] == eos else full
+                if context is not None:
+                    cond[b] = context.condition_on_prev_tokens and conditions_next_window(temp)
                 if not seq or skip:
                     seek[b] += nf[i]
                     continue
@@ -1208,19 +1535,89 @@ class Whisper(nn.Module):
                 if step <= 0:
                     raise _C.F5EError(f"Whisper.transcribe_long: the window at frame {seek[b]} of row {b} does not advance")
                 out[b].extend(Segment(s0, s1, tok, seek[b], avg, ns, cr, temp) for s0, s1, tok in parts)
+                if context is not None:
+                    history[b].extend(tok for _, _, tok in parts)
                 seek[b] += step
+
+    def _decode_with_context(self, kv, plist, ix, temp, beam_size, sync_every, seed, keys, serial):
+        """One attempt of the windows ``ix`` (indices into ``kv`` and ``plist``, the rows' decoder inputs) at ``temp`` ->
+        (generated tokens with the closing eos, sum_logp, no_speech_logp) per row of ``ix``, each what the row's own B = 1 run
+        gives.  Temperature 0: the rows are left-padded to their longest prompt and decoded together; the bound counts the pad
+        columns, so a padded row that was still open when the last step of that shared bound ran (``at_bound``) is decoded again
+        alone, with its own bound.  A sampled attempt keys its noise by the position, which padding would shift, so rows are
+        batched only with rows of their own prompt length (a batch that falls back with ragged prompts costs one decode per
+        length, not one per row)."""
+        eos, dev, res = self.cfg.eos_token_id, kv[0][0].device, {}
+
+        def run(group):
+            rows = [plist[i] for i in group]
+            width = max(len(r) for r in rows)
+            begin = [width - len(r) for r in rows]
+            sub = kv
+            if group != list(range(kv[0][0].shape[0])):                  # gathered, not encoded again
+                idx = torch.tensor(group, device=dev)
+                sub = [(k[idx], v[idx]) for k, v in kv]
+            kw, st = {}, {}
+            if temp > 0:
+                at = [ix.index(i) for i in group]
+                kw = dict(temperature=temp, seed=seed, row_key=torch.tensor([keys[j] for j in at], dtype=I32).to(dev),
+                          serial=torch.tensor([serial[j] for j in at], dtype=I32).to(dev))
+            tokens, n = self.generate_from_kv(sub, [[eos] * pad + r for pad, r in zip(begin, rows)], None, sync_every,
+                                              1 if temp > 0 else beam_size, 1.0, return_timestamps=True, stats=st, begin=begin,
+                                              prefill=True, **kw)[:2]
+            tokens, n = tokens.tolist(), n.tolist()
+            sl, ns, open_ = st["sum_logp"].tolist(), st["no_speech_logp"].tolist(), st["at_bound"].tolist()
+            for j, i in enumerate(group):
+                res[i] = (tokens[j][width:n[j]], sl[j], ns[j])
+            return [i for j, i in enumerate(group) if begin[j] > 0 and open_[j]]
+
+        if temp > 0:
+            for length in sorted({len(plist[i]) for i in ix}):
+                run([i for i in ix if len(plist[i]) == length])
+        else:
+            for i in run(list(ix)):
+                run([i])
+        return [res[i][0] for i in ix], [res[i][1] for i in ix], [res[i][2] for i in ix]
+
+    def _check_context(self, context) -> None:
+        """Refusals of ``transcribe_long(context=)`` by name, before any launch."""
+        cfg = self.cfg
+        if not isinstance(context, Context):
+            raise _C.F5EError(f"Whisper.transcribe_long: context = {context!r} must be a Context or None")
+        if (context.condition_on_prev_tokens or context.prompt_ids is not None) and cfg.prev_sot_token_id is None:
+            raise _C.F5EError("Whisper.transcribe_long: generation_config has no prev_sot_token_id (<|startofprev|>); conditioning "
+                              "on previous tokens and prompt_ids need it")
+        ids = context.prompt_ids or ()
+        if any(not 0 <= t < cfg.vocab_size for t in ids):
+            raise _C.F5EError(f"Whisper.transcribe_long: prompt_ids {list(ids)} must be ids in [0, {cfg.vocab_size})")
+        cut, cap = cfg.max_target_positions // 2 - 1, cfg.max_target_positions
+        longest = len(ids) + 3
+        if context.condition_on_prev_tokens:
+            longest = max(longest, (len(ids) if context.prompt_condition_type == "all-segments" and ids else 1) + cut + 3)
+        if longest >= cap:
+            raise _C.F5EError(f"Whisper.transcribe_long: a prompt of {len(ids)} tokens, up to {cut} previous tokens and 3 forced "
+                              f"tokens make {longest} positions, which leaves no room below max_target_positions = {cap}")
 
 
 class WhisperRecognizer:
     """The duck type ``eval_wer.run_asr_wer`` and ``preprocess_ref_audio_text`` take: ``transcribe(wav_or_path, sr) -> str``."""
 
     def __init__(self, path: str, device="cuda", language: Optional[str] = "en", beam_size: int = 1, long_form: bool = False,
-                 fallback: Optional[Fallback] = None):
+                 fallback: Optional[Fallback] = None, initial_prompt: Optional[str] = None,
+                 condition_on_previous_text: bool = False):
         """``language``: a name or code, or None / "auto" to detect it per recording.  ``long_form``: ``transcribe`` runs the
         seek loop over the whole recording (``Whisper.transcribe_long``) instead of cutting it to the first chunk.  ``fallback``:
-        the temperature fallback of that loop (needs ``long_form``)."""
+        the temperature fallback of that loop (needs ``long_form``).  ``initial_prompt``: text (a name, a domain word; ``Whisper.get_prompt_ids``, so
+        the checkpoint needs merges.txt) given as a "first-segment" prompt: without conditioning it is put in front of EVERY
+        window; with it, it leads the first window's previous text and then scrolls out of the cut (``Context``).
+        ``condition_on_previous_text``: every window is conditioned on the text of the windows before it.  Both need
+        ``long_form``."""
         if fallback is not None and not (long_form and isinstance(fallback, Fallback)):
             raise _C.F5EError("WhisperRecognizer: fallback needs long_form=True and a Fallback record")
+        if (initial_prompt is not None or condition_on_previous_text) and not long_form:
+            raise _C.F5EError("WhisperRecognizer: initial_prompt and condition_on_previous_text need long_form=True")
+        if initial_prompt is not None and not isinstance(initial_prompt, str):
+            raise _C.F5EError(f"WhisperRecognizer: initial_prompt = {initial_prompt!r} must be text or None")
         self.fallback = fallback
         self.device = torch.device(device)
         self.language = language
@@ -1233,6 +1630,11 @@ class WhisperRecognizer:
             raise _C.F5EError("WhisperRecognizer: language detection needs lang_to_id in generation_config.json")
         if self.long_form:
             self.model.cfg.timestamp_begin                   # refused by name here, not per file
+        self.context = None
+        if initial_prompt is not None or condition_on_previous_text:
+            ids = None if initial_prompt is None else tuple(self.model.get_prompt_ids(initial_prompt))
+            self.context = Context(condition_on_prev_tokens=bool(condition_on_previous_text), prompt_ids=ids)
+            self.model._check_context(self.context)          # a prompt that leaves no room fails here, not per file
         self._warned = set()
 
     def _lang(self) -> Optional[str]:
@@ -1274,6 +1676,8 @@ class WhisperRecognizer:
     def transcribe_segments(self, audio, sr: Optional[int] = None) -> List[Tuple[float, float, str]]:
         """-> [(start_s, end_s, text)] over the whole recording, however long (``Whisper.transcribe_long``)."""
         kw = {} if getattr(self, "fallback", None) is None else dict(fallback=self.fallback)
+        if getattr(self, "context", None) is not None:
+            kw["context"] = self.context
         segs = self.model.transcribe_long(self._audio(audio, sr, cut=False), None, self._lang(), beam_size=self.beam_size, **kw)[0]
         return [(s.start_s, s.end_s, self.model.decode_ids(s.tokens)) for s in segs]
 

@@ -996,11 +996,13 @@ def log_softmax_rows(x: Tensor, out: Optional[Tensor] = None):
 
 
 def attn_decode_f32(qkv: Tensor, kc: Tensor, vc: Tensor, p: int, heads: int, scale: float, anc: Optional[Tensor] = None,
-                    out: Optional[Tensor] = None):
+                    out: Optional[Tensor] = None, begin: Optional[Tensor] = None):
     """Cached single-query self-attention of decode step ``p`` (f5e_attn_decode_f32): qkv f32 [R, >= 3 D] (q | k | v of the
     step), kc / vc f32 [R, Umax, D] views of the layer's caches (row and position strides free, unit channel stride, the same
     strides for both), anc i32 [R, >= p] or None -> out f32 [R, D].  Slot [r, p] of both caches receives the step's k / v;
-    position j < p is read from cache row ``anc[r, j]`` (row r when None)."""
+    position j < p is read from cache row ``anc[r, j]`` (row r when None).  ``begin`` i32 [R] on the device (None: the launch
+    as it always was): row r reads positions begin[r] .. p only (f5e_attn_decode_from_f32, the step after a left-padded
+    prompt)."""
     if qkv.ndim != 2 or kc.ndim != 3 or kc.shape != vc.shape or kc.stride() != vc.stride():
         raise _C.F5EError("attn_decode_f32: qkv [R, >= 3 D] and kc, vc [R, Umax, D] with equal strides; there is no CPU path")
     R, Umax, D = kc.shape
@@ -1027,9 +1029,72 @@ def attn_decode_f32(qkv: Tensor, kc: Tensor, vc: Tensor, p: int, heads: int, sca
     if out.shape != (R, D):
         raise _C.F5EError(f"attn_decode_f32: out must be [{R}, {D}]")
     op, ldo = _rows(out, (F32,), "attn_decode_f32: out", D, vec=1)
+    if begin is not None:
+        check(lib().f5e_attn_decode_from_f32(_stream(), qp, ldq, C.c_void_p(kc.data_ptr()), C.c_void_p(vc.data_ptr()), row_stride,
+                                             pos_stride, ap, ld_anc, _vec(begin, I32, "attn_decode_f32: begin", (R,)), op, ldo, R,
+                                             Umax, heads, D // heads, int(p), float(scale)), "f5e_attn_decode_from_f32")
+        return out
     check(lib().f5e_attn_decode_f32(_stream(), qp, ldq, C.c_void_p(kc.data_ptr()), C.c_void_p(vc.data_ptr()), row_stride,
                                     pos_stride, ap, ld_anc, op, ldo, R, Umax, heads, D // heads, int(p), float(scale)),
           "f5e_attn_decode_f32")
+    return out
+
+
+def attn_prefill_f32(qkv: Tensor, kc: Tensor, vc: Tensor, U: int, heads: int, scale: float, begin: Optional[Tensor] = None,
+                     out: Optional[Tensor] = None):
+    """Causal self-attention of a prompt in one pass (f5e_attn_prefill_f32): qkv f32 [R * U, >= 3 D] (q | k | v of positions
+    0 .. U - 1 of every row), kc / vc f32 [R, Umax, D] views of the layer's caches (the strides ``attn_decode_f32`` takes),
+    begin i32 [R] on the device or None -> out f32 [R * U, D].  Query i of row r sees keys begin[r] .. i (a query below
+    begin[r] yields zeros); slots [r, :U] of both caches receive the k / v columns of qkv, nothing else of them is written."""
+    if qkv.ndim != 2 or kc.ndim != 3 or kc.shape != vc.shape or kc.stride() != vc.stride():
+        raise _C.F5EError("attn_prefill_f32: qkv [R * U, >= 3 D] and kc, vc [R, Umax, D] with equal strides; there is no CPU path")
+    R, Umax, D = kc.shape
+    for t, nm in ((kc, "kc"), (vc, "vc")):
+        if not t.is_cuda or t.dtype != F32 or t.stride(2) != 1:
+            raise _C.F5EError(f"attn_prefill_f32: {nm} must be an f32 GPU tensor with unit channel stride")
+    U = int(U)
+    if not 1 <= U <= Umax or qkv.shape[0] != R * U or D % heads:
+        raise _C.F5EError(f"attn_prefill_f32: need 1 <= U = {U} <= {Umax} cached positions, {R} * U = {qkv.shape[0]} rows of qkv "
+                          f"and heads {heads} dividing {D}")
+    pos_stride = kc.stride(1) if Umax > 1 else max(D, kc.stride(1))
+    row_stride = kc.stride(0) if R > 1 else max(kc.stride(0), (Umax - 1) * pos_stride + D)
+    for t in (kc, vc):
+        have = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+        if pos_stride < D or row_stride < (Umax - 1) * pos_stride + D or have < (R - 1) * row_stride + (Umax - 1) * pos_stride + D \
+                or pos_stride % 4 or row_stride % 4 or t.data_ptr() % 16:
+            raise _C.F5EError(f"attn_prefill_f32: cache strides ({row_stride}, {pos_stride}) must be multiples of 4 spanning "
+                              f"[{R}, {Umax}, {D}] inside the storage, kc and vc 16-byte aligned")
+    qp, ldq = _rows(qkv, (F32,), "attn_prefill_f32: qkv", 3 * D)
+    bp = None if begin is None else _vec(begin, I32, "attn_prefill_f32: begin", (R,))
+    require_device()
+    out = torch.empty(R * U, D, dtype=F32, device=qkv.device) if out is None else out
+    if out.shape != (R * U, D):
+        raise _C.F5EError(f"attn_prefill_f32: out must be [{R * U}, {D}]")
+    op, ldo = _rows(out, (F32,), "attn_prefill_f32: out", D)
+    check(lib().f5e_attn_prefill_f32(_stream(), qp, ldq, C.c_void_p(kc.data_ptr()), C.c_void_p(vc.data_ptr()), row_stride,
+                                     pos_stride, bp, op, ldo, R, U, Umax, heads, D // heads, float(scale)), "f5e_attn_prefill_f32")
+    return out
+
+
+def whisper_embed(ids: Tensor, emb: Tensor, pos: Tensor, out: Tensor, p0: int = 0, begin: Optional[Tensor] = None):
+    """out[r, u] = emb[ids[r, u]] + pos[max(p0 + u - begin[r], 0)] (f5e_whisper_embed): ids i32 [R, U], emb f32 [V, D], pos f32
+    [P, D], begin i32 [R] or None, out f32 [R, U, D], all contiguous on the device.  U = 1 with p0 = p feeds a decode step."""
+    if ids.ndim != 2 or emb.ndim != 2 or pos.ndim != 2 or out.ndim != 3:
+        raise _C.F5EError("whisper_embed: ids [R, U], emb [V, D], pos [P, D] and out [R, U, D]; there is no CPU path")
+    (R, U), D = ids.shape, emb.shape[1]
+    p0 = int(p0)
+    if R < 1 or U < 1 or out.shape != (R, U, D) or pos.shape[1] != D or D % 4 or p0 < 0 or p0 + U > pos.shape[0]:
+        raise _C.F5EError(f"whisper_embed: ids {tuple(ids.shape)}, emb {tuple(emb.shape)}, pos {tuple(pos.shape)}, out "
+                          f"{tuple(out.shape)}: out must be [R, U, D], D a multiple of 4, and positions {p0} .. {p0 + U - 1} "
+                          f"inside the {pos.shape[0]} rows of pos")
+    for t, nm in ((emb, "emb"), (pos, "pos"), (out, "out")):
+        if t.is_cuda and t.data_ptr() % 16:
+            raise _C.F5EError(f"whisper_embed: {nm} must be 16-byte aligned")
+    bp = None if begin is None else _vec(begin, I32, "whisper_embed: begin", (R,))
+    ptrs = (_p(ids, I32, "whisper_embed: ids"), bp, _p(emb, F32, "whisper_embed: emb"), _p(pos, F32, "whisper_embed: pos"),
+            _p(out, F32, "whisper_embed: out"))
+    require_device()
+    check(lib().f5e_whisper_embed(_stream(), *ptrs, R, U, D, p0, pos.shape[0], emb.shape[0]), "f5e_whisper_embed")
     return out
 
 

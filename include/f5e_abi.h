@@ -926,6 +926,34 @@ F5E_API int f5e_dtw_workspace_bytes(int B, int N_cap, int M_cap, unsigned long l
 F5E_API int f5e_dtw_path(f5e_stream st, const float* C, int ldc, const int* n_rows, const int* m_len, int* first,
                  void* workspace, unsigned long long workspace_bytes, int B, int N_cap, int M_cap);
 
+/* ---- Whisper decoder prefill (csrc/whisper_prefill.hip): a prompt of U positions per row in ONE pass per layer.
+ *
+ * Causal self-attention of positions 0 .. U-1 of R rows against themselves, which also files their keys and values:
+ *   qkv     f32 [R*U][ld_qkv >= 3*H*dk]: the fused projection q | k | v, row r*U + i = position i of row r
+ *   kc, vc  the layer's caches as f5e_attn_decode_f32 takes them: element (r, j, c) at r*row_stride + j*pos_stride + c
+ *   begin   i32 [R] on the device or NULL (all 0): row r is left-padded by begin[r] positions (clamped to [0, U])
+ *   out     f32 [R*U][ldo >= H*dk]
+ * out[r*U + i][h*dk + d] = sum_{j = begin[r] .. i} softmax_j(scale * q_i . k_j) * v_j[d]; a query i < begin[r] yields zeros.
+ * Slots [r][0 .. U-1] of kc / vc receive the k / v columns of qkv bit for bit (the padded positions too: nobody reads them);
+ * no other byte of the caches is written, and keys / values are read from qkv, never from the caches.  The wave tile of
+ * f5e_mha_f32 (16 queries per wave on v_mfma_f32_16x16x4_f32); the tile that owns 16 positions of a head stores their k and v.
+ * Limits: 1 <= U <= Umax <= 4096; dk = 16, 32, 64, 128; R, H <= 65535; every stride a multiple of 4 floats; qkv, kc, vc and out
+ * 16-byte aligned.  Refusals happen before the launch.  No allocation, no synchronisation. */
+F5E_API int f5e_attn_prefill_f32(f5e_stream st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                         int pos_stride, const int* begin, float* out, int ldo, int R, int U, int Umax, int H, int dk,
+                         float scale);
+/* f5e_attn_decode_f32 for a row whose first begin[r] positions are padding: keys / values begin[r] .. p (begin clamped to
+ * [0, p]).  begin i32 [R] on the device; NULL runs f5e_attn_decode_f32 itself, and zeros give its bits.  Everything else
+ * (slot [r][p], the ancestry table, the limits) as there. */
+F5E_API int f5e_attn_decode_from_f32(f5e_stream st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                             int pos_stride, const int* anc, int ld_anc, const int* begin, float* out, int ldo, int R, int Umax,
+                             int H, int dk, int p, float scale);
+/* out[r][u] = emb[ids[r][u]] + pos[max(p0 + u - begin[r], 0)]: ids i32 [R][U], begin i32 [R] or NULL, emb f32 [table_rows][D],
+ * pos f32 [max_pos][D], out f32 [R][U][D] (all contiguous, D a multiple of 4, 16-byte aligned).  U = 1 with p0 = p is the decode
+ * step's form.  An id outside the table is clamped (the host refuses it where it knows the ids); p0 + U <= max_pos. */
+F5E_API int f5e_whisper_embed(f5e_stream st, const int* ids, const int* begin, const float* emb, const float* pos, float* out,
+                      int R, int U, int D, int p0, int max_pos, int table_rows);
+
 /* ---------------------------------------------------------------- UTMOS (csrc/utmos.hip) ---------------------- */
 /* The UTMOS predictor (utmos22_strong, reference eval/eval_utmos.py): a wav2vec2-base upstream (group-norm feature extractor,
  * post-LayerNorm encoder), a BiLSTM over its frames and a per-frame score averaged per utterance.  The strided convolutions 1-6,

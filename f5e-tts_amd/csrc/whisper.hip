@@ -26,6 +26,7 @@
 //
 // Nothing here allocates, synchronises or reads back.  Per-row lengths are DEVICE int32.
 #include "f5e_common.h"
+#include "whisper_pick.h"
 
 namespace {
 
@@ -205,9 +206,7 @@ __global__ __launch_bounds__(256) void cross_attn_decode_kernel(const float* __r
   }
 }
 
-// ---- greedy pick -----------------------------------------------------------------------------------------------------------------
-constexpr int GP_MAX_V = 262144;   // one bit per class in LDS
-
+// ---- greedy pick (the body is whisper_pick.h's) -----------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void greedy_pick_kernel(const float* __restrict__ logits, long long ld,
                                                           const int* __restrict__ suppress, int n_sup,
                                                           const int* __restrict__ begin_suppress, int n_beg, int* tokens,
@@ -223,26 +222,10 @@ __global__ __launch_bounds__(256) void greedy_pick_kernel(const float* __restric
   const int words = (V + 31) / 32;
   for (int i = tid; i < words; i += 256) bits[i] = 0u;
   __syncthreads();
-  for (int i = tid; i < n_sup + n_beg; i += 256) {
-    const int v = i < n_sup ? suppress[i] : begin_suppress[i - n_sup];
-    if (v >= 0 && v < V) atomicOr(&bits[v >> 5], 1u << (v & 31));
-  }
+  pick_mark_bits(bits, suppress, n_sup, begin_suppress, n_beg, V);
   __syncthreads();
-  const float* row = logits + (size_t)r * ld;
-  float m = -__builtin_inff();
-  int arg = WAVE_NONE;
-  for (int v = tid; v < V; v += 256) {            // ascending per thread: '>' keeps the first maximum; -inf takes the lowest index
-    float x = row[v];
-    if ((bits[v >> 5] >> (v & 31)) & 1u) x = -__builtin_inff();
-    if (x > m || (arg == WAVE_NONE && !(x != x))) m = x, arg = v;
-  }
-  wave_argmax(m, arg);
-  if ((tid & 63) == 0) rm[tid >> 6] = m, ra[tid >> 6] = arg;
-  __syncthreads();
+  const int arg = greedy_pick_row(logits + (size_t)r * ld, bits, rm, ra, V);
   if (tid == 0) {
-    for (int v = 1; v < 4; ++v)
-      if (rm[v] > m || (rm[v] == m && ra[v] < arg)) m = rm[v], arg = ra[v];
-    if (arg == WAVE_NONE) arg = 0;                // a row of NaN only
     tokens[(size_t)r * ld_tok + p + 1] = arg;
     last[r] = arg;
     if (arg == eos) done[r] = 1;
@@ -260,86 +243,7 @@ __global__ __launch_bounds__(256) void alive_count_kernel(const int* __restrict_
   if (threadIdx.x == 0) *alive = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// ---- timestamp rules (transformers' WhisperTimeStampLogitsProcessor, after the two suppress processors) ---------------------------
-// Everything the processor bans is an interval: the text classes [0, eos) or [0, ts_begin), and the timestamps outside [lo, hi].
-// One workgroup per row reads the logits once; a lane keeps, for the allowed timestamps and for the allowed text classes
-// apart, a running maximum with its first index and the sum of exp(x - maximum).  The groups are folded across the wave by
-// shuffles and across the waves through LDS in wave order, so the result does not depend on timing.  log-sum-exp(timestamps) >
-// max(text) bans all text: the log-softmax normaliser of the processor is common to both sides and drops out.
-struct TsRule {
-  int kind, lo, hi;   // text ban: 0 none, 1 [0, eos), 2 [0, ts_begin); allowed timestamps [lo, hi] (lo > hi: none)
-};
-
-struct TsGroup {
-  float m, s;         // maximum (-inf: no class), sum of exp(x - m)
-  int a;              // lowest index of the maximum
-};
-
-// Four classes of a lane at once, v0 + 256 k (ascending): x[k] counts iff in[k].  One rescale of the sum per call, then four
-// independent exponentials: the dependent chain of a lane is a quarter of the one-class-at-a-time form.
-__device__ __forceinline__ void ts_group_add4(TsGroup& g, const float (&x)[4], const bool (&in)[4], int v0) {
-  const float NEG = -__builtin_inff();
-  float m4 = NEG;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) m4 = in[k] ? fmaxf(m4, x[k]) : m4;
-  if (!(m4 > NEG)) return;
-  if (m4 > g.m) {                                 // '>' keeps the first maximum; the first class: 0 * exp(-inf) = 0
-    g.s *= expf(g.m - m4);
-    g.m = m4;
-#pragma unroll
-    for (int k = 3; k >= 0; --k)
-      if (in[k] && x[k] == m4) g.a = v0 + 256 * k;
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) g.s += in[k] ? expf(x[k] - g.m) : 0.f;
-}
-
-__device__ __forceinline__ void ts_group_merge(TsGroup& g, float om, float os, int oa) {
-  const float M = fmaxf(g.m, om);
-  const float fa = g.m == M ? 1.f : expf(g.m - M), fb = om == M ? 1.f : expf(om - M);   // -inf == -inf: no exp(NaN)
-  g.s = g.s * fa + os * fb;
-  if (om > g.m || (om == g.m && oa < g.a)) g.a = oa;
-  g.m = M;
-}
-
-__device__ __forceinline__ void ts_group_wave(TsGroup& g) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float om = __shfl_xor(g.m, o, 64), os = __shfl_xor(g.s, o, 64);
-    const int oa = __shfl_xor(g.a, o, 64);
-    ts_group_merge(g, om, os, oa);
-  }
-}
-
-// The state of a row from its generated tokens hist[0 .. len) (uniform over the workgroup; `slot` is one LDS word).
-__device__ TsRule ts_rule_of(const int* __restrict__ hist, int len, int V, int ts_begin, int max_initial, int* slot) {
-  const int tid = threadIdx.x;
-  if (tid == 0) *slot = -1;
-  __syncthreads();
-  int li = -1;
-  for (int i = tid; i < len; i += 256)
-    if (hist[i] >= ts_begin) li = i;
-  if (li >= 0) atomicMax(slot, li);
-  __syncthreads();
-  li = *slot;
-  TsRule d = {0, ts_begin, V - 1};
-  const bool last_ts = len >= 1 && hist[len - 1] >= ts_begin;
-  const bool pen_ts = len < 2 || hist[len - 2] >= ts_begin;
-  if (last_ts) {
-    if (pen_ts) d.lo = V;                         // a closed pair, or the opening timestamp: text has to follow
-    else d.kind = 1;                              // text, timestamp: only [eos, ts_begin) and timestamps may follow
-  }
-  if (li >= 0) {                                  // timestamps do not decrease; only the one that closes a segment may repeat
-    const int tl = min(hist[li], V - 1);
-    d.lo = max(d.lo, last_ts && !pen_ts ? tl : tl + 1);
-  }
-  if (len == 0) {
-    d.kind = 2;
-    if (max_initial >= 0) d.hi = min(d.hi, ts_begin + min(max_initial, V));
-  }
-  return d;
-}
-
+// ---- timestamp rules: TsRule, TsGroup, ts_rule_of and the ruled pick live in whisper_pick.h ----------------------------------------
 // PICK: the greedy step (tokens, last, done, sum_logp).  Otherwise the rule descriptor of the row goes to desc[r][0..4) for the
 // beam's chunk kernel: kind, lo, hi, 0.  The generated tokens of row r are tokens[r][n0 .. p].
 template <bool PICK>
@@ -359,58 +263,19 @@ __global__ __launch_bounds__(256) void ts_rule_kernel(const float* __restrict__ 
   const int words = (V + 31) / 32, ts_begin = no_ts + 1;
   for (int i = tid; i < words; i += 256) bits[i] = 0u;
   const TsRule d = ts_rule_of(tokens + (size_t)r * ld_tok + n0, p + 1 - n0, V, ts_begin, max_initial, &slot);   // syncs twice
-  for (int i = tid; i < n_sup + n_beg; i += 256) {
-    const int v = i < n_sup ? suppress[i] : begin_suppress[i - n_sup];
-    if (v >= 0 && v < V) atomicOr(&bits[v >> 5], 1u << (v & 31));
-  }
+  pick_mark_bits(bits, suppress, n_sup, begin_suppress, n_beg, V);
   __syncthreads();
-  const float NEG = -__builtin_inff();
-  const float* row = logits + (size_t)r * ld;
-  TsGroup ts = {NEG, 0.f, WAVE_NONE}, tx = {NEG, 0.f, WAVE_NONE};
-  const int text_from = d.kind == 2 ? ts_begin : d.kind == 1 ? eos : 0;
-  for (int v0 = tid; v0 < V; v0 += 1024) {        // ascending per thread: '>' keeps the first maximum
-    float x[4];
-    bool is_ts[4], is_tx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int v = v0 + 256 * k;
-      x[k] = v < V ? row[v] : NEG;
-      const bool ok = v < V && !((bits[(v >> 5) & (GP_MAX_V / 32 - 1)] >> (v & 31)) & 1u) && v != no_ts && x[k] > NEG &&
-                      x[k] < __builtin_inff();    // NaN, +-inf: no class
-      is_ts[k] = ok && v >= ts_begin && v >= d.lo && v <= d.hi;
-      is_tx[k] = ok && v < ts_begin && v >= text_from;
-    }
-    ts_group_add4(ts, x, is_ts, v0);
-    ts_group_add4(tx, x, is_tx, v0);
-  }
-  ts_group_wave(ts);
-  ts_group_wave(tx);
-  if ((tid & 63) == 0) {
-    const int w = tid >> 6;
-    rm[0][w] = ts.m, rs[0][w] = ts.s, ra[0][w] = ts.a;
-    rm[1][w] = tx.m, rs[1][w] = tx.s, ra[1][w] = tx.a;
-  }
-  __syncthreads();
+  const TsPick pk = ts_pick_row(logits + (size_t)r * ld, bits, d, rm, rs, ra, V, eos, no_ts);
   if (tid == 0) {
-    ts = {rm[0][0], rs[0][0], ra[0][0]}, tx = {rm[1][0], rs[1][0], ra[1][0]};
-    for (int w = 1; w < 4; ++w) ts_group_merge(ts, rm[0][w], rs[0][w], ra[0][w]), ts_group_merge(tx, rm[1][w], rs[1][w], ra[1][w]);
-    const float lse_ts = ts.m > NEG ? ts.m + logf(ts.s) : NEG;
-    const bool only_ts = lse_ts > tx.m;           // the sum of the timestamps' probabilities beats every text class
     if (!PICK) {
       int* dr = desc + (size_t)r * 4;
-      dr[0] = only_ts ? 2 : d.kind, dr[1] = d.lo, dr[2] = d.hi, dr[3] = 0;
+      dr[0] = pk.only_ts ? 2 : d.kind, dr[1] = d.lo, dr[2] = d.hi, dr[3] = 0;
       return;
     }
-    if (only_ts) tx = {NEG, 0.f, WAVE_NONE};
-    const bool text_wins = tx.m >= ts.m && tx.a != WAVE_NONE;   // text ids lie below the timestamps: the lower index at a tie
-    int arg = text_wins ? tx.a : ts.a;
-    const float xm = text_wins ? tx.m : ts.m;
-    ts_group_merge(tx, ts.m, ts.s, ts.a);         // all allowed classes: tx.m = xm
-    if (arg == WAVE_NONE) arg = 0;                // nothing is allowed
-    else sum_logp[r] += (xm - tx.m) - logf(tx.s);
-    tokens[(size_t)r * ld_tok + p + 1] = arg;
-    last[r] = arg;
-    if (arg == eos) done[r] = 1;
+    if (pk.has) sum_logp[r] += pk.logp;
+    tokens[(size_t)r * ld_tok + p + 1] = pk.arg;
+    last[r] = pk.arg;
+    if (pk.arg == eos) done[r] = 1;
   }
 }
 

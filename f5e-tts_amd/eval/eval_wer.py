@@ -7,6 +7,8 @@
     python -m f5e_tts_amd.eval.eval_wer --gen_wav_dir D --metalst F --lang en --asr whisper --whisper_dir W [--language english]
                                         [--whisper_beam 5] [--whisper_long [--whisper_fallback [--whisper_seed S]]
                                         [--whisper_prompt TEXT] [--whisper_condition]]
+                                        [--whisper_assistant DIR [--whisper_assistant_tokens N]
+                                         [--whisper_assistant_shares_encoder]]
 
 ``--asr whisper`` is the reference's English recogniser of the voice-conversion and LibriSpeech evaluations
 (``run_asr_wer_whisper_large_v3``, eval/utils_eval.py:631-712: whisper-large-v3, greedy, prompt ``english / transcribe``) on the
@@ -195,6 +197,12 @@ def build_parser() -> argparse.ArgumentParser:
                          "recording; with it, it leads the first window's previous text and then scrolls out of it")
     ap.add_argument("--whisper_condition", action="store_true",
                     help="--whisper_long: condition every window on the text of the windows before it")
+    ap.add_argument("--whisper_assistant", default=None, metavar="DIR",
+                    help="--asr whisper: a local draft model directory (whisper-large-v3-turbo, a distil-whisper checkpoint) for "
+                         "assisted generation: the same transcripts with fewer passes of the large decoder; greedy only")
+    ap.add_argument("--whisper_assistant_tokens", type=int, default=5, help="--whisper_assistant: tokens drafted per round")
+    ap.add_argument("--whisper_assistant_shares_encoder", action="store_true",
+                    help="--whisper_assistant: the draft reads the large model's encoder output instead of running its own")
     ap.add_argument("--whisper_beam", type=int, default=1,
                     help="--asr whisper: 1 = greedy (run_asr_wer_whisper_large_v3); N > 1 = the pooled beam search of "
                          "generate(num_beams=N) (--beam_size is the wenet flag and does not reach Whisper)")
@@ -232,6 +240,9 @@ def main(argv=None, aligner=None) -> float:
         ctx = {}
         if args.whisper_prompt is not None or args.whisper_condition:
             ctx = dict(initial_prompt=args.whisper_prompt, condition_on_previous_text=args.whisper_condition)
+        if args.whisper_assistant is not None:
+            ctx.update(assistant_dir=args.whisper_assistant, num_assistant_tokens=args.whisper_assistant_tokens,
+                       assistant_shares_encoder=args.whisper_assistant_shares_encoder)
         aligner = WhisperRecognizer(args.whisper_dir, args.device, args.language, beam_size=args.whisper_beam,
                                     long_form=args.whisper_long, **({} if fb is None else dict(fallback=fb)), **ctx)
     elif aligner is None:

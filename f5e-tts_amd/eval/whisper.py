@@ -34,7 +34,14 @@ Conditioning and prompts (``transcribe_long(context=Context(...))``, ``get_promp
 (``decoder_prefill``: f5e_whisper_embed, f5e_attn_prefill_f32, f5e_mha_f32 with U queries per row; csrc/whisper_prefill.hip), and
 ragged prefixes of a batch are left-padded (f5e_attn_decode_from_f32 for the steps that follow).
 
-Out of scope: beam-sample, top-k / top-p, the pipeline's strided ``chunk_length_s`` merging, word timestamps across windows,
+Assisted generation (``generate`` / ``transcribe_long`` / ``generate_from_kv(assistant=)``): a draft model (large-v3-turbo's
+4-layer decoder, a distil-whisper decoder on the shared encoder) proposes a few tokens per round with cheap cached steps and
+this model checks them in one pass behind its cache (``decoder_append``: f5e_attn_append_f32, f5e_gemm_f32_skinny for the
+handful of rows; f5e_whisper_verify, f5e_whisper_accept; csrc/whisper_append.hip, csrc/gemm_f32_skinny.hip).  Greedy, with or
+without the timestamp rules; the tokens are those of this model alone.
+
+Out of scope: speculative sampling (an assistant with temperature > 0), beam search with an assistant, ``transformers``'
+heuristic draft schedule and confidence threshold, per-row positions (the rows of a batch advance together), beam-sample, top-k / top-p, the pipeline's strided ``chunk_length_s`` merging, word timestamps across windows,
 the prefill inside ``alignment_probs`` / ``token_timestamps``, patience, CTranslate2's exact search, bf16 / fp16 weights (fp16
 checkpoints are widened), a graph-captured step.
 
@@ -934,6 +941,73 @@ class Whisper(nn.Module):
         return ops.gemm_f32(rows, fd["emb"], None, out=logits).view(R, len(want), V)
 
     @torch.no_grad()
+    def decoder_append(self, st: dict, kv: List[Tuple[Tensor, Tensor]], ids: Tensor, p0: int, begin: Optional[Tensor] = None,
+                       want: Optional[Sequence[int]] = None) -> Optional[Tensor]:
+        """Feeds ``ids`` i32 [R, U] on the device at positions p0 .. p0 + U - 1 BEHIND what the caches of ``st`` hold, in one pass
+        per layer (the verify pass of assisted generation): ``decoder_prefill``'s body at p0, with
+        f5e_attn_append_f32 for the self-attention (cached positions begin[r] .. p0 - 1 from the caches, the new ones from the
+        projection; slots p0 .. p0 + U - 1 are filed) and, while R * U <= 16 rows, f5e_gemm_f32_skinny for the projections, the
+        feed-forward and the vocabulary (f5e_gemm_f32 beyond; ``_append_gemm``).  The cross-attention is f5e_mha_f32 with U queries per row.
+        -> logits f32 [R, len(want), V] of the positions p0 + w for w in ``want`` (None: all U), or None for an empty ``want``.
+        Slots beyond p0 + U - 1 keep what they held: whatever a rejected draft left there is overwritten before it is read."""
+        cfg, fd = self.cfg, self._fold()
+        if not isinstance(ids, Tensor) or ids.ndim != 2 or ids.shape[0] < 1 or ids.shape[1] < 1 or not ids.is_cuda:
+            raise _C.F5EError("Whisper.decoder_append: ids must be [R, U] ids with U >= 1 on the GPU; there is no CPU path")
+        R, U = ids.shape
+        kc0 = st["caches"][0][0]
+        Rs, Umax, D = kc0.shape
+        B, dev, p0 = kv[0][0].shape[0], kc0.device, int(p0)
+        want = list(range(U)) if want is None else [int(w) for w in want]
+        if Rs % R or R % B or p0 < 0 or p0 + U > Umax or any(not 0 <= w < U for w in want):
+            raise _C.F5EError(f"Whisper.decoder_append: {R} rows of {U} tokens at position {p0} do not fit a state of {Rs} rows and "
+                              f"{Umax} positions over {B} utterances (or a wanted position of {want} lies outside the {U} new ones)")
+        if begin is not None and (not isinstance(begin, Tensor) or begin.shape != (R,) or begin.dtype != I32 or not begin.is_cuda):
+            raise _C.F5EError(f"Whisper.decoder_append: begin must be i32 [{R}] on the device")
+        ids = ids.to(I32).contiguous()
+        K, H, M = Rs // R, cfg.decoder_attention_heads, R * U
+        scale, at = (D // H) ** -0.5, SimpleNamespace(i=0)
+        scratch = st.setdefault("append", {})             # the pass's buffers, kept per row count: a round allocates nothing
+        if M not in scratch:
+            z = lambda *n: torch.empty(*n, dtype=F32, device=dev)   # noqa: E731
+            scratch[M] = (z(R, U, D), (z(M, D), z(M, 3 * D), z(M, D), z(M, D), z(M, cfg.decoder_ffn_dim)))
+        x3, bufs = scratch[M]
+        x = ops.whisper_embed(ids, fd["emb"], fd["dec_pos"], x3, p0, begin).view(M, D)
+
+        def gemm(a, w, bias=None, *, out, act=ops.ACT_NONE, addend=None):
+            return self._append_gemm(a.shape[0], w.shape[0], w.shape[1])(a, w, bias, out=out, act=act, addend=addend)
+
+        def self_attn(_W, _xn, qkv, ao):
+            kc, vc = st["caches"][at.i]
+            ops.attn_append_f32(qkv, kc[::K], vc[::K], U, p0, H, scale, begin=begin, out=ao)
+
+        def cross_attn(_W, q, ao):                       # the R / B rows of an utterance are (R / B) * U queries on its keys
+            Kx, Vx = kv[at.i]
+            ops.mha_f32(q, Kx.view(-1, D), Vx.view(-1, D), H, scale, B=B, out=ao)
+
+        for i, W in enumerate(fd["dec"]):
+            at.i = i
+            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn, cross_attn=cross_attn,
+                  gemm=gemm)
+        if not want:
+            return None
+        V, Mw = cfg.vocab_size, R * len(want)
+        rows = x if len(want) == U and want == list(range(U)) else x.view(R, U, D)[:, want].reshape(Mw, D)
+        ops.layernorm(rows, rows, *fd["dec_ln"], eps=1e-5)
+        key = ("logits", Mw)
+        if key not in scratch:
+            scratch[key] = torch.empty(Mw, (V + 3) // 4 * 4, dtype=F32, device=dev)
+        return gemm(rows, fd["emb"], None, out=scratch[key][:, :V]).view(R, len(want), V)
+
+    @staticmethod
+    def _append_gemm(M: int, N: int, K: int):
+        """The GEMM a verify pass of M rows runs against an [N, K] weight: f5e_gemm_f32_skinny up to 16 rows, f5e_gemm_f32
+        beyond.  Launched back to back on one cache-resident weight the two are level at the decoder's K = 1280 shapes (one
+        launch latency each; the skinny one wins 3.4x at K = 5120 and 1.3x .. 1.9x on the vocabulary), but inside a pass, where
+        every weight comes from HBM, sending those shapes to f5e_gemm_f32 made the pass slower, 21.5 ms against 19.7 ms (and
+        23.2 ms with f5e_gemm_f32 everywhere), so no shape is routed away."""
+        return ops.gemm_f32_skinny if M <= ops.SKINNY_MAX_M else ops.gemm_f32
+
+    @torch.no_grad()
     def decoder_logits(self, kv: List[Tuple[Tensor, Tensor]], ids: Tensor, one_pass: bool = False) -> Tensor:
         """Teacher forcing through the cached step: ids i32 [B, U] on the device -> logits f32 [B, U, V] (position u predicts
         token u + 1).  ``one_pass``: through ``decoder_prefill`` instead (the same numbers up to fp32 summation order)."""
@@ -1081,7 +1155,8 @@ class Whisper(nn.Module):
                          sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0, return_beams: bool = False,
                          return_token_timestamps: bool = False, frames=None, return_timestamps: bool = False,
                          stats: Optional[dict] = None, temperature: float = 0.0, seed: int = 0, row_key: Optional[Tensor] = None,
-                         serial: Optional[Tensor] = None, begin: Optional[Tensor] = None, prefill: bool = False):
+                         serial: Optional[Tensor] = None, begin: Optional[Tensor] = None, prefill: bool = False,
+                         assistant: Optional[tuple] = None, num_assistant_tokens: int = 5):
         """``generate`` from the cross keys / values.  ``prompt``: ids for all rows, or [B, n0] ids.  ``return_token_timestamps``:
         one more item at the end, the times f32 [B, U] of the returned best hypothesis = ``token_timestamps`` on the returned
         tokens (a teacher-forced pass after the search, greedy or beam); ``frames``: mel frames per utterance (None: the whole
@@ -1100,10 +1175,18 @@ class Whisper(nn.Module):
         <|startoftranscript|> (the last one of row 0; left-padding puts it in the same column for every row).  The bound
         ``max_target_positions`` counts the padded columns, so a padded row has begin[b] fewer picks than alone: with ``begin``,
         ``stats`` also receives ``at_bound`` i32 [B], non-zero for a row that was still open when the last step of the bound ran
-        (only such a row can differ from its own unpadded run; ``transcribe_long`` decodes it again alone).  The defaults take
-        the launches they always took."""
+        (only such a row can differ from its own unpadded run; ``transcribe_long`` decodes it again alone).
+        ``assistant`` = (draft, draft_kv): assisted generation (speculative decoding, ``_assisted_from_kv``): ``draft``, a
+        smaller ``Whisper`` with the same vocabulary, proposes up to ``num_assistant_tokens`` tokens per round from its own
+        cross keys / values ``draft_kv``, and this model checks them in one pass (``decoder_append``, f5e_whisper_verify,
+        f5e_whisper_accept).  Greedy only; the tokens are those of the run without an assistant, and ``stats`` also receives
+        ``assistant`` = {"rounds", "drafted", "accepted"}.  The defaults take the launches they always took."""
         n0 = _prompt_len(prompt)
         sample = self._check_sampling(temperature, seed, beam_size, return_beams)
+        if assistant is not None:
+            if not isinstance(assistant, (tuple, list)) or len(assistant) != 2:
+                raise _C.F5EError("Whisper.generate: assistant must be (draft, draft_kv): a Whisper and its cross keys / values")
+            self._check_assistant(assistant[0], num_assistant_tokens, beam_size, return_beams, temperature)
         sot_pos = 0
         if begin is not None or prefill:
             if return_token_timestamps:
@@ -1118,7 +1201,8 @@ class Whisper(nn.Module):
                 raise _C.F5EError("Whisper.generate: return_token_timestamps needs alignment_heads in generation_config.json")
             res = self.generate_from_kv(kv, prompt, max_new_tokens, sync_every, beam_size, length_penalty, return_beams,
                                         return_timestamps=return_timestamps, stats=stats, temperature=temperature, seed=seed,
-                                        row_key=row_key, serial=serial)
+                                        row_key=row_key, serial=serial, assistant=assistant,
+                                        num_assistant_tokens=num_assistant_tokens)
             times = self.token_timestamps(kv, res[0], res[1], self.n_frames if frames is None else frames, n0)
             return tuple(res) + (times,)
         if int(beam_size) != 1 or return_beams:
@@ -1126,6 +1210,9 @@ class Whisper(nn.Module):
                 return self._beam_from_kv(kv, prompt, max_new_tokens, sync_every, int(beam_size), float(length_penalty), return_beams)
             return self._beam_from_kv(kv, prompt, max_new_tokens, sync_every, int(beam_size), float(length_penalty), return_beams,
                                       bool(return_timestamps), stats)
+        if assistant is not None:
+            return self._assisted_from_kv(kv, prompt, max_new_tokens, bool(return_timestamps), stats, begin, bool(prefill), sot_pos,
+                                          assistant[0], assistant[1], int(num_assistant_tokens))
         cfg, fd = self.cfg, self._fold()
         B = kv[0][0].shape[0]
         dev = kv[0][0].device
@@ -1184,6 +1271,149 @@ class Whisper(nn.Module):
             stats["sum_logp"] = sum_logp
             if begin is not None:
                 stats["at_bound"] = torch.zeros(B, dtype=I32, device=dev) if at_bound is None else at_bound
+        return tokens, (first + n0).to(I32)
+
+    def _check_assistant(self, draft, num_assistant_tokens, beam_size, return_beams, temperature) -> None:
+        """Refusals of assisted generation by name, before any launch."""
+        if not isinstance(draft, Whisper):
+            raise _C.F5EError(f"Whisper.generate: assistant = {type(draft).__name__} must be a Whisper model")
+        if int(beam_size) != 1 or return_beams:
+            raise _C.F5EError(f"Whisper.generate: assistant with beam_size = {beam_size} / return_beams is out of scope (assisted "
+                              "generation is greedy: the draft proposes one continuation per row)")
+        if temperature != 0:
+            raise _C.F5EError(f"Whisper.generate: assistant with temperature = {temperature!r} is out of scope (speculative "
+                              "sampling is not built; sampled attempts take the path without an assistant)")
+        if isinstance(num_assistant_tokens, bool) or not isinstance(num_assistant_tokens, int) or num_assistant_tokens < 1:
+            raise _C.F5EError(f"Whisper.generate: num_assistant_tokens = {num_assistant_tokens!r} must be an integer >= 1")
+        for name in ("vocab_size", "eos_token_id", "max_target_positions", "suppress_tokens", "begin_suppress_tokens"):
+            mine, theirs = getattr(self.cfg, name), getattr(draft.cfg, name)
+            if (tuple(mine) != tuple(theirs)) if isinstance(mine, (tuple, list)) else (mine != theirs):
+                raise _C.F5EError(f"Whisper.generate: the assistant's {name} differs from this model's ({theirs!r} vs {mine!r}); "
+                                  "a draft must share the vocabulary, eos, positions and suppress lists")
+
+    def _check_shared_encoder(self, draft: "Whisper", shares: bool, who: str) -> None:
+        """A draft that reads this model's encoder output needs this model's width and encoder shape; one that encodes the
+        window's features itself (``transcribe_long``) needs this model's mel bins and window."""
+        names = ("d_model", "max_source_positions", "encoder_layers", "encoder_attention_heads", "encoder_ffn_dim",
+                 "num_mel_bins") if shares else (("num_mel_bins", "max_source_positions") if who == "transcribe_long" else ())
+        for name in names:
+            if getattr(self.cfg, name) != getattr(draft.cfg, name):
+                raise _C.F5EError(f"Whisper.{who}: the assistant's {name} = {getattr(draft.cfg, name)} differs from this model's "
+                                  f"{getattr(self.cfg, name)}" + ("; assistant_shares_encoder needs one encoder shape" if shares else
+                                                                 "; the windows' features are computed once, with this model's front-end"))
+
+    @torch.no_grad()
+    def _assisted_from_kv(self, kv, prompt, max_new_tokens, ts: bool, stats: Optional[dict], begin: Optional[Tensor], prefill: bool,
+                          sot_pos: int, draft: "Whisper", dkv, N: int):
+        """Greedy decoding with a draft model (``transformers``' assisted generation with a constant schedule and a confidence
+        threshold of 0).  A round at position p, with U = min(N, Umax - 2 - p) (0: an ordinary step of this model):
+          1. the draft catches up: the final tokens from the first position its cache does not hold to p - 1, one cached step
+             each (one or two per round);
+          2. the draft makes U ordinary steps from p on its own table ``hist`` (a copy of ``tokens`` up to p) with this model's
+             pick kernel and rules, on its own last / done / alive scratch;
+          3. this model feeds hist[:, p .. p + U] at p0 = p through ``decoder_append`` and takes the logits of all U + 1 positions;
+          4. f5e_whisper_verify picks at all of them; f5e_whisper_accept keeps, per row, the picks up to the first one that
+             differs from its draft, advances ALL rows by the smallest such count a (so the position stays one scalar: a row that
+             keeps fewer tokens than it could is still its own greedy run), and writes tokens, last, done, sum_logp and alive
+             as a single steps would have;
+          5. the host reads a and the alive count (one synchronisation per round).  Cache slots of rejected drafts, this model's
+             and the draft's, are overwritten before they are read.
+        Both models prefill the same left-padded prompt.  The outputs are those of the path without an assistant; ``stats`` on a
+        model without timestamp classes (no <|nospeech|>) carries no ``no_speech_logp`` instead of refusing, since it is also how
+        the assistant's figures are returned."""
+        cfg, fd = self.cfg, self._fold()
+        n0 = _prompt_len(prompt)
+        B, dev = kv[0][0].shape[0], kv[0][0].device
+        if len(dkv) != draft.cfg.decoder_layers or dkv[0][0].shape[0] != B or dkv[0][0].shape[-1] != draft.cfg.d_model:
+            raise _C.F5EError(f"Whisper.generate: the assistant's cross keys / values must be those of its {draft.cfg.decoder_layers} "
+                              f"decoder layers for the same {B} utterances")
+        draft._fold()
+        want_ns = stats is not None and cfg.no_timestamps_token_id is not None and \
+            cfg.eos_token_id <= cfg.no_timestamps_token_id < cfg.vocab_size - 1
+        no_ts = cfg.timestamp_begin - 1 if ts else None
+        max_initial = cfg.max_initial_timestamp_index if ts else None
+        Umax = cfg.max_target_positions if max_new_tokens is None else min(cfg.max_target_positions, n0 + int(max_new_tokens))
+        if n0 < 1 or n0 >= Umax:
+            raise _C.F5EError(f"Whisper.generate: a prompt of {n0} tokens leaves no room below {Umax} positions")
+        eos, V = cfg.eos_token_id, cfg.vocab_size
+        tokens = torch.full((B, Umax), eos, dtype=I32, device=dev)
+        tokens[:, :n0] = self._prompt_rows(prompt, B, dev)
+        hist = tokens.clone()                                # the draft's table
+        zi = lambda *s: torch.zeros(*s, dtype=I32, device=dev)   # noqa: E731
+        last, done, sync = tokens[:, 0].clone(), zi(B), zi(2)
+        alive, adv = sync[0:1], sync[1:2]                    # read together, once per round
+        alive.fill_(B)
+        sum_logp = torch.zeros(B, dtype=F32, device=dev) if ts else None
+        dlast, ddone, dalive = last.clone(), zi(B), zi(1)
+        dsum = torch.zeros(B, dtype=F32, device=dev) if ts else None
+        out = {u: (torch.empty(B, u + 1, dtype=I32, device=dev), torch.empty(B, u + 1, dtype=F32, device=dev))
+               for u in range(1, N + 1)}                     # cand, logp per draft length (only the last rounds are shorter)
+        st, dst = self._dec_state(B, Umax, dev), draft._dec_state(B, Umax, dev)
+
+        def pick(logits, table, last_, done_, alive_, sum_, p):
+            if ts:
+                ops.whisper_ts_pick(logits, table, last_, done_, alive_, sum_, p, n0, eos, no_ts, suppress=fd["suppress"],
+                                    begin_suppress=fd["begin_suppress"], max_initial=max_initial)
+            else:
+                ops.greedy_pick(logits, table, last_, done_, alive_, p, eos, suppress=fd["suppress"],
+                                begin_suppress=fd["begin_suppress"], first_step=p + 1 == n0)
+
+        p = 0
+        if prefill and n0 > 1:
+            p = n0 - 1
+            ids = tokens[:, :p].contiguous()
+            logits = self.decoder_prefill(st, kv, ids, begin, (sot_pos,) if want_ns and sot_pos < p else ())
+            if logits is not None:
+                stats["no_speech_logp"] = self._no_speech_logp(logits[:, 0])
+            draft.decoder_prefill(dst, dkv, ids, begin)
+            last.copy_(tokens[:, p])
+        dnext = p                                            # the first position the draft's cache does not hold
+        while p + 1 < n0:                                    # the forced tokens: the cached step, nothing is picked
+            logits = self._dec_step(st, kv, last, p, p == sot_pos and want_ns, begin=begin)
+            if p == sot_pos and want_ns:
+                stats["no_speech_logp"] = self._no_speech_logp(logits)
+            p += 1
+            last.copy_(tokens[:, p])
+        rounds = drafted = accepted = 0
+        while p < Umax - 1:
+            U = min(N, Umax - 2 - p)
+            rounds += 1
+            if U == 0:                                       # the last position below the bound: nothing to draft
+                logits = self._dec_step(st, kv, last, p, True, begin=begin)
+                if p == sot_pos and want_ns:
+                    stats["no_speech_logp"] = self._no_speech_logp(logits)
+                pick(logits, tokens, last, done, alive, sum_logp, p)
+                p += 1
+                break
+            for q in range(dnext, p):
+                draft._dec_step(dst, dkv, tokens[:, q].contiguous(), q, False, begin=begin)
+            dlast.copy_(last)
+            ddone.copy_(done)
+            for k in range(U):
+                pick(draft._dec_step(dst, dkv, dlast, p + k, True, begin=begin), hist, dlast, ddone, dalive, dsum, p + k)
+            logits = self.decoder_append(st, kv, hist[:, p:p + U + 1], p, begin)
+            if p == sot_pos and want_ns:
+                stats["no_speech_logp"] = self._no_speech_logp(logits[:, 0])
+            cand, logp = out[U]
+            ops.whisper_verify(logits.view(B * (U + 1), V), hist, cand, logp, p, n0, eos, no_ts, suppress=fd["suppress"],
+                               begin_suppress=fd["begin_suppress"], max_initial=max_initial)
+            ops.whisper_accept(cand, logp, hist, tokens, last, done, alive, sum_logp, adv, p, eos)
+            n_alive, a = sync.tolist()
+            dnext = min(p + U, p + a)
+            drafted += U
+            accepted += min(a - 1, U)
+            p += a
+            if n_alive == 0:
+                break
+        gen = tokens[:, n0:]
+        is_eos = gen == eos
+        first = torch.where(is_eos.any(1), is_eos.to(torch.int64).argmax(1) + 1, torch.full((B,), Umax - n0, dtype=torch.int64, device=dev))
+        if stats is not None:
+            stats["sum_logp"] = sum_logp
+            stats["assistant"] = dict(rounds=rounds, drafted=drafted, accepted=accepted)
+            if begin is not None:                            # rows still open when the last step of the shared bound ran
+                open_ = ~(tokens[:, n0:Umax - 1] == eos).any(1) if p == Umax - 1 else torch.zeros(B, dtype=torch.bool, device=dev)
+                stats["at_bound"] = open_.to(I32)
         return tokens, (first + n0).to(I32)
 
     @staticmethod
@@ -1317,7 +1547,8 @@ class Whisper(nn.Module):
     def generate(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe",
                  max_new_tokens: Optional[int] = None, sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0,
                  return_beams: bool = False, return_token_timestamps: bool = False, return_timestamps: bool = False,
-                 temperature: float = 0.0, seed: int = 0):
+                 temperature: float = 0.0, seed: int = 0, assistant: Optional["Whisper"] = None, num_assistant_tokens: int = 5,
+                 assistant_shares_encoder: bool = False, stats: Optional[dict] = None):
         """Recognition of B utterances: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> (tokens i32 [B, U] starting
         with the prompt, eos from a row's end on; n i32 [B] = tokens of every row, its closing eos included when it ended by
         itself).  The host reads the alive count every ``sync_every`` steps; the result does not depend on it.  The bound is
@@ -1330,7 +1561,26 @@ class Whisper(nn.Module):
         per row (``detect_language``); "" is refused as before.  ``return_timestamps``: the prompt has no <|notimestamps|> and
         the picks follow the timestamp rules, so the tokens carry <|t|> ids (``cfg.timestamp_begin`` + t / 0.02).
         ``temperature`` > 0: the picks are draws from softmax(logits / temperature) over the allowed classes, a function of
-        ``seed``, the row's index and the position (``generate_from_kv``); with ``beam_size`` > 1 that is refused."""
+        ``seed``, the row's index and the position (``generate_from_kv``); with ``beam_size`` > 1 that is refused.
+        ``assistant``: a draft ``Whisper`` for assisted generation (``generate_from_kv(assistant=)``; greedy only, the same
+        tokens as without it).  ``assistant_shares_encoder`` False: the draft encodes the same audio itself; True: its cross keys
+        and values are projected from THIS model's encoder output (large-v3-turbo and distil-whisper drafts; equal ``d_model``
+        and encoder shape, checked).  ``stats`` (with an assistant): receives what ``generate_from_kv`` puts there."""
+        if assistant is not None:
+            self._check_sampling(temperature, seed, beam_size, return_beams)
+            self._check_assistant(assistant, num_assistant_tokens, beam_size, return_beams, temperature)
+            self._check_shared_encoder(assistant, assistant_shares_encoder, "generate")
+            if return_timestamps:
+                self.cfg.timestamp_begin                                    # refused by name before any launch
+            elif language is not None:
+                self.prompt_ids(language, task)
+            enc = self.encode_features(self.features(wav, lens))
+            kv = self.cross_kv(enc)
+            dkv = assistant.cross_kv(enc) if assistant_shares_encoder else assistant.encode(wav, lens)
+            return self.generate_from_kv(kv, self._prompts(kv, language, task, return_timestamps), max_new_tokens, sync_every, 1,
+                                         length_penalty, False, return_token_timestamps,
+                                         self._frames_of(wav, lens) if return_token_timestamps else None, return_timestamps,
+                                         stats=stats, assistant=(assistant, dkv), num_assistant_tokens=num_assistant_tokens)
         if self._check_sampling(temperature, seed, beam_size, return_beams):
             if return_timestamps:
                 self.cfg.timestamp_begin                                    # refused by name before any launch
@@ -1358,7 +1608,9 @@ class Whisper(nn.Module):
     def transcribe_long(self, wav: Tensor, lens=None, language: Optional[str] = None, task: str = "transcribe", beam_size: int = 1,
                         no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = None,
                         sync_every: int = 8, fallback: Optional[Fallback] = None, row_keys: Optional[Sequence[int]] = None,
-                        trace: Optional[list] = None, context: Optional[Context] = None, **unbuilt) -> List[List[Segment]]:
+                        trace: Optional[list] = None, context: Optional[Context] = None, assistant: Optional["Whisper"] = None,
+                        num_assistant_tokens: int = 5, assistant_shares_encoder: bool = False,
+                        **unbuilt) -> List[List[Segment]]:
         """Recordings of any length: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> the segments of every row.
         The seek loop of ``transformers``' long-form ``generate`` (``return_timestamps=True``, ``condition_on_prev_tokens=False``,
         temperature 0): every window of ``n_frames`` mel frames is decoded with timestamp tokens, cut into segments at the
@@ -1400,7 +1652,14 @@ class Whisper(nn.Module):
         0's history whether ANY row of a batch is conditioned, a row is conditioned iff it has previous segments of its own:
         a row equals its own B = 1 run.  Two things keep that true under padding (``_decode_with_context``): a padded row that
         runs into the batch's token bound, which counts its pad columns, is decoded again alone with its own bound, and a
-        sampled attempt batches a row only with rows of its own prompt length, since the noise is keyed by the position."""
+        sampled attempt batches a row only with rows of its own prompt length, since the noise is keyed by the position.
+        ``assistant`` (a draft ``Whisper``; ``generate``): every temperature-0 attempt is assisted generation under the timestamp
+        rules; sampled attempts of a ``fallback`` take the path without it.  The draft reads the window's features (computed
+        once, with this model's front-end) through its own encoder, or with ``assistant_shares_encoder`` this model's encoder
+        output.  Segments, seeks and tokens are those of the run without an assistant."""
+        if assistant is not None:
+            self._check_assistant(assistant, num_assistant_tokens, beam_size, False, 0.0)
+            self._check_shared_encoder(assistant, assistant_shares_encoder, "transcribe_long")
         for name, value in unbuilt.items():
             off = {"temperature": (None, 0, 0.0, (0.0,), [0.0]), "condition_on_prev_tokens": (None, False), "prompt_ids": (None,),
                    "chunk_length_s": (None,), "stride_length_s": (None,), "return_token_timestamps": (None, False),
@@ -1462,7 +1721,13 @@ class Whisper(nn.Module):
             win = torch.zeros(len(act), W, M, dtype=F32, device=dev)
             for i, b in enumerate(act):
                 win[i, :nf[i]] = feats[b][seek[b]:seek[b] + nf[i]]
-            kv = self.cross_kv(self.encode_features(win))
+            if assistant is None:
+                kv, asst = self.cross_kv(self.encode_features(win)), None
+            else:
+                enc = self.encode_features(win)
+                kv = self.cross_kv(enc)
+                asst = (assistant, assistant.cross_kv(enc if assistant_shares_encoder else assistant.encode_features(win)),
+                        num_assistant_tokens)
             if prompts is None:                                        # the first iteration: every row is in it, at seek 0
                 prompts = self._prompts(kv, None, task, True)
             prompt = prompts[torch.tensor(act, device=dev)] if isinstance(prompts, Tensor) else prompts
@@ -1479,16 +1744,20 @@ class Whisper(nn.Module):
                     rows = [act[i] for i in pend]
                     fulls, sum_logp, ns_logp = self._decode_with_context(
                         kv, plist, pend, temp, beam_size, sync_every, 0 if fallback is None else fallback.seed,
-                        [keys[b] for b in rows], [serial[b] for b in rows])
+                        [keys[b] for b in rows], [serial[b] for b in rows], *(() if asst is None else (asst,)))
                     if temp > 0:
                         for b in rows:
                             serial[b] += 1
                 else:
-                    sub, sub_prompt = kv, prompt
+                    sub, sub_prompt, akw = kv, prompt, {}
+                    if asst is not None and temp == 0:
+                        akw = dict(assistant=asst[:2], num_assistant_tokens=asst[2])
                     if len(pend) < len(act):                           # only the rows that fall back: gathered, not re-encoded
                         idx = torch.tensor(pend, device=dev)
                         sub = [(k[idx], v[idx]) for k, v in kv]
                         sub_prompt = prompt[idx] if isinstance(prompt, Tensor) else prompt
+                        if akw:
+                            akw["assistant"] = (asst[0], [(k[idx], v[idx]) for k, v in asst[1]])
                     stats = {}
                     if temp > 0:
                         rows = [act[i] for i in pend]
@@ -1500,7 +1769,7 @@ class Whisper(nn.Module):
                             serial[b] += 1
                     else:
                         tokens, n = self.generate_from_kv(sub, sub_prompt, None, sync_every, beam_size, 1.0, return_timestamps=True,
-                                                          stats=stats)[:2]
+                                                          stats=stats, **akw)[:2]
                     tokens, n = tokens.tolist(), n.tolist()
                     fulls = [tokens[j][n0:n[j]] for j in range(len(pend))]
                     sum_logp, ns_logp = stats["sum_logp"].tolist(), stats["no_speech_logp"].tolist()
@@ -1539,25 +1808,28 @@ class Whisper(nn.Module):
                     history[b].extend(tok for _, _, tok in parts)
                 seek[b] += step
 
-    def _decode_with_context(self, kv, plist, ix, temp, beam_size, sync_every, seed, keys, serial):
+    def _decode_with_context(self, kv, plist, ix, temp, beam_size, sync_every, seed, keys, serial, asst=None):
         """One attempt of the windows ``ix`` (indices into ``kv`` and ``plist``, the rows' decoder inputs) at ``temp`` ->
         (generated tokens with the closing eos, sum_logp, no_speech_logp) per row of ``ix``, each what the row's own B = 1 run
         gives.  Temperature 0: the rows are left-padded to their longest prompt and decoded together; the bound counts the pad
         columns, so a padded row that was still open when the last step of that shared bound ran (``at_bound``) is decoded again
         alone, with its own bound.  A sampled attempt keys its noise by the position, which padding would shift, so rows are
         batched only with rows of their own prompt length (a batch that falls back with ragged prompts costs one decode per
-        length, not one per row)."""
+        length, not one per row).  ``asst`` = (draft, draft_kv, num_assistant_tokens): the temperature-0 decodes are assisted."""
         eos, dev, res = self.cfg.eos_token_id, kv[0][0].device, {}
 
         def run(group):
             rows = [plist[i] for i in group]
             width = max(len(r) for r in rows)
             begin = [width - len(r) for r in rows]
-            sub = kv
+            sub, dsub = kv, None if asst is None else asst[1]
             if group != list(range(kv[0][0].shape[0])):                  # gathered, not encoded again
                 idx = torch.tensor(group, device=dev)
                 sub = [(k[idx], v[idx]) for k, v in kv]
+                dsub = None if asst is None else [(k[idx], v[idx]) for k, v in asst[1]]
             kw, st = {}, {}
+            if asst is not None and temp == 0:
+                kw = dict(assistant=(asst[0], dsub), num_assistant_tokens=asst[2])
             if temp > 0:
                 at = [ix.index(i) for i in group]
                 kw = dict(temperature=temp, seed=seed, row_key=torch.tensor([keys[j] for j in at], dtype=I32).to(dev),
@@ -1604,14 +1876,18 @@ class WhisperRecognizer:
 
     def __init__(self, path: str, device="cuda", language: Optional[str] = "en", beam_size: int = 1, long_form: bool = False,
                  fallback: Optional[Fallback] = None, initial_prompt: Optional[str] = None,
-                 condition_on_previous_text: bool = False):
+                 condition_on_previous_text: bool = False, assistant_dir: Optional[str] = None, num_assistant_tokens: int = 5,
+                 assistant_shares_encoder: bool = False):
         """``language``: a name or code, or None / "auto" to detect it per recording.  ``long_form``: ``transcribe`` runs the
         seek loop over the whole recording (``Whisper.transcribe_long``) instead of cutting it to the first chunk.  ``fallback``:
         the temperature fallback of that loop (needs ``long_form``).  ``initial_prompt``: text (a name, a domain word; ``Whisper.get_prompt_ids``, so
         the checkpoint needs merges.txt) given as a "first-segment" prompt: without conditioning it is put in front of EVERY
         window; with it, it leads the first window's previous text and then scrolls out of the cut (``Context``).
         ``condition_on_previous_text``: every window is conditioned on the text of the windows before it.  Both need
-        ``long_form``."""
+        ``long_form``.  ``assistant_dir``: a local directory of a draft model (large-v3-turbo, a distil-whisper checkpoint) for
+        assisted generation with ``num_assistant_tokens`` drafts per round: the same transcripts, fewer passes of the large
+        decoder; greedy only (``beam_size`` 1).  ``assistant_shares_encoder``: the draft has no encoder of its own to run and
+        reads this model's encoder output."""
         if fallback is not None and not (long_form and isinstance(fallback, Fallback)):
             raise _C.F5EError("WhisperRecognizer: fallback needs long_form=True and a Fallback record")
         if (initial_prompt is not None or condition_on_previous_text) and not long_form:
@@ -1635,6 +1911,14 @@ class WhisperRecognizer:
             ids = None if initial_prompt is None else tuple(self.model.get_prompt_ids(initial_prompt))
             self.context = Context(condition_on_prev_tokens=bool(condition_on_previous_text), prompt_ids=ids)
             self.model._check_context(self.context)          # a prompt that leaves no room fails here, not per file
+        self.assistant, self._assist = None, {}
+        if assistant_dir is not None:
+            self.assistant = Whisper.from_pretrained_dir(assistant_dir).to(self.device)
+            self.model._check_assistant(self.assistant, num_assistant_tokens, self.beam_size, False, 0.0)     # fails here, not per file
+            self.model._check_shared_encoder(self.assistant, bool(assistant_shares_encoder),
+                                             "transcribe_long" if self.long_form else "generate")
+            self._assist = dict(assistant=self.assistant, num_assistant_tokens=int(num_assistant_tokens),
+                                assistant_shares_encoder=bool(assistant_shares_encoder))
         self._warned = set()
 
     def _lang(self) -> Optional[str]:
@@ -1669,7 +1953,8 @@ class WhisperRecognizer:
     def transcribe(self, audio, sr: Optional[int] = None, mode=None, **ignored) -> str:
         if getattr(self, "long_form", False):
             return "".join(text for _, _, text in self.transcribe_segments(audio, sr)).strip()
-        tokens, n = self.model.generate(self._audio(audio, sr), None, self._lang(), beam_size=self.beam_size)
+        tokens, n = self.model.generate(self._audio(audio, sr), None, self._lang(), beam_size=self.beam_size,
+                                        **getattr(self, "_assist", {}))
         return self.model.decode_ids(tokens[0, :int(n[0])].tolist()).strip()
 
     @torch.no_grad()
@@ -1678,6 +1963,7 @@ class WhisperRecognizer:
         kw = {} if getattr(self, "fallback", None) is None else dict(fallback=self.fallback)
         if getattr(self, "context", None) is not None:
             kw["context"] = self.context
+        kw.update(getattr(self, "_assist", {}))
         segs = self.model.transcribe_long(self._audio(audio, sr, cut=False), None, self._lang(), beam_size=self.beam_size, **kw)[0]
         return [(s.start_s, s.end_s, self.model.decode_ids(s.tokens)) for s in segs]
 

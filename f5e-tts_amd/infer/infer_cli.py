@@ -73,6 +73,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ref_language", type=str, default="english", help="--whisper_dir: the language spoken in the reference audio; auto: detected "
                    "from the audio")
     p.add_argument("--whisper_beam", type=int, default=1, help="--whisper_dir: 1 = greedy; N > 1 = beam search with N beams")
+    p.add_argument("--whisper_assistant", type=str, default=None, metavar="DIR",
+                   help="--whisper_dir: a local draft model directory (whisper-large-v3-turbo, distil-whisper) for assisted "
+                        "generation: the same transcript with fewer passes of the large decoder; greedy only")
     p.add_argument("--whisper_prompt", type=str, default=None, metavar="TEXT",
                    help="--whisper_dir: an initial prompt for the transcription (a name, a domain word), in front of every window; the "
                         "reference audio is then transcribed with the long-form loop")
@@ -227,6 +230,8 @@ def main(argv=None):
     if args.whisper_dir and any(not v["ref_text"].strip() for v in voices.values()):
         from ..eval.whisper import WhisperRecognizer
         prompt = {} if args.whisper_prompt is None else dict(long_form=True, initial_prompt=args.whisper_prompt)
+        if args.whisper_assistant is not None:
+            prompt["assistant_dir"] = args.whisper_assistant
         transcriber = WhisperRecognizer(args.whisper_dir, s["device"], args.ref_language, beam_size=args.whisper_beam, **prompt)
     for v in voices.values():   # reference infer_cli.py:297-303
         v["ref_audio"], v["ref_text"] = U.preprocess_ref_audio_text(v["ref_audio"], v["ref_text"], transcriber=transcriber)

@@ -1076,6 +1076,105 @@ def attn_prefill_f32(qkv: Tensor, kc: Tensor, vc: Tensor, U: int, heads: int, sc
     return out
 
 
+def attn_append_f32(qkv: Tensor, kc: Tensor, vc: Tensor, U: int, p0: int, heads: int, scale: float,
+                    begin: Optional[Tensor] = None, out: Optional[Tensor] = None):
+    """Causal self-attention of U new positions behind a cache (f5e_attn_append_f32): qkv f32 [R * U, >= 3 D] (q | k | v of
+    positions p0 .. p0 + U - 1 of every row), kc / vc f32 [R, Umax, D] views of the layer's caches (the strides
+    ``attn_prefill_f32`` takes), begin i32 [R] on the device or None -> out f32 [R * U, D].  Query u of row r sees the cached
+    positions begin[r] .. p0 - 1 and the new ones 0 .. u (a query below begin[r] yields zeros); slots [r, p0:p0 + U] of both
+    caches receive the k / v columns of qkv, nothing else of them is written and nothing at or beyond p0 is read."""
+    if qkv.ndim != 2 or kc.ndim != 3 or kc.shape != vc.shape or kc.stride() != vc.stride():
+        raise _C.F5EError("attn_append_f32: qkv [R * U, >= 3 D] and kc, vc [R, Umax, D] with equal strides; there is no CPU path")
+    R, Umax, D = kc.shape
+    for t, nm in ((kc, "kc"), (vc, "vc")):
+        if not t.is_cuda or t.dtype != F32 or t.stride(2) != 1:
+            raise _C.F5EError(f"attn_append_f32: {nm} must be an f32 GPU tensor with unit channel stride")
+    U, p0 = int(U), int(p0)
+    if U < 1 or p0 < 0 or p0 + U > Umax or qkv.shape[0] != R * U or D % heads:
+        raise _C.F5EError(f"attn_append_f32: need U = {U} >= 1 new positions from p0 = {p0} >= 0 inside the {Umax} cached ones, "
+                          f"{R} * U = {qkv.shape[0]} rows of qkv and heads {heads} dividing {D}")
+    pos_stride = kc.stride(1) if Umax > 1 else max(D, kc.stride(1))
+    row_stride = kc.stride(0) if R > 1 else max(kc.stride(0), (Umax - 1) * pos_stride + D)
+    for t in (kc, vc):
+        have = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+        if pos_stride < D or row_stride < (Umax - 1) * pos_stride + D or have < (R - 1) * row_stride + (Umax - 1) * pos_stride + D \
+                or pos_stride % 4 or row_stride % 4 or t.data_ptr() % 16:
+            raise _C.F5EError(f"attn_append_f32: cache strides ({row_stride}, {pos_stride}) must be multiples of 4 spanning "
+                              f"[{R}, {Umax}, {D}] inside the storage, kc and vc 16-byte aligned")
+    qp, ldq = _rows(qkv, (F32,), "attn_append_f32: qkv", 3 * D)
+    bp = None if begin is None else _vec(begin, I32, "attn_append_f32: begin", (R,))
+    require_device()
+    out = torch.empty(R * U, D, dtype=F32, device=qkv.device) if out is None else out
+    if out.shape != (R * U, D):
+        raise _C.F5EError(f"attn_append_f32: out must be [{R * U}, {D}]")
+    op, ldo = _rows(out, (F32,), "attn_append_f32: out", D)
+    check(lib().f5e_attn_append_f32(_stream(), qp, ldq, C.c_void_p(kc.data_ptr()), C.c_void_p(vc.data_ptr()), row_stride,
+                                    pos_stride, bp, op, ldo, R, U, Umax, heads, D // heads, p0, float(scale)), "f5e_attn_append_f32")
+    return out
+
+
+SKINNY_MAX_M = 16
+_skinny_ws: dict = {}
+_skinny_needs: dict = {}
+
+
+def gemm_f32_skinny_workspace(N: int, K: int) -> int:
+    """Scratch bytes of ``gemm_f32_skinny`` for an [N, K] weight (host arithmetic on N, K and the CU count; 0: K is not split)."""
+    n = C.c_ulonglong(0)
+    check(lib().f5e_gemm_f32_skinny_workspace(int(N), int(K), C.byref(n)), "f5e_gemm_f32_skinny_workspace")
+    return int(n.value)
+
+
+def _skinny_need(N: int, K: int, device) -> int:
+    """``gemm_f32_skinny_workspace`` once per shape and device (the answer depends on the device's CU count)."""
+    key = (N, K, device)
+    if key not in _skinny_needs:
+        _skinny_needs[key] = gemm_f32_skinny_workspace(N, K)
+    return _skinny_needs[key]
+
+
+def gemm_f32_skinny(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, out: Tensor, act: int = ACT_NONE,
+                    addend: Optional[Tensor] = None, workspace: Optional[Tensor] = None):
+    """out[m, n] = act(sum_k a[m, k] w[n, k] + bias[n]) + addend[m, n] for 1 <= M <= 16 rows (f5e_gemm_f32_skinny): the weight
+    read of a verify pass spread over the whole chip.  a f32 [M, K] and w f32 [N, K] row-strided views (K and the row strides
+    multiples of 4, 16-byte aligned), out / addend f32 [M, >= N] views with unit column stride (addend may be out), bias f32
+    [>= N].  ``act``: ACT_NONE or ACT_GELU_ERF.  A row's result does not depend on M; two launches give the same bits.
+    ``workspace``: a device tensor of ``gemm_f32_skinny_workspace`` bytes (None: one is kept per device and stream, whose
+    launches are ordered)."""
+    for t, nm in ((a, "a"), (w, "w"), (out, "out")) + (((addend, "addend"),) if addend is not None else ()):
+        if not isinstance(t, Tensor) or t.ndim != 2 or not t.is_cuda or t.dtype != F32 or (t.stride(1) != 1 and t.shape[1] > 1):
+            raise _C.F5EError(f"gemm_f32_skinny: {nm} must be a 2-D f32 GPU tensor with unit column stride; there is no CPU path")
+    (M, K), N = a.shape, w.shape[0]
+    if not 1 <= M <= SKINNY_MAX_M:
+        raise _C.F5EError(f"gemm_f32_skinny: built for 1 <= M <= {SKINNY_MAX_M} rows (got {M}); gemm_f32 takes the rest")
+    if N < 1 or K < 4 or K % 4 or w.shape[1] != K:
+        raise _C.F5EError(f"gemm_f32_skinny: a [{M}, {K}] against w {tuple(w.shape)}: K must be a positive multiple of 4 and equal")
+    if act not in (ACT_NONE, ACT_GELU_ERF):
+        raise _C.F5EError(f"gemm_f32_skinny: act = {act} is not built (ACT_NONE and ACT_GELU_ERF are)")
+    if out.shape[0] != M or out.shape[1] < N or (addend is not None and (addend.shape[0] != M or addend.shape[1] < N)):
+        raise _C.F5EError(f"gemm_f32_skinny: out and addend must be [{M}, >= {N}]")
+    if bias is not None and bias.numel() < N:
+        raise _C.F5EError(f"gemm_f32_skinny: bias must hold at least {N} elements (got {bias.numel()})")
+    ap, lda = _rows(a, (F32,), "gemm_f32_skinny: a", K)
+    wp, ldw = _rows(w, (F32,), "gemm_f32_skinny: w", K)
+    op, ldo = _rows(out, (F32,), "gemm_f32_skinny: out", N, vec=1)
+    dp, ldd = (None, 0) if addend is None else _rows(addend, (F32,), "gemm_f32_skinny: addend", N, vec=1)
+    require_device()
+    need = _skinny_need(N, K, a.device)
+    if workspace is None and need:
+        key = (a.device, _stream())                      # launches of one stream are ordered: they can share the scratch
+        workspace = _skinny_ws.get(key)
+        if workspace is None or workspace.numel() * 4 < need:
+            workspace = _skinny_ws[key] = torch.empty(max(need, 1 << 20) // 4, dtype=F32, device=a.device)
+    if need and (not workspace.is_cuda or not workspace.is_contiguous() or workspace.data_ptr() % 16 or
+                 workspace.numel() * workspace.element_size() < need):
+        raise _C.F5EError(f"gemm_f32_skinny: workspace must be a contiguous 16-byte aligned GPU tensor of at least {need} bytes")
+    check(lib().f5e_gemm_f32_skinny(_stream(), ap, lda, wp, ldw, _p(bias, F32, "bias"), int(act), dp, ldd, op, ldo,
+                                    C.c_void_p(workspace.data_ptr()) if need else None,
+                                    workspace.numel() * workspace.element_size() if need else 0, M, N, K), "f5e_gemm_f32_skinny")
+    return out
+
+
 def whisper_embed(ids: Tensor, emb: Tensor, pos: Tensor, out: Tensor, p0: int = 0, begin: Optional[Tensor] = None):
     """out[r, u] = emb[ids[r, u]] + pos[max(p0 + u - begin[r], 0)] (f5e_whisper_embed): ids i32 [R, U], emb f32 [V, D], pos f32
     [P, D], begin i32 [R] or None, out f32 [R, U, D], all contiguous on the device.  U = 1 with p0 = p feeds a decode step."""
@@ -1873,6 +1972,56 @@ def whisper_ts_pick(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, 
                                     _p(sum_logp, F32, "sum_logp"), R, V, int(p), int(n0), int(eos), int(no_timestamps),
                                     -1 if max_initial is None else int(max_initial)), "f5e_whisper_ts_pick")
     return last
+
+
+def whisper_verify(logits: Tensor, hist: Tensor, cand: Tensor, logp: Tensor, p: int, n0: int, eos: int,
+                   no_timestamps: Optional[int] = None, *, V: Optional[int] = None, suppress: Optional[Tensor] = None,
+                   begin_suppress: Optional[Tensor] = None, max_initial: Optional[int] = None):
+    """f5e_whisper_verify: the picks of U + 1 positions per row at once.  logits f32 [R * (U + 1), >= V] (row r * (U + 1) + j =
+    position p + j of row r), hist i32 [R, >= p + U + 1] (the final tokens up to column p, the drafts behind), cand i32 [R, U + 1]
+    and logp f32 [R, U + 1] (written): what ``greedy_pick`` (``no_timestamps`` None) or ``whisper_ts_pick`` would pick at p + j
+    with the history hist[r, n0:p + j + 1], and the ``sum_logp`` increment of the latter (zeros without rules), bit for bit."""
+    if logits.ndim != 2 or hist.ndim != 2 or cand.ndim != 2 or cand.shape != logp.shape or cand.shape[0] != hist.shape[0] or \
+            logits.shape[0] != cand.numel():
+        raise _C.F5EError("whisper_verify: logits [R * (U + 1), >= V], hist [R, >= p + U + 1], cand and logp [R, U + 1]; there is "
+                          "no CPU path")
+    R, U = cand.shape[0], cand.shape[1] - 1
+    V = logits.shape[1] if V is None else int(V)
+    if V > logits.shape[1]:
+        raise _C.F5EError(f"whisper_verify: V = {V} exceeds the {logits.shape[1]} columns of logits")
+    lp, ld = _rows(logits, (F32,), "whisper_verify: logits", max(V, 1), vec=1)
+    hp, ld_hist = _rows(hist, (I32,), "whisper_verify: hist", int(p) + U + 1, vec=1)
+    require_device()
+    check(lib().f5e_whisper_verify(_stream(), lp, ld, _p(suppress, I32, "suppress"), suppress.numel() if suppress is not None else 0,
+                                   _p(begin_suppress, I32, "begin_suppress"),
+                                   begin_suppress.numel() if begin_suppress is not None else 0, hp, ld_hist, _p(cand, I32, "cand"),
+                                   _p(logp, F32, "logp"), R, U, V, int(p), int(n0), int(eos),
+                                   -1 if no_timestamps is None else int(no_timestamps),
+                                   -1 if max_initial is None else int(max_initial)), "f5e_whisper_verify")
+    return cand, logp
+
+
+def whisper_accept(cand: Tensor, logp: Tensor, hist: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor,
+                   sum_logp: Optional[Tensor], adv: Tensor, p: int, eos: int):
+    """f5e_whisper_accept: the accept step behind ``whisper_verify``.  cand i32 / logp f32 [R, U + 1]; hist and tokens i32
+    [R, >= p + U + 2]; last, done i32 [R]; alive, adv i32 [1]; sum_logp f32 [R] or None.  An open row agrees with its drafts
+    hist[r, p + 1:p + 1 + m] = cand[r, :m]; the common advance a = min(m + 1) over the open rows goes to ``adv``; every row gets
+    tokens[r, p + 1:p + a + 1] (eos from a row's end on), last, done, sum_logp (the kept picks' logp) and alive as ``a`` single
+    steps would have left them, and hist is put right (tokens up to p + a, eos on the rejected drafts)."""
+    if cand.ndim != 2 or cand.shape != logp.shape or hist.ndim != 2 or tokens.ndim != 2 or cand.shape[1] < 2:
+        raise _C.F5EError("whisper_accept: cand and logp [R, U + 1] with U >= 1, hist and tokens [R, >= p + U + 2]; there is no CPU "
+                          "path")
+    R, U = cand.shape[0], cand.shape[1] - 1
+    if hist.shape[0] != R or tokens.shape[0] != R or last.shape != (R,) or done.shape != (R,) or alive.numel() != 1 or \
+            adv.numel() != 1 or (sum_logp is not None and sum_logp.shape != (R,)):
+        raise _C.F5EError(f"whisper_accept: hist / tokens [{R}, .], last / done / sum_logp [{R}], alive / adv [1]")
+    hp, ld_hist = _rows(hist, (I32,), "whisper_accept: hist", int(p) + U + 2, vec=1)
+    tp, ld_tok = _rows(tokens, (I32,), "whisper_accept: tokens", int(p) + U + 2, vec=1)
+    require_device()
+    check(lib().f5e_whisper_accept(_stream(), _p(cand, I32, "cand"), _p(logp, F32, "logp"), hp, ld_hist, tp, ld_tok,
+                                   _p(last, I32, "last"), _p(done, I32, "done"), _p(alive, I32, "alive"),
+                                   _p(sum_logp, F32, "sum_logp"), _p(adv, I32, "adv"), R, U, int(p), int(eos)), "f5e_whisper_accept")
+    return adv
 
 
 def whisper_sample_pick(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, sum_logp: Tensor, p: int, n0: int,

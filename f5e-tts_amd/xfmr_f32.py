@@ -64,14 +64,15 @@ def fold_layer(dev, ln1, q, k, v, out, ln_ff, fc1, fc2, *, ln_x=None, xq=None, x
 
 
 def layer(src: Tensor, dst: Tensor, W: LayerWeights, bufs: tuple, *, pre_norm: bool, act: int, eps: float, self_attn,
-          cross_attn=None) -> None:
+          cross_attn=None, gemm=None) -> None:
     """One layer from ``src`` [M, D] into ``dst`` (may be ``src``) on the scratch ``bufs`` = (xn [M, D], qkv [M, 3 D], ao [M, D],
     q [M, D], ff [M, FF]); xn is unused post-norm, q without source attention.  ``self_attn(W, h, qkv, ao)``: the attention
     launch(es) on q | k | v = ``qkv`` into ``ao``; h is the projection's input (WavLM's gate reads it, with ``W.extra``).
     ``cross_attn(W, q, ao)``: the source attention of the queries ``q`` (``W.xkv`` for a caller that projects the memory per
-    layer).  Allocates nothing."""
+    layer).  ``gemm``: a replacement for ``ops.gemm_f32`` with its keywords ``out``, ``act`` and ``addend`` (a pass of a handful
+    of rows hands in ``ops.gemm_f32_skinny``); None takes the path it always took.  Allocates nothing."""
     xn, qkv, ao, q, ff = bufs
-    gemm, ln = ops.gemm_f32, ops.layernorm
+    gemm, ln = ops.gemm_f32 if gemm is None else gemm, ops.layernorm
     h = src
     if pre_norm:
         h = ln(src, xn, W.ln1[0], W.ln1[1], eps=eps)

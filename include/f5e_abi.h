@@ -954,6 +954,54 @@ F5E_API int f5e_attn_decode_from_f32(f5e_stream st, const float* qkv, int ld_qkv
 F5E_API int f5e_whisper_embed(f5e_stream st, const int* ids, const int* begin, const float* emb, const float* pos, float* out,
                       int R, int U, int D, int p0, int max_pos, int table_rows);
 
+/* ---- Whisper speculative decoding (csrc/whisper_append.hip, csrc/gemm_f32_skinny.hip): a draft model proposes U tokens with
+ * cheap steps, the large model checks them in ONE pass per layer and keeps the longest prefix it agrees with plus its own next
+ * token.
+ *
+ * f5e_attn_append_f32: causal self-attention of the U NEW positions p0 .. p0+U-1 of R rows behind an existing cache.  qkv f32
+ * [R*U][ld_qkv >= 3*H*dk] (row r*U + u = position p0 + u of row r), kc / vc / begin / out as f5e_attn_prefill_f32 takes them.
+ * Query u of row r sees the cached keys begin[r] .. p0-1, read from kc / vc (16-key tiles from begin[r] & ~15, masked at both
+ * edges, no causal mask), and the new keys 0 .. u of its own row, read from qkv and never from the caches (causal mask); one
+ * online softmax runs across both.  A query whose position lies below begin[r] (clamped to [0, p0 + U]) yields exact zeros.
+ * Slots [r][p0 .. p0+U-1] of kc / vc receive the k / v columns of qkv bit for bit; the launch reads only slots below p0 and
+ * writes only those, so it reads nothing that it writes.  p0 = 0 computes what f5e_attn_prefill_f32 computes.  The wave tile,
+ * the cache strides (the beam view included) and the limits are f5e_attn_prefill_f32's; p0 < 0 and p0 + U > Umax are refused. */
+F5E_API int f5e_attn_append_f32(f5e_stream st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                        int pos_stride, const int* begin, float* out, int ldo, int R, int U, int Umax, int H, int dk, int p0,
+                        float scale);
+/* f5e_whisper_verify: for every row r and every j in 0 .. U, the pick that f5e_greedy_pick (no_timestamps = -1) or
+ * f5e_whisper_ts_pick would make at position p + j on logits row r*(U+1) + j with the generated tokens hist[r][n0 .. p+j]:
+ *   logits  f32 [R*(U+1)][ld >= V], only read once
+ *   hist    i32 [R][ld_hist >= p + U + 1]: the final tokens up to column p, the drafts in columns p+1 .. p+U
+ *   cand    i32 [R][U+1], logp f32 [R][U+1]: the pick, and the sum_logp increment of f5e_whisper_ts_pick (0 without rules)
+ * begin_suppress counts iff p + j + 1 == n0.  One workgroup per (r, j); picks and increments are bit-equal to the single-step
+ * kernels on the same inputs (one body, csrc/whisper_pick.h).  Rows that are done are computed like the others.
+ * Limits: R <= 65535, U >= 0, 2 <= V <= 262144, n0 >= 1, p >= n0 - 1; with rules those of f5e_whisper_ts_pick. */
+F5E_API int f5e_whisper_verify(f5e_stream st, const float* logits, long long ld, const int* suppress, int n_sup,
+                       const int* begin_suppress, int n_beg, const int* hist, int ld_hist, int* cand, float* logp, int R, int U,
+                       int V, int p, int n0, int eos, int no_timestamps, int max_initial);
+/* f5e_whisper_accept: one launch after f5e_whisper_verify.  For a row that is not done, m[r] = the number of leading j < U with
+ * cand[r][j] == hist[r][p+1+j], counting no further than a cand that is eos.  The common advance a = min over the open rows of
+ * m[r] + 1 (1 .. U + 1; 1 when no row is open).  Every row gets tokens[r][p+1 .. p+a]: an open row cand[r][0 .. a-1], from its
+ * first eos on eos (done 0 -> 1); a done row eos.  last[r] = tokens[r][p+a]; sum_logp[r] (may be NULL) gains the logp of the
+ * kept picks one by one, the closing eos included, nothing after it and nothing for done rows; *alive = rows still open;
+ * adv[0] = a.  hist is put right: tokens on columns p+1 .. p+a, eos on p+a+1 .. p+U.  Columns of tokens beyond p + a are not
+ * touched.  tokens and hist rows hold at least p + U + 2 columns; U >= 1. */
+F5E_API int f5e_whisper_accept(f5e_stream st, const int* cand, const float* logp, int* hist, int ld_hist, int* tokens, int ld_tok,
+                       int* last, int* done, int* alive, float* sum_logp, int* adv, int R, int U, int p, int eos);
+/* f5e_gemm_f32_skinny: out[m][n] = act(sum_k A[m][k] W[n][k] + bias[n]) + addend[m][n] for 1 <= M <= 16 rows, fp32: the GEMM of a
+ * verify pass, which is one read of W.  W is cut into tiles of 16 rows and, where N is small, K into KS slices, so that the read
+ * is spread over every CU; the K ranges are summed in a fixed order (through LDS inside a workgroup, through `workspace` and a
+ * second launch across workgroups): no floating-point atomics, a launch is bit-reproducible, and a row's result does not
+ * depend on M.  act: F5E_ACT_NONE or F5E_ACT_GELU_ERF; bias [N] and addend [M][ld_add] may be NULL; addend may alias out.
+ * K % 4 == 0, lda and ldw multiples of 4, A and W 16-byte aligned; ldo and ld_add are free.  A must not alias out.
+ * workspace: f5e_gemm_f32_skinny_workspace(N, K) bytes (0 when K is not split; host arithmetic on N, K and the CU count), 16-byte
+ * aligned.  M = 17 and the rest are refused before the launch. */
+F5E_API int f5e_gemm_f32_skinny_workspace(int N, int K, unsigned long long* bytes_out_host);
+F5E_API int f5e_gemm_f32_skinny(f5e_stream st, const float* A, int lda, const float* W, int ldw, const float* bias, int act,
+                        const float* addend, int ld_add, float* out, int ldo, void* workspace,
+                        unsigned long long workspace_bytes, int M, int N, int K);
+
 /* ---------------------------------------------------------------- UTMOS (csrc/utmos.hip) ---------------------- */
 /* The UTMOS predictor (utmos22_strong, reference eval/eval_utmos.py): a wav2vec2-base upstream (group-norm feature extractor,
  * post-LayerNorm encoder), a BiLSTM over its frames and a per-frame score averaged per utterance.  The strided convolutions 1-6,

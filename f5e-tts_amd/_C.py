@@ -85,6 +85,11 @@ SIGNATURES = {
     "f5e_whisper_accept": [_P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I],
     "f5e_gemm_f32_skinny_workspace": [_I, _I, C.POINTER(C.c_ulonglong)],
     "f5e_gemm_f32_skinny": [_P, _P, _I, _P, _I, _P, _I, _P, _I, _P, _I, _P, C.c_ulonglong, _I, _I, _I],
+    "f5e_attn_decode_dev_f32": [_P, _P, _I, _P, _P, _LL, _I, _P, _P, _I, _I, _I, _I, _I, _P, _F],
+    "f5e_whisper_embed_dev": [_P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I],
+    "f5e_greedy_pick_dev": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _I],
+    "f5e_whisper_ts_pick_dev": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I],
+    "f5e_whisper_sample_pick_dev": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P],
     "f5e_beam_step": [_P, _P, _LL, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I],
     "f5e_layer_mix_inorm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
     "f5e_res2_dconv": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],

@@ -29,91 +29,19 @@
 //      rows) and appends the class at column p + 1, the parent's row at column p.
 // No atomics on memory, no sort.
 #include "f5e_common.h"
+#include "attn_decode_body.h"
 
 namespace {
 
-constexpr int DEC_MAX_U = 4096;    // cached positions per row (the LDS score row of the attention wave)
 constexpr int STEP_MAX_K = 16;
 
+// the body (and DEC_MAX_U) is attn_decode_body.h's, shared with the device-position kernel of whisper_step.hip
 template <int DK, bool FROM>
 __global__ __launch_bounds__(64) void attn_decode_kernel(const float* __restrict__ qkv, int ld_qkv, float* kc, float* vc,
                                                           long long row_stride, int pos_stride, const int* __restrict__ anc,
                                                           int ld_anc, float* __restrict__ out, int ldo, int R, int H, int p,
                                                           float scale, const int* __restrict__ begin) {
-  __shared__ float s[DEC_MAX_U];
-  constexpr int G = DK >= 64 ? 1 : 64 / DK;     // key groups of the context pass
-  constexpr int DPL = DK > 64 ? DK / 64 : 1;    // channels per lane of the context pass
-  const int lane = threadIdx.x, h = blockIdx.x, r = blockIdx.y;
-  const int HD = H * DK;
-  const float* me = qkv + (long long)r * ld_qkv + h * DK;   // q; k at + HD, v at + 2 HD
-  const long long head = (long long)h * DK;
-  const int lo = FROM ? min(max(begin[r], 0), p) : 0;       // the first visible position
-
-  // the new key / value into slot [r][p]
-  for (int d = lane; d < DK; d += 64) {
-    const long long o = (long long)r * row_stride + (long long)p * pos_stride + head + d;
-    kc[o] = me[HD + d];
-    vc[o] = me[2 * HD + d];
-  }
-
-  f32x4 q[DK / 4];
-#pragma unroll
-  for (int i = 0; i < DK / 4; ++i) q[i] = *(const f32x4*)(me + 4 * i);
-
-  // ---- 1. scores
-  float m = -__builtin_inff();
-  for (int j = lo + lane; j <= p; j += 64) {
-    const float* kr;
-    if (j == p) {
-      kr = me + HD;
-    } else {
-      const int src = anc ? min(max(anc[(long long)r * ld_anc + j], 0), R - 1) : r;   // the clamp keeps garbage in bounds
-      kr = kc + (long long)src * row_stride + (long long)j * pos_stride + head;
-    }
-    float acc = 0.f;
-#pragma unroll
-    for (int i = 0; i < DK / 4; ++i) {
-      const f32x4 kv = *(const f32x4*)(kr + 4 * i);
-      acc += q[i].x * kv.x + q[i].y * kv.y + q[i].z * kv.z + q[i].w * kv.w;
-    }
-    acc *= scale;
-    s[j] = acc;
-    m = fmaxf(m, acc);
-  }
-  m = wave_max(m);
-  // ---- 2. weights (a lane rewrites only the entries it wrote)
-  float sum = 0.f;
-  for (int j = lo + lane; j <= p; j += 64) {
-    const float e = expf(s[j] - m);
-    s[j] = e;
-    sum += e;
-  }
-  sum = wave_sum(sum);
-  __syncthreads();
-  // ---- 3. context
-  const int g = DK >= 64 ? 0 : lane / DK, d0 = DK >= 64 ? lane : lane % DK;
-  float acc[DPL];
-#pragma unroll
-  for (int i = 0; i < DPL; ++i) acc[i] = 0.f;
-  for (int j = lo + g; j <= p; j += G) {
-    const float* vr;
-    if (j == p) {
-      vr = me + 2 * HD;
-    } else {
-      const int src = anc ? min(max(anc[(long long)r * ld_anc + j], 0), R - 1) : r;
-      vr = vc + (long long)src * row_stride + (long long)j * pos_stride + head;
-    }
-    const float w = s[j];
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) acc[i] += w * vr[d0 + 64 * i];
-  }
-#pragma unroll
-  for (int o = 32; o >= DK; o >>= 1) acc[0] += __shfl_xor(acc[0], o, 64);   // fold the key groups (DK < 64 only)
-  if (g == 0) {
-    const float inv = 1.f / sum;
-#pragma unroll
-    for (int i = 0; i < DPL; ++i) out[(long long)r * ldo + head + d0 + 64 * i] = acc[i] * inv;
-  }
+  attn_decode_body<DK, FROM>(qkv, ld_qkv, kc, vc, row_stride, pos_stride, anc, ld_anc, out, ldo, R, H, p, scale, begin);
 }
 
 __global__ __launch_bounds__(1024) void beam_step_kernel(const float* __restrict__ logits, long long ld_logits, float* score,

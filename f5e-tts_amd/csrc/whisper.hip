@@ -206,124 +206,31 @@ __global__ __launch_bounds__(256) void cross_attn_decode_kernel(const float* __r
   }
 }
 
-// ---- greedy pick (the body is whisper_pick.h's) -----------------------------------------------------------------------------------
+// ---- the picks: the bodies (greedy_pick_step, ts_rule_step, ts_sample_step, alive_count_rows) are whisper_pick.h's, shared with
+// the device-position kernels of whisper_step.hip --------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void greedy_pick_kernel(const float* __restrict__ logits, long long ld,
                                                           const int* __restrict__ suppress, int n_sup,
                                                           const int* __restrict__ begin_suppress, int n_beg, int* tokens,
                                                           int ld_tok, int* last, int* done, int V, int p, int eos) {
-  __shared__ unsigned bits[GP_MAX_V / 32];
-  __shared__ float rm[4];
-  __shared__ int ra[4];
-  const int tid = threadIdx.x, r = blockIdx.x;
-  if (done[r]) {                                  // uniform over the workgroup
-    if (tid == 0) tokens[(size_t)r * ld_tok + p + 1] = eos, last[r] = eos;
-    return;
-  }
-  const int words = (V + 31) / 32;
-  for (int i = tid; i < words; i += 256) bits[i] = 0u;
-  __syncthreads();
-  pick_mark_bits(bits, suppress, n_sup, begin_suppress, n_beg, V);
-  __syncthreads();
-  const int arg = greedy_pick_row(logits + (size_t)r * ld, bits, rm, ra, V);
-  if (tid == 0) {
-    tokens[(size_t)r * ld_tok + p + 1] = arg;
-    last[r] = arg;
-    if (arg == eos) done[r] = 1;
-  }
+  greedy_pick_step(logits, ld, suppress, n_sup, begin_suppress, n_beg, tokens, ld_tok, last, done, V, p, eos);
 }
 
 __global__ __launch_bounds__(256) void alive_count_kernel(const int* __restrict__ done, int* __restrict__ alive, int R) {
   __shared__ int red[4];
-  int c = 0;
-  for (int r = threadIdx.x; r < R; r += 256) c += done[r] ? 0 : 1;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) *alive = (red[0] + red[1]) + (red[2] + red[3]);
+  const int n = alive_count_rows(done, R, red);
+  if (threadIdx.x == 0) *alive = n;
 }
 
-// ---- timestamp rules: TsRule, TsGroup, ts_rule_of and the ruled pick live in whisper_pick.h ----------------------------------------
-// PICK: the greedy step (tokens, last, done, sum_logp).  Otherwise the rule descriptor of the row goes to desc[r][0..4) for the
-// beam's chunk kernel: kind, lo, hi, 0.  The generated tokens of row r are tokens[r][n0 .. p].
 template <bool PICK>
 __global__ __launch_bounds__(256) void ts_rule_kernel(const float* __restrict__ logits, long long ld,
                                                       const int* __restrict__ suppress, int n_sup,
                                                       const int* __restrict__ begin_suppress, int n_beg, int* tokens, int ld_tok,
                                                       int* last, int* done, float* sum_logp, int* __restrict__ desc, int V, int p,
                                                       int n0, int eos, int no_ts, int max_initial) {
-  __shared__ unsigned bits[GP_MAX_V / 32];
-  __shared__ float rm[2][4], rs[2][4];
-  __shared__ int ra[2][4], slot;
-  const int tid = threadIdx.x, r = blockIdx.x;
-  if (PICK && done[r]) {                          // uniform over the workgroup
-    if (tid == 0) tokens[(size_t)r * ld_tok + p + 1] = eos, last[r] = eos;
-    return;
-  }
-  const int words = (V + 31) / 32, ts_begin = no_ts + 1;
-  for (int i = tid; i < words; i += 256) bits[i] = 0u;
-  const TsRule d = ts_rule_of(tokens + (size_t)r * ld_tok + n0, p + 1 - n0, V, ts_begin, max_initial, &slot);   // syncs twice
-  pick_mark_bits(bits, suppress, n_sup, begin_suppress, n_beg, V);
-  __syncthreads();
-  const TsPick pk = ts_pick_row(logits + (size_t)r * ld, bits, d, rm, rs, ra, V, eos, no_ts);
-  if (tid == 0) {
-    if (!PICK) {
-      int* dr = desc + (size_t)r * 4;
-      dr[0] = pk.only_ts ? 2 : d.kind, dr[1] = d.lo, dr[2] = d.hi, dr[3] = 0;
-      return;
-    }
-    if (pk.has) sum_logp[r] += pk.logp;
-    tokens[(size_t)r * ld_tok + p + 1] = pk.arg;
-    last[r] = pk.arg;
-    if (pk.arg == eos) done[r] = 1;
-  }
+  ts_rule_step<PICK>(logits, ld, suppress, n_sup, begin_suppress, n_beg, tokens, ld_tok, last, done, sum_logp, desc, V, p, n0, eos,
+                     no_ts, max_initial);
 }
 
-// ---- the sampled step under the rules (f5e_whisper_sample_pick) ---------------------------------------------------------------
-// The noise is a function of counters only: class i takes word i & 3 of Philox4x32-10(counter = (i >> 2, step, serial, row_key),
-// key = (seed_lo, seed_hi)), so a draw depends on neither the launch geometry nor the row's batch-mates.
-__host__ __device__ inline void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1,
-                                              unsigned (&w)[4]) {
-#pragma unroll
-  for (int round = 0; round < 10; ++round) {
-    const unsigned long long a = 0xD2511F53ull * c0, b = 0xCD9E8D57ull * c2;
-    const unsigned n0 = (unsigned)(b >> 32) ^ c1 ^ k0, n2 = (unsigned)(a >> 32) ^ c3 ^ k1;
-    c0 = n0, c1 = (unsigned)b, c2 = n2, c3 = (unsigned)a;
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-  w[0] = c0, w[1] = c1, w[2] = c2, w[3] = c3;
-}
-
-// g = -log(-log(u)), u = ((w >> 8) + 0.5) 2^-24.  n + 0.5 has 25 significant bits from n = 2^23 on and would round (to u = 1 at
-// the top), so the upper half goes through 1 - u = ((2^24 - 1 - n) + 0.5) 2^-24, which is exact there, and log1p.
-__device__ __forceinline__ float ws_gumbel(unsigned w) {
-  const unsigned n = w >> 8;
-  const float e = n < (1u << 23) ? -logf(((float)n + 0.5f) * 0x1p-24f) : -log1pf(-(((float)(0xffffffu - n) + 0.5f) * 0x1p-24f));
-  return -logf(e);
-}
-
-struct WsDraw {
-  float y, x;         // the largest perturbed value x / T + g and its raw logit
-  int a;              // its lowest index (WAVE_NONE: no class)
-};
-
-__device__ __forceinline__ void ws_draw_merge(WsDraw& d, float oy, float ox, int oa) {
-  if (oa != WAVE_NONE && (d.a == WAVE_NONE || oy > d.y || (oy == d.y && oa < d.a))) d = {oy, ox, oa};
-}
-
-__device__ __forceinline__ void ws_draw_wave(WsDraw& d) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float oy = __shfl_xor(d.y, o, 64), ox = __shfl_xor(d.x, o, 64);
-    const int oa = __shfl_xor(d.a, o, 64);
-    ws_draw_merge(d, oy, ox, oa);
-  }
-}
-
-// ts_rule_kernel<true> with a draw for the argmax: the rules and the running log-sum-exp are decided on the raw logits (the
-// temperature warper runs after the Whisper processors), the pick is the first maximum of x / T + g, kept for the timestamps and
-// for the text apart because rule 6 is only known after the pass.  A lane owns 4 consecutive classes = one Philox block.
-// no_ts < 0: no timestamp rules (every class is text, nothing but the suppressed classes is banned).
 __global__ __launch_bounds__(256) void ts_sample_kernel(const float* __restrict__ logits, long long ld,
                                                         const int* __restrict__ suppress, int n_sup,
                                                         const int* __restrict__ begin_suppress, int n_beg, int* tokens, int ld_tok,
@@ -331,80 +238,8 @@ __global__ __launch_bounds__(256) void ts_sample_kernel(const float* __restrict_
                                                         int no_ts, int max_initial, float temperature, unsigned seed_lo,
                                                         unsigned seed_hi, const int* __restrict__ row_key,
                                                         const int* __restrict__ serial) {
-  __shared__ unsigned bits[GP_MAX_V / 32];
-  __shared__ float rm[2][4], rs[2][4], ry[2][4], rx[2][4];
-  __shared__ int ra[2][4], slot;
-  const int tid = threadIdx.x, r = blockIdx.x;
-  if (done[r]) {                                  // uniform over the workgroup
-    if (tid == 0) tokens[(size_t)r * ld_tok + p + 1] = eos, last[r] = eos;
-    return;
-  }
-  const int words = (V + 31) / 32, ts_begin = no_ts >= 0 ? no_ts + 1 : V;
-  for (int i = tid; i < words; i += 256) bits[i] = 0u;
-  TsRule d = {0, V, V - 1};
-  if (no_ts >= 0) d = ts_rule_of(tokens + (size_t)r * ld_tok + n0, p + 1 - n0, V, ts_begin, max_initial, &slot);   // syncs twice
-  else __syncthreads();
-  for (int i = tid; i < n_sup + n_beg; i += 256) {
-    const int v = i < n_sup ? suppress[i] : begin_suppress[i - n_sup];
-    if (v >= 0 && v < V) atomicOr(&bits[v >> 5], 1u << (v & 31));
-  }
-  __syncthreads();
-  const float NEG = -__builtin_inff();
-  const float* row = logits + (size_t)r * ld;
-  const unsigned key_row = (unsigned)row_key[r], key_serial = (unsigned)serial[r];
-  TsGroup ts = {NEG, 0.f, WAVE_NONE}, tx = {NEG, 0.f, WAVE_NONE};   // maximum and sum only: their index is not used here
-  WsDraw dts = {NEG, NEG, WAVE_NONE}, dtx = {NEG, NEG, WAVE_NONE};
-  const int text_from = d.kind == 2 ? ts_begin : d.kind == 1 ? eos : 0;
-  for (int v0 = 4 * tid; v0 < V; v0 += 1024) {    // ascending per thread: '>' keeps the first maximum
-    unsigned w[4];
-    philox4x32_10((unsigned)(v0 >> 2), (unsigned)p, key_serial, key_row, seed_lo, seed_hi, w);
-    float x[4];
-    bool is_ts[4], is_tx[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int v = v0 + k;
-      x[k] = v < V ? row[v] : NEG;
-      const bool ok = v < V && !((bits[(v >> 5) & (GP_MAX_V / 32 - 1)] >> (v & 31)) & 1u) && v != no_ts && x[k] > NEG &&
-                      x[k] < __builtin_inff();    // NaN, +-inf: no class
-      is_ts[k] = ok && v >= ts_begin && v >= d.lo && v <= d.hi;
-      is_tx[k] = ok && v < ts_begin && v >= text_from;
-      if (is_ts[k] || is_tx[k]) {
-        const float y = x[k] / temperature + ws_gumbel(w[k]);
-        WsDraw& dr = is_ts[k] ? dts : dtx;
-        if (dr.a == WAVE_NONE || y > dr.y) dr = {y, x[k], v};
-      }
-    }
-    ts_group_add4(ts, x, is_ts, v0);
-    ts_group_add4(tx, x, is_tx, v0);
-  }
-  ts_group_wave(ts);
-  ts_group_wave(tx);
-  ws_draw_wave(dts);
-  ws_draw_wave(dtx);
-  if ((tid & 63) == 0) {
-    const int w = tid >> 6;
-    rm[0][w] = ts.m, rs[0][w] = ts.s, ry[0][w] = dts.y, rx[0][w] = dts.x, ra[0][w] = dts.a;
-    rm[1][w] = tx.m, rs[1][w] = tx.s, ry[1][w] = dtx.y, rx[1][w] = dtx.x, ra[1][w] = dtx.a;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    ts = {rm[0][0], rs[0][0], 0}, tx = {rm[1][0], rs[1][0], 0};
-    dts = {ry[0][0], rx[0][0], ra[0][0]}, dtx = {ry[1][0], rx[1][0], ra[1][0]};
-    for (int w = 1; w < 4; ++w) {
-      ts_group_merge(ts, rm[0][w], rs[0][w], 0), ts_group_merge(tx, rm[1][w], rs[1][w], 0);
-      ws_draw_merge(dts, ry[0][w], rx[0][w], ra[0][w]), ws_draw_merge(dtx, ry[1][w], rx[1][w], ra[1][w]);
-    }
-    const float lse_ts = ts.m > NEG ? ts.m + logf(ts.s) : NEG;
-    if (lse_ts > tx.m) tx = {NEG, 0.f, 0}, dtx = {NEG, NEG, WAVE_NONE};   // rule 6, on the raw logits: all text is banned
-    ws_draw_merge(dtx, dts.y, dts.x, dts.a);      // the draw over all allowed classes
-    ts_group_merge(tx, ts.m, ts.s, 0);            // their maximum and sum of exponentials at T = 1
-    int arg = dtx.a;
-    if (arg == WAVE_NONE) arg = 0;                // nothing is allowed
-    else sum_logp[r] += (dtx.x - tx.m) - logf(tx.s);
-    tokens[(size_t)r * ld_tok + p + 1] = arg;
-    last[r] = arg;
-    if (arg == eos) done[r] = 1;
-  }
+  ts_sample_step(logits, ld, suppress, n_sup, begin_suppress, n_beg, tokens, ld_tok, last, done, sum_logp, V, p, n0, eos, no_ts,
+                 max_initial, temperature, seed_lo, seed_hi, row_key, serial);
 }
 
 // ---- beam step (transformers' GenerationMixin._beam_search: K open rows, a pool of finished hypotheses) ------------------------

@@ -9,6 +9,7 @@
                                         [--whisper_prompt TEXT] [--whisper_condition]]
                                         [--whisper_assistant DIR [--whisper_assistant_tokens N]
                                          [--whisper_assistant_shares_encoder]]
+                                        [--whisper_step_graph [--whisper_step_gemm skinny]]
 
 ``--asr whisper`` is the reference's English recogniser of the voice-conversion and LibriSpeech evaluations
 (``run_asr_wer_whisper_large_v3``, eval/utils_eval.py:631-712: whisper-large-v3, greedy, prompt ``english / transcribe``) on the
@@ -203,6 +204,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--whisper_assistant_tokens", type=int, default=5, help="--whisper_assistant: tokens drafted per round")
     ap.add_argument("--whisper_assistant_shares_encoder", action="store_true",
                     help="--whisper_assistant: the draft reads the large model's encoder output instead of running its own")
+    ap.add_argument("--whisper_step_graph", action="store_true",
+                    help="--asr whisper: replay every pick from one decode step captured as a hipGraph (the same transcripts; "
+                         "greedy, --whisper_beam 1, no --whisper_assistant; the time is won with --whisper_step_gemm skinny)")
+    ap.add_argument("--whisper_step_gemm", choices=("f32", "skinny"), default="f32",
+                    help="--whisper_step_graph: the GEMM of the captured step; skinny spreads each weight read over the whole chip")
     ap.add_argument("--whisper_beam", type=int, default=1,
                     help="--asr whisper: 1 = greedy (run_asr_wer_whisper_large_v3); N > 1 = the pooled beam search of "
                          "generate(num_beams=N) (--beam_size is the wenet flag and does not reach Whisper)")
@@ -243,6 +249,10 @@ def main(argv=None, aligner=None) -> float:
         if args.whisper_assistant is not None:
             ctx.update(assistant_dir=args.whisper_assistant, num_assistant_tokens=args.whisper_assistant_tokens,
                        assistant_shares_encoder=args.whisper_assistant_shares_encoder)
+        if args.whisper_step_gemm != "f32" and not args.whisper_step_graph:
+            ap.error("--whisper_step_gemm needs --whisper_step_graph")
+        if args.whisper_step_graph:
+            ctx.update(step_graph=True, step_gemm=args.whisper_step_gemm)
         aligner = WhisperRecognizer(args.whisper_dir, args.device, args.language, beam_size=args.whisper_beam,
                                     long_form=args.whisper_long, **({} if fb is None else dict(fallback=fb)), **ctx)
     elif aligner is None:

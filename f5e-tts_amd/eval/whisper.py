@@ -43,7 +43,12 @@ without the timestamp rules; the tokens are those of this model alone.
 Out of scope: speculative sampling (an assistant with temperature > 0), beam search with an assistant, ``transformers``'
 heuristic draft schedule and confidence threshold, per-row positions (the rows of a batch advance together), beam-sample, top-k / top-p, the pipeline's strided ``chunk_length_s`` merging, word timestamps across windows,
 the prefill inside ``alignment_probs`` / ``token_timestamps``, patience, CTranslate2's exact search, bf16 / fp16 weights (fp16
-checkpoints are widened), a graph-captured step.
+checkpoints are widened), beam search, assisted generation and word timestamps from a captured step.
+
+The captured step (``generate`` / ``transcribe_long`` / ``generate_from_kv(step_graph=True)``): the picks of a greedy, ruled or
+sampled decode are replayed from one decode step captured as a hipGraph; the position lives in a device record that the
+device-position kernels read and advance (f5e_attn_decode_dev_f32, f5e_whisper_embed_dev, f5e_greedy_pick_dev,
+f5e_whisper_ts_pick_dev, f5e_whisper_sample_pick_dev; csrc/whisper_step.hip).  The same bits as the eager step.
 
 Ragged batches: samples at or beyond ``lens[b]`` count as zero, and the row is zero-padded to the chunk length as the feature
 extractor does; Whisper attends those frames, and so does this.  Row b of a batch equals its own B = 1 run."""
@@ -334,6 +339,7 @@ def group_tokens(id_to_piece: Dict[int, str], first_special: int, ids: Sequence[
 
 # ---- long-form: a window's tokens -> segments (transformers' generation_whisper.py: _retrieve_segment) ----------------------------
 TIME_PRECISION, INPUT_STRIDE = 0.02, 2      # seconds per timestamp step; mel frames per encoder position
+STEP_STATES = 4                             # captured decode steps kept per model (``step_graph``): an LRU
 
 
 @dataclass
@@ -814,17 +820,22 @@ class Whisper(nn.Module):
         return x.view(B, Tp, D)
 
     @torch.no_grad()
-    def cross_kv(self, enc_out: Tensor) -> List[Tuple[Tensor, Tensor]]:
-        """Every decoder layer's cross keys and values, once per utterance: views [B, Tp, D] of one [B, Tp, 2 D] buffer each."""
+    def cross_kv(self, enc_out: Tensor, out: Optional[Sequence[Tensor]] = None) -> List[Tuple[Tensor, Tensor]]:
+        """Every decoder layer's cross keys and values, once per utterance: views [B, Tp, D] of one [B, Tp, 2 D] buffer each.
+        ``out``: one contiguous f32 [B, Tp, 2 D] buffer per layer to project into (the storage of a captured step's state, so
+        that nothing is copied afterwards); None: fresh buffers, as always."""
         fd = self._fold()
         B, Tp, D = enc_out.shape
-        out = []
-        for p in fd["dec"]:
-            kv = torch.empty(B * Tp, 2 * D, dtype=F32, device=enc_out.device)
+        if out is not None and (len(out) != len(fd["dec"]) or any(tuple(b.shape) != (B, Tp, 2 * D) or b.dtype != F32 or
+                                                                  not b.is_contiguous() for b in out)):
+            raise _C.F5EError(f"Whisper.cross_kv: out must be {len(fd['dec'])} contiguous f32 buffers [{B}, {Tp}, {2 * D}]")
+        res = []
+        for i, p in enumerate(fd["dec"]):
+            kv = torch.empty(B * Tp, 2 * D, dtype=F32, device=enc_out.device) if out is None else out[i].view(B * Tp, 2 * D)
             ops.gemm_f32(enc_out.view(B * Tp, D), *p.xkv, out=kv)
             kv = kv.view(B, Tp, 2 * D)
-            out.append((kv[..., :D], kv[..., D:]))
-        return out
+            res.append((kv[..., :D], kv[..., D:]))
+        return res
 
     @torch.no_grad()
     def encode(self, wav: Tensor, lens=None) -> List[Tuple[Tensor, Tensor]]:
@@ -1144,6 +1155,134 @@ class Whisper(nn.Module):
             times[bi, last] = times[bi, last - 1]
         return times
 
+    # ---- the captured step: one decode step as a hipGraph, replayed per token -----------------------------------------
+    @staticmethod
+    def _check_step_graph(step_graph, step_gemm, beam_size, return_beams, assistant, return_token_timestamps) -> bool:
+        """-> whether the picks are replayed from a captured step; refusals by name, before any launch."""
+        if step_gemm not in ("f32", "skinny"):
+            raise _C.F5EError(f"Whisper.generate: step_gemm = {step_gemm!r} must be 'f32' or 'skinny'")
+        if not isinstance(step_graph, bool):
+            raise _C.F5EError(f"Whisper.generate: step_graph = {step_graph!r} must be a bool")
+        if not step_graph:
+            if step_gemm != "f32":
+                raise _C.F5EError(f"Whisper.generate: step_gemm = {step_gemm!r} needs step_graph = True (it chooses the GEMM of "
+                                  "the captured step; the eager step keeps f5e_gemm_f32)")
+            return False
+        if int(beam_size) != 1 or return_beams:
+            raise _C.F5EError(f"Whisper.generate: step_graph with beam_size = {beam_size} / return_beams is out of scope (the beam's "
+                              "two table pairs alternate per step: it needs a two-step graph and device-position beam kernels)")
+        if assistant is not None:
+            raise _C.F5EError("Whisper.generate: step_graph with assistant is out of scope (assisted generation from a graph is "
+                              "not built)")
+        if return_token_timestamps:
+            raise _C.F5EError("Whisper.generate: step_graph with return_token_timestamps is out of scope (the teacher-forced "
+                              "pass of token_timestamps writes alignment rows at a host position)")
+        return True
+
+    def _step_state(self, B: int, kind: str, padded: bool, step_gemm: str, Tp: int, dev) -> SimpleNamespace:
+        """The decode state a captured step runs on, cached on the folded weights (so a reload or a move drops it with its
+        graph) under (rows, pick kind, begin present, GEMM, cross positions, device): an LRU of at most ``STEP_STATES``.  The
+        state owns every buffer the graph's kernels touch: the self-attention caches, ``max_target_positions`` deep, its own
+        cross keys / values (``_step_load`` copies a call's into them), tokens, last, done, alive, sum_logp, begin, row_key,
+        serial, the step's scratch and logits, the step record and the skinny GEMM's workspace."""
+        if step_gemm == "skinny" and B > ops.SKINNY_MAX_M:
+            raise _C.F5EError(f"Whisper.generate: step_gemm = 'skinny' is built for at most {ops.SKINNY_MAX_M} rows (got {B}); "
+                              "step_gemm = 'f32' takes the rest")
+        cfg, fd = self.cfg, self._fold()
+        cache = fd.setdefault("step_states", {})
+        key = (B, kind, padded, step_gemm, Tp, str(dev))
+        S = cache.pop(key, None)
+        if S is None:
+            D, P, FF, V = cfg.d_model, cfg.max_target_positions, cfg.decoder_ffn_dim, cfg.vocab_size
+            zi = lambda *s: torch.zeros(*s, dtype=I32, device=dev)   # noqa: E731
+            S = SimpleNamespace(key=key, kind=kind, R=B, graph=None, captures=0, replays=0, st=self._dec_state(B, P, dev), tokens=zi(B, P), last=zi(B),
+                                done=zi(B), alive=zi(1), sum_logp=torch.zeros(B, dtype=F32, device=dev), row_key=zi(B),
+                                serial=zi(B), begin=zi(B) if padded else None, rec=zi(ops.STEP_REC_WORDS),
+                                xkv=[torch.empty(B, Tp, 2 * D, dtype=F32, device=dev) for _ in fd["dec"]], gemm=None,
+                                stream=torch.cuda.Stream(device=dev))
+            S.kv = [(b[..., :D], b[..., D:]) for b in S.xkv]
+            H, scale, at = cfg.decoder_attention_heads, (D // cfg.decoder_attention_heads) ** -0.5, S.st["layer"][0]
+
+            def self_attn(_W, _xn, qkv, ao):
+                kc, vc = S.st["caches"][at.i]
+                ops.attn_decode_dev_f32(qkv, kc, vc, S.rec, H, scale, out=ao, begin=S.begin)
+            S.self_attn = self_attn
+            if step_gemm == "skinny":      # its scratch belongs to the state: the default one is kept per stream, allocated on use
+                need = max(ops._skinny_need(n, k, dev) for n, k in ((3 * D, D), (D, D), (FF, D), (D, FF), (V, D)))
+                ws = torch.empty(max(need, 16) // 4, dtype=F32, device=dev)
+
+                def gemm(a, w, bias=None, *, out, act=ops.ACT_NONE, addend=None):
+                    return ops.gemm_f32_skinny(a, w, bias, out=out, act=act, addend=addend, workspace=ws)
+                S.gemm, S.ws = gemm, ws
+        cache[key] = S                                          # most recently used last
+        while len(cache) > STEP_STATES:
+            old = cache.pop(next(iter(cache)))
+            if old.graph is not None:                           # its launches may still be queued: parked behind an event
+                old.graph.retire()
+        ops.Graph.reap()
+        return S
+
+    @staticmethod
+    def _step_load(S: SimpleNamespace, kv: List[Tuple[Tensor, Tensor]]) -> None:
+        """A call's cross keys / values into the state's own storage, whose addresses the graph holds: one device copy per
+        layer when k | v are the two halves of one buffer (what ``cross_kv`` returns), two otherwise, none when they ARE the
+        state's storage (``cross_kv(enc, out=S.xkv)``, what ``generate`` does)."""
+        B, Tp, D2 = S.xkv[0].shape
+        if len(kv) != len(S.xkv):
+            raise _C.F5EError(f"Whisper.generate: {len(kv)} layers of cross keys / values for {len(S.xkv)} decoder layers")
+        for buf, (k, v) in zip(S.xkv, kv):
+            if tuple(k.shape) != (B, Tp, D2 // 2) or tuple(v.shape) != tuple(k.shape) or k.dtype != F32 or v.dtype != F32:
+                raise _C.F5EError(f"Whisper.generate: cross keys / values must be f32 [{B}, {Tp}, {D2 // 2}] per layer")
+            if k.data_ptr() == buf.data_ptr() and v.data_ptr() == buf.data_ptr() + 2 * D2 and k.stride() == (Tp * D2, D2, 1) and \
+                    v.stride() == k.stride():
+                continue
+            if k.stride() == (Tp * D2, D2, 1) and v.stride() == k.stride() and v.data_ptr() == k.data_ptr() + 2 * D2 and \
+                    k.untyped_storage().data_ptr() == v.untyped_storage().data_ptr():
+                buf.copy_(torch.as_strided(k, (B, Tp, D2), k.stride()))
+            else:
+                buf[..., :D2 // 2].copy_(k)
+                buf[..., D2 // 2:].copy_(v)
+
+    def _step_dev(self, S: SimpleNamespace, ts: bool) -> None:
+        """The launches of ONE pick step on the state ``S`` with the position read from ``S.rec``: ``_dec_step`` and the pick
+        with the device-position kernels (csrc/whisper_step.hip) in the place of the host-position ones, nothing else.  No
+        allocation, no copy, no host read: this is what the graph captures."""
+        cfg, fd = self.cfg, self._fold()
+        R, D, eos = S.R, cfg.d_model, cfg.eos_token_id
+        st = S.st
+        at, bufs, _, cross_attn = st["layer"]
+        at.anc, at.kv, at.align, at.begin = None, S.kv, None, S.begin
+        ops.whisper_embed_dev(S.last, fd["emb"], fd["dec_pos"], st["x"], S.rec, S.begin)
+        x = st["x"].view(R, D)
+        for i, W in enumerate(fd["dec"]):
+            at.i = i
+            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=S.self_attn, cross_attn=cross_attn,
+                  gemm=S.gemm)
+        ops.layernorm(x, st["xn"], *fd["dec_ln"], eps=1e-5)
+        (S.gemm or ops.gemm_f32)(st["xn"], fd["emb"], None, out=st["logits"])
+        kw = dict(suppress=fd["suppress"], begin_suppress=fd["begin_suppress"])
+        if S.kind.startswith("sample"):
+            ops.whisper_sample_pick_dev(st["logits"], S.tokens, S.last, S.done, S.alive, S.sum_logp, S.rec, eos,
+                                        cfg.timestamp_begin - 1 if ts else None, S.row_key, S.serial,
+                                        max_initial=cfg.max_initial_timestamp_index if ts else None, **kw)
+        elif ts:
+            ops.whisper_ts_pick_dev(st["logits"], S.tokens, S.last, S.done, S.alive, S.sum_logp, S.rec, eos, cfg.timestamp_begin - 1,
+                                    max_initial=cfg.max_initial_timestamp_index, **kw)
+        else:
+            ops.greedy_pick_dev(st["logits"], S.tokens, S.last, S.done, S.alive, S.rec, eos, **kw)
+
+    def _step_capture(self, S: SimpleNamespace, ts: bool) -> None:
+        """Captures ``_step_dev`` on the state's side stream: one stream, a linear chain.  Capturing executes nothing, so it
+        needs no ordering against the caller's stream, where the graph is then launched."""
+        g = ops.Graph()
+        with torch.cuda.stream(S.stream):
+            g.begin()
+            try:
+                self._step_dev(S, ts)
+            finally:
+                g.end()
+        S.graph = g
+
     def _frames_of(self, wav: Tensor, lens) -> List[int]:
         """Mel frames of every row of a batch: samples // hop, at most the chunk."""
         B, S = wav.shape
@@ -1156,7 +1295,8 @@ class Whisper(nn.Module):
                          return_token_timestamps: bool = False, frames=None, return_timestamps: bool = False,
                          stats: Optional[dict] = None, temperature: float = 0.0, seed: int = 0, row_key: Optional[Tensor] = None,
                          serial: Optional[Tensor] = None, begin: Optional[Tensor] = None, prefill: bool = False,
-                         assistant: Optional[tuple] = None, num_assistant_tokens: int = 5):
+                         assistant: Optional[tuple] = None, num_assistant_tokens: int = 5, *, step_graph: bool = False,
+                         step_gemm: str = "f32"):
         """``generate`` from the cross keys / values.  ``prompt``: ids for all rows, or [B, n0] ids.  ``return_token_timestamps``:
         one more item at the end, the times f32 [B, U] of the returned best hypothesis = ``token_timestamps`` on the returned
         tokens (a teacher-forced pass after the search, greedy or beam); ``frames``: mel frames per utterance (None: the whole
@@ -1180,7 +1320,17 @@ class Whisper(nn.Module):
         smaller ``Whisper`` with the same vocabulary, proposes up to ``num_assistant_tokens`` tokens per round from its own
         cross keys / values ``draft_kv``, and this model checks them in one pass (``decoder_append``, f5e_whisper_verify,
         f5e_whisper_accept).  Greedy only; the tokens are those of the run without an assistant, and ``stats`` also receives
-        ``assistant`` = {"rounds", "drafted", "accepted"}.  The defaults take the launches they always took."""
+        ``assistant`` = {"rounds", "drafted", "accepted"}.
+        ``step_graph``: the picks are replayed from ONE decode step captured as a hipGraph: the prompt runs as
+        above, then the step record (position, prompt length, seed, temperature) is written and the captured step, which reads
+        and advances it on the device, is launched once per token.  The state it runs on (caches ``max_target_positions`` deep,
+        its own copy of the cross keys / values, the token table) is cached on the model per (rows, pick, ``begin`` present,
+        ``step_gemm``), at most ``STEP_STATES`` of them, so only the first call of a key captures; the results are fresh
+        tensors.  Greedy, ruled and sampled picks, ``begin``, ``prefill`` and ``stats``, which also receives ``step_graph`` =
+        {"captures", "replays"}; the step that ``no_speech_logp`` is read at stays eager.  Same bits as the eager run.
+        ``step_gemm``: "f32" replays the eager step's launches; "skinny" runs the step's GEMMs through f5e_gemm_f32_skinny (at
+        most 16 rows; the same numbers up to fp32 summation order).  The defaults take the launches they always took."""
+        graphed = self._check_step_graph(step_graph, step_gemm, beam_size, return_beams, assistant, return_token_timestamps)
         n0 = _prompt_len(prompt)
         sample = self._check_sampling(temperature, seed, beam_size, return_beams)
         if assistant is not None:
@@ -1221,16 +1371,35 @@ class Whisper(nn.Module):
         if n0 < 1 or n0 >= Umax or sync_every < 1:
             raise _C.F5EError(f"Whisper.generate: a prompt of {n0} tokens leaves no room below {Umax} positions (or sync_every < 1)")
         eos = cfg.eos_token_id
-        tokens = torch.full((B, Umax), eos, dtype=I32, device=dev)
-        tokens[:, :n0] = self._prompt_rows(prompt, B, dev)
-        last = tokens[:, 0].clone()
-        done = torch.zeros(B, dtype=I32, device=dev)
-        alive = torch.full((1,), B, dtype=I32, device=dev)
-        sum_logp = torch.zeros(B, dtype=F32, device=dev) if return_timestamps or sample else None
-        if sample:
-            row_key = torch.arange(B, dtype=I32, device=dev) if row_key is None else row_key.to(dev, I32).contiguous()
-            serial = torch.zeros(B, dtype=I32, device=dev) if serial is None else serial.to(dev, I32).contiguous()
-        st = self._dec_state(B, Umax, dev)
+        S = None
+        if graphed:                          # the cached state's buffers in the place of fresh ones; everything else as below
+            kind = ("sample" if sample else "greedy") + ("_ts" if return_timestamps else "")
+            S = self._step_state(B, kind, begin is not None, step_gemm, kv[0][0].shape[1], dev)
+            self._step_load(S, kv)
+            kv, st, tokens, last, done, alive = S.kv, S.st, S.tokens[:, :Umax], S.last, S.done, S.alive
+            tokens.fill_(eos)
+            tokens[:, :n0] = self._prompt_rows(prompt, B, dev)
+            last.copy_(tokens[:, 0])
+            done.zero_()
+            alive.fill_(B)
+            sum_logp = S.sum_logp.zero_() if return_timestamps or sample else None
+            if sample:
+                row_key = S.row_key.copy_(torch.arange(B, dtype=I32, device=dev) if row_key is None else row_key.to(dev, I32))
+                serial = S.serial.zero_() if serial is None else S.serial.copy_(serial.to(dev, I32))
+            if begin is not None:
+                begin = S.begin.copy_(begin)
+            armed, counts = False, dict(captures=0, replays=0)
+        else:
+            tokens = torch.full((B, Umax), eos, dtype=I32, device=dev)
+            tokens[:, :n0] = self._prompt_rows(prompt, B, dev)
+            last = tokens[:, 0].clone()
+            done = torch.zeros(B, dtype=I32, device=dev)
+            alive = torch.full((1,), B, dtype=I32, device=dev)
+            sum_logp = torch.zeros(B, dtype=F32, device=dev) if return_timestamps or sample else None
+            if sample:
+                row_key = torch.arange(B, dtype=I32, device=dev) if row_key is None else row_key.to(dev, I32).contiguous()
+                serial = torch.zeros(B, dtype=I32, device=dev) if serial is None else serial.to(dev, I32).contiguous()
+            st = self._dec_state(B, Umax, dev)
         first_p = 0
         if prefill and n0 > 1:
             first_p = n0 - 1
@@ -1244,6 +1413,18 @@ class Whisper(nn.Module):
             forced = p + 1 < n0
             if p == Umax - 2 and begin is not None and stats is not None:
                 at_bound = 1 - done                          # rows still open when the last step of the shared bound runs
+            if S is not None and not forced and not (p == sot_pos and stats is not None):
+                if not armed:                # the record once per call; the step advances it on the device from here on
+                    S.rec.copy_(ops.whisper_step_record(p, n0, seed if sample else 0, temperature if sample else 0.0))
+                    armed = True
+                    if S.graph is None:
+                        self._step_capture(S, bool(return_timestamps))
+                        counts["captures"] += 1
+                S.graph.launch()
+                counts["replays"] += 1
+                if (p + 2 - n0) % sync_every == 0 and int(alive.item()) == 0:
+                    break
+                continue
             logits = self._dec_step(st, kv, last, p, not forced or (p == sot_pos and stats is not None), begin=begin)
             if p == sot_pos and stats is not None:
                 stats["no_speech_logp"] = self._no_speech_logp(logits)
@@ -1263,6 +1444,12 @@ class Whisper(nn.Module):
                                 begin_suppress=fd["begin_suppress"], first_step=p + 1 == n0)
             if (p + 2 - n0) % sync_every == 0 and int(alive.item()) == 0:
                 break
+        if S is not None:                    # fresh tensors, never views of the state
+            S.captures, S.replays = S.captures + counts["captures"], S.replays + counts["replays"]
+            tokens = tokens.clone(memory_format=torch.contiguous_format)
+            sum_logp = None if sum_logp is None else sum_logp.clone()
+            if stats is not None:
+                stats["step_graph"] = counts
         # a finished row holds eos from its end on (done rows keep getting eos; untouched columns were eos from the start)
         gen = tokens[:, n0:]
         is_eos = gen == eos
@@ -1548,7 +1735,8 @@ class Whisper(nn.Module):
                  max_new_tokens: Optional[int] = None, sync_every: int = 8, beam_size: int = 1, length_penalty: float = 1.0,
                  return_beams: bool = False, return_token_timestamps: bool = False, return_timestamps: bool = False,
                  temperature: float = 0.0, seed: int = 0, assistant: Optional["Whisper"] = None, num_assistant_tokens: int = 5,
-                 assistant_shares_encoder: bool = False, stats: Optional[dict] = None):
+                 assistant_shares_encoder: bool = False, stats: Optional[dict] = None, *, step_graph: bool = False,
+                 step_gemm: str = "f32"):
         """Recognition of B utterances: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> (tokens i32 [B, U] starting
         with the prompt, eos from a row's end on; n i32 [B] = tokens of every row, its closing eos included when it ended by
         itself).  The host reads the alive count every ``sync_every`` steps; the result does not depend on it.  The bound is
@@ -1565,7 +1753,22 @@ class Whisper(nn.Module):
         ``assistant``: a draft ``Whisper`` for assisted generation (``generate_from_kv(assistant=)``; greedy only, the same
         tokens as without it).  ``assistant_shares_encoder`` False: the draft encodes the same audio itself; True: its cross keys
         and values are projected from THIS model's encoder output (large-v3-turbo and distil-whisper drafts; equal ``d_model``
-        and encoder shape, checked).  ``stats`` (with an assistant): receives what ``generate_from_kv`` puts there."""
+        and encoder shape, checked).  ``stats`` (with an assistant or ``step_graph``): receives what ``generate_from_kv`` puts
+        there.  ``step_graph`` / ``step_gemm``: the picks are replayed from a captured decode step (``generate_from_kv``; greedy,
+        ruled or sampled, one row per utterance)."""
+        if self._check_step_graph(step_graph, step_gemm, beam_size, return_beams, assistant, return_token_timestamps):
+            self._check_sampling(temperature, seed, beam_size, return_beams)
+            if return_timestamps:
+                self.cfg.timestamp_begin                                    # refused by name before any launch
+            elif language is not None:
+                self.prompt_ids(language, task)
+            enc = self.encode_features(self.features(wav, lens))
+            kind = ("sample" if temperature > 0 else "greedy") + ("_ts" if return_timestamps else "")
+            S = self._step_state(enc.shape[0], kind, False, step_gemm, enc.shape[1], enc.device)
+            kv = self.cross_kv(enc, out=S.xkv)               # straight into the state the call below finds under the same key
+            return self.generate_from_kv(kv, self._prompts(kv, language, task, return_timestamps), max_new_tokens, sync_every, 1,
+                                         length_penalty, return_timestamps=return_timestamps, stats=stats, temperature=temperature,
+                                         seed=seed, step_graph=True, step_gemm=step_gemm)
         if assistant is not None:
             self._check_sampling(temperature, seed, beam_size, return_beams)
             self._check_assistant(assistant, num_assistant_tokens, beam_size, return_beams, temperature)
@@ -1609,8 +1812,8 @@ class Whisper(nn.Module):
                         no_speech_threshold: Optional[float] = None, logprob_threshold: Optional[float] = None,
                         sync_every: int = 8, fallback: Optional[Fallback] = None, row_keys: Optional[Sequence[int]] = None,
                         trace: Optional[list] = None, context: Optional[Context] = None, assistant: Optional["Whisper"] = None,
-                        num_assistant_tokens: int = 5, assistant_shares_encoder: bool = False,
-                        **unbuilt) -> List[List[Segment]]:
+                        num_assistant_tokens: int = 5, assistant_shares_encoder: bool = False, *, step_graph: bool = False,
+                        step_gemm: str = "f32", **unbuilt) -> List[List[Segment]]:
         """Recordings of any length: wav f32 [B, S] at 16 kHz on the GPU, lens samples per row -> the segments of every row.
         The seek loop of ``transformers``' long-form ``generate`` (``return_timestamps=True``, ``condition_on_prev_tokens=False``,
         temperature 0): every window of ``n_frames`` mel frames is decoded with timestamp tokens, cut into segments at the
@@ -1656,7 +1859,13 @@ class Whisper(nn.Module):
         ``assistant`` (a draft ``Whisper``; ``generate``): every temperature-0 attempt is assisted generation under the timestamp
         rules; sampled attempts of a ``fallback`` take the path without it.  The draft reads the window's features (computed
         once, with this model's front-end) through its own encoder, or with ``assistant_shares_encoder`` this model's encoder
-        output.  Segments, seeks and tokens are those of the run without an assistant."""
+        output.  Segments, seeks and tokens are those of the run without an assistant.
+        ``step_graph`` / ``step_gemm`` (``generate_from_kv``): every attempt's picks are replayed from a captured decode step,
+        ``beam_size`` 1 only; an attempt with another row count or a sampled one runs on another cached state.  Segments,
+        seeks and tokens are those of the eager run."""
+        skw = {}
+        if self._check_step_graph(step_graph, step_gemm, beam_size, False, assistant, False):
+            skw = dict(step_graph=True, step_gemm=step_gemm)
         if assistant is not None:
             self._check_assistant(assistant, num_assistant_tokens, beam_size, False, 0.0)
             self._check_shared_encoder(assistant, assistant_shares_encoder, "transcribe_long")
@@ -1744,7 +1953,7 @@ class Whisper(nn.Module):
                     rows = [act[i] for i in pend]
                     fulls, sum_logp, ns_logp = self._decode_with_context(
                         kv, plist, pend, temp, beam_size, sync_every, 0 if fallback is None else fallback.seed,
-                        [keys[b] for b in rows], [serial[b] for b in rows], *(() if asst is None else (asst,)))
+                        [keys[b] for b in rows], [serial[b] for b in rows], *(() if asst is None else (asst,)), **skw)
                     if temp > 0:
                         for b in rows:
                             serial[b] += 1
@@ -1764,12 +1973,12 @@ class Whisper(nn.Module):
                         tokens, n = self.generate_from_kv(
                             sub, sub_prompt, None, sync_every, 1, 1.0, return_timestamps=True, stats=stats, temperature=temp,
                             seed=fallback.seed, row_key=torch.tensor([keys[b] for b in rows], dtype=I32).to(dev),
-                            serial=torch.tensor([serial[b] for b in rows], dtype=I32).to(dev))[:2]
+                            serial=torch.tensor([serial[b] for b in rows], dtype=I32).to(dev), **skw)[:2]
                         for b in rows:
                             serial[b] += 1
                     else:
                         tokens, n = self.generate_from_kv(sub, sub_prompt, None, sync_every, beam_size, 1.0, return_timestamps=True,
-                                                          stats=stats, **akw)[:2]
+                                                          stats=stats, **akw, **skw)[:2]
                     tokens, n = tokens.tolist(), n.tolist()
                     fulls = [tokens[j][n0:n[j]] for j in range(len(pend))]
                     sum_logp, ns_logp = stats["sum_logp"].tolist(), stats["no_speech_logp"].tolist()
@@ -1808,14 +2017,15 @@ class Whisper(nn.Module):
                     history[b].extend(tok for _, _, tok in parts)
                 seek[b] += step
 
-    def _decode_with_context(self, kv, plist, ix, temp, beam_size, sync_every, seed, keys, serial, asst=None):
+    def _decode_with_context(self, kv, plist, ix, temp, beam_size, sync_every, seed, keys, serial, asst=None, **skw):
         """One attempt of the windows ``ix`` (indices into ``kv`` and ``plist``, the rows' decoder inputs) at ``temp`` ->
         (generated tokens with the closing eos, sum_logp, no_speech_logp) per row of ``ix``, each what the row's own B = 1 run
         gives.  Temperature 0: the rows are left-padded to their longest prompt and decoded together; the bound counts the pad
         columns, so a padded row that was still open when the last step of that shared bound ran (``at_bound``) is decoded again
         alone, with its own bound.  A sampled attempt keys its noise by the position, which padding would shift, so rows are
         batched only with rows of their own prompt length (a batch that falls back with ragged prompts costs one decode per
-        length, not one per row).  ``asst`` = (draft, draft_kv, num_assistant_tokens): the temperature-0 decodes are assisted."""
+        length, not one per row).  ``asst`` = (draft, draft_kv, num_assistant_tokens): the temperature-0 decodes are assisted.
+        ``skw``: ``step_graph`` / ``step_gemm`` for every decode."""
         eos, dev, res = self.cfg.eos_token_id, kv[0][0].device, {}
 
         def run(group):
@@ -1836,7 +2046,7 @@ class Whisper(nn.Module):
                           serial=torch.tensor([serial[j] for j in at], dtype=I32).to(dev))
             tokens, n = self.generate_from_kv(sub, [[eos] * pad + r for pad, r in zip(begin, rows)], None, sync_every,
                                               1 if temp > 0 else beam_size, 1.0, return_timestamps=True, stats=st, begin=begin,
-                                              prefill=True, **kw)[:2]
+                                              prefill=True, **kw, **skw)[:2]
             tokens, n = tokens.tolist(), n.tolist()
             sl, ns, open_ = st["sum_logp"].tolist(), st["no_speech_logp"].tolist(), st["at_bound"].tolist()
             for j, i in enumerate(group):
@@ -1877,7 +2087,7 @@ class WhisperRecognizer:
     def __init__(self, path: str, device="cuda", language: Optional[str] = "en", beam_size: int = 1, long_form: bool = False,
                  fallback: Optional[Fallback] = None, initial_prompt: Optional[str] = None,
                  condition_on_previous_text: bool = False, assistant_dir: Optional[str] = None, num_assistant_tokens: int = 5,
-                 assistant_shares_encoder: bool = False):
+                 assistant_shares_encoder: bool = False, step_graph: bool = False, step_gemm: str = "f32"):
         """``language``: a name or code, or None / "auto" to detect it per recording.  ``long_form``: ``transcribe`` runs the
         seek loop over the whole recording (``Whisper.transcribe_long``) instead of cutting it to the first chunk.  ``fallback``:
         the temperature fallback of that loop (needs ``long_form``).  ``initial_prompt``: text (a name, a domain word; ``Whisper.get_prompt_ids``, so
@@ -1887,7 +2097,13 @@ class WhisperRecognizer:
         ``long_form``.  ``assistant_dir``: a local directory of a draft model (large-v3-turbo, a distil-whisper checkpoint) for
         assisted generation with ``num_assistant_tokens`` drafts per round: the same transcripts, fewer passes of the large
         decoder; greedy only (``beam_size`` 1).  ``assistant_shares_encoder``: the draft has no encoder of its own to run and
-        reads this model's encoder output."""
+        reads this model's encoder output.  ``step_graph`` / ``step_gemm``: ``transcribe`` and ``transcribe_segments`` replay
+        their picks from a captured decode step (``Whisper.generate_from_kv``; ``beam_size`` 1, no assistant): the same
+        transcripts; the replay alone is level with the eager step, ``step_gemm="skinny"`` takes 1.7x .. 1.95x off a token at
+        the large-v3 / turbo decoder shapes."""
+        self._step = {}
+        if Whisper._check_step_graph(step_graph, step_gemm, beam_size, False, assistant_dir, False):
+            self._step = dict(step_graph=True, step_gemm=step_gemm)
         if fallback is not None and not (long_form and isinstance(fallback, Fallback)):
             raise _C.F5EError("WhisperRecognizer: fallback needs long_form=True and a Fallback record")
         if (initial_prompt is not None or condition_on_previous_text) and not long_form:
@@ -1954,7 +2170,7 @@ class WhisperRecognizer:
         if getattr(self, "long_form", False):
             return "".join(text for _, _, text in self.transcribe_segments(audio, sr)).strip()
         tokens, n = self.model.generate(self._audio(audio, sr), None, self._lang(), beam_size=self.beam_size,
-                                        **getattr(self, "_assist", {}))
+                                        **getattr(self, "_assist", {}), **getattr(self, "_step", {}))
         return self.model.decode_ids(tokens[0, :int(n[0])].tolist()).strip()
 
     @torch.no_grad()
@@ -1964,6 +2180,7 @@ class WhisperRecognizer:
         if getattr(self, "context", None) is not None:
             kw["context"] = self.context
         kw.update(getattr(self, "_assist", {}))
+        kw.update(getattr(self, "_step", {}))
         segs = self.model.transcribe_long(self._audio(audio, sr, cut=False), None, self._lang(), beam_size=self.beam_size, **kw)[0]
         return [(s.start_s, s.end_s, self.model.decode_ids(s.tokens)) for s in segs]
 

@@ -76,6 +76,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--whisper_assistant", type=str, default=None, metavar="DIR",
                    help="--whisper_dir: a local draft model directory (whisper-large-v3-turbo, distil-whisper) for assisted "
                         "generation: the same transcript with fewer passes of the large decoder; greedy only")
+    p.add_argument("--whisper_step_graph", action="store_true",
+                   help="--whisper_dir: replay every pick of the transcription from one decode step captured as a hipGraph (the "
+                        "same transcript; --whisper_beam 1, no --whisper_assistant)")
     p.add_argument("--whisper_prompt", type=str, default=None, metavar="TEXT",
                    help="--whisper_dir: an initial prompt for the transcription (a name, a domain word), in front of every window; the "
                         "reference audio is then transcribed with the long-form loop")
@@ -232,6 +235,8 @@ def main(argv=None):
         prompt = {} if args.whisper_prompt is None else dict(long_form=True, initial_prompt=args.whisper_prompt)
         if args.whisper_assistant is not None:
             prompt["assistant_dir"] = args.whisper_assistant
+        if args.whisper_step_graph:
+            prompt["step_graph"] = True
         transcriber = WhisperRecognizer(args.whisper_dir, s["device"], args.ref_language, beam_size=args.whisper_beam, **prompt)
     for v in voices.values():   # reference infer_cli.py:297-303
         v["ref_audio"], v["ref_text"] = U.preprocess_ref_audio_text(v["ref_audio"], v["ref_text"], transcriber=transcriber)

@@ -2048,6 +2048,147 @@ def whisper_sample_pick(logits: Tensor, tokens: Tensor, last: Tensor, done: Tens
     return last
 
 
+# ---- Whisper's decode step with the position on the device (csrc/whisper_step.hip) ----
+
+STEP_REC_WORDS = 8     # the step record: i32 [8] = p, n0, seed_lo, seed_hi, temperature bits, 3 reserved words
+
+
+def whisper_step_record(p: int, n0: int, seed: int = 0, temperature: float = 0.0) -> Tensor:
+    """The step record's words as a HOST i32 [8] tensor, to be copied into the device record: p, n0, the seed's low / high
+    word, the fp32 temperature's bits, three zeros."""
+    import struct
+    if not 0 <= int(seed) < 1 << 64:
+        raise _C.F5EError(f"whisper_step_record: the seed must lie in 0 .. 2^64 - 1 (got {seed})")
+
+    def i32(u):
+        return u - (1 << 32) if u >= 1 << 31 else u
+    seed = int(seed)
+    bits = struct.unpack("<I", struct.pack("<f", float(temperature)))[0]
+    return torch.tensor([int(p), int(n0), i32(seed & 0xffffffff), i32(seed >> 32), i32(bits), 0, 0, 0], dtype=I32)
+
+
+def _rec(rec: Tensor, name: str):
+    if not isinstance(rec, Tensor) or not rec.is_cuda:
+        raise _C.F5EError(f"{name}: the step record must live on the GPU; there is no CPU path")
+    return _vec(rec, I32, f"{name}: rec", (STEP_REC_WORDS,), align=16)
+
+
+def attn_decode_dev_f32(qkv: Tensor, kc: Tensor, vc: Tensor, rec: Tensor, heads: int, scale: float, out: Optional[Tensor] = None,
+                        begin: Optional[Tensor] = None):
+    """``attn_decode_f32`` without an ancestry table at the position the step record holds (f5e_attn_decode_dev_f32): qkv f32
+    [R, >= 3 D], kc / vc f32 [R, P, D] views of the layer's caches (the strides ``attn_decode_f32`` takes), rec i32 [8] on the
+    device, begin i32 [R] on the device or None -> out f32 [R, D].  p = rec[0] clamped to [0, P - 1] on the device; slot [r, p]
+    of both caches receives the step's k / v.  The launch does not depend on p, so it can be captured once."""
+    if not isinstance(qkv, Tensor) or qkv.ndim != 2 or kc.ndim != 3 or kc.shape != vc.shape or kc.stride() != vc.stride():
+        raise _C.F5EError("attn_decode_dev_f32: qkv [R, >= 3 D] and kc, vc [R, P, D] with equal strides; there is no CPU path")
+    R, P, D = kc.shape
+    for t, nm in ((qkv, "qkv"), (kc, "kc"), (vc, "vc")):
+        if not t.is_cuda or t.dtype != F32 or t.stride(-1) != 1:
+            raise _C.F5EError(f"attn_decode_dev_f32: {nm} must be an f32 GPU tensor with unit channel stride; there is no CPU path")
+    if qkv.shape[0] != R or D % heads:
+        raise _C.F5EError(f"attn_decode_dev_f32: qkv rows {qkv.shape[0]} != {R}, heads {heads} must divide {D}")
+    pos_stride = kc.stride(1) if P > 1 else max(D, kc.stride(1))
+    row_stride = kc.stride(0) if R > 1 else max(kc.stride(0), (P - 1) * pos_stride + D)
+    for t in (kc, vc):
+        have = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+        if pos_stride < D or row_stride < (P - 1) * pos_stride + D or have < (R - 1) * row_stride + (P - 1) * pos_stride + D \
+                or pos_stride % 4 or row_stride % 4 or t.data_ptr() % 16:
+            raise _C.F5EError(f"attn_decode_dev_f32: cache strides ({row_stride}, {pos_stride}) must be multiples of 4 spanning "
+                              f"[{R}, {P}, {D}] inside the storage, kc and vc 16-byte aligned")
+    qp, ldq = _rows(qkv, (F32,), "attn_decode_dev_f32: qkv", 3 * D)
+    rp = _rec(rec, "attn_decode_dev_f32")
+    bp = None if begin is None else _vec(begin, I32, "attn_decode_dev_f32: begin", (R,))
+    require_device()
+    out = torch.empty(R, D, dtype=F32, device=qkv.device) if out is None else out
+    if out.shape != (R, D):
+        raise _C.F5EError(f"attn_decode_dev_f32: out must be [{R}, {D}]")
+    op, ldo = _rows(out, (F32,), "attn_decode_dev_f32: out", D, vec=1)
+    check(lib().f5e_attn_decode_dev_f32(_stream(), qp, ldq, C.c_void_p(kc.data_ptr()), C.c_void_p(vc.data_ptr()), row_stride,
+                                        pos_stride, bp, op, ldo, R, P, heads, D // heads, rp, float(scale)),
+          "f5e_attn_decode_dev_f32")
+    return out
+
+
+def whisper_embed_dev(last: Tensor, emb: Tensor, pos: Tensor, out: Tensor, rec: Tensor, begin: Optional[Tensor] = None):
+    """out[r] = emb[last[r]] + pos[max(p - begin[r], 0)] with p from the step record (f5e_whisper_embed_dev): last i32 [R], emb f32
+    [V, D], pos f32 [P, D], begin i32 [R] or None, rec i32 [8], out f32 [R, D] (or [R, 1, D]), all contiguous on the device."""
+    if not isinstance(last, Tensor) or last.ndim != 1 or emb.ndim != 2 or pos.ndim != 2 or out.ndim not in (2, 3):
+        raise _C.F5EError("whisper_embed_dev: last [R], emb [V, D], pos [P, D] and out [R, D]; there is no CPU path")
+    R, D = last.shape[0], emb.shape[1]
+    if R < 1 or out.numel() != R * D or out.shape[0] != R or out.shape[-1] != D or pos.shape[1] != D or D % 4:
+        raise _C.F5EError(f"whisper_embed_dev: last {tuple(last.shape)}, emb {tuple(emb.shape)}, pos {tuple(pos.shape)}, out "
+                          f"{tuple(out.shape)}: out must be [R, D] and D a multiple of 4")
+    for t, nm in ((emb, "emb"), (pos, "pos"), (out, "out")):
+        if t.is_cuda and t.data_ptr() % 16:
+            raise _C.F5EError(f"whisper_embed_dev: {nm} must be 16-byte aligned")
+    bp = None if begin is None else _vec(begin, I32, "whisper_embed_dev: begin", (R,))
+    ptrs = (_p(last, I32, "whisper_embed_dev: last"), bp, _p(emb, F32, "whisper_embed_dev: emb"),
+            _p(pos, F32, "whisper_embed_dev: pos"), _p(out, F32, "whisper_embed_dev: out"))
+    rp = _rec(rec, "whisper_embed_dev")
+    require_device()
+    check(lib().f5e_whisper_embed_dev(_stream(), *ptrs, R, D, rp, pos.shape[0], emb.shape[0]), "f5e_whisper_embed_dev")
+    return out
+
+
+def _pick_dev_common(name: str, logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, rec: Tensor,
+                     V: Optional[int], suppress, begin_suppress):
+    if not isinstance(logits, Tensor) or logits.ndim != 2 or tokens.ndim != 2 or tokens.shape[0] != logits.shape[0]:
+        raise _C.F5EError(f"{name}: logits [R, >= V] and tokens [R, >= 2]; there is no CPU path")
+    R = logits.shape[0]
+    V = logits.shape[1] if V is None else int(V)
+    if V > logits.shape[1]:
+        raise _C.F5EError(f"{name}: V = {V} exceeds the {logits.shape[1]} columns of logits")
+    if last.shape != (R,) or done.shape != (R,) or alive.numel() != 1:
+        raise _C.F5EError(f"{name}: last [{R}], done [{R}], alive [1]")
+    lp, ld = _rows(logits, (F32,), f"{name}: logits", max(V, 1), vec=1)
+    tp, ld_tok = _rows(tokens, (I32,), f"{name}: tokens", 2, vec=1)
+    head = (_stream(), lp, ld, _p(suppress, I32, "suppress"), suppress.numel() if suppress is not None else 0,
+            _p(begin_suppress, I32, "begin_suppress"), begin_suppress.numel() if begin_suppress is not None else 0, tp, ld_tok,
+            tokens.shape[1], _p(last, I32, "last"), _p(done, I32, "done"), _p(alive, I32, "alive"))
+    return head, R, V, _rec(rec, name)
+
+
+def greedy_pick_dev(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, rec: Tensor, eos: int, *,
+                    V: Optional[int] = None, suppress: Optional[Tensor] = None, begin_suppress: Optional[Tensor] = None):
+    """f5e_greedy_pick_dev: ``greedy_pick`` at the step record's position (p clamped to the token table; ``begin_suppress``
+    counts iff p + 1 == n0), then ``alive`` and p += 1 by one thread.  rec i32 [8] on the device."""
+    head, R, V, rp = _pick_dev_common("greedy_pick_dev", logits, tokens, last, done, alive, rec, V, suppress, begin_suppress)
+    require_device()
+    check(lib().f5e_greedy_pick_dev(*head, R, V, rp, int(eos)), "f5e_greedy_pick_dev")
+    return last
+
+
+def whisper_ts_pick_dev(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, sum_logp: Tensor, rec: Tensor,
+                        eos: int, no_timestamps: int, *, V: Optional[int] = None, suppress: Optional[Tensor] = None,
+                        begin_suppress: Optional[Tensor] = None, max_initial: Optional[int] = None):
+    """f5e_whisper_ts_pick_dev: ``whisper_ts_pick`` with p and n0 from the step record, then ``alive`` and p += 1."""
+    head, R, V, rp = _pick_dev_common("whisper_ts_pick_dev", logits, tokens, last, done, alive, rec, V, suppress, begin_suppress)
+    if sum_logp.shape != (R,):
+        raise _C.F5EError(f"whisper_ts_pick_dev: sum_logp [{R}]")
+    require_device()
+    check(lib().f5e_whisper_ts_pick_dev(*head, _p(sum_logp, F32, "sum_logp"), R, V, rp, int(eos), int(no_timestamps),
+                                        -1 if max_initial is None else int(max_initial)), "f5e_whisper_ts_pick_dev")
+    return last
+
+
+def whisper_sample_pick_dev(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, sum_logp: Tensor,
+                            rec: Tensor, eos: int, no_timestamps: Optional[int], row_key: Tensor, serial: Tensor, *,
+                            V: Optional[int] = None, suppress: Optional[Tensor] = None, begin_suppress: Optional[Tensor] = None,
+                            max_initial: Optional[int] = None):
+    """f5e_whisper_sample_pick_dev: ``whisper_sample_pick`` with p, n0, the seed and the temperature from the step record
+    (``whisper_step_record``), then ``alive`` and p += 1."""
+    head, R, V, rp = _pick_dev_common("whisper_sample_pick_dev", logits, tokens, last, done, alive, rec, V, suppress,
+                                      begin_suppress)
+    if sum_logp.shape != (R,) or row_key.shape != (R,) or serial.shape != (R,):
+        raise _C.F5EError(f"whisper_sample_pick_dev: sum_logp [{R}], row_key [{R}], serial [{R}]")
+    require_device()
+    check(lib().f5e_whisper_sample_pick_dev(*head, _p(sum_logp, F32, "sum_logp"), R, V, rp, int(eos),
+                                            -1 if no_timestamps is None else int(no_timestamps),
+                                            -1 if max_initial is None else int(max_initial), _p(row_key, I32, "row_key"),
+                                            _p(serial, I32, "serial")), "f5e_whisper_sample_pick_dev")
+    return last
+
+
 def whisper_ts_rule(logits: Tensor, tokens: Tensor, p: int, n0: int, eos: int, no_timestamps: int, *, V: Optional[int] = None,
                     suppress: Optional[Tensor] = None, begin_suppress: Optional[Tensor] = None, max_initial: Optional[int] = None,
                     out: Optional[Tensor] = None) -> Tensor:

@@ -1002,6 +1002,39 @@ F5E_API int f5e_gemm_f32_skinny(f5e_stream st, const float* A, int lda, const fl
                         const float* addend, int ld_add, float* out, int ldo, void* workspace,
                         unsigned long long workspace_bytes, int M, int N, int K);
 
+/* ---- Whisper's decode step with the position on the device (csrc/whisper_step.hip): what a hipGraph of ONE step needs so that
+ * it can be captured once and replayed per token.  Everything that changes from token to token is read from the
+ * step record `rec`, DEVICE i32 [8], 16-byte aligned:
+ *   rec[0] p (the position fed; the pick writes token column p + 1), rec[1] n0 (the prompt length; first_step = p + 1 == n0),
+ *   rec[2], rec[3] the low / high word of the sampled pick's seed, rec[4] the bits of its fp32 temperature, rec[5..7] reserved.
+ * The arithmetic is that of the host-position entry points (one body each), so the bits are theirs.  Every kernel clamps what
+ * it reads from the record to the extents of its launch, the grids do not depend on it, and no kernel waits for another
+ * workgroup.  p is advanced by exactly one thread: thread 0 of the one-workgroup launch that follows a pick.
+ *
+ * f5e_attn_decode_dev_f32: f5e_attn_decode_f32 (begin NULL) / f5e_attn_decode_from_f32 without an ancestry table, at
+ * p = clamp(rec[0], 0, P - 1), P = the cached positions per row.  Grid (H, R).  Limits as there. */
+F5E_API int f5e_attn_decode_dev_f32(f5e_stream st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                            int pos_stride, const int* begin, float* out, int ldo, int R, int P, int H, int dk, const int* rec,
+                            float scale);
+/* out[r] = emb[last[r]] + pos[p - begin[r]] with p = max(rec[0], 0), begin[r] clamped to [0, p] (NULL: 0) and the row of pos
+ * to the table: f5e_whisper_embed with U = 1 (and f5e_text_gather with one position row).  last i32 [R], out f32 [R][D]. */
+F5E_API int f5e_whisper_embed_dev(f5e_stream st, const int* last, const int* begin, const float* emb, const float* pos, float* out,
+                          int R, int D, const int* rec, int max_pos, int table_rows);
+/* f5e_greedy_pick / f5e_whisper_ts_pick / f5e_whisper_sample_pick at p = clamp(rec[0], 0, n_tok - 2), n_tok = the columns of a
+ * token row (ld_tok its stride), n0 = rec[1] (the ruled picks: clamped to [1, p + 1]), begin_suppress counted iff p + 1 == n0,
+ * the seed and the temperature from the record; then one workgroup writes *alive and rec[0] += 1.  Nothing else of the record
+ * is written. */
+F5E_API int f5e_greedy_pick_dev(f5e_stream st, const float* logits, long long ld, const int* suppress, int n_sup,
+                        const int* begin_suppress, int n_beg, int* tokens, int ld_tok, int n_tok, int* last, int* done, int* alive,
+                        int R, int V, int* rec, int eos);
+F5E_API int f5e_whisper_ts_pick_dev(f5e_stream st, const float* logits, long long ld, const int* suppress, int n_sup,
+                            const int* begin_suppress, int n_beg, int* tokens, int ld_tok, int n_tok, int* last, int* done,
+                            int* alive, float* sum_logp, int R, int V, int* rec, int eos, int no_timestamps, int max_initial);
+F5E_API int f5e_whisper_sample_pick_dev(f5e_stream st, const float* logits, long long ld, const int* suppress, int n_sup,
+                                const int* begin_suppress, int n_beg, int* tokens, int ld_tok, int n_tok, int* last, int* done,
+                                int* alive, float* sum_logp, int R, int V, int* rec, int eos, int no_timestamps, int max_initial,
+                                const int* row_key, const int* serial);
+
 /* ---------------------------------------------------------------- UTMOS (csrc/utmos.hip) ---------------------- */
 /* The UTMOS predictor (utmos22_strong, reference eval/eval_utmos.py): a wav2vec2-base upstream (group-norm feature extractor,
  * post-LayerNorm encoder), a BiLSTM over its frames and a per-frame score averaged per utterance.  The strided convolutions 1-6,

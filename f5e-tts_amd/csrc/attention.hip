@@ -249,8 +249,10 @@ __global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) { 
       const f32x2 ml = *(const f32x2*)(red + (w - 1) * 64 * 34 + 64 * 32 + lane * 2);
       const float m_new = fmaxf(m_run, ml[0]);
       // a wave that saw no tile has m = -inf, l = 0, O = 0: its factor is exp2(-inf) = 0 (m_new is finite because
-      // wave 0 always owns tile 0 when kv_len > 0)
-      const float fa = fast_exp2(m_run - m_new), fb = fast_exp2(ml[0] - m_new);
+      // wave 0 always owns tile 0 when kv_len > 0).  kv_len = 0 leaves EVERY wave at -inf: against the clamped maximum the
+      // differences stay -inf (factors 0, output rows 0) instead of -inf - -inf = NaN; a finite m_new is unchanged by it
+      const float m_ref = fmaxf(m_new, -3.4028234663852886e38f);
+      const float fa = fast_exp2(m_run - m_ref), fb = fast_exp2(ml[0] - m_ref);
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const f32x4 s0 = sq[g * 64 + lane], s1 = sq[(4 + g) * 64 + lane];
@@ -466,8 +468,9 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_b1_kernel(AttnArgs a) {   // 
       const f32x2 ml = *(const f32x2*)(red + w * PART + 64 * 32 + lane * 2);
       const float m_new = fmaxf(m_mrg, ml[0]);
       // a wave that saw no tile has m = -inf, l = 0, O = 0: its factor is exp2(-inf) = 0 (m_new is finite because
-      // wave 0 always owns tile 0 when kv_len > 0)
-      const float fa = fast_exp2(m_mrg - m_new), fb = fast_exp2(ml[0] - m_new);
+      // wave 0 always owns tile 0 when kv_len > 0; kv_len = 0: the clamp, as in attn_fwd_kernel's merge)
+      const float m_ref = fmaxf(m_new, -3.4028234663852886e38f);
+      const float fa = fast_exp2(m_mrg - m_ref), fb = fast_exp2(ml[0] - m_ref);
       const f32x4 s0 = sq[g * 64 + lane], s1 = sq[(4 + g) * 64 + lane];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {

@@ -117,6 +117,7 @@ F5E_API int f5e_gemm_bf16_qkv_rope_ln(f5e_stream st, const void* A, int lda, con
 /* ---------------------------------------------------------------- attention ---------------------------------- */
 
 /* o[S*rows_per_seq][ldo] (bf16, column = head*64 + d) = softmax(q k^T / 8 + keymask) v, keys >= kv_len[s] masked.
+ * kv_len[s] above rows_per_seq counts as rows_per_seq; kv_len[s] = 0 (no key at all) gives all-zero rows for sequence s.
  * q as f5e_gemm_bf16_qkv_rope writes it: already multiplied by log2(e) / 8, so the kernel computes 2^(q' k^T - max).
  * q, k, v use the fragment-major layouts documented in csrc/attention.hip; splits: KV splits per 32-query tile
  * (0 = auto, 1, 2 or 4; -1 = the LDS-shared 128-query kernel that auto picks for large problems).

@@ -37,6 +37,7 @@
 //     bf16 P operand as accurate as at any other scale.  Rare by construction: every pass through it raises a query's
 //     m_run by at least ~19 octaves.
 // Left per step: 32 v_exp, 32 v_add (row sums, half-wave partials: the two halves meet once at the end), 16 v_cvt_pk.
+#include <cstddef>
 #include <cstdlib>
 #include "attention_step.h"
 
@@ -53,6 +54,19 @@ struct AttnArgs {
   unsigned long long* trace;   // tools build: [workgroup][wave][8] timestamps of the traced kernel builds (f5e_debug_attn_trace)
 #endif
 };
+
+// attn_fwd_kernel / attn_fwd_b1_kernel take what they need before (and for) their first Q / K / V loads once more as LEADING
+// SCALAR parameters, 14 dwords: built with -amdgpu-kernarg-preload-count=16 these arrive in SGPRs at wave launch, and no
+// (cold) scalar-cache miss of the kernarg segment stands in front of the loads.  An aggregate is never preloaded and ends the
+// preloaded run, so the struct goes last (ldo, pf, trace are read from it).  One list for the signatures and the launches:
+#define F5E_ATTN_HOT_PARAMS                                                                                              \
+  const bf16 *h_q, const bf16 *h_k, const bf16 *h_v, bf16 *h_o, const int *h_kv_len, int h_n_pad, int h_H,               \
+      int h_rows_per_seq, int h_n_main
+#define F5E_ATTN_HOT_ARGS(a) (a).q, (a).k, (a).v, (a).o, (a).kv_len, (a).n_pad, (a).H, (a).rows_per_seq, (a).n_main
+enum { F5E_ATTN_HOT_DWORDS = 14 };
+// a.ldo is wanted by the output stores only: requested late, under the loads' flight (f5e_kernarg_late, f5e_common.h)
+static_assert(alignof(AttnArgs) == 8 && F5E_ATTN_HOT_DWORDS * 4 % 8 == 0, "AttnArgs sits right behind the scalar parameters");
+__device__ __forceinline__ int attn_ldo_late() { return f5e_kernarg_late<int>(F5E_ATTN_HOT_DWORDS * 4 + offsetof(AttnArgs, ldo)); }
 
 // In-kernel timeline of the TOOLS build (tools/attn_timeline.py): ATTN_STAMP(i) reads the shader clock into ts[i],
 // ATTN_LANDED(n, i) first waits until at most n of the wave's vector loads are outstanding.  The waits and fences exist in
@@ -90,46 +104,48 @@ struct AttnArgs {
 #endif
 
 template <int NSPLIT, bool TRC = false>
-__global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) {   // 2 waves per SIMD: <= 256 VGPRs
+__global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(F5E_ATTN_HOT_PARAMS, AttnArgs a) {   // 2 waves per SIMD: <= 256 VGPRs
   // merge buffers: per extra wave, per lane: 32 O values + m + l
   __shared__ __attribute__((aligned(16))) float red[(NSPLIT > 1 ? NSPLIT - 1 : 1) * 64 * 34];
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ql = lane & 31, hh = lane >> 5;
-  if ((int)blockIdx.x >= a.n_main) {   // grid-tail workgroups: Infinity-Cache prefetch only (f5e_common.h)
-    f5e_prefetch_run<NSPLIT * 64>(a.pf, (int)blockIdx.x - a.n_main, threadIdx.x, red);
+  [[maybe_unused]] unsigned long long ts[8] = {};   // tools build, traced instantiation only
+  ATTN_STAMP(7);   // the wave's first instruction: [7] -> [0] is what stands in front of the prefetch branch (n_main)
+  if ((int)blockIdx.x >= h_n_main) {   // grid-tail workgroups: Infinity-Cache prefetch only (f5e_common.h)
+    f5e_prefetch_run<NSPLIT * 64>(a.pf, (int)blockIdx.x - h_n_main, threadIdx.x, red);
     return;
   }
-  [[maybe_unused]] unsigned long long ts[8] = {};   // tools build, traced instantiation only
   ATTN_STAMP(0);
 
-  const int qtiles = (a.rows_per_seq + 31) / 32;
+  const int qtiles = (h_rows_per_seq + 31) / 32;
   // XCD-aware order: blocks with equal blockIdx%8 share an XCD (and its L2); give each XCD a contiguous range of
   // logical ids so all q-tiles of one (sequence, head) -- which re-read the same K/V -- hit the same L2.
   int bid = blockIdx.x;
   {
-    const int nblk = a.n_main;
+    const int nblk = h_n_main;
     const int q8 = nblk >> 3, r8 = nblk & 7;
     const int xcd = bid & 7, idx = bid >> 3;
     bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
   }
   const int qt = bid % qtiles;
   bid /= qtiles;
-  const int head = bid % a.H;
-  const int seq = bid / a.H;
-  const size_t sh = (size_t)seq * a.H + head;
-  const int kv_len = a.kv_len ? min(a.kv_len[seq], a.rows_per_seq) : a.rows_per_seq;
+  const int head = bid % h_H;
+  const int seq = bid / h_H;
+  const size_t sh = (size_t)seq * h_H + head;
+  const int kv_len = h_kv_len ? min(h_kv_len[seq], h_rows_per_seq) : h_rows_per_seq;
   const int ntiles = (kv_len + 63) / 64;  // 64-key steps
 
-  const bf16* Qg = a.q + sh * a.n_pad * 64;
-  const bf16* Kg = a.k + sh * a.n_pad * 64;
-  const bf16* Vg = a.v + sh * a.n_pad * 64;
+  const bf16* Qg = h_q + sh * h_n_pad * 64;
+  const bf16* Kg = h_k + sh * h_n_pad * 64;
+  const bf16* Vg = h_v + sh * h_n_pad * 64;
 
   // Q fragments (B operand of S^T = K.Q^T): 4 x 16 B
   bf16x8 qf[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8*)(Qg + ((size_t)(qt * 4 + ks) * 32 + ql) * 16 + hh * 8);
+  const int ldo = attn_ldo_late();   // the struct's (cold) kernarg line: requested under the Q loads, not in front of the stores
 
   // this wave's 64-key steps: wave, wave + NSPLIT, ...
   bf16x8 kf[2][4], vf[2][2][2];   // [t32][ks], [t32][s16][dt]
@@ -287,8 +303,8 @@ __global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) { 
       const int r = it * 8 + (lane >> 3), c = lane & 7;
       const int q_row = qt * 32 + r;
       const uint4 v = *(const uint4*)(stg + r * 144 + c * 16);
-      if (q_row < a.rows_per_seq)
-        *(uint4*)(a.o + ((size_t)seq * a.rows_per_seq + q_row) * a.ldo + head * 64 + c * 8) = v;
+      if (q_row < h_rows_per_seq)
+        *(uint4*)(h_o + ((size_t)seq * h_rows_per_seq + q_row) * ldo + head * 64 + c * 8) = v;
     }
   }
   ATTN_STAMP(6);
@@ -311,7 +327,7 @@ __global__ __launch_bounds__(NSPLIT * 64, 2) void attn_fwd_kernel(AttnArgs a) { 
 //     tile; after a second barrier each wave issues one of the four store instructions.
 // Every output element sees the operations of attn_fwd_kernel<4> in the same order: the two kernels agree bit for bit.
 template <bool TRC>
-__global__ __launch_bounds__(256, 2) void attn_fwd_b1_kernel(AttnArgs a) {   // 2 waves per SIMD: <= 256 VGPRs
+__global__ __launch_bounds__(256, 2) void attn_fwd_b1_kernel(F5E_ATTN_HOT_PARAMS, AttnArgs a) {   // 2 waves per SIMD: <= 256 VGPRs
   constexpr int NSPLIT = 4, PART = 64 * 34;   // one partial: per lane 32 O values + m + l
   // [4 partials][PART] + the 32 x 64 bf16 output tile in 144-byte rows
   __shared__ __attribute__((aligned(16))) float red[NSPLIT * PART + 32 * 36];
@@ -319,41 +335,42 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_b1_kernel(AttnArgs a) {   // 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ql = lane & 31, hh = lane >> 5;
-  if ((int)blockIdx.x >= a.n_main) {   // grid-tail workgroups: Infinity-Cache prefetch only (first 4 KiB of red)
-    f5e_prefetch_run<NSPLIT * 64>(a.pf, (int)blockIdx.x - a.n_main, threadIdx.x, red);
+  [[maybe_unused]] unsigned long long ts[8] = {};   // tools build, traced instantiation only
+  ATTN_STAMP(7);   // the wave's first instruction: [7] -> [0] is what stands in front of the prefetch branch (n_main)
+  if ((int)blockIdx.x >= h_n_main) {   // grid-tail workgroups: Infinity-Cache prefetch only (first 4 KiB of red)
+    f5e_prefetch_run<NSPLIT * 64>(a.pf, (int)blockIdx.x - h_n_main, threadIdx.x, red);
     return;
   }
   // Nothing is outstanding here, so this vmcnt(0) lgkmcnt(0) costs nothing -- but the compiler sees a path from the prefetch
   // branch's LDS-DMAs to this point, and while it believes one pending it turns the first wait below into vmcnt(0): the
   // first step would wait for the second tile too.  With the explicit wait every fragment gets its own counted vmcnt(N).
   __builtin_amdgcn_s_waitcnt(0x0070);
-  [[maybe_unused]] unsigned long long ts[8] = {};   // tools build, traced instantiation only
   ATTN_STAMP(0);
 
-  const int qtiles = (a.rows_per_seq + 31) / 32;
+  const int qtiles = (h_rows_per_seq + 31) / 32;
   int bid = blockIdx.x;
   {   // XCD-aware order, as in attn_fwd_kernel
-    const int nblk = a.n_main;
+    const int nblk = h_n_main;
     const int q8 = nblk >> 3, r8 = nblk & 7;
     const int xcd = bid & 7, idx = bid >> 3;
     bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
   }
   const int qt = bid % qtiles;
   bid /= qtiles;
-  const int head = bid % a.H;
-  const int seq = bid / a.H;
-  const size_t sh = (size_t)seq * a.H + head;
+  const int head = bid % h_H;
+  const int seq = bid / h_H;
+  const size_t sh = (size_t)seq * h_H + head;
 
-  const bf16* Qg = a.q + sh * a.n_pad * 64;
-  const bf16* Kg = a.k + sh * a.n_pad * 64;
-  const bf16* Vg = a.v + sh * a.n_pad * 64;
+  const bf16* Qg = h_q + sh * h_n_pad * 64;
+  const bf16* Kg = h_k + sh * h_n_pad * 64;
+  const bf16* Vg = h_v + sh * h_n_pad * 64;
 
   bf16x8 qf[4];
 #pragma unroll
   for (int ks = 0; ks < 4; ++ks) qf[ks] = *(const bf16x8*)(Qg + ((size_t)(qt * 4 + ks) * 32 + ql) * 16 + hh * 8);
   // both tiles' fragments, [step][t32][ks] and [step][t32][s16][dt]; a clamped index re-reads the last padded tile
   bf16x8 kf[2][2][4], vf[2][2][2][2];
-  const int last64 = a.n_pad / 64 - 1;
+  const int last64 = h_n_pad / 64 - 1;
   auto load_k = [&](int st) {
     const int t64 = min(wave + st * NSPLIT, last64);
 #pragma unroll
@@ -376,8 +393,11 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_b1_kernel(AttnArgs a) {   // 
   load_v(0);
   load_k(1);
   load_v(1);
+  // up to here the wave has read preloaded SGPRs only; the struct's (cold) kernarg line is requested under the loads' flight,
+  // next to kv_len -- not at entry, and not in front of the output stores that need ldo
+  const int ldo = attn_ldo_late();
   // kv_len: a scalar load through the constant address space, in flight beside the 36 vector loads above
-  const int kv_len = a.kv_len ? min(load_uniform_i32(a.kv_len + seq), a.rows_per_seq) : a.rows_per_seq;
+  const int kv_len = h_kv_len ? min(load_uniform_i32(h_kv_len + seq), h_rows_per_seq) : h_rows_per_seq;
   const int ntiles = (kv_len + 63) / 64;  // 64-key steps; the host guarantees ntiles <= 2 NSPLIT
   ATTN_LANDED(32, 1);   // Q
   ATTN_LANDED(16, 2);   // first tile
@@ -491,8 +511,8 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_b1_kernel(AttnArgs a) {   // 
     const int r = wave * 8 + (lane >> 3), c = lane & 7;
     const int q_row = qt * 32 + r;
     const uint4 v = *(const uint4*)(stg + r * 144 + c * 16);
-    if (q_row < a.rows_per_seq)
-      *(uint4*)(a.o + ((size_t)seq * a.rows_per_seq + q_row) * a.ldo + head * 64 + c * 8) = v;
+    if (q_row < h_rows_per_seq)
+      *(uint4*)(h_o + ((size_t)seq * h_rows_per_seq + q_row) * ldo + head * 64 + c * 8) = v;
   }
   ATTN_STAMP(6);
   ATTN_TRACE_OUT();
@@ -676,8 +696,9 @@ __global__ __launch_bounds__(256, OCC) void attn_fwd_lds_kernel(AttnArgs a) {
 
 // Diagnostics hook of the TOOLS build only (make tools-lib -> libf5e_hip_tools.so, -DF5E_TOOLS; tools/attn_timeline.py): while
 // buf != NULL the 4-way split launches of f5e_flash_attn run their stamped instantiation, which writes per workgroup and wave
-// 8 uint64: s_memtime at [0] entry, [1] Q landed, [2] first tile landed, [3] second tile landed, [4] at the merge barrier,
-// [5] past it, [6] last store issued ([7] unused; the general loop waits for Q and its first tile at once: [1] stays 0).
+// 8 uint64: s_memtime at [0] entry (past the prefetch branch), [1] Q landed, [2] first tile landed, [3] second tile landed,
+// [4] at the merge barrier, [5] past it, [6] last store issued, [7] the wave's first instruction (the general loop waits for Q
+// and its first tile at once: [1] stays 0).
 // Process-wide, not for concurrent callers; the shipped library has no process-wide mutable state and does not export it.
 #ifdef F5E_TOOLS
 static unsigned long long* g_attn_trace = nullptr;
@@ -730,13 +751,13 @@ int f5e_flash_attn_pf(hipStream_t st, const void* q, const void* k, const void* 
     case 1: {
       const int npf = f5e_prefetch_wgs(pf);
       if (npf) a.pf = *pf;
-      hipLaunchKernelGGL(attn_fwd_kernel<1>, dim3(grid + npf), dim3(64), 0, st, a);
+      hipLaunchKernelGGL(attn_fwd_kernel<1>, dim3(grid + npf), dim3(64), 0, st, F5E_ATTN_HOT_ARGS(a), a);
       break;
     }
     case 2: {
       const int npf = f5e_prefetch_wgs(pf);
       if (npf) a.pf = *pf;
-      hipLaunchKernelGGL(attn_fwd_kernel<2>, dim3(grid + npf), dim3(128), 0, st, a);
+      hipLaunchKernelGGL(attn_fwd_kernel<2>, dim3(grid + npf), dim3(128), 0, st, F5E_ATTN_HOT_ARGS(a), a);
       break;
     }
     case 4: {
@@ -751,18 +772,18 @@ int f5e_flash_attn_pf(hipStream_t st, const void* q, const void* k, const void* 
       a.trace = g_attn_trace;
       if (a.trace || variant4 == 4) {
         if (two_steps && variant4 != 4) {
-          if (a.trace) hipLaunchKernelGGL(attn_fwd_b1_kernel<true>, dim3(grid + npf), dim3(256), 0, st, a);
-          else hipLaunchKernelGGL(attn_fwd_b1_kernel<false>, dim3(grid + npf), dim3(256), 0, st, a);
+          if (a.trace) hipLaunchKernelGGL(attn_fwd_b1_kernel<true>, dim3(grid + npf), dim3(256), 0, st, F5E_ATTN_HOT_ARGS(a), a);
+          else hipLaunchKernelGGL(attn_fwd_b1_kernel<false>, dim3(grid + npf), dim3(256), 0, st, F5E_ATTN_HOT_ARGS(a), a);
         } else if (a.trace) {
-          hipLaunchKernelGGL((attn_fwd_kernel<4, true>), dim3(grid + npf), dim3(256), 0, st, a);
+          hipLaunchKernelGGL((attn_fwd_kernel<4, true>), dim3(grid + npf), dim3(256), 0, st, F5E_ATTN_HOT_ARGS(a), a);
         } else {
-          hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(grid + npf), dim3(256), 0, st, a);
+          hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(grid + npf), dim3(256), 0, st, F5E_ATTN_HOT_ARGS(a), a);
         }
         break;
       }
 #endif
-      if (two_steps) hipLaunchKernelGGL(attn_fwd_b1_kernel<false>, dim3(grid + npf), dim3(256), 0, st, a);
-      else hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(grid + npf), dim3(256), 0, st, a);
+      if (two_steps) hipLaunchKernelGGL(attn_fwd_b1_kernel<false>, dim3(grid + npf), dim3(256), 0, st, F5E_ATTN_HOT_ARGS(a), a);
+      else hipLaunchKernelGGL(attn_fwd_kernel<4>, dim3(grid + npf), dim3(256), 0, st, F5E_ATTN_HOT_ARGS(a), a);
       break;
     }
     default: F5E_REQUIRE(false, "flash_attn: splits must be 0 (auto), -1 (LDS-shared), 1, 2 or 4");

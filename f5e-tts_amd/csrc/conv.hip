@@ -17,6 +17,8 @@
 // f5e_im2col: [B][T][Cin] -> [B][T][k*Cin] fp32 patches (zero padded) so small dense convs (Vocos embed k7,
 //   PPG k5: backbones/dit.py:124-132) run on f5e_gemm_f32.
 #include <cstdlib>
+#include <cstddef>
+
 #include "f5e_common.h"
 
 namespace {
@@ -211,6 +213,17 @@ __global__ __launch_bounds__(256) void convpos_kernel(ConvPosArgs a) {
   }
 }
 
+// convpos_split_kernel (the batch-1 launches) takes what it needs up to its last prologue DMA once more as LEADING SCALAR
+// parameters, 14 dwords, preloaded into SGPRs at wave launch (f5e_common.h, f5e_kernarg_late); the output pointers and strides
+// come from the struct behind them, requested under the weight tiles' flight.  One list for the signature and the launches:
+#define F5E_CONVPOS_HOT_PARAMS                                                                                           \
+  const bf16 *h_x, const bf16 *h_w, const float *h_bias, const float *h_resid, int h_ldx, int h_ldr, int h_N, int h_D,    \
+      int h_mode, int h_cpg
+#define F5E_CONVPOS_HOT_ARGS(a) (a).x, (a).w, (a).bias, (a).resid, (a).ldx, (a).ldr, (a).N, (a).D, (a).mode, (a).cpg
+enum { F5E_CONVPOS_HOT_DWORDS = 14 };
+static_assert(alignof(ConvPosArgs) == 8 && F5E_CONVPOS_HOT_DWORDS * 4 % 8 == 0, "ConvPosArgs sits right behind the scalar parameters");
+#define F5E_CONVPOS_LATE(T, field) f5e_kernarg_late<T>(F5E_CONVPOS_HOT_DWORDS * 4 + offsetof(ConvPosArgs, field))
+
 // Split-tap variant: the four waves each own the whole 64 x 64 output tile for every fourth tap and the partial sums are
 // added through LDS at the end.  Against the output-split kernel above this halves the ds_read traffic per tap (16
 // fragment reads feed 32 MFMAs instead of 8 feeding 8), and the tap loop has no workgroup barrier: every wave streams
@@ -218,7 +231,7 @@ __global__ __launch_bounds__(256) void convpos_kernel(ConvPosArgs a) {
 //   LDS: activation tile 96 x 128 B | 4 waves x 4 stages x 8 KB of weights; the partial sums 4 x [64][64 + 4] floats
 //   reuse the ring space after the loop.
 template <bool TRC = false>
-__global__ __launch_bounds__(256) void convpos_split_kernel(ConvPosArgs a) {
+__global__ __launch_bounds__(256) void convpos_split_kernel(F5E_CONVPOS_HOT_PARAMS, ConvPosArgs a) {
   unsigned long long ts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if constexpr (TRC) { ts[0] = __builtin_amdgcn_s_memrealtime(); ts[1] = __builtin_amdgcn_s_memtime(); }
   constexpr int BT = 64, HALO = 15, XR = BT + 2 * HALO;
@@ -232,23 +245,23 @@ __global__ __launch_bounds__(256) void convpos_split_kernel(ConvPosArgs a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int g = blockIdx.x, tt = blockIdx.y, seq = blockIdx.z;
-  const int c0 = g * a.cpg;
+  const int c0 = g * h_cpg;
   const int t0 = tt * BT;
   const int fr = lane & 15, fq = lane >> 4;
 
   // epilogue operands first (oldest in the in-order vmcnt queue, so the counted waits below are unaffected): the
   // residual rows of mode 1, from clamped addresses
   const int oc = (lane & 15) * 4;
-  const int n = c0 + (oc < a.cpg ? oc : 0);
+  const int n = c0 + (oc < h_cpg ? oc : 0);
   f32x4 rv[4];
-  if (a.mode == 1) {
+  if (h_mode == 1) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int t = t0 + wave * 16 + p * 4 + (lane >> 4);
-      rv[p] = *(const f32x4*)(a.resid + ((size_t)seq * a.N + (t < a.N ? t : a.N - 1)) * a.ldr + n);
+      rv[p] = *(const f32x4*)(h_resid + ((size_t)seq * h_N + (t < h_N ? t : h_N - 1)) * h_ldr + n);
     }
   }
-  const f32x4 bias = *(const f32x4*)(a.bias + n);
+  const f32x4 bias = *(const f32x4*)(h_bias + n);
   asm volatile("" ::: "memory");
   __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -257,7 +270,7 @@ __global__ __launch_bounds__(256) void convpos_split_kernel(ConvPosArgs a) {
     const int row = i >> 3, c = (i & 7) ^ ((row >> 1) & 7);
     const int t = t0 - HALO + row;
     const void* src = &conv_zero16;
-    if (row < XR && t >= 0 && t < a.N && c0 + c * 8 < a.D) src = a.x + ((size_t)seq * a.N + t) * a.ldx + c0 + c * 8;
+    if (row < XR && t >= 0 && t < h_N && c0 + c * 8 < h_D) src = h_x + ((size_t)seq * h_N + t) * h_ldx + c0 + c * 8;
     glds16c(src, Xs + (wave * 64 + 256 * r) * 16);
   }
   asm volatile("" ::: "memory");
@@ -265,7 +278,7 @@ __global__ __launch_bounds__(256) void convpos_split_kernel(ConvPosArgs a) {
 
   // wave-private weight ring: tile of tap = 8 KB = 8 DMAs of 1 KB; chunk i = lane + 64 j -> (row = i >> 3, c = i & 7)
   char* ring = ring_base + wave * (NST * W_BYTES);
-  const bf16* wg = a.w + (size_t)g * TAPS * 4096;
+  const bf16* wg = h_w + (size_t)g * TAPS * 4096;
   const bf16* w_src[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -281,6 +294,10 @@ __global__ __launch_bounds__(256) void convpos_split_kernel(ConvPosArgs a) {
   };
 #pragma unroll
   for (int u = 0; u < NST - 1; ++u) stage_w(u, u);
+  // up to here the wave has read preloaded SGPRs only; what the output stores need is requested now
+  bf16* const o_bf16 = F5E_CONVPOS_LATE(bf16*, out_bf16);
+  float* const o_f32 = F5E_CONVPOS_LATE(float*, out_f32);
+  const int ldo = F5E_CONVPOS_LATE(int, ldo), ldo32 = F5E_CONVPOS_LATE(int, ldo32);
 
   f32x4 acc[4][4];
 #pragma unroll
@@ -349,22 +366,22 @@ __global__ __launch_bounds__(256) void convpos_split_kernel(ConvPosArgs a) {
 #pragma unroll
   for (int p = 0; p < 4; ++p) asm volatile("" : "+v"(rv[p]));  // see convpos_kernel: one wait here, none between the stores
 
-  if (oc < a.cpg) {
+  if (oc < h_cpg) {
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const int row = wave * 16 + p * 4 + (lane >> 4);
       const int t = t0 + row;
-      const size_t m = (size_t)seq * a.N + t;
+      const size_t m = (size_t)seq * h_N + t;
       const float* rp = Red + row * RS + oc;
       f32x4 v = (*(const f32x4*)rp + *(const f32x4*)(rp + 64 * RS)) + (*(const f32x4*)(rp + 2 * 64 * RS) + *(const f32x4*)(rp + 3 * 64 * RS));
       v += bias;
       v[0] = mish_f(v[0]); v[1] = mish_f(v[1]); v[2] = mish_f(v[2]); v[3] = mish_f(v[3]);
-      if (t >= a.N) continue;
-      if (a.mode == 0) {
-        *(bf16x4*)(a.out_bf16 + m * a.ldo + n) = f2bf4(v[0], v[1], v[2], v[3]);
+      if (t >= h_N) continue;
+      if (h_mode == 0) {
+        *(bf16x4*)(o_bf16 + m * ldo + n) = f2bf4(v[0], v[1], v[2], v[3]);
       } else {
         v += rv[p];
-        *(f32x4*)(a.out_f32 + m * a.ldo32 + n) = v;
+        *(f32x4*)(o_f32 + m * ldo32 + n) = v;
       }
     }
   }
@@ -487,13 +504,13 @@ static int convpos_launch(hipStream_t st, const void* x, int ldx, const void* w_
   static F5eDeviceOnce once_split_trace;
   if (split && a.trace) {
     F5E_OPT_IN_LDS(once_split_trace, convpos_split_kernel<true>, lds_split);
-    hipLaunchKernelGGL(convpos_split_kernel<true>, grid, dim3(256), lds_split, st, a);
+    hipLaunchKernelGGL(convpos_split_kernel<true>, grid, dim3(256), lds_split, st, F5E_CONVPOS_HOT_ARGS(a), a);
   } else if (a.trace) {
     hipLaunchKernelGGL((convpos_kernel<4, true>), grid, dim3(256), lds_ring, st, a);
   } else
 #endif
   if (split) {
-    hipLaunchKernelGGL(convpos_split_kernel<false>, grid, dim3(256), lds_split, st, a);
+    hipLaunchKernelGGL(convpos_split_kernel<false>, grid, dim3(256), lds_split, st, F5E_CONVPOS_HOT_ARGS(a), a);
   } else {
     hipLaunchKernelGGL((convpos_kernel<4, false>), grid, dim3(256), lds_ring, st, a);
   }

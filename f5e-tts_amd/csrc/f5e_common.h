@@ -168,6 +168,22 @@ __device__ __forceinline__ int load_uniform_i32(const int* p) {
   return *(const __attribute__((address_space(4))) int*)(uintptr_t)p;
 }
 
+// Kernel-argument preload (gemm_bf16.hip, attention.hip, conv.hip, gemm_f32.hip; csrc/Makefile PRELOAD_UNITS): the batch-1
+// chain's kernels take what they need before their first memory instruction as LEADING SCALAR parameters -- the command
+// processor delivers the first 14 kernarg dwords in SGPRs at wave launch -- and the argument struct behind them.  A field
+// that only the tail of the kernel needs must then be REQUESTED where its (cold) scalar-cache miss is hidden, and written as
+// a.field it is not: the load is invariant, so the optimiser hoists it to kernel entry (in front of whatever waits there) or
+// sinks it to its use (in front of the output stores).  This reads it from the kernarg segment through a pointer the
+// optimiser cannot see through; the s_load goes out at the call, the wait where the value is first used.
+// byte_off: offset in the kernarg segment = bytes of the scalar parameters (the struct's alignment respected) + offsetof.
+template <typename T>
+__device__ __forceinline__ T f5e_kernarg_late(unsigned byte_off) {
+  const __attribute__((address_space(4))) char* p = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" : "+s"(p)::"memory");
+  return *(const __attribute__((address_space(4))) T*)(p + byte_off);
+}
+
 __device__ __forceinline__ bf16x4 f2bf4(float a, float b, float c, float d) {
   f32x4 v = {a, b, c, d};
   return __builtin_convertvector(v, bf16x4);

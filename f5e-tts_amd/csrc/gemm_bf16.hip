@@ -69,7 +69,7 @@ __device__ __forceinline__ void wait_stages(int nst) {
 // consumer waves of 32 x 32), 128 x 128 and 128 x 192 (consumers, 8 / 12 waves of 64 x 32) -- again a ONE-round grid of at
 // most 16 x 16 tiles, where the 64-row tiles would need two rounds of classic three-per-CU workgroups.
 template <int BM, int BN, int EPI, int NSTAGE, int DBG = 0, int WGM = 2, int WGN = 2, int FUSE = 0, int NLOAD = 0, int DSTEP = 1, int DBUF = 1>
-__global__ __launch_bounds__(64 * (WGM * WGN + NLOAD)) void gemm_bf16_kernel(GemmArgs a) {
+__global__ __launch_bounds__(64 * (WGM * WGN + NLOAD)) void gemm_bf16_kernel(F5E_GEMM_HOT_PARAMS, GemmArgs a) {
   constexpr int BK = 64;
   constexpr int CPR = BK / 8;                    // 16-byte chunks per LDS row
   constexpr int ROWB = BK * 2;                   // bytes per LDS row
@@ -91,31 +91,18 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLOAD)) void gemm_bf16_kernel(Gem
   const int stid = NLOAD ? tid - NC : tid;               // index among the staging threads (loaders: 0 .. NT - 1)
   const int swave = NLOAD ? wave - NCW : wave;
   unsigned long long* trc = nullptr;
-  if constexpr (DBG >= 3) {
-    trc = a.trace + (size_t)blockIdx.x * 48;
-    if (tid == 0) { trc[0] = __builtin_amdgcn_s_memrealtime(); trc[1] = __builtin_amdgcn_s_memtime(); }
-  }
+  [[maybe_unused]] unsigned long long t_entry_rt = 0, t_entry = 0;   // DBG: stored with slot 46 / 47 (a.trace is a kernarg load)
+  if constexpr (DBG >= 3) { t_entry_rt = __builtin_amdgcn_s_memrealtime(); t_entry = __builtin_amdgcn_s_memtime(); }
 
-  // Kernarg lines beyond the first: request them NOW, next to the first line, so their (cold) scalar-cache misses overlap
-  // instead of surfacing one by one where the compiler first needs a field (the prefetch block behind the prologue).
-  if (FUSE == 1)
-    asm volatile("" ::"s"(a.ln_stats), "s"(a.ln_c), "s"(a.ln_d), "s"(a.ln_parts), "s"(a.cd_stride), "s"(a.cd_rows),
-                 "s"(a.cd_eval_stride), "s"(a.eval_ptr));
-  if (EPI == EPI_GATE_RES)
-    asm volatile("" ::"s"(a.resid), "s"(a.gate), "s"(a.seq_len), "s"(a.eval_ptr), "s"(a.ldr), "s"(a.gate_stride),
-                 "s"(a.gate_rows), "s"(a.eval_stride), "s"(a.bias));
-  if (FUSE == 2) asm volatile("" ::"s"(a.next_scale), "s"(a.xs_out), "s"(a.stats_out), "s"(a.ld_xs), "s"(a.row_mean));
-  if (EPI == EPI_QKV_ROPE) asm volatile("" ::"s"(a.q), "s"(a.k), "s"(a.vt), "s"(a.cos_sin), "s"(a.n_pad), "s"(a.heads), "s"(a.rope_heads));
-
-  if ((int)blockIdx.x >= a.n_main) {   // grid-tail workgroups: Infinity-Cache prefetch only (f5e_common.h), 256 threads of them
-    if (NLOAD > 0 && a.pf_per_wg) f5e_prefetch_run_packed(a.pf, (int)blockIdx.x - a.n_main, tid, 64 * (NCW + NLOAD), a.pf_per_wg, smem);
-    else if (tid < 256) f5e_prefetch_run(a.pf, (int)blockIdx.x - a.n_main, tid, smem);
+  if ((int)blockIdx.x >= h_n_main) {   // grid-tail workgroups: Infinity-Cache prefetch only (f5e_common.h), 256 threads of them
+    if (NLOAD > 0 && a.pf_per_wg) f5e_prefetch_run_packed(a.pf, (int)blockIdx.x - h_n_main, tid, 64 * (NCW + NLOAD), a.pf_per_wg, smem);
+    else if (tid < 256) f5e_prefetch_run(a.pf, (int)blockIdx.x - h_n_main, tid, smem);
     return;
   }
   // XCD-aware tile order: blocks that share blockIdx%8 (one XCD) walk tiles with the same n-panel.
   int bid = blockIdx.x;
   {
-    const int nblk = a.n_main;
+    const int nblk = h_n_main;
     const int q8 = nblk >> 3, r8 = nblk & 7;
     const int xcd = bid & 7, idx = bid >> 3;
     bid = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + idx;
@@ -127,12 +114,12 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLOAD)) void gemm_bf16_kernel(Gem
   // tiles instead of whole n-panels: its private L2 then pulls (rows + G) 64-row panels through the fabric instead of
   // (tiles_m + n-panels).  G is picked on the host (pick_group_shift); G = 1 is the plain n-major walk.
   int tile_m, tile_n;
-  if (a.m_major > 0) {
-    tile_m = div_magic(bid, a.tiles_n, a.tile_magic);
-    tile_n = bid - tile_m * a.tiles_n;
+  if (h_m_major > 0) {
+    tile_m = div_magic(bid, h_tiles_n, h_tile_magic);
+    tile_n = bid - tile_m * h_tiles_n;
   } else {
-    const int sh = -a.m_major, per = a.tiles_m << sh;
-    const int g = div_magic(bid, per, a.tile_magic);
+    const int sh = -h_m_major, per = h_tiles_m << sh;
+    const int g = div_magic(bid, per, h_tile_magic);
     const int r = bid - g * per;
     tile_m = r >> sh;
     tile_n = (g << sh) + (r & ((1 << sh) - 1));
@@ -153,17 +140,17 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLOAD)) void gemm_bf16_kernel(Gem
   for (int j = 0; j < A_IT; ++j) {
     const int i = (stid & (NT - 1)) + NT * j;
     const int row = i / CPR, c = (i % CPR) ^ swz(row);
-    a_off[j] = (unsigned)(min(m0 + row, a.M - 1) - m0) * (unsigned)(a.lda * 2) + (unsigned)c * 16u;   // m0 < M: never negative
+    a_off[j] = (unsigned)(min(m0 + row, h_M - 1) - m0) * (unsigned)(h_lda * 2) + (unsigned)c * 16u;   // m0 < M: never negative
   }
 #pragma unroll
   for (int j = 0; j < W_IT; ++j) {
     const int i = (stid & (NT - 1)) + NT * j;
     const int row = i / CPR, c = (i % CPR) ^ swz(row);
-    w_off[j] = (unsigned)(min(n0 + row, a.N - 1) - n0) * (unsigned)(a.ldw * 2) + (unsigned)c * 16u;
+    w_off[j] = (unsigned)(min(n0 + row, h_N - 1) - n0) * (unsigned)(h_ldw * 2) + (unsigned)c * 16u;
   }
-  const char* const a_base = (const char*)(a.A + (size_t)m0 * a.lda);   // uniform
-  const char* const w_base = (const char*)(a.W + (size_t)n0 * a.ldw);
-  const int KT = a.K / BK;
+  const char* const a_base = (const char*)(h_A + (size_t)m0 * h_lda);   // uniform
+  const char* const w_base = (const char*)(h_W + (size_t)n0 * h_ldw);
+  const int KT = h_K / BK;
   char* const ring = smem;
   auto stage = [&](int buf, int kt) {
     char* base = ring + buf * STAGE;
@@ -197,6 +184,7 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLOAD)) void gemm_bf16_kernel(Gem
     for (int s = 0; s < NPRO; ++s)
       if (s < KT) stage(s, s);
   }
+  if constexpr (DBG >= 3) trc = a.trace + (size_t)blockIdx.x * 48;
   if constexpr (NLOAD > 0) {
     if (is_loader) {
       // ---- loader waves: wait for tiles kt .. kt + DSTEP - 1, meet the consumers at the barrier that hands them over (and
@@ -229,8 +217,25 @@ __global__ __launch_bounds__(64 * (WGM * WGN + NLOAD)) void gemm_bf16_kernel(Gem
   // conservative) and tools/check_vmcnt.py verifies on the compiled ISA that every instantiation issues >= NPC plain
   // vector loads between the prologue's LDS-DMAs and the first counted wait (run by `make check`).  `volatile` is no
   // way to pin them: hipcc turns volatile loads into flat_load sc0 sc1 + s_waitcnt vmcnt(0) each.
+  // The struct's kernarg lines: request all of them HERE, so their (cold) scalar-cache misses overlap instead of surfacing
+  // one by one where the compiler first needs a field.  Up to this point a wave has read preloaded SGPRs only (the h_
+  // parameters) and the first tiles' DMAs are on their way -- a loader wave of a role-split launch never gets here -- so the
+  // one miss is paid under the first tile's flight, not in front of it (at kernel entry it was the first thing every wave
+  // waited for: an asm operand has to be in its register).
+  asm volatile("" ::"s"(a.M), "s"(a.N), "s"(a.K), "s"(a.rows_per_seq), "s"(a.rps_magic));   // the struct's own first line
+  if (FUSE == 1)
+    asm volatile("" ::"s"(a.ln_stats), "s"(a.ln_c), "s"(a.ln_d), "s"(a.ln_parts), "s"(a.cd_stride), "s"(a.cd_rows),
+                 "s"(a.cd_eval_stride), "s"(a.eval_ptr));
+  if (EPI == EPI_GATE_RES)
+    asm volatile("" ::"s"(a.resid), "s"(a.gate), "s"(a.seq_len), "s"(a.eval_ptr), "s"(a.ldr), "s"(a.gate_stride),
+                 "s"(a.gate_rows), "s"(a.eval_stride), "s"(a.bias));
+  if (FUSE == 2) asm volatile("" ::"s"(a.next_scale), "s"(a.xs_out), "s"(a.stats_out), "s"(a.ld_xs), "s"(a.row_mean));
+  if (EPI == EPI_QKV_ROPE) asm volatile("" ::"s"(a.q), "s"(a.k), "s"(a.vt), "s"(a.cos_sin), "s"(a.n_pad), "s"(a.heads), "s"(a.rope_heads),
+                                        "s"(a.q_scale), "s"(a.qn_w), "s"(a.kn_w), "s"(a.qk_eps));
   asm volatile("" ::: "memory");
-  if constexpr (DBG >= 3) { if (tid == 0) trc[46] = __builtin_amdgcn_s_memtime(); }
+  if constexpr (DBG >= 3) {
+    if (tid == 0) { const unsigned long long t = __builtin_amdgcn_s_memtime(); trc[0] = t_entry_rt; trc[1] = t_entry; trc[46] = t; }
+  }
   constexpr bool PREF = (TM * TN <= 4);
   // fused AdaLN: 64-row tiles of 32 x 32 wave sub-tiles (row statistics: 4 threads per row = the first 256 threads); the
   // producer is 64 x 64, a role-split consumer may be wider (64 x 128 / 64 x 192: the A panel is staged once per K-step)
@@ -756,7 +761,7 @@ int launch(GemmArgs& a, hipStream_t st) {
   static_assert(lds <= 160 * 1024, "LDS budget");
   static F5eDeviceOnce lds_once;  // > 64 KiB of dynamic LDS needs the opt-in attribute, per device (host-only call)
   if (lds > 65536) F5E_OPT_IN_LDS(lds_once, (gemm_bf16_kernel<BM, BN, EPI, NSTAGE, DBG, WGM, WGN, FUSE, NLOAD, DSTEP, DBUF>), lds);
-  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, EPI, NSTAGE, DBG, WGM, WGN, FUSE, NLOAD, DSTEP, DBUF>), dim3(grid), dim3(64 * (WGM * WGN + NLOAD)), lds, st, a);
+  hipLaunchKernelGGL((gemm_bf16_kernel<BM, BN, EPI, NSTAGE, DBG, WGM, WGN, FUSE, NLOAD, DSTEP, DBUF>), dim3(grid), dim3(64 * (WGM * WGN + NLOAD)), lds, st, F5E_GEMM_HOT_ARGS(a), a);
   F5E_LAUNCH_CHECK("gemm_bf16");
   return F5E_OK;
 }

@@ -55,6 +55,19 @@ struct GemmArgs {
 
 static_assert(offsetof(GemmArgs, n_main) + sizeof(int) == 64, "hot kernarg fields must fill exactly the first 64-byte line");
 
+// The ring kernels of gemm_bf16.hip take the fields of that line they need before their first LDS-DMA (all of it but
+// rows_per_seq / rps_magic, which only the epilogues read) once more as LEADING SCALAR parameters: built with
+// -amdgpu-kernarg-preload-count=16, the command processor delivers the first 14 kernarg dwords in SGPRs at wave launch, and
+// the prologue -- tile decode, prefetch branch, DMA addresses -- waits for no (cold) scalar-cache miss.  An aggregate is
+// never preloaded and ends the preloaded run, so the struct goes last; 4 + 10 dwords fill the budget exactly
+// (tools/check_kernarg_preload.py checks the kernel descriptors).  One list for the kernel's signature and its launcher:
+#define F5E_GEMM_HOT_PARAMS                                                                                              \
+  const bf16 *h_A, const bf16 *h_W, int h_lda, int h_ldw, int h_M, int h_N, int h_K, int h_tiles_m, int h_tiles_n,        \
+      int h_m_major, unsigned h_tile_magic, int h_n_main
+#define F5E_GEMM_HOT_ARGS(a)                                                                                             \
+  (a).A, (a).W, (a).lda, (a).ldw, (a).M, (a).N, (a).K, (a).tiles_m, (a).tiles_n, (a).m_major, (a).tile_magic, (a).n_main
+enum { F5E_GEMM_HOT_DWORDS = 14 };
+
 // floor(n / d) for 0 <= n < 2^31, d >= 1, magic = min(floor(2^32 / d), 2^32 - 1): one mul_hi + one correction step
 // (s_mul_hi_u32 on uniform operands) instead of the ~40-instruction reciprocal sequence hipcc emits for `/`.
 __host__ __device__ inline unsigned div_magic_of(int d) {

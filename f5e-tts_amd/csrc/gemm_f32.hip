@@ -127,8 +127,15 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(Gemm32Args a) {
 // row and feeds them to 4 MFMAs; both operands use the same k permutation, so every k is visited exactly once.
 // The simple kernel above takes ~1.4 us per 16-wide K step (exposed global latency + 2 barriers): 45 us for
 // 281 x 1536 x 512; this one ~8 us.
+// The fields the prologue needs before its first LDS-DMA come once more as LEADING SCALAR parameters (11 dwords, preloaded
+// into SGPRs at wave launch: f5e_common.h, f5e_kernarg_late); the struct's kernarg lines are requested behind the prologue's
+// DMAs, under the first tile's flight.  One list for the signature and the launcher:
+#define F5E_GEMM32_HOT_PARAMS                                                                                            \
+  const float *h_A, const float *h_W, int h_lda, int h_ldw, int h_a_rows, int h_M, int h_N, int h_K, int h_tiles_m
+#define F5E_GEMM32_HOT_ARGS(a) (a).A, (a).W, (a).lda, (a).ldw, (a).a_rows, (a).M, (a).N, (a).K, (a).tiles_m
+enum { F5E_GEMM32_HOT_DWORDS = 11 };
 template <int BM, int BN, int WGM, int WGN, int NSTAGE>
-__global__ __launch_bounds__(256) void gemm_f32_dma_kernel(Gemm32Args a) {
+__global__ __launch_bounds__(256) void gemm_f32_dma_kernel(F5E_GEMM32_HOT_PARAMS, Gemm32Args a) {
   constexpr int BK = 64, NT = 256, ROWB = BK * 4;
   constexpr int A_BYTES = BM * ROWB, W_BYTES = BN * ROWB, STAGE = A_BYTES + W_BYTES;
   constexpr int WM = BM / WGM, WN = BN / WGN, TM = WM / 16, TN = WN / 16;
@@ -138,7 +145,7 @@ __global__ __launch_bounds__(256) void gemm_f32_dma_kernel(Gemm32Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem32[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile_n = blockIdx.x / a.tiles_m, tile_m = blockIdx.x - tile_n * a.tiles_m;
+  const int tile_n = blockIdx.x / h_tiles_m, tile_m = blockIdx.x - tile_n * h_tiles_m;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
 
   const float* a_src[A_IT];
@@ -147,13 +154,13 @@ __global__ __launch_bounds__(256) void gemm_f32_dma_kernel(Gemm32Args a) {
 #pragma unroll
   for (int j = 0; j < A_IT; ++j) {
     const int i = tid + NT * j, row = i >> 4, c = (i & 15) ^ (row & 15);
-    a_src[j] = a.A + (size_t)(min(m0 + row, a.M - 1) % a.a_rows) * a.lda + c * 4;
+    a_src[j] = h_A + (size_t)(min(m0 + row, h_M - 1) % h_a_rows) * h_lda + c * 4;
     a_k[j] = c * 4;
   }
 #pragma unroll
   for (int j = 0; j < W_IT; ++j) {
     const int i = tid + NT * j, row = i >> 4, c = (i & 15) ^ (row & 15);
-    w_src[j] = a.W + (size_t)min(n0 + row, a.N - 1) * a.ldw + c * 4;
+    w_src[j] = h_W + (size_t)min(n0 + row, h_N - 1) * h_ldw + c * 4;
     w_k[j] = c * 4;
   }
   auto dma = [](const void* g, void* l) {
@@ -166,10 +173,10 @@ __global__ __launch_bounds__(256) void gemm_f32_dma_kernel(Gemm32Args a) {
     char* base = smem32 + buf * STAGE;
 #pragma unroll
     for (int j = 0; j < A_IT; ++j)
-      dma(kt * BK + a_k[j] < a.K ? a_src[j] + kt * BK : a_src[j] - a_k[j], base + (wave * 64 + NT * j) * 16);
+      dma(kt * BK + a_k[j] < h_K ? a_src[j] + kt * BK : a_src[j] - a_k[j], base + (wave * 64 + NT * j) * 16);
 #pragma unroll
     for (int j = 0; j < W_IT; ++j)
-      dma(kt * BK + w_k[j] < a.K ? w_src[j] + kt * BK : w_src[j] - w_k[j], base + A_BYTES + (wave * 64 + NT * j) * 16);
+      dma(kt * BK + w_k[j] < h_K ? w_src[j] + kt * BK : w_src[j] - w_k[j], base + A_BYTES + (wave * 64 + NT * j) * 16);
   };
 
   const int wm0 = (wave / WGN) * WM, wn0 = (wave % WGN) * WN;
@@ -180,10 +187,13 @@ __global__ __launch_bounds__(256) void gemm_f32_dma_kernel(Gemm32Args a) {
 #pragma unroll
     for (int j = 0; j < TM; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  const int KT = (a.K + BK - 1) / BK;
+  const int KT = (h_K + BK - 1) / BK;
 #pragma unroll
   for (int s = 0; s < NSTAGE - 1; ++s)
     if (s < KT) stage(s, s);
+  // every wave waits below for its first tile anyway: the struct's (cold) kernarg lines are requested here, all at once
+  asm volatile("" ::"s"(a.vec), "s"(a.addend), "s"(a.ld_add), "s"(a.add_rows), "s"(a.row_scale), "s"(a.bias), "s"(a.act),
+               "s"(a.ch_scale), "s"(a.out), "s"(a.ldo), "s"(a.out_bf16), "s"(a.ldo_bf16));
   int buf = 0, nbuf = NSTAGE - 1;
   for (int kt = 0; kt < KT; ++kt) {
     const int rem = KT - 1 - kt;
@@ -308,7 +318,7 @@ int launch_dma(Gemm32Args& a, hipStream_t st) {
   // input projection (K = 100: 2 tiles) then takes 64 instead of 96 KiB and two workgroups share a CU.
   const int kt = (a.K + 63) / 64;
   const int lds = (kt < NSTAGE ? kt : NSTAGE) * (BM + BN) * 256;
-  hipLaunchKernelGGL((gemm_f32_dma_kernel<BM, BN, WGM, WGN, NSTAGE>), dim3(grid), dim3(256), lds, st, a);
+  hipLaunchKernelGGL((gemm_f32_dma_kernel<BM, BN, WGM, WGN, NSTAGE>), dim3(grid), dim3(256), lds, st, F5E_GEMM32_HOT_ARGS(a), a);
   F5E_LAUNCH_CHECK("gemm_f32_dma");
   return F5E_OK;
 }

@@ -2,7 +2,7 @@
 hipGraph, the way it runs inside one DiT evaluation.   usage: python tools/attn_timeline.py [S H N] [--out FILE]
 
 Needs the TOOLS build (make -C f5e-tts_amd/csrc tools-lib; F5E_HIP_LIB=f5e-tts_amd/libf5e_hip_tools.so): its stamped kernel
-instantiations write per workgroup and wave the shader clock at entry, Q landed, first / second tile landed, at and past the
+instantiations write per workgroup and wave the shader clock at the first instruction, at entry (past the prefetch branch), Q landed, first / second tile landed, at and past the
 merge barrier and after the last store (f5e_debug_attn_trace).  F5E_ATTN_VARIANT=4 keeps the general attn_fwd_kernel<4> loop
 at every size (the kernel before the batch-1 variant).  The stamped build's fences forbid overlaps the real kernel has: read
 its shares, not its length; the per-launch time printed first is the UNSTAMPED kernel in the same chain."""
@@ -101,6 +101,10 @@ for i, nm in enumerate(names):
         cell = f"{qs[0]:6.0f} | {qs[1]:6.0f} | {qs[2]:6.0f}"
         row.append(cell if w is None else f"w{w} {qs[0]:6.0f}")
     lines.append("  ".join(row))
+head = (t[:, :, 0] - t[:, :, 7]).reshape(-1)   # [7]: the wave's first instruction; [0]: past the prefetch branch (needs n_main)
+hq = torch.quantile(head, torch.tensor([0.5, 0.1, 0.9], dtype=torch.double))
+lines.append(f"wave's first instruction -> entry stamp (what the launch head waits for before its first load can go out): "
+             f"{hq[0]:.0f} | {hq[1]:.0f} | {hq[2]:.0f} cycles")
 entry_spread = t[:, :, 0].amax(dim=1) - t[:, :, 0].amin(dim=1)
 lines.append(f"workgroup span (first wave's entry -> last stamp of any wave): median {wg_span.median():.0f} cycles, "
              f"90 % {torch.quantile(wg_span, 0.9):.0f}; entry spread inside a workgroup: median {entry_spread.median():.0f}")

@@ -11,6 +11,7 @@ LIB_PATH = os.environ.get("F5E_HIP_LIB") or os.path.join(_HERE, "libf5e_hip.so")
 ABI_VERSION = 2   # F5E_ABI_VERSION of include/f5e_abi.h
 
 ACT_NONE, ACT_SILU, ACT_GELU_ERF, ACT_GELU_TANH, ACT_RELU, ACT_MISH = range(6)
+W_FP16, W_BF16 = 1, 2   # F5E_W_*: the element type of a 16-bit weight operand
 
 _P, _I, _F, _LL = C.c_void_p, C.c_int, C.c_float, C.c_longlong
 
@@ -90,6 +91,11 @@ SIGNATURES = {
     "f5e_greedy_pick_dev": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _P, _I],
     "f5e_whisper_ts_pick_dev": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I],
     "f5e_whisper_sample_pick_dev": [_P, _P, _LL, _P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _I, _I, _P, _P],
+    "f5e_gemm_f32_w16_skinny_workspace": [_I, _I, C.POINTER(C.c_ulonglong)],
+    "f5e_gemm_f32_w16_skinny": [_P, _P, _I, _P, _I, _I, _P, _I, _P, _I, _P, _I, _P, C.c_ulonglong, _I, _I, _I],
+    "f5e_gemm_f32_w16": [_P, _P, _I, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _I],
+    "f5e_whisper_embed_w16": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I],
+    "f5e_whisper_embed_w16_dev": [_P, _P, _P, _P, _I, _P, _P, _I, _I, _P, _I, _I],
     "f5e_beam_step": [_P, _P, _LL, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I],
     "f5e_layer_mix_inorm": [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I],
     "f5e_res2_dconv": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I],

@@ -16,6 +16,7 @@
 // The decode step that follows a padded prompt, f5e_attn_decode_from_f32, is attn_decode_kernel's FROM instantiation
 // (attn_decode.hip).
 #include "f5e_common.h"
+#include "w_load.h"
 
 namespace {
 
@@ -111,8 +112,9 @@ __global__ __launch_bounds__(64) void attn_prefill_kernel(PrefillArgs a) {
   }
 }
 
-__global__ void whisper_embed_kernel(const int* __restrict__ ids, const int* __restrict__ begin, const float* __restrict__ emb,
-                                     const float* __restrict__ pos, float* __restrict__ out, int R, int U, int D, int p0,
+template <class WL>   // the token table's loader (w_load.h): fp32, or 16-bit widened in registers
+__global__ void whisper_embed_kernel(const int* __restrict__ ids, const int* __restrict__ begin,
+                                     const typename WL::elem* __restrict__ emb, const float* __restrict__ pos, float* __restrict__ out, int R, int U, int D, int p0,
                                      int max_pos, int table_rows) {
   const int d4 = D / 4;
   const size_t total = (size_t)R * U * d4;
@@ -124,7 +126,7 @@ __global__ void whisper_embed_kernel(const int* __restrict__ ids, const int* __r
     // reading outside the table (as f5e_text_gather)
     const int id = min(max(ids[ru], 0), table_rows - 1);
     const int at = min(max(p0 + u - (begin ? begin[r] : 0), 0), max_pos - 1);
-    *(f32x4*)(out + ru * D + c) = *(const f32x4*)(emb + (size_t)id * D + c) + *(const f32x4*)(pos + (size_t)at * D + c);
+    *(f32x4*)(out + ru * D + c) = WL::load4(emb + (size_t)id * D + c) + *(const f32x4*)(pos + (size_t)at * D + c);
   }
 }
 
@@ -162,15 +164,32 @@ int f5e_attn_prefill_f32(hipStream_t st, const float* qkv, int ld_qkv, float* kc
   return F5E_OK;
 }
 
+template <class WL>
+int whisper_embed_launch(const char* name, hipStream_t st, const int* ids, const int* begin, const void* emb, int emb_align,
+                         const float* pos, float* out, int R, int U, int D, int p0, int max_pos, int table_rows) {
+  F5E_REQUIRE(ids && emb && pos && out, "%s: null operand", name);
+  F5E_REQUIRE(R > 0 && U > 0 && D > 0 && D % 4 == 0 && table_rows > 0 && max_pos > 0 && p0 >= 0 && (long long)p0 + U <= max_pos,
+              "%s: need R, U > 0, D a multiple of 4 and positions p0 .. p0 + U - 1 inside the table (p0=%d U=%d "
+              "max_pos=%d)", name, p0, U, max_pos);
+  F5E_REQUIRE((((uintptr_t)pos | (uintptr_t)out) & 15) == 0 && ((uintptr_t)emb & (uintptr_t)(emb_align - 1)) == 0,
+              "%s: emb, pos and out must be 16-byte aligned (a 16-bit emb: 8-byte)", name);
+  hipLaunchKernelGGL(whisper_embed_kernel<WL>, dim3(grid_for((size_t)R * U * D / 4)), dim3(256), 0, st, ids, begin,
+                     (const typename WL::elem*)emb, pos, out, R, U, D, p0, max_pos, table_rows);
+  F5E_LAUNCH_CHECK(name);
+  return F5E_OK;
+}
+
 int f5e_whisper_embed(hipStream_t st, const int* ids, const int* begin, const float* emb, const float* pos, float* out, int R,
                       int U, int D, int p0, int max_pos, int table_rows) {
-  F5E_REQUIRE(ids && emb && pos && out, "whisper_embed: null operand");
-  F5E_REQUIRE(R > 0 && U > 0 && D > 0 && D % 4 == 0 && table_rows > 0 && max_pos > 0 && p0 >= 0 && (long long)p0 + U <= max_pos,
-              "whisper_embed: need R, U > 0, D a multiple of 4 and positions p0 .. p0 + U - 1 inside the table (p0=%d U=%d "
-              "max_pos=%d)", p0, U, max_pos);
-  F5E_REQUIRE((((uintptr_t)emb | (uintptr_t)pos | (uintptr_t)out) & 15) == 0, "whisper_embed: emb, pos and out must be 16-byte aligned");
-  hipLaunchKernelGGL(whisper_embed_kernel, dim3(grid_for((size_t)R * U * D / 4)), dim3(256), 0, st, ids, begin, emb, pos, out, R,
-                     U, D, p0, max_pos, table_rows);
-  F5E_LAUNCH_CHECK("whisper_embed");
-  return F5E_OK;
+  return whisper_embed_launch<WLoadF32>("whisper_embed", st, ids, begin, emb, 16, pos, out, R, U, D, p0, max_pos, table_rows);
+}
+
+int f5e_whisper_embed_w16(hipStream_t st, const int* ids, const int* begin, const void* emb, int wtype, const float* pos,
+                          float* out, int R, int U, int D, int p0, int max_pos, int table_rows) {
+  F5E_REQUIRE(wtype == F5E_W_FP16 || wtype == F5E_W_BF16, "whisper_embed_w16: wtype %d is neither F5E_W_FP16 nor F5E_W_BF16", wtype);
+  if (wtype == F5E_W_FP16)
+    return whisper_embed_launch<WLoad16<F5E_W_FP16>>("whisper_embed_w16", st, ids, begin, emb, 8, pos, out, R, U, D, p0, max_pos,
+                                                     table_rows);
+  return whisper_embed_launch<WLoad16<F5E_W_BF16>>("whisper_embed_w16", st, ids, begin, emb, 8, pos, out, R, U, D, p0, max_pos,
+                                                   table_rows);
 }

@@ -21,6 +21,7 @@
 //   f5e_whisper_ts_pick_dev       f5e_whisper_ts_pick      + advance
 //   f5e_whisper_sample_pick_dev   f5e_whisper_sample_pick  + advance
 #include "f5e_common.h"
+#include "w_load.h"
 #include "attn_decode_body.h"
 #include "whisper_pick.h"
 
@@ -42,8 +43,9 @@ __global__ __launch_bounds__(64) void attn_decode_dev_kernel(const float* __rest
   attn_decode_body<DK, FROM>(qkv, ld_qkv, kc, vc, row_stride, pos_stride, nullptr, 0, out, ldo, R, H, p, scale, begin);
 }
 
+template <class WL>   // the token table's loader (w_load.h): fp32, or 16-bit widened in registers
 __global__ __launch_bounds__(256) void embed_dev_kernel(const int* __restrict__ last, const int* __restrict__ begin,
-                                                        const float* __restrict__ emb, const float* __restrict__ pos,
+                                                        const typename WL::elem* __restrict__ emb, const float* __restrict__ pos,
                                                         float* __restrict__ out, int R, int D, const int* __restrict__ rec,
                                                         int max_pos, int table_rows) {
   const int d4 = D / 4, p = rec[REC_P];
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(256) void embed_dev_kernel(const int* __restrict__ 
     const int id = min(max(last[r], 0), table_rows - 1);
     const int b = begin ? begin[r] : 0;
     const int at = min(max(p, 0) - min(max(b, 0), max(p, 0)), max_pos - 1);   // max(p - begin[r], 0), without overflow
-    *(f32x4*)(out + (size_t)r * D + c) = *(const f32x4*)(emb + (size_t)id * D + c) + *(const f32x4*)(pos + (size_t)at * D + c);
+    *(f32x4*)(out + (size_t)r * D + c) = WL::load4(emb + (size_t)id * D + c) + *(const f32x4*)(pos + (size_t)at * D + c);
   }
 }
 
@@ -160,17 +162,34 @@ extern "C" int f5e_attn_decode_dev_f32(hipStream_t st, const float* qkv, int ld_
   return F5E_OK;
 }
 
+template <class WL>
+static int embed_dev_launch(const char* name, hipStream_t st, const int* last, const int* begin, const void* emb, int emb_align,
+                            const float* pos, float* out, int R, int D, const int* rec, int max_pos, int table_rows) {
+  F5E_REQUIRE(last && emb && pos && out && rec, "%s: null operand", name);
+  F5E_REQUIRE(R > 0 && D > 0 && D % 4 == 0 && table_rows > 0 && max_pos > 0,
+              "%s: need R > 0, D a multiple of 4 and non-empty tables (R=%d D=%d max_pos=%d)", name, R, D, max_pos);
+  F5E_REQUIRE((((uintptr_t)pos | (uintptr_t)out | (uintptr_t)rec) & 15) == 0 && ((uintptr_t)emb & (uintptr_t)(emb_align - 1)) == 0,
+              "%s: emb, pos, out and the record must be 16-byte aligned (a 16-bit emb: 8-byte)", name);
+  hipLaunchKernelGGL(embed_dev_kernel<WL>, dim3(grid_for((size_t)R * D / 4)), dim3(256), 0, st, last, begin,
+                     (const typename WL::elem*)emb, pos, out, R, D, rec, max_pos, table_rows);
+  F5E_LAUNCH_CHECK(name);
+  return F5E_OK;
+}
+
 extern "C" int f5e_whisper_embed_dev(hipStream_t st, const int* last, const int* begin, const float* emb, const float* pos,
                                      float* out, int R, int D, const int* rec, int max_pos, int table_rows) {
-  F5E_REQUIRE(last && emb && pos && out && rec, "whisper_embed_dev: null operand");
-  F5E_REQUIRE(R > 0 && D > 0 && D % 4 == 0 && table_rows > 0 && max_pos > 0,
-              "whisper_embed_dev: need R > 0, D a multiple of 4 and non-empty tables (R=%d D=%d max_pos=%d)", R, D, max_pos);
-  F5E_REQUIRE((((uintptr_t)emb | (uintptr_t)pos | (uintptr_t)out | (uintptr_t)rec) & 15) == 0,
-              "whisper_embed_dev: emb, pos, out and the record must be 16-byte aligned");
-  hipLaunchKernelGGL(embed_dev_kernel, dim3(grid_for((size_t)R * D / 4)), dim3(256), 0, st, last, begin, emb, pos, out, R, D, rec,
-                     max_pos, table_rows);
-  F5E_LAUNCH_CHECK("whisper_embed_dev");
-  return F5E_OK;
+  return embed_dev_launch<WLoadF32>("whisper_embed_dev", st, last, begin, emb, 16, pos, out, R, D, rec, max_pos, table_rows);
+}
+
+extern "C" int f5e_whisper_embed_w16_dev(hipStream_t st, const int* last, const int* begin, const void* emb, int wtype,
+                                         const float* pos, float* out, int R, int D, const int* rec, int max_pos, int table_rows) {
+  F5E_REQUIRE(wtype == F5E_W_FP16 || wtype == F5E_W_BF16, "whisper_embed_w16_dev: wtype %d is neither F5E_W_FP16 nor F5E_W_BF16",
+              wtype);
+  if (wtype == F5E_W_FP16)
+    return embed_dev_launch<WLoad16<F5E_W_FP16>>("whisper_embed_w16_dev", st, last, begin, emb, 8, pos, out, R, D, rec, max_pos,
+                                                 table_rows);
+  return embed_dev_launch<WLoad16<F5E_W_BF16>>("whisper_embed_w16_dev", st, last, begin, emb, 8, pos, out, R, D, rec, max_pos,
+                                               table_rows);
 }
 
 extern "C" int f5e_greedy_pick_dev(hipStream_t st, const float* logits, long long ld, const int* suppress, int n_sup,

@@ -209,6 +209,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "greedy, --whisper_beam 1, no --whisper_assistant; the time is won with --whisper_step_gemm skinny)")
     ap.add_argument("--whisper_step_gemm", choices=("f32", "skinny"), default="f32",
                     help="--whisper_step_graph: the GEMM of the captured step; skinny spreads each weight read over the whole chip")
+    ap.add_argument("--whisper_weights", choices=("f32", "fp16", "bf16", "auto"), default="f32",
+                    help="--asr whisper: the type the matrices are held in on the device; fp16 / bf16 halve the weight memory and "
+                         "the bytes of a decode step (an fp16 checkpoint then gives the f32 transcripts, bit for bit); auto: the "
+                         "type the checkpoint stores")
     ap.add_argument("--whisper_beam", type=int, default=1,
                     help="--asr whisper: 1 = greedy (run_asr_wer_whisper_large_v3); N > 1 = the pooled beam search of "
                          "generate(num_beams=N) (--beam_size is the wenet flag and does not reach Whisper)")
@@ -253,6 +257,8 @@ def main(argv=None, aligner=None) -> float:
             ap.error("--whisper_step_gemm needs --whisper_step_graph")
         if args.whisper_step_graph:
             ctx.update(step_graph=True, step_gemm=args.whisper_step_gemm)
+        if args.whisper_weights != "f32":
+            ctx.update(weights=args.whisper_weights)
         aligner = WhisperRecognizer(args.whisper_dir, args.device, args.language, beam_size=args.whisper_beam,
                                     long_form=args.whisper_long, **({} if fb is None else dict(fallback=fb)), **ctx)
     elif aligner is None:

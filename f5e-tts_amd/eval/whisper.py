@@ -42,8 +42,20 @@ without the timestamp rules; the tokens are those of this model alone.
 
 Out of scope: speculative sampling (an assistant with temperature > 0), beam search with an assistant, ``transformers``'
 heuristic draft schedule and confidence threshold, per-row positions (the rows of a batch advance together), beam-sample, top-k / top-p, the pipeline's strided ``chunk_length_s`` merging, word timestamps across windows,
-the prefill inside ``alignment_probs`` / ``token_timestamps``, patience, CTranslate2's exact search, bf16 / fp16 weights (fp16
-checkpoints are widened), beam search, assisted generation and word timestamps from a captured step.
+the prefill inside ``alignment_probs`` / ``token_timestamps``, patience, CTranslate2's exact search, beam search, assisted
+generation and word timestamps from a captured step.
+
+16-bit weights (``Whisper(config, weights="fp16" | "bf16")``, ``from_pretrained_dir(path, weights="auto")``): every
+Linear matrix, both conv kernels and the token embedding live on the device once, in the checkpoint's 16 bits, and are widened in
+registers by the GEMM that reads them (f5e_gemm_f32_w16, f5e_gemm_f32_w16_skinny, f5e_whisper_embed_w16(_dev);
+csrc/gemm_f32_w16.hip).  Biases, LayerNorms, both position tables, activations and caches stay fp32.  Widening is exact and the
+summation order is the fp32 kernels', so every decode mode gives the bits of the fp32 model that holds the same (rounded)
+values, at half the weight memory and half the bytes per decode step.  That buys memory, not time: the step is bound by its
+launches (measured, DESIGN 4o: the captured skinny step is level with fp32), the eager step runs on the register-staged tile and
+is 2.3x slower than in fp32, so decode a 16-bit model with ``step_graph=True, step_gemm="skinny"``; the encoder, on the same
+tile, is 5 % slower per window.  Out of scope there: 16-bit self or cross K/V caches,
+16-bit activations or bf16 / fp16 MFMA for the encoder (it stays compute-bound on the fp32 MFMA and gains memory only), 16-bit
+weights for WavLM, wav2vec2 or the wenet models, fp8.
 
 The captured step (``generate`` / ``transcribe_long`` / ``generate_from_kv(step_graph=True)``): the picks of a greedy, ruled or
 sampled decode are replayed from one decode step captured as a hipGraph; the position lives in a device record that the
@@ -72,6 +84,9 @@ from ..xfmr_f32 import fold, fold_layer, layer
 
 Tensor = torch.Tensor
 F32, I32 = torch.float32, torch.int32
+# ``Whisper(weights=)``: the type the matrices are stored in on the device (None: fp32, as always)
+WEIGHT_MODES = {"f32": None, "fp16": torch.float16, "bf16": torch.bfloat16}
+
 SAMPLE_RATE, N_FFT, HOP = 16000, 400, 160
 
 LANGUAGE_NAMES = {"english": "en", "chinese": "zh", "mandarin": "zh", "german": "de", "spanish": "es", "russian": "ru",
@@ -499,8 +514,9 @@ def compression_ratio(tokens: Sequence[int], vocab_size: int) -> float:
 _ST_DTYPES = {"F32": np.dtype("<f4"), "F16": np.dtype("<f2"), "BF16": np.dtype("<u2"), "F64": np.dtype("<f8")}
 
 
-def read_safetensors(path: str) -> Dict[str, Tensor]:
-    """Every floating tensor of a ``.safetensors`` file as float32 (fp16 and bf16 are widened, which is exact)."""
+def read_safetensors(path: str, stored: bool = False) -> Dict[str, Tensor]:
+    """Every floating tensor of a ``.safetensors`` file as float32 (fp16 and bf16 are widened, which is exact).  ``stored``: in
+    the type the file stores it in instead (F16 -> torch.float16, BF16 -> torch.bfloat16, F32, F64), bit for bit."""
     out = {}
     with open(path, "rb") as f:
         (n,) = struct.unpack("<Q", f.read(8))
@@ -512,10 +528,39 @@ def read_safetensors(path: str) -> Dict[str, Tensor]:
             lo, hi = meta["data_offsets"]
             f.seek(base + lo)
             arr = np.frombuffer(f.read(hi - lo), dtype=_ST_DTYPES[meta["dtype"]])
+            if stored:
+                t = torch.from_numpy(np.array(arr).view(np.int16) if meta["dtype"] == "BF16" else np.array(arr))
+                out[name] = (t.view(torch.bfloat16) if meta["dtype"] == "BF16" else t).reshape(meta["shape"])
+                continue
             if meta["dtype"] == "BF16":
                 arr = (arr.astype(np.uint32) << 16).view(np.float32)
             out[name] = torch.from_numpy(np.array(arr, dtype=np.float32).reshape(meta["shape"]))
     return out
+
+
+def cast_checked(name: str, t: Tensor, dtype) -> Tensor:
+    """``t`` in ``dtype``: a pure copy when it has that type, otherwise rounded to nearest-even where ``dtype`` does not hold
+    the value.  A finite value that would become infinite (fp32 -> fp16 beyond 65504) is refused, naming the parameter."""
+    if not isinstance(t, Tensor) or not t.is_floating_point():
+        raise _C.F5EError(f"Whisper.load_state_dict: {name} must be a floating tensor (got {getattr(t, 'dtype', type(t))})")
+    if t.dtype == dtype:
+        return t
+    r = t.detach().to(dtype)                     # torch converts floating types with round-to-nearest-even
+    bad = torch.isinf(r) & torch.isfinite(t)
+    if bool(bad.any()):
+        worst = float(t.detach()[bad].double().abs().max())
+        raise _C.F5EError(f"Whisper.load_state_dict: {name} holds {worst:g}, which {str(dtype).replace('torch.', '')} cannot "
+                          f"hold (its largest finite value is {torch.finfo(dtype).max:g}): load it with another weights= mode")
+    return r
+
+
+_MATRIX_SUFFIXES = ("_proj.weight", "fc1.weight", "fc2.weight", "conv1.weight", "conv2.weight", "embed_tokens.weight")
+
+
+def is_matrix(name: str) -> bool:
+    """Whether the parameter ``name`` is stored in the weight mode's type: the Linear matrices, both conv kernels and the token
+    embedding.  Everything else (biases, LayerNorms, both position tables) is fp32 in every mode."""
+    return name.endswith(_MATRIX_SUFFIXES)
 
 
 # ---- weight holders -------------------------------------------------------------------------------------------------------------
@@ -575,16 +620,39 @@ def _prompt_len(prompt) -> int:
     return len(prompt[0]) if len(prompt) and isinstance(prompt[0], (list, tuple)) else len(prompt)
 
 
+def _gemm(a, w, bias=None, **kw):
+    """``ops.gemm_f32`` or, for a 16-bit weight, ``ops.gemm_f32_w16``: the ``gemm`` hook of ``xfmr_f32.layer``."""
+    return (ops.gemm_f32 if w.dtype == F32 else ops.gemm_f32_w16)(a, w, bias, **kw)
+
+
+def _gemm_skinny(a, w, bias=None, **kw):
+    return (ops.gemm_f32_skinny if w.dtype == F32 else ops.gemm_f32_w16_skinny)(a, w, bias, **kw)
+
+
+def _embed(ids, emb, *a):
+    return (ops.whisper_embed if emb.dtype == F32 else ops.whisper_embed_w16)(ids, emb, *a)
+
+
 def _f(t: Tensor, dev) -> Tensor:
     return t.detach().to(dev, F32).contiguous()
 
 
 class Whisper(nn.Module):
-    def __init__(self, config: Optional[WhisperConfig] = None):
+    def __init__(self, config: Optional[WhisperConfig] = None, weights: str = "f32"):
+        """``weights``: "f32" (the default: nothing changes), or "fp16" / "bf16": the matrices (``is_matrix``) are held in that
+        type, once, and widened in registers by the GEMMs that read them; every decode path gives the bits of the fp32 model
+        with the same values."""
         super().__init__()
         self.cfg = cfg = config or WhisperConfig()
         cfg.check()
+        if weights not in WEIGHT_MODES:
+            raise _C.F5EError(f"Whisper: weights = {weights!r} must be one of {sorted(WEIGHT_MODES)}")
+        self.weights, self.wdtype = weights, WEIGHT_MODES[weights]
         self.model = _Model(cfg)
+        if self.wdtype is not None:
+            for name, p in self.named_parameters():
+                if is_matrix(name):
+                    p.data = p.data.to(self.wdtype)
         self.id_to_piece: Dict[int, str] = {}
         self.first_special = cfg.eos_token_id
         self.bpe_ranks: Dict[Tuple[str, str], int] = {}
@@ -596,9 +664,13 @@ class Whisper(nn.Module):
 
     # ---- loading ---------------------------------------------------------------------------------------------------------------
     @classmethod
-    def from_pretrained_dir(cls, path: str) -> "Whisper":
+    def from_pretrained_dir(cls, path: str, weights: str = "f32") -> "Whisper":
         """A local Hugging Face model directory: ``config.json``, ``generation_config.json``, ``model.safetensors`` (or
-        ``model.safetensors.index.json`` and its shards), ``vocab.json`` and ``added_tokens.json``."""
+        ``model.safetensors.index.json`` and its shards), ``vocab.json`` and ``added_tokens.json``.  ``weights``: the mode of
+        ``Whisper(weights=)``, or "auto": the type the checkpoint stores its matrices in (fp16 files load as "fp16" without
+        a rounding; a file of mixed or other types as "f32")."""
+        if weights != "auto" and weights not in WEIGHT_MODES:
+            raise _C.F5EError(f"Whisper.from_pretrained_dir: weights = {weights!r} must be 'auto' or one of {sorted(WEIGHT_MODES)}")
         def js(name, required=True):
             p = os.path.join(path, name)
             if not os.path.exists(p):
@@ -607,7 +679,7 @@ class Whisper(nn.Module):
                 return None
             with open(p, encoding="utf-8") as f:
                 return json.load(f)
-        model = cls(WhisperConfig.from_dicts(js("config.json"), js("generation_config.json", False)))
+        config = WhisperConfig.from_dicts(js("config.json"), js("generation_config.json", False))
         index = js("model.safetensors.index.json", False)
         files = sorted(set(index["weight_map"].values())) if index else ["model.safetensors"]
         sd = {}
@@ -615,7 +687,11 @@ class Whisper(nn.Module):
             p = os.path.join(path, name)
             if not os.path.exists(p):
                 raise _C.F5EError(f"Whisper.from_pretrained_dir: {p} is missing")
-            sd.update(read_safetensors(p))
+            sd.update(read_safetensors(p, stored=weights != "f32"))
+        if weights == "auto":
+            stored = {v.dtype for k, v in sd.items() if is_matrix(k)}
+            weights = {(torch.float16,): "fp16", (torch.bfloat16,): "bf16"}.get(tuple(stored), "f32")
+        model = cls(config, weights=weights)
         model.load_state_dict(sd)
         vocab = js("vocab.json", False)
         if vocab is not None:
@@ -705,9 +781,29 @@ class Whisper(nn.Module):
         return out
 
     def load_state_dict(self, state_dict, strict: bool = True, **kw):
-        sd = {k: v for k, v in state_dict.items() if k != "proj_out.weight"}       # tied to model.decoder.embed_tokens.weight
+        """Any floating dtype per tensor (``cast_checked``): a matrix goes to the weight mode's type, everything else to fp32; a
+        tensor that has its target type is copied as it is."""
+        sd = {k: cast_checked(k, v, self.wdtype if self.wdtype is not None and is_matrix(k) else F32)
+              for k, v in state_dict.items() if k != "proj_out.weight"}            # tied to model.decoder.embed_tokens.weight
         self._folded = None
         return super().load_state_dict(sd, strict=strict, **kw)
+
+    def device_bytes(self) -> int:
+        """Bytes of device memory behind every tensor the model holds (parameters and what ``_fold`` keeps beside them: stacked
+        projections, the front-end's tables, suppression lists; no decode state), each storage counted once."""
+        fd = self._fold()
+        seen, stack = {}, [list(self.parameters()), {k: v for k, v in fd.items() if k != "step_states"}]
+        while stack:
+            o = stack.pop()
+            if isinstance(o, Tensor):
+                if o.is_cuda:
+                    st = o.untyped_storage()
+                    seen[st.data_ptr()] = st.nbytes()
+            elif isinstance(o, dict):
+                stack.extend(o.values())
+            elif isinstance(o, (list, tuple)):
+                stack.extend(o)
+        return sum(seen.values())
 
     def train(self, mode: bool = True):
         if mode:
@@ -730,16 +826,38 @@ class Whisper(nn.Module):
         def rec(lyr, ca=None):        # k_proj has no bias: fold_layer leaves zeros in the k third of qkv[1], the k half of xkv[1]
             sa = lyr.self_attn
             x = dict(ln_x=lyr.encoder_attn_layer_norm, xq=ca.q_proj, xk=ca.k_proj, xv=ca.v_proj, xout=ca.out_proj) if ca else {}
-            return fold_layer(dev, lyr.self_attn_layer_norm, sa.q_proj, sa.k_proj, sa.v_proj, sa.out_proj, lyr.final_layer_norm,
-                              lyr.fc1, lyr.fc2, **x)
+            W = fold_layer(dev, lyr.self_attn_layer_norm, sa.q_proj, sa.k_proj, sa.v_proj, sa.out_proj, lyr.final_layer_norm,
+                           lyr.fc1, lyr.fc2, wdtype=wd, **x)
+            if wd is not None:        # stored once: q, k, v (and the cross k, v) become views of the stacked record
+                share(W.qkv, sa.q_proj, sa.k_proj, sa.v_proj)
+                if ca:
+                    share(W.xkv, ca.k_proj, ca.v_proj)
+            return W
+
+        def share(pair, *ms):
+            r = 0
+            for m in ms:
+                n = m.weight.shape[0]
+                m.weight.data = pair[0][r:r + n]
+                if m.bias is not None:
+                    m.bias.data = pair[1][r:r + n]
+                r += n
+
+        def conv_w(conv):             # tap-major: k = tap * C_in + ic, the column order of f5e_im2col
+            w = conv.weight.detach().to(dev).permute(0, 2, 1)
+            w2 = w.reshape(w.shape[0], -1).contiguous()
+            if wd is not None:        # the parameter becomes the [out, in, tap] view of the layout the GEMM reads
+                conv.weight.data = w2.view(w.shape).permute(0, 2, 1)
+            return w2
+        wd = self.wdtype
+        mat = (lambda t: _f(t, dev)) if wd is None else (lambda t: t.detach().to(dev).contiguous())   # noqa: E731
         fd = dict(device=dev,
                   window=torch.from_numpy(hann_window()).to(dev, F32), twiddle=torch.from_numpy(dft_twiddle()).to(dev, F32).contiguous(),
                   fb=torch.from_numpy(mel_filters(cfg.num_mel_bins)).to(dev, F32).contiguous(),
-                  # tap-major conv weights: k = tap * C_in + ic, the column order of f5e_im2col
-                  c1_w=_f(enc.conv1.weight.permute(0, 2, 1).reshape(cfg.d_model, -1), dev), c1_b=_f(enc.conv1.bias, dev),
-                  c2_w=_f(enc.conv2.weight.permute(0, 2, 1).reshape(cfg.d_model, -1), dev), c2_b=_f(enc.conv2.bias, dev),
+                  c1_w=mat(conv_w(enc.conv1)), c1_b=_f(enc.conv1.bias, dev),
+                  c2_w=mat(conv_w(enc.conv2)), c2_b=_f(enc.conv2.bias, dev),
                   enc_pos=_f(enc.embed_positions.weight, dev), enc_ln=fold(dev, enc.layer_norm), enc=[rec(l) for l in enc.layers],
-                  emb=_f(dec.embed_tokens.weight, dev), dec_pos=_f(dec.embed_positions.weight, dev), dec_ln=fold(dev, dec.layer_norm),
+                  emb=mat(dec.embed_tokens.weight), dec_pos=_f(dec.embed_positions.weight, dev), dec_ln=fold(dev, dec.layer_norm),
                   dec=[rec(l, l.encoder_attn) for l in dec.layers])
         fd["suppress"] = torch.tensor(list(cfg.suppress_tokens), dtype=I32, device=dev) if cfg.suppress_tokens else None
         fd["begin_suppress"] = torch.tensor(list(cfg.begin_suppress_tokens), dtype=I32, device=dev) if cfg.begin_suppress_tokens else None
@@ -800,12 +918,12 @@ class Whisper(nn.Module):
         dev = feats.device
         col1 = ops.im2col(feats.contiguous(), torch.empty(B, T, 3 * M, dtype=F32, device=dev), 3, 1)
         h1 = torch.empty(B * T, D, dtype=F32, device=dev)
-        ops.gemm_f32(col1.view(B * T, 3 * M), fd["c1_w"], fd["c1_b"], out=h1, act=ops.ACT_GELU_ERF)
+        _gemm(col1.view(B * T, 3 * M), fd["c1_w"], fd["c1_b"], out=h1, act=ops.ACT_GELU_ERF)
         col2 = ops.im2col(h1.view(B, T, D), torch.empty(B, T, 3 * D, dtype=F32, device=dev), 3, 1)
         x = torch.empty(B * Tp, D, dtype=F32, device=dev)
         # stride 2: output frame t reads im2col row 2 t (T is even, so this holds across the rows of a batch): lda doubled
-        ops.gemm_f32(torch.as_strided(col2, (B * Tp, 3 * D), (6 * D, 1)), fd["c2_w"], fd["c2_b"], out=x, act=ops.ACT_GELU_ERF,
-                     addend=fd["enc_pos"])
+        _gemm(torch.as_strided(col2, (B * Tp, 3 * D), (6 * D, 1)), fd["c2_w"], fd["c2_b"], out=x, act=ops.ACT_GELU_ERF,
+              addend=fd["enc_pos"])
         del col1, h1, col2
         M_ = B * Tp
         z = lambda n: torch.empty(M_, n, dtype=F32, device=dev)   # noqa: E731
@@ -815,7 +933,7 @@ class Whisper(nn.Module):
             ops.mha_f32(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], H, (D // H) ** -0.5, B=B, out=ao)
 
         for W in fd["enc"]:
-            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn)
+            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn, gemm=_gemm)
         ops.layernorm(x, x, *fd["enc_ln"], eps=1e-5)
         return x.view(B, Tp, D)
 
@@ -832,7 +950,7 @@ class Whisper(nn.Module):
         res = []
         for i, p in enumerate(fd["dec"]):
             kv = torch.empty(B * Tp, 2 * D, dtype=F32, device=enc_out.device) if out is None else out[i].view(B * Tp, 2 * D)
-            ops.gemm_f32(enc_out.view(B * Tp, D), *p.xkv, out=kv)
+            _gemm(enc_out.view(B * Tp, D), *p.xkv, out=kv)
             kv = kv.view(B, Tp, 2 * D)
             res.append((kv[..., :D], kv[..., D:]))
         return res
@@ -882,18 +1000,19 @@ class Whisper(nn.Module):
         R, D = last.shape[0], cfg.d_model
         x3, xn, (at, bufs, self_attn, cross_attn) = st["x"], st["xn"], st["layer"]
         at.p, at.anc, at.kv, at.align, at.begin = p, anc, kv, align, begin
-        if begin is None:
+        if begin is None and fd["emb"].dtype == F32:
             ops.text_gather(last.view(R, 1), fd["emb"], fd["dec_pos"][p:p + 1], None, x3)
-        else:
-            ops.whisper_embed(last.view(R, 1), fd["emb"], fd["dec_pos"], x3, p, begin)
+        else:                         # a 16-bit table without padding: the same sum, emb[last] + pos[p]
+            _embed(last.view(R, 1), fd["emb"], fd["dec_pos"], x3, p, begin)
         x = x3.view(R, D)
         for i, W in enumerate(fd["dec"]):
             at.i = i
-            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn, cross_attn=cross_attn)
+            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn, cross_attn=cross_attn,
+                  gemm=_gemm)
         if not want_logits:
             return None
         ops.layernorm(x, xn, *fd["dec_ln"], eps=1e-5)
-        return ops.gemm_f32(xn, fd["emb"], None, out=st["logits"])
+        return _gemm(xn, fd["emb"], None, out=st["logits"])
 
     @torch.no_grad()
     def decoder_prefill(self, st: dict, kv: List[Tuple[Tensor, Tensor]], ids, begin: Optional[Tensor] = None,
@@ -929,7 +1048,7 @@ class Whisper(nn.Module):
         K, H, M = Rs // R, cfg.decoder_attention_heads, R * U0
         scale, at = (D // H) ** -0.5, SimpleNamespace(i=0)
         z = lambda n: torch.empty(M, n, dtype=F32, device=dev)   # noqa: E731
-        x = ops.whisper_embed(ids, fd["emb"], fd["dec_pos"], torch.empty(R, U0, D, dtype=F32, device=dev), 0, begin).view(M, D)
+        x = _embed(ids, fd["emb"], fd["dec_pos"], torch.empty(R, U0, D, dtype=F32, device=dev), 0, begin).view(M, D)
         bufs = (z(D), z(3 * D), z(D), z(D), z(cfg.decoder_ffn_dim))
 
         def self_attn(_W, _xn, qkv, ao):
@@ -942,14 +1061,15 @@ class Whisper(nn.Module):
 
         for i, W in enumerate(fd["dec"]):
             at.i = i
-            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn, cross_attn=cross_attn)
+            layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=self_attn, cross_attn=cross_attn,
+                  gemm=_gemm)
         if not want:
             return None
         V = cfg.vocab_size
         rows = x.view(R, U0, D)[:, want].reshape(R * len(want), D)
         ops.layernorm(rows, rows, *fd["dec_ln"], eps=1e-5)
         logits = torch.empty(R * len(want), (V + 3) // 4 * 4, dtype=F32, device=dev)[:, :V]
-        return ops.gemm_f32(rows, fd["emb"], None, out=logits).view(R, len(want), V)
+        return _gemm(rows, fd["emb"], None, out=logits).view(R, len(want), V)
 
     @torch.no_grad()
     def decoder_append(self, st: dict, kv: List[Tuple[Tensor, Tensor]], ids: Tensor, p0: int, begin: Optional[Tensor] = None,
@@ -982,10 +1102,13 @@ class Whisper(nn.Module):
             z = lambda *n: torch.empty(*n, dtype=F32, device=dev)   # noqa: E731
             scratch[M] = (z(R, U, D), (z(M, D), z(M, 3 * D), z(M, D), z(M, D), z(M, cfg.decoder_ffn_dim)))
         x3, bufs = scratch[M]
-        x = ops.whisper_embed(ids, fd["emb"], fd["dec_pos"], x3, p0, begin).view(M, D)
+        x = _embed(ids, fd["emb"], fd["dec_pos"], x3, p0, begin).view(M, D)
 
         def gemm(a, w, bias=None, *, out, act=ops.ACT_NONE, addend=None):
-            return self._append_gemm(a.shape[0], w.shape[0], w.shape[1])(a, w, bias, out=out, act=act, addend=addend)
+            fn = self._append_gemm(a.shape[0], w.shape[0], w.shape[1])
+            if w.dtype != F32:        # the 16-bit sibling of whichever the rule chose
+                fn = ops.gemm_f32_w16_skinny if fn is ops.gemm_f32_skinny else ops.gemm_f32_w16
+            return fn(a, w, bias, out=out, act=act, addend=addend)
 
         def self_attn(_W, _xn, qkv, ao):
             kc, vc = st["caches"][at.i]
@@ -1190,7 +1313,8 @@ class Whisper(nn.Module):
                               "step_gemm = 'f32' takes the rest")
         cfg, fd = self.cfg, self._fold()
         cache = fd.setdefault("step_states", {})
-        key = (B, kind, padded, step_gemm, Tp, str(dev))
+        # the GEMM field names the weight mode too where there is one: "skinny+fp16" captures the _w16 launches
+        key = (B, kind, padded, step_gemm if self.wdtype is None else f"{step_gemm}+{self.weights}", Tp, str(dev))
         S = cache.pop(key, None)
         if S is None:
             D, P, FF, V = cfg.d_model, cfg.max_target_positions, cfg.decoder_ffn_dim, cfg.vocab_size
@@ -1198,7 +1322,7 @@ class Whisper(nn.Module):
             S = SimpleNamespace(key=key, kind=kind, R=B, graph=None, captures=0, replays=0, st=self._dec_state(B, P, dev), tokens=zi(B, P), last=zi(B),
                                 done=zi(B), alive=zi(1), sum_logp=torch.zeros(B, dtype=F32, device=dev), row_key=zi(B),
                                 serial=zi(B), begin=zi(B) if padded else None, rec=zi(ops.STEP_REC_WORDS),
-                                xkv=[torch.empty(B, Tp, 2 * D, dtype=F32, device=dev) for _ in fd["dec"]], gemm=None,
+                                xkv=[torch.empty(B, Tp, 2 * D, dtype=F32, device=dev) for _ in fd["dec"]], gemm=_gemm,
                                 stream=torch.cuda.Stream(device=dev))
             S.kv = [(b[..., :D], b[..., D:]) for b in S.xkv]
             H, scale, at = cfg.decoder_attention_heads, (D // cfg.decoder_attention_heads) ** -0.5, S.st["layer"][0]
@@ -1212,7 +1336,7 @@ class Whisper(nn.Module):
                 ws = torch.empty(max(need, 16) // 4, dtype=F32, device=dev)
 
                 def gemm(a, w, bias=None, *, out, act=ops.ACT_NONE, addend=None):
-                    return ops.gemm_f32_skinny(a, w, bias, out=out, act=act, addend=addend, workspace=ws)
+                    return _gemm_skinny(a, w, bias, out=out, act=act, addend=addend, workspace=ws)
                 S.gemm, S.ws = gemm, ws
         cache[key] = S                                          # most recently used last
         while len(cache) > STEP_STATES:
@@ -1252,14 +1376,15 @@ class Whisper(nn.Module):
         st = S.st
         at, bufs, _, cross_attn = st["layer"]
         at.anc, at.kv, at.align, at.begin = None, S.kv, None, S.begin
-        ops.whisper_embed_dev(S.last, fd["emb"], fd["dec_pos"], st["x"], S.rec, S.begin)
+        (ops.whisper_embed_dev if fd["emb"].dtype == F32 else ops.whisper_embed_w16_dev)(S.last, fd["emb"], fd["dec_pos"], st["x"],
+                                                                                         S.rec, S.begin)
         x = st["x"].view(R, D)
         for i, W in enumerate(fd["dec"]):
             at.i = i
             layer(x, x, W, bufs, pre_norm=True, act=ops.ACT_GELU_ERF, eps=1e-5, self_attn=S.self_attn, cross_attn=cross_attn,
                   gemm=S.gemm)
         ops.layernorm(x, st["xn"], *fd["dec_ln"], eps=1e-5)
-        (S.gemm or ops.gemm_f32)(st["xn"], fd["emb"], None, out=st["logits"])
+        S.gemm(st["xn"], fd["emb"], None, out=st["logits"])
         kw = dict(suppress=fd["suppress"], begin_suppress=fd["begin_suppress"])
         if S.kind.startswith("sample"):
             ops.whisper_sample_pick_dev(st["logits"], S.tokens, S.last, S.done, S.alive, S.sum_logp, S.rec, eos,
@@ -2087,8 +2212,11 @@ class WhisperRecognizer:
     def __init__(self, path: str, device="cuda", language: Optional[str] = "en", beam_size: int = 1, long_form: bool = False,
                  fallback: Optional[Fallback] = None, initial_prompt: Optional[str] = None,
                  condition_on_previous_text: bool = False, assistant_dir: Optional[str] = None, num_assistant_tokens: int = 5,
-                 assistant_shares_encoder: bool = False, step_graph: bool = False, step_gemm: str = "f32"):
-        """``language``: a name or code, or None / "auto" to detect it per recording.  ``long_form``: ``transcribe`` runs the
+                 assistant_shares_encoder: bool = False, step_graph: bool = False, step_gemm: str = "f32", weights: str = "f32", assistant_weights: Optional[str] = None):
+        """``weights``: "f32", "fp16", "bf16" or "auto" (``Whisper.from_pretrained_dir``), for the model and, unless
+        ``assistant_weights`` names another mode for it, its assistant (the two need not agree; the transcripts are the model's): a
+        16-bit mode halves the weight memory and the bytes of a decode step and gives the fp32 path's transcripts on an fp16
+        checkpoint.  ``language``: a name or code, or None / "auto" to detect it per recording.  ``long_form``: ``transcribe`` runs the
         seek loop over the whole recording (``Whisper.transcribe_long``) instead of cutting it to the first chunk.  ``fallback``:
         the temperature fallback of that loop (needs ``long_form``).  ``initial_prompt``: text (a name, a domain word; ``Whisper.get_prompt_ids``, so
         the checkpoint needs merges.txt) given as a "first-segment" prompt: without conditioning it is put in front of EVERY
@@ -2115,7 +2243,7 @@ class WhisperRecognizer:
         self.language = language
         self.beam_size = int(beam_size)      # the constructor's alone: transcribe() ignores the wenet flag of the same name
         self.long_form = bool(long_form)
-        self.model = Whisper.from_pretrained_dir(path).to(self.device)
+        self.model = Whisper.from_pretrained_dir(path, weights=weights).to(self.device)
         if self._lang() is not None:
             self.model.prompt_ids(language)                  # a language the checkpoint does not know fails here, not per file
         elif not self.model.cfg.lang_to_id:
@@ -2129,7 +2257,7 @@ class WhisperRecognizer:
             self.model._check_context(self.context)          # a prompt that leaves no room fails here, not per file
         self.assistant, self._assist = None, {}
         if assistant_dir is not None:
-            self.assistant = Whisper.from_pretrained_dir(assistant_dir).to(self.device)
+            self.assistant = Whisper.from_pretrained_dir(assistant_dir, weights=assistant_weights or weights).to(self.device)
             self.model._check_assistant(self.assistant, num_assistant_tokens, self.beam_size, False, 0.0)     # fails here, not per file
             self.model._check_shared_encoder(self.assistant, bool(assistant_shares_encoder),
                                              "transcribe_long" if self.long_form else "generate")

@@ -73,6 +73,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--ref_language", type=str, default="english", help="--whisper_dir: the language spoken in the reference audio; auto: detected "
                    "from the audio")
     p.add_argument("--whisper_beam", type=int, default=1, help="--whisper_dir: 1 = greedy; N > 1 = beam search with N beams")
+    p.add_argument("--whisper_weights", type=str, choices=("f32", "fp16", "bf16", "auto"), default="f32",
+                   help="--whisper_dir: the type the model's matrices are held in on the device (fp16 / bf16: half the memory; auto: "
+                        "the type the checkpoint stores)")
     p.add_argument("--whisper_assistant", type=str, default=None, metavar="DIR",
                    help="--whisper_dir: a local draft model directory (whisper-large-v3-turbo, distil-whisper) for assisted "
                         "generation: the same transcript with fewer passes of the large decoder; greedy only")
@@ -237,6 +240,8 @@ def main(argv=None):
             prompt["assistant_dir"] = args.whisper_assistant
         if args.whisper_step_graph:
             prompt["step_graph"] = True
+        if args.whisper_weights != "f32":
+            prompt["weights"] = args.whisper_weights
         transcriber = WhisperRecognizer(args.whisper_dir, s["device"], args.ref_language, beam_size=args.whisper_beam, **prompt)
     for v in voices.values():   # reference infer_cli.py:297-303
         v["ref_audio"], v["ref_text"] = U.preprocess_ref_audio_text(v["ref_audio"], v["ref_text"], transcriber=transcriber)

@@ -144,6 +144,9 @@ def build_parser() -> argparse.ArgumentParser:
                                                    "instead (needs alignment_heads in its generation_config.json)")
     p.add_argument("--whisper_language", type=str, default="en", help="The recording's language, for --whisper_dir")
     p.add_argument("--whisper_beam", type=int, default=1, help="Beam size of the --whisper_dir transcription (1: greedy)")
+    p.add_argument("--whisper_weights", type=str, choices=("f32", "fp16", "bf16", "auto"), default="f32",
+                   help="The type the --whisper_dir model's matrices are held in on the device (fp16 / bf16: half the memory; auto: "
+                        "the type the checkpoint stores)")
     p.add_argument("-m", "--model", type=str, default="F5TTS_v1_Base", help="The model name")
     p.add_argument("-mc", "--model_cfg", type=str, default="", help="The path to the model config file .yaml")
     p.add_argument("-p", "--ckpt_file", type=str, required=True, help="The path to model checkpoint .pt/.safetensors")
@@ -184,7 +187,8 @@ def main(argv=None):
         aligner = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, args.device, asr=True)
     elif parts is None:
         from ..eval.whisper import WhisperRecognizer
-        aligner = WhisperRecognizer(args.whisper_dir, args.device, args.whisper_language, args.whisper_beam)
+        aligner = WhisperRecognizer(args.whisper_dir, args.device, args.whisper_language, args.whisper_beam,
+                                    **({} if args.whisper_weights == "f32" else dict(weights=args.whisper_weights)))
     wave, sr, _mel = speech_edit_process(args.audio, args.origin_text, args.target_text, model, vocoder,
                                          parts_to_edit=parts, fix_duration=fix, aligner=aligner,
                                          mel_spec_type=args.vocoder_name, nfe_step=args.nfe_step,

@@ -43,6 +43,9 @@ def _p(t: Optional[Tensor], dtype=None, name="tensor"):
 
 
 BF, F32, I32, U8 = torch.bfloat16, torch.float32, torch.int32, torch.uint8
+F16 = torch.float16
+# the 16-bit weight types of the _w16 ops and their F5E_W_* codes
+W16_TYPES = {F16: _C.W_FP16, BF: _C.W_BF16}
 
 
 def _rows(t: Tensor, dtypes, name: str, cols: int, vec: int = 4, whole_rows: bool = False):
@@ -399,25 +402,73 @@ def grn(x: Tensor, out: Tensor, gamma: Tensor, beta: Tensor, ws: Tensor):
     return out
 
 
-def _gemm_view(t: Tensor, dtype, name: str, cols: int, rows: int, overlap: bool = False):
+def _gemm_view(t: Tensor, dtype, name: str, cols: int, rows: int, overlap: bool = False, op: str = "gemm_f32"):
     """A row-strided operand of ``gemm_f32`` of which the kernel touches ``cols`` elements in each of ``rows`` rows: 2-D,
     ``dtype``, on the GPU, unit column stride, at least ``cols`` wide, and the storage behind the view holds
     (rows - 1) * row stride + cols elements.  Any alignment (the scalar epilogue and the plain kernel take what the vector
     paths cannot).  ``overlap``: rows may overlap (row stride < cols), for operands that are only read."""
-    if t.ndim != 2 or not t.is_cuda or t.dtype != dtype or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise _C.F5EError(f"gemm_f32: {name} must be a 2-D {dtype} GPU tensor with unit column stride (got {t.dtype}, "
+    if t.ndim != 2 or not t.is_cuda or t.dtype not in (dtype if isinstance(dtype, tuple) else (dtype,)) \
+            or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise _C.F5EError(f"{op}: {name} must be a 2-D {dtype} GPU tensor with unit column stride (got {t.dtype}, "
                           f"{t.device}, shape {tuple(t.shape)}, strides {tuple(t.stride())})")
     if t.shape[1] < cols:
-        raise _C.F5EError(f"gemm_f32: {name} has {t.shape[1]} columns, fewer than the {cols} the problem needs")
+        raise _C.F5EError(f"{op}: {name} has {t.shape[1]} columns, fewer than the {cols} the problem needs")
     ld = t.stride(0)
     if rows > 1 and ld < (0 if overlap else cols):
-        raise _C.F5EError(f"gemm_f32: {name}: row stride {ld} is smaller than the {cols} columns of a row")
+        raise _C.F5EError(f"{op}: {name}: row stride {ld} is smaller than the {cols} columns of a row")
     if rows <= t.shape[0]:
         return                        # inside the view itself, which torch keeps inside its storage
     have = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
     need = (rows - 1) * ld + cols
     if have < need:
-        raise _C.F5EError(f"gemm_f32: {name}: {rows} rows of stride {ld} need {need} elements, the storage holds {have}")
+        raise _C.F5EError(f"{op}: {name}: {rows} rows of stride {ld} need {need} elements, the storage holds {have}")
+
+
+def _gemm_f32(op: str, w_dtypes, a, w, bias, out, out_bf16, M, a_act, act, ch_scale, addend, row_scale, K):
+    """``gemm_f32`` and ``gemm_f32_w16``: one set of checks, the entry point follows ``w.dtype``."""
+    require_device()
+    for t, nm, dts in ((a, "a", (F32,)), (w, "w", w_dtypes)):
+        if t.ndim != 2 or not t.is_cuda or t.dtype not in dts or (t.stride(1) != 1 and t.shape[1] > 1):
+            raise _C.F5EError(f"{op}: {nm} must be a 2-D {'f32' if dts == (F32,) else 'fp16 / bf16'} GPU tensor with unit column "
+                              f"stride (got {getattr(t, 'dtype', None)})")
+    a_rows = a.shape[0]
+    K = a.shape[1] if K is None else int(K)
+    N = w.shape[0]
+    M = a_rows if M is None else int(M)
+    if K > a.shape[1] or K > w.shape[1]:
+        raise _C.F5EError(f"{op}: K = {K} is larger than a's width {a.shape[1]} or w's width {w.shape[1]}")
+    if out is None and out_bf16 is None:
+        raise _C.F5EError(f"{op}: needs out or out_bf16")
+    if M > 0 and N > 0 and K > 0:     # the library refuses the empty problem itself
+        _gemm_view(a, F32, "a", K, min(M, a_rows), overlap=True, op=op)
+        _gemm_view(w, w_dtypes, "w", K, N, overlap=True, op=op)
+        if out is not None:
+            _gemm_view(out, F32, "out", N, M, op=op)
+        if out_bf16 is not None:
+            _gemm_view(out_bf16, BF, "out_bf16", N, M, op=op)
+        if addend is not None:
+            if addend.ndim == 2 and addend.shape[0] < 1:      # its data_ptr() is null: the library would see no addend at all
+                raise _C.F5EError(f"{op}: addend must have at least one row")
+            _gemm_view(addend, F32, "addend", N, min(M, addend.shape[0]) if addend.ndim == 2 else 1, op=op)
+        for t, nm, n in ((bias, "bias", N), (ch_scale, "ch_scale", N), (row_scale, "row_scale", M)):
+            if t is not None and t.numel() < n:
+                raise _C.F5EError(f"{op}: {nm} must hold at least {n} elements (got {t.numel()})")
+    ad = addend
+    if w.dtype != F32 and (w.data_ptr() % 8 or w.stride(0) % 4):    # the fp32 op takes any alignment; 16-bit loads are 8 bytes
+        raise _C.F5EError(f"{op}: w must be 8-byte aligned with a row stride that is a multiple of 4 (got offset "
+                          f"{w.data_ptr() % 8}, stride {w.stride(0)})")
+    front = (_stream(), C.c_void_p(a.data_ptr()), a.stride(0), a_rows, a_act, C.c_void_p(w.data_ptr()), w.stride(0))
+    rest = (_p(bias, F32, "bias"), act, _p(ch_scale, F32, "ch_scale"),
+            C.c_void_p(ad.data_ptr()) if ad is not None else None, ad.stride(0) if ad is not None else 0,
+            ad.shape[0] if ad is not None else 0, _p(row_scale, F32, "row_scale"),
+            C.c_void_p(out.data_ptr()) if out is not None else None, out.stride(0) if out is not None else 0,
+            C.c_void_p(out_bf16.data_ptr()) if out_bf16 is not None else None,
+            out_bf16.stride(0) if out_bf16 is not None else 0, M, N, K)
+    if w.dtype == F32:
+        check(lib().f5e_gemm_f32(*front, *rest), "f5e_gemm_f32")
+    else:
+        check(lib().f5e_gemm_f32_w16(*front, W16_TYPES[w.dtype], *rest), "f5e_gemm_f32_w16")
+    return out if out is not None else out_bf16
 
 
 def gemm_f32(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, out: Optional[Tensor] = None,
@@ -428,42 +479,19 @@ def gemm_f32(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, out: Option
     smaller than its width: overlapping rows).  out f32 / out_bf16 bf16 [>= M rows of storage, >= N] and addend f32
     [add_rows, >= N] are row-strided views with unit column stride, of any alignment; bias, ch_scale [>= N] and row_scale
     [>= M] are contiguous.  Row m reads a[m % a_rows] and addend[m % add_rows].  Everything is refused here, before any launch."""
-    require_device()
-    for t, nm in ((a, "a"), (w, "w")):
-        if t.ndim != 2 or not t.is_cuda or t.dtype != F32 or (t.stride(1) != 1 and t.shape[1] > 1):
-            raise _C.F5EError(f"gemm_f32: {nm} must be a 2-D f32 GPU tensor with unit column stride")
-    a_rows = a.shape[0]
-    K = a.shape[1] if K is None else int(K)
-    N = w.shape[0]
-    M = a_rows if M is None else int(M)
-    if K > a.shape[1] or K > w.shape[1]:
-        raise _C.F5EError(f"gemm_f32: K = {K} is larger than a's width {a.shape[1]} or w's width {w.shape[1]}")
-    if out is None and out_bf16 is None:
-        raise _C.F5EError("gemm_f32: needs out or out_bf16")
-    if M > 0 and N > 0 and K > 0:     # the library refuses the empty problem itself
-        _gemm_view(a, F32, "a", K, min(M, a_rows), overlap=True)
-        _gemm_view(w, F32, "w", K, N, overlap=True)
-        if out is not None:
-            _gemm_view(out, F32, "out", N, M)
-        if out_bf16 is not None:
-            _gemm_view(out_bf16, BF, "out_bf16", N, M)
-        if addend is not None:
-            if addend.ndim == 2 and addend.shape[0] < 1:      # its data_ptr() is null: the library would see no addend at all
-                raise _C.F5EError("gemm_f32: addend must have at least one row")
-            _gemm_view(addend, F32, "addend", N, min(M, addend.shape[0]) if addend.ndim == 2 else 1)
-        for t, nm, n in ((bias, "bias", N), (ch_scale, "ch_scale", N), (row_scale, "row_scale", M)):
-            if t is not None and t.numel() < n:
-                raise _C.F5EError(f"gemm_f32: {nm} must hold at least {n} elements (got {t.numel()})")
-    ad = addend
-    check(lib().f5e_gemm_f32(
-        _stream(), C.c_void_p(a.data_ptr()), a.stride(0), a_rows, a_act, C.c_void_p(w.data_ptr()), w.stride(0),
-        _p(bias, F32, "bias"), act, _p(ch_scale, F32, "ch_scale"),
-        C.c_void_p(ad.data_ptr()) if ad is not None else None, ad.stride(0) if ad is not None else 0,
-        ad.shape[0] if ad is not None else 0, _p(row_scale, F32, "row_scale"),
-        C.c_void_p(out.data_ptr()) if out is not None else None, out.stride(0) if out is not None else 0,
-        C.c_void_p(out_bf16.data_ptr()) if out_bf16 is not None else None,
-        out_bf16.stride(0) if out_bf16 is not None else 0, M, N, K), "f5e_gemm_f32")
-    return out if out is not None else out_bf16
+    return _gemm_f32("gemm_f32", (F32,), a, w, bias, out, out_bf16, M, a_act, act, ch_scale, addend, row_scale, K)
+
+
+def gemm_f32_w16(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, out: Optional[Tensor] = None,
+                 out_bf16: Optional[Tensor] = None, M: Optional[int] = None, a_act: int = ACT_NONE, act: int = ACT_NONE,
+                 ch_scale: Optional[Tensor] = None, addend: Optional[Tensor] = None, row_scale: Optional[Tensor] = None,
+                 K: Optional[int] = None):
+    """``gemm_f32`` with a 16-bit weight (f5e_gemm_f32_w16): ``w`` fp16 or bf16 [N, >= K], 8-byte aligned, row stride a multiple
+    of 4; it is widened to fp32 in registers, everything else is fp32 and as ``gemm_f32`` takes it.  Bit-equal to
+    ``gemm_f32(a, w.float(), ...)`` with that widened copy 16-byte aligned (a contiguous ``w.float()`` is; ``gemm_f32`` sums in
+    another order for a widened view that is not, and this op cannot know of it), at half the bytes of ``w``.  Everything is
+    refused here, before any launch."""
+    return _gemm_f32("gemm_f32_w16", tuple(W16_TYPES), a, w, bias, out, out_bf16, M, a_act, act, ch_scale, addend, row_scale, K)
 
 
 def pack_convpos_weight(w: Tensor, groups: int = 16) -> Tensor:
@@ -1125,12 +1153,61 @@ def gemm_f32_skinny_workspace(N: int, K: int) -> int:
     return int(n.value)
 
 
+def gemm_f32_w16_skinny_workspace(N: int, K: int) -> int:
+    """Scratch bytes of ``gemm_f32_w16_skinny`` (f5e_gemm_f32_w16_skinny_workspace): the K split, and so the answer, is
+    ``gemm_f32_skinny``'s."""
+    n = C.c_ulonglong(0)
+    check(lib().f5e_gemm_f32_w16_skinny_workspace(int(N), int(K), C.byref(n)), "f5e_gemm_f32_w16_skinny_workspace")
+    return int(n.value)
+
+
 def _skinny_need(N: int, K: int, device) -> int:
     """``gemm_f32_skinny_workspace`` once per shape and device (the answer depends on the device's CU count)."""
     key = (N, K, device)
     if key not in _skinny_needs:
         _skinny_needs[key] = gemm_f32_skinny_workspace(N, K)
     return _skinny_needs[key]
+
+
+def _gemm_skinny(op: str, w_dtypes, a, w, bias, out, act, addend, workspace):
+    """``gemm_f32_skinny`` and ``gemm_f32_w16_skinny``: one set of checks, the entry point follows ``w.dtype``."""
+    for t, nm in ((a, "a"), (w, "w"), (out, "out")) + (((addend, "addend"),) if addend is not None else ()):
+        dts = w_dtypes if nm == "w" else (F32,)
+        if not isinstance(t, Tensor) or t.ndim != 2 or not t.is_cuda or t.dtype not in dts or (t.stride(1) != 1 and t.shape[1] > 1):
+            raise _C.F5EError(f"{op}: {nm} must be a 2-D {'f32' if dts == (F32,) else 'fp16 / bf16'} GPU tensor with unit column "
+                              f"stride; there is no CPU path")
+    (M, K), N = a.shape, w.shape[0]
+    if not 1 <= M <= SKINNY_MAX_M:
+        raise _C.F5EError(f"{op}: built for 1 <= M <= {SKINNY_MAX_M} rows (got {M}); gemm_f32 takes the rest")
+    if N < 1 or K < 4 or K % 4 or w.shape[1] != K:
+        raise _C.F5EError(f"{op}: a [{M}, {K}] against w {tuple(w.shape)}: K must be a positive multiple of 4 and equal")
+    if act not in (ACT_NONE, ACT_GELU_ERF):
+        raise _C.F5EError(f"{op}: act = {act} is not built (ACT_NONE and ACT_GELU_ERF are)")
+    if out.shape[0] != M or out.shape[1] < N or (addend is not None and (addend.shape[0] != M or addend.shape[1] < N)):
+        raise _C.F5EError(f"{op}: out and addend must be [{M}, >= {N}]")
+    if bias is not None and bias.numel() < N:
+        raise _C.F5EError(f"{op}: bias must hold at least {N} elements (got {bias.numel()})")
+    ap, lda = _rows(a, (F32,), f"{op}: a", K)
+    wp, ldw = _rows(w, w_dtypes, f"{op}: w", K)        # vec = 4: 16-byte (fp32) / 8-byte (16-bit) base, row stride % 4
+    op_, ldo = _rows(out, (F32,), f"{op}: out", N, vec=1)
+    dp, ldd = (None, 0) if addend is None else _rows(addend, (F32,), f"{op}: addend", N, vec=1)
+    require_device()
+    need = _skinny_need(N, K, a.device)
+    if workspace is None and need:
+        key = (a.device, _stream())                      # launches of one stream are ordered: they can share the scratch
+        workspace = _skinny_ws.get(key)
+        if workspace is None or workspace.numel() * 4 < need:
+            workspace = _skinny_ws[key] = torch.empty(max(need, 1 << 20) // 4, dtype=F32, device=a.device)
+    if need and (not workspace.is_cuda or not workspace.is_contiguous() or workspace.data_ptr() % 16 or
+                 workspace.numel() * workspace.element_size() < need):
+        raise _C.F5EError(f"{op}: workspace must be a contiguous 16-byte aligned GPU tensor of at least {need} bytes")
+    tail = (_p(bias, F32, "bias"), int(act), dp, ldd, op_, ldo, C.c_void_p(workspace.data_ptr()) if need else None,
+            workspace.numel() * workspace.element_size() if need else 0, M, N, K)
+    if w.dtype == F32:
+        check(lib().f5e_gemm_f32_skinny(_stream(), ap, lda, wp, ldw, *tail), "f5e_gemm_f32_skinny")
+    else:
+        check(lib().f5e_gemm_f32_w16_skinny(_stream(), ap, lda, wp, ldw, W16_TYPES[w.dtype], *tail), "f5e_gemm_f32_w16_skinny")
+    return out
 
 
 def gemm_f32_skinny(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, out: Tensor, act: int = ACT_NONE,
@@ -1141,60 +1218,53 @@ def gemm_f32_skinny(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, out:
     [>= N].  ``act``: ACT_NONE or ACT_GELU_ERF.  A row's result does not depend on M; two launches give the same bits.
     ``workspace``: a device tensor of ``gemm_f32_skinny_workspace`` bytes (None: one is kept per device and stream, whose
     launches are ordered)."""
-    for t, nm in ((a, "a"), (w, "w"), (out, "out")) + (((addend, "addend"),) if addend is not None else ()):
-        if not isinstance(t, Tensor) or t.ndim != 2 or not t.is_cuda or t.dtype != F32 or (t.stride(1) != 1 and t.shape[1] > 1):
-            raise _C.F5EError(f"gemm_f32_skinny: {nm} must be a 2-D f32 GPU tensor with unit column stride; there is no CPU path")
-    (M, K), N = a.shape, w.shape[0]
-    if not 1 <= M <= SKINNY_MAX_M:
-        raise _C.F5EError(f"gemm_f32_skinny: built for 1 <= M <= {SKINNY_MAX_M} rows (got {M}); gemm_f32 takes the rest")
-    if N < 1 or K < 4 or K % 4 or w.shape[1] != K:
-        raise _C.F5EError(f"gemm_f32_skinny: a [{M}, {K}] against w {tuple(w.shape)}: K must be a positive multiple of 4 and equal")
-    if act not in (ACT_NONE, ACT_GELU_ERF):
-        raise _C.F5EError(f"gemm_f32_skinny: act = {act} is not built (ACT_NONE and ACT_GELU_ERF are)")
-    if out.shape[0] != M or out.shape[1] < N or (addend is not None and (addend.shape[0] != M or addend.shape[1] < N)):
-        raise _C.F5EError(f"gemm_f32_skinny: out and addend must be [{M}, >= {N}]")
-    if bias is not None and bias.numel() < N:
-        raise _C.F5EError(f"gemm_f32_skinny: bias must hold at least {N} elements (got {bias.numel()})")
-    ap, lda = _rows(a, (F32,), "gemm_f32_skinny: a", K)
-    wp, ldw = _rows(w, (F32,), "gemm_f32_skinny: w", K)
-    op, ldo = _rows(out, (F32,), "gemm_f32_skinny: out", N, vec=1)
-    dp, ldd = (None, 0) if addend is None else _rows(addend, (F32,), "gemm_f32_skinny: addend", N, vec=1)
+    return _gemm_skinny("gemm_f32_skinny", (F32,), a, w, bias, out, act, addend, workspace)
+
+
+def gemm_f32_w16_skinny(a: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, out: Tensor, act: int = ACT_NONE,
+                        addend: Optional[Tensor] = None, workspace: Optional[Tensor] = None):
+    """``gemm_f32_skinny`` with a 16-bit weight (f5e_gemm_f32_w16_skinny): ``w`` fp16 or bf16 [N, K], 8-byte aligned, widened to
+    fp32 in registers; everything else as there.  Bit-equal to ``gemm_f32_skinny(a, w.float(), ...)`` at half the bytes of
+    ``w``, which is all a decode step reads."""
+    return _gemm_skinny("gemm_f32_w16_skinny", tuple(W16_TYPES), a, w, bias, out, act, addend, workspace)
+
+
+def _whisper_embed(op: str, emb_dtypes, ids, emb, pos, out, p0, begin):
+    """``whisper_embed`` and ``whisper_embed_w16``: one set of checks, the entry point follows ``emb.dtype``."""
+    if ids.ndim != 2 or emb.ndim != 2 or pos.ndim != 2 or out.ndim != 3:
+        raise _C.F5EError(f"{op}: ids [R, U], emb [V, D], pos [P, D] and out [R, U, D]; there is no CPU path")
+    (R, U), D = ids.shape, emb.shape[1]
+    p0 = int(p0)
+    if R < 1 or U < 1 or out.shape != (R, U, D) or pos.shape[1] != D or D % 4 or p0 < 0 or p0 + U > pos.shape[0]:
+        raise _C.F5EError(f"{op}: ids {tuple(ids.shape)}, emb {tuple(emb.shape)}, pos {tuple(pos.shape)}, out "
+                          f"{tuple(out.shape)}: out must be [R, U, D], D a multiple of 4, and positions {p0} .. {p0 + U - 1} "
+                          f"inside the {pos.shape[0]} rows of pos")
+    for t, nm in ((emb, "emb"), (pos, "pos"), (out, "out")):
+        if t.is_cuda and t.data_ptr() % (8 if t.dtype in W16_TYPES else 16):
+            raise _C.F5EError(f"{op}: {nm} must be 16-byte aligned (a 16-bit emb: 8-byte)")
+    bp = None if begin is None else _vec(begin, I32, f"{op}: begin", (R,))
+    if emb.dtype not in emb_dtypes:
+        raise _C.F5EError(f"{op}: emb must be {'f32' if emb_dtypes == (F32,) else 'fp16 / bf16'} (got {emb.dtype})")
+    front = (_p(ids, I32, f"{op}: ids"), bp, _p(emb, None, f"{op}: emb"))
+    back = (_p(pos, F32, f"{op}: pos"), _p(out, F32, f"{op}: out"), R, U, D, p0, pos.shape[0], emb.shape[0])
     require_device()
-    need = _skinny_need(N, K, a.device)
-    if workspace is None and need:
-        key = (a.device, _stream())                      # launches of one stream are ordered: they can share the scratch
-        workspace = _skinny_ws.get(key)
-        if workspace is None or workspace.numel() * 4 < need:
-            workspace = _skinny_ws[key] = torch.empty(max(need, 1 << 20) // 4, dtype=F32, device=a.device)
-    if need and (not workspace.is_cuda or not workspace.is_contiguous() or workspace.data_ptr() % 16 or
-                 workspace.numel() * workspace.element_size() < need):
-        raise _C.F5EError(f"gemm_f32_skinny: workspace must be a contiguous 16-byte aligned GPU tensor of at least {need} bytes")
-    check(lib().f5e_gemm_f32_skinny(_stream(), ap, lda, wp, ldw, _p(bias, F32, "bias"), int(act), dp, ldd, op, ldo,
-                                    C.c_void_p(workspace.data_ptr()) if need else None,
-                                    workspace.numel() * workspace.element_size() if need else 0, M, N, K), "f5e_gemm_f32_skinny")
+    if emb.dtype == F32:
+        check(lib().f5e_whisper_embed(_stream(), *front, *back), "f5e_whisper_embed")
+    else:
+        check(lib().f5e_whisper_embed_w16(_stream(), *front, W16_TYPES[emb.dtype], *back), "f5e_whisper_embed_w16")
     return out
 
 
 def whisper_embed(ids: Tensor, emb: Tensor, pos: Tensor, out: Tensor, p0: int = 0, begin: Optional[Tensor] = None):
     """out[r, u] = emb[ids[r, u]] + pos[max(p0 + u - begin[r], 0)] (f5e_whisper_embed): ids i32 [R, U], emb f32 [V, D], pos f32
     [P, D], begin i32 [R] or None, out f32 [R, U, D], all contiguous on the device.  U = 1 with p0 = p feeds a decode step."""
-    if ids.ndim != 2 or emb.ndim != 2 or pos.ndim != 2 or out.ndim != 3:
-        raise _C.F5EError("whisper_embed: ids [R, U], emb [V, D], pos [P, D] and out [R, U, D]; there is no CPU path")
-    (R, U), D = ids.shape, emb.shape[1]
-    p0 = int(p0)
-    if R < 1 or U < 1 or out.shape != (R, U, D) or pos.shape[1] != D or D % 4 or p0 < 0 or p0 + U > pos.shape[0]:
-        raise _C.F5EError(f"whisper_embed: ids {tuple(ids.shape)}, emb {tuple(emb.shape)}, pos {tuple(pos.shape)}, out "
-                          f"{tuple(out.shape)}: out must be [R, U, D], D a multiple of 4, and positions {p0} .. {p0 + U - 1} "
-                          f"inside the {pos.shape[0]} rows of pos")
-    for t, nm in ((emb, "emb"), (pos, "pos"), (out, "out")):
-        if t.is_cuda and t.data_ptr() % 16:
-            raise _C.F5EError(f"whisper_embed: {nm} must be 16-byte aligned")
-    bp = None if begin is None else _vec(begin, I32, "whisper_embed: begin", (R,))
-    ptrs = (_p(ids, I32, "whisper_embed: ids"), bp, _p(emb, F32, "whisper_embed: emb"), _p(pos, F32, "whisper_embed: pos"),
-            _p(out, F32, "whisper_embed: out"))
-    require_device()
-    check(lib().f5e_whisper_embed(_stream(), *ptrs, R, U, D, p0, pos.shape[0], emb.shape[0]), "f5e_whisper_embed")
-    return out
+    return _whisper_embed("whisper_embed", (F32,), ids, emb, pos, out, p0, begin)
+
+
+def whisper_embed_w16(ids: Tensor, emb: Tensor, pos: Tensor, out: Tensor, p0: int = 0, begin: Optional[Tensor] = None):
+    """``whisper_embed`` reading a 16-bit token table (f5e_whisper_embed_w16): emb fp16 or bf16 [V, D], 8-byte aligned; pos and
+    out stay f32.  Bit-equal to ``whisper_embed(ids, emb.float(), ...)``."""
+    return _whisper_embed("whisper_embed_w16", tuple(W16_TYPES), ids, emb, pos, out, p0, begin)
 
 
 def beam_step(logits: Tensor, score: Tensor, hyp_in: Tensor, anc_in: Tensor, hyp_out: Tensor, anc_out: Tensor, last: Tensor,
@@ -2109,25 +2179,39 @@ def attn_decode_dev_f32(qkv: Tensor, kc: Tensor, vc: Tensor, rec: Tensor, heads:
     return out
 
 
+def _whisper_embed_dev(op: str, emb_dtypes, last, emb, pos, out, rec, begin):
+    """``whisper_embed_dev`` and ``whisper_embed_w16_dev``: one set of checks, the entry point follows ``emb.dtype``."""
+    if not isinstance(last, Tensor) or last.ndim != 1 or emb.ndim != 2 or pos.ndim != 2 or out.ndim not in (2, 3):
+        raise _C.F5EError(f"{op}: last [R], emb [V, D], pos [P, D] and out [R, D]; there is no CPU path")
+    R, D = last.shape[0], emb.shape[1]
+    if R < 1 or out.numel() != R * D or out.shape[0] != R or out.shape[-1] != D or pos.shape[1] != D or D % 4:
+        raise _C.F5EError(f"{op}: last {tuple(last.shape)}, emb {tuple(emb.shape)}, pos {tuple(pos.shape)}, out "
+                          f"{tuple(out.shape)}: out must be [R, D] and D a multiple of 4")
+    for t, nm in ((emb, "emb"), (pos, "pos"), (out, "out")):
+        if t.is_cuda and t.data_ptr() % (8 if t.dtype in W16_TYPES else 16):
+            raise _C.F5EError(f"{op}: {nm} must be 16-byte aligned (a 16-bit emb: 8-byte)")
+    bp = None if begin is None else _vec(begin, I32, f"{op}: begin", (R,))
+    if emb.dtype not in emb_dtypes:
+        raise _C.F5EError(f"{op}: emb must be {'f32' if emb_dtypes == (F32,) else 'fp16 / bf16'} (got {emb.dtype})")
+    front = (_p(last, I32, f"{op}: last"), bp, _p(emb, None, f"{op}: emb"))
+    back = (_p(pos, F32, f"{op}: pos"), _p(out, F32, f"{op}: out"), R, D, _rec(rec, op), pos.shape[0], emb.shape[0])
+    require_device()
+    if emb.dtype == F32:
+        check(lib().f5e_whisper_embed_dev(_stream(), *front, *back), "f5e_whisper_embed_dev")
+    else:
+        check(lib().f5e_whisper_embed_w16_dev(_stream(), *front, W16_TYPES[emb.dtype], *back), "f5e_whisper_embed_w16_dev")
+    return out
+
+
 def whisper_embed_dev(last: Tensor, emb: Tensor, pos: Tensor, out: Tensor, rec: Tensor, begin: Optional[Tensor] = None):
     """out[r] = emb[last[r]] + pos[max(p - begin[r], 0)] with p from the step record (f5e_whisper_embed_dev): last i32 [R], emb f32
     [V, D], pos f32 [P, D], begin i32 [R] or None, rec i32 [8], out f32 [R, D] (or [R, 1, D]), all contiguous on the device."""
-    if not isinstance(last, Tensor) or last.ndim != 1 or emb.ndim != 2 or pos.ndim != 2 or out.ndim not in (2, 3):
-        raise _C.F5EError("whisper_embed_dev: last [R], emb [V, D], pos [P, D] and out [R, D]; there is no CPU path")
-    R, D = last.shape[0], emb.shape[1]
-    if R < 1 or out.numel() != R * D or out.shape[0] != R or out.shape[-1] != D or pos.shape[1] != D or D % 4:
-        raise _C.F5EError(f"whisper_embed_dev: last {tuple(last.shape)}, emb {tuple(emb.shape)}, pos {tuple(pos.shape)}, out "
-                          f"{tuple(out.shape)}: out must be [R, D] and D a multiple of 4")
-    for t, nm in ((emb, "emb"), (pos, "pos"), (out, "out")):
-        if t.is_cuda and t.data_ptr() % 16:
-            raise _C.F5EError(f"whisper_embed_dev: {nm} must be 16-byte aligned")
-    bp = None if begin is None else _vec(begin, I32, "whisper_embed_dev: begin", (R,))
-    ptrs = (_p(last, I32, "whisper_embed_dev: last"), bp, _p(emb, F32, "whisper_embed_dev: emb"),
-            _p(pos, F32, "whisper_embed_dev: pos"), _p(out, F32, "whisper_embed_dev: out"))
-    rp = _rec(rec, "whisper_embed_dev")
-    require_device()
-    check(lib().f5e_whisper_embed_dev(_stream(), *ptrs, R, D, rp, pos.shape[0], emb.shape[0]), "f5e_whisper_embed_dev")
-    return out
+    return _whisper_embed_dev("whisper_embed_dev", (F32,), last, emb, pos, out, rec, begin)
+
+
+def whisper_embed_w16_dev(last: Tensor, emb: Tensor, pos: Tensor, out: Tensor, rec: Tensor, begin: Optional[Tensor] = None):
+    """``whisper_embed_dev`` reading a 16-bit token table (f5e_whisper_embed_w16_dev): emb fp16 or bf16 [V, D], 8-byte aligned."""
+    return _whisper_embed_dev("whisper_embed_w16_dev", tuple(W16_TYPES), last, emb, pos, out, rec, begin)
 
 
 def _pick_dev_common(name: str, logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, rec: Tensor,

@@ -41,26 +41,32 @@ def _pair(m) -> Pair:
     return m if isinstance(m, tuple) else (m.weight, m.bias)
 
 
-def stack(dev, *ms) -> Pair:
-    """Row-wise q | k | v (or k | v) of holders or (weight, bias) pairs, f32 on ``dev``; a missing bias (None) is zeros."""
+def stack(dev, *ms, wdtype=None) -> Pair:
+    """Row-wise q | k | v (or k | v) of holders or (weight, bias) pairs on ``dev``: ONE weight tensor (f32, or ``wdtype``) and
+    one f32 bias; a missing bias (None) is zeros."""
     ws, bs = zip(*(_pair(m) for m in ms))
     have = next(b for b in bs if b is not None)
-    return fold(dev, (torch.cat(ws, 0), torch.cat([have.new_zeros(w.shape[0]) if b is None else b for w, b in zip(ws, bs)], 0)))
+    return fold(dev, (torch.cat(ws, 0), torch.cat([have.new_zeros(w.shape[0]) if b is None else b for w, b in zip(ws, bs)], 0)),
+                wdtype=wdtype)
 
 
-def fold(dev, m) -> Pair:
+def fold(dev, m, wdtype=None) -> Pair:
+    """(weight, bias) on ``dev``: f32, or with ``wdtype`` (torch.float16 / torch.bfloat16) the weight in that type, rounded to
+    nearest-even where it does not hold the value, for a ``gemm`` hook that reads 16-bit weights (``layer``).  The bias is f32
+    either way; LayerNorm pairs are folded without ``wdtype``."""
     w, b = _pair(m)
-    return w.detach().to(dev, F32).contiguous(), b.detach().to(dev, F32).contiguous()
+    return w.detach().to(dev, F32 if wdtype is None else wdtype).contiguous(), b.detach().to(dev, F32).contiguous()
 
 
 def fold_layer(dev, ln1, q, k, v, out, ln_ff, fc1, fc2, *, ln_x=None, xq=None, xk=None, xv=None, xout=None,
-               extra=None) -> LayerWeights:
-    """The record from ``nn.Linear`` / ``nn.LayerNorm`` holders or (weight, bias) pairs."""
-    cross = ln_x is not None
-    return LayerWeights(ln1=fold(dev, ln1), qkv=stack(dev, q, k, v), out=fold(dev, out),
-                        ln_x=fold(dev, ln_x) if cross else None, xq=fold(dev, xq) if cross else None,
-                        xkv=stack(dev, xk, xv) if cross else None, xout=fold(dev, xout) if cross else None,
-                        ln_ff=fold(dev, ln_ff), ff=fold(dev, fc1) + fold(dev, fc2), extra=extra)
+               extra=None, wdtype=None) -> LayerWeights:
+    """The record from ``nn.Linear`` / ``nn.LayerNorm`` holders or (weight, bias) pairs.  ``wdtype``: the matrices' type (None:
+    f32); biases and LayerNorm pairs stay f32."""
+    cross, wd = ln_x is not None, wdtype
+    return LayerWeights(ln1=fold(dev, ln1), qkv=stack(dev, q, k, v, wdtype=wd), out=fold(dev, out, wd),
+                        ln_x=fold(dev, ln_x) if cross else None, xq=fold(dev, xq, wd) if cross else None,
+                        xkv=stack(dev, xk, xv, wdtype=wd) if cross else None, xout=fold(dev, xout, wd) if cross else None,
+                        ln_ff=fold(dev, ln_ff), ff=fold(dev, fc1, wd) + fold(dev, fc2, wd), extra=extra)
 
 
 def layer(src: Tensor, dst: Tensor, W: LayerWeights, bufs: tuple, *, pre_norm: bool, act: int, eps: float, self_attn,
@@ -70,7 +76,8 @@ def layer(src: Tensor, dst: Tensor, W: LayerWeights, bufs: tuple, *, pre_norm: b
     launch(es) on q | k | v = ``qkv`` into ``ao``; h is the projection's input (WavLM's gate reads it, with ``W.extra``).
     ``cross_attn(W, q, ao)``: the source attention of the queries ``q`` (``W.xkv`` for a caller that projects the memory per
     layer).  ``gemm``: a replacement for ``ops.gemm_f32`` with its keywords ``out``, ``act`` and ``addend`` (a pass of a handful
-    of rows hands in ``ops.gemm_f32_skinny``); None takes the path it always took.  Allocates nothing."""
+    of rows hands in ``ops.gemm_f32_skinny``; a record folded with ``wdtype`` needs one that reads 16-bit weights); None takes
+    the path it always took.  Allocates nothing."""
     xn, qkv, ao, q, ff = bufs
     gemm, ln = ops.gemm_f32 if gemm is None else gemm, ops.layernorm
     h = src

@@ -33,6 +33,8 @@ enum { F5E_OK = 0, F5E_ERR_BAD_SHAPE = -1, F5E_ERR_UNSUPPORTED = -2, F5E_ERR_HIP
 
 /* activation selectors */
 enum { F5E_ACT_NONE = 0, F5E_ACT_SILU = 1, F5E_ACT_GELU_ERF = 2, F5E_ACT_GELU_TANH = 3, F5E_ACT_RELU = 4, F5E_ACT_MISH = 5 };
+/* the element type of a 16-bit weight operand (the _w16 entry points) */
+enum { F5E_W_FP16 = 1, F5E_W_BF16 = 2 };
 
 #ifdef F5E_STREAM_T
 typedef F5E_STREAM_T f5e_stream; /* library build: the real hipStream_t (same ABI: one pointer) */
@@ -1035,6 +1037,30 @@ F5E_API int f5e_whisper_sample_pick_dev(f5e_stream st, const float* logits, long
                                 const int* begin_suppress, int n_beg, int* tokens, int ld_tok, int n_tok, int* last, int* done,
                                 int* alive, float* sum_logp, int R, int V, int* rec, int eos, int no_timestamps, int max_initial,
                                 const int* row_key, const int* serial);
+
+/* ---- The fp32 GEMM family with a 16-bit weight operand (csrc/gemm_f32_w16.hip, csrc/w_load.h; DESIGN 4o "16-bit weights").
+ * W is fp16 (wtype = F5E_W_FP16) or bf16 (F5E_W_BF16), row-major [N][ldw] with ldw in ELEMENTS, 8-byte aligned, ldw % 4 == 0.
+ * It is widened to fp32 in registers on load (bf16: the 16 bits become the high half of the float; fp16: the hardware
+ * convert, subnormals kept); activations, accumulation, bias, epilogue and outputs are fp32 as in the fp32 entry points, whose
+ * kernel bodies these share.  Widening is exact and the summation order is the fp32 kernel's, so each call gives THE BITS of
+ * its fp32 sibling on the (16-byte aligned) widened copy of W, reading half the bytes of W.  Every other argument, limit and
+ * refusal is the sibling's; another wtype is refused.
+ *
+ * f5e_gemm_f32_w16_skinny (+ _workspace, which answers what f5e_gemm_f32_skinny_workspace answers): 1 <= M <= 16 rows.
+ * f5e_gemm_f32_w16: every epilogue term of f5e_gemm_f32, a_rows / add_rows broadcast, a_act, out and / or out_bf16.
+ * f5e_whisper_embed_w16 / _dev: f5e_whisper_embed / f5e_whisper_embed_dev with a 16-bit token table emb [table_rows][D] (8-byte
+ * aligned); pos stays fp32. */
+F5E_API int f5e_gemm_f32_w16_skinny_workspace(int N, int K, unsigned long long* bytes_out_host);
+F5E_API int f5e_gemm_f32_w16_skinny(f5e_stream st, const float* A, int lda, const void* W, int ldw, int wtype, const float* bias,
+                            int act, const float* addend, int ld_add, float* out, int ldo, void* workspace,
+                            unsigned long long workspace_bytes, int M, int N, int K);
+F5E_API int f5e_gemm_f32_w16(f5e_stream st, const float* A, int lda, int a_rows, int a_act, const void* W, int ldw, int wtype,
+                     const float* bias, int act, const float* ch_scale, const float* addend, int ld_add, int add_rows,
+                     const float* row_scale, float* out, int ldo, void* out_bf16, int ldo_bf16, int M, int N, int K);
+F5E_API int f5e_whisper_embed_w16(f5e_stream st, const int* ids, const int* begin, const void* emb, int wtype, const float* pos,
+                          float* out, int R, int U, int D, int p0, int max_pos, int table_rows);
+F5E_API int f5e_whisper_embed_w16_dev(f5e_stream st, const int* last, const int* begin, const void* emb, int wtype,
+                              const float* pos, float* out, int R, int D, const int* rec, int max_pos, int table_rows);
 
 /* ---------------------------------------------------------------- UTMOS (csrc/utmos.hip) ---------------------- */
 /* The UTMOS predictor (utmos22_strong, reference eval/eval_utmos.py): a wav2vec2-base upstream (group-norm feature extractor,

@@ -35,12 +35,12 @@ F32, I32 = torch.float32, torch.int32
 N0 = 4
 
 
-def build(name, B, seed):
+def build(name, B, seed, weights="f32"):
     from f5e_tts_amd.eval import whisper as W
     from tools import synth as SY
     cfg = W.WhisperConfig(**SY.whisper_config_fields(name, encoder_layers=1))         # the decoder is what is timed
     with torch.device("cuda"):
-        model = W.Whisper(cfg)
+        model = W.Whisper(cfg, weights=weights)
     shapes = {k: v.shape for k, v in model.state_dict().items()}
     model.load_state_dict(SY.init_whisper_state(shapes, seed, 4.0, device="cuda"), strict=False)
     g = torch.Generator(device="cuda").manual_seed(seed + 1)
@@ -51,9 +51,9 @@ def build(name, B, seed):
     return model, kv
 
 
-def time_shape(name, B, tokens, repeats):
+def time_shape(name, B, tokens, repeats, weights="f32", inspect=None):
     from f5e_tts_amd import ops
-    model, kv = build(name, B, 99)
+    model, kv = build(name, B, 99, weights)
     cfg, fd = model.cfg, model._fold()
     eos, P = cfg.eos_token_id, cfg.max_target_positions
     sup = dict(suppress=fd["suppress"], begin_suppress=fd["begin_suppress"])
@@ -123,6 +123,8 @@ def time_shape(name, B, tokens, repeats):
     rec["speedup_over_eager"] = {arm: e / rec["ms_per_token"][arm]["median"] for arm in states}
     rec["break_even_tokens"] = {arm: (capture_ms[arm] / (e - rec["ms_per_token"][arm]["median"])
                                       if e > rec["ms_per_token"][arm]["median"] else None) for arm in states}
+    if inspect is not None:                                # a caller's own fields, read off the model that was timed
+        rec.update(inspect(model))
     del model, kv, st, states, arms
     torch.cuda.empty_cache()
     return rec

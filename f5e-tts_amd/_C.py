@@ -132,6 +132,12 @@ SIGNATURES = {
                          _I, _I, _F],
     "f5e_lstm_f32": [_P, _P, _LL, _P, _P, _P, _P, _I, _I, _I, _I],
     "f5e_score_mean": [_P, _P, _LL, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F],
+    "f5e_lfr_cmvn_f32": [_P, _P, _P, _I, _I, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F],
+    "f5e_fsmn_f32": [_P, _P, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I],
+    "f5e_mask_rows_f32": [_P, _P, _I, _P, _I, _I, _I],
+    "f5e_cif_alpha_f32": [_P, _P, _I, _P, _P, _I, _P, _I, _I, _F, _F, _F],
+    "f5e_cif_fire_f32": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F],
+    "f5e_nar_pick": [_P, _P, _LL, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
     "f5e_dit_forward": [_P, _P],
     "f5e_sample_loop": [_P, _P],
     "f5e_workspace_bytes": [_P, _P],

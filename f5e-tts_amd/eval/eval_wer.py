@@ -10,6 +10,10 @@
                                         [--whisper_assistant DIR [--whisper_assistant_tokens N]
                                          [--whisper_assistant_shares_encoder]]
                                         [--whisper_step_graph [--whisper_step_gemm skinny]]
+    python -m f5e_tts_amd.eval.eval_wer --gen_wav_dir D --metalst F --lang zh --asr paraformer --paraformer_dir P
+
+``--asr paraformer`` is the reference's Chinese recogniser (``load_asr_model("zh")``, eval/utils_eval.py:472-482: funasr
+paraformer-zh) on the device (eval/paraformer.py), with ``normalize`` as the clean-up; parity with funasr is unpinned.
 
 ``--asr whisper`` is the reference's English recogniser of the voice-conversion and LibriSpeech evaluations
 (``run_asr_wer_whisper_large_v3``, eval/utils_eval.py:631-712: whisper-large-v3, greedy, prompt ``english / transcribe``) on the
@@ -181,8 +185,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--metalst", required=True, help="utt|prompt_text|prompt_wav|gt_text per line")
     ap.add_argument("--gen_wav_dir", required=True)
     ap.add_argument("--lang", required=True, choices=LANGS)
-    ap.add_argument("--asr", default="wenet", choices=("wenet", "whisper"),
-                    help="wenet: the project's conformer recogniser; whisper: the reference's English WER recogniser on the device")
+    ap.add_argument("--asr", default="wenet", choices=("wenet", "whisper", "paraformer"),
+                    help="wenet: the project's conformer recogniser; whisper: the reference's English WER recogniser on the device; "
+                         "paraformer: the reference's Chinese WER recogniser (funasr paraformer-zh) on the device")
+    ap.add_argument("--paraformer_dir", default=None, help="--asr paraformer: a local funasr model directory (config.yaml, "
+                    "model.pt, am.mvn, tokens.json)")
     ap.add_argument("--whisper_dir", default=None, help="--asr whisper: a local whisper-large-v3 directory (config.json, "
                     "generation_config.json, model.safetensors, vocab.json, added_tokens.json)")
     ap.add_argument("--language", default="english", help="--asr whisper: the language token of the forced prompt")
@@ -232,7 +239,7 @@ def main(argv=None, aligner=None) -> float:
     ap = build_parser()
     args = ap.parse_args(argv)
     if aligner is None:
-        need = ("whisper_dir",) if args.asr == "whisper" else ("asr_model", "asr_config", "asr_dict")
+        need = {"whisper": ("whisper_dir",), "paraformer": ("paraformer_dir",)}.get(args.asr, ("asr_model", "asr_config", "asr_dict"))
         missing = [f"--{n}" for n in need if getattr(args, n) is None]
         if missing:
             ap.error(f"the following arguments are required: {', '.join(missing)}")
@@ -261,6 +268,9 @@ def main(argv=None, aligner=None) -> float:
             ctx.update(weights=args.whisper_weights)
         aligner = WhisperRecognizer(args.whisper_dir, args.device, args.language, beam_size=args.whisper_beam,
                                     long_form=args.whisper_long, **({} if fb is None else dict(fallback=fb)), **ctx)
+    elif aligner is None and args.asr == "paraformer":
+        from .paraformer import ParaformerRecognizer
+        aligner = ParaformerRecognizer(args.paraformer_dir, args.device)
     elif aligner is None:
         from ..ppg.ctc_align import CTCAligner
         aligner = CTCAligner(args.asr_model, args.asr_config, args.asr_dict, args.device, asr=True,

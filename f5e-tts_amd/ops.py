@@ -2484,6 +2484,124 @@ def score_mean(hid: Tensor, w2: Tensor, b2: Optional[Tensor], frames: Optional[T
     return out
 
 
+# ---- Paraformer (csrc/paraformer.hip) ----
+
+def _i32(t: Optional[Tensor], n: int, name: str):
+    """Pointer of a contiguous i32 GPU tensor with at least ``n`` elements (None stays None)."""
+    return _flat(t, I32, name, n)
+
+
+def lfr_cmvn(fbank: Tensor, count: Optional[Tensor], shift: Tensor, scale: Tensor, pos: Optional[Tensor], out: Tensor,
+             frames_out: Optional[Tensor], m: int, n: int, xscale: float = 1.0, win: int = 0, hop: int = 0):
+    """f5e_lfr_cmvn_f32: fbank f32 [B, T, n_mels] -> out f32 [B, T', m n_mels] = LFR (m frames stacked every n, (m - 1) // 2 copies
+    of frame 0 in front, the last frame repeated behind), (x + shift) * scale, * xscale, + pos[i] (f32 [>= T', m n_mels] or None),
+    each step rounded on its own; rows at or beyond ceil(T_b / n) are zero.  ``count`` i32 [B]: frames per row, or with ``hop``
+    > 0 SAMPLES per row (T_b = 1 + (count - win) // hop, 0 below ``win``); ``frames_out`` i32 [B] receives ceil(T_b / n)."""
+    B, T, n_mels = _shape3(fbank, "lfr_cmvn: fbank")
+    W = int(m) * n_mels
+    if out.ndim != 3 or out.shape[0] != B or out.shape[2] != W or shift.numel() != W or scale.numel() != W or \
+            (pos is not None and (pos.ndim != 2 or pos.shape[1] != W)):
+        raise _C.F5EError(f"lfr_cmvn: out [{B}, T', {W}], shift / scale [{W}], pos [>= T', {W}] (got {tuple(out.shape)}, "
+                          f"{tuple(shift.shape)}, {tuple(scale.shape)}, {None if pos is None else tuple(pos.shape)})")
+    require_device()
+    check(lib().f5e_lfr_cmvn_f32(_stream(), _p(fbank, F32, "fbank"), _i32(count, B, "lfr_cmvn: count"), int(win), int(hop),
+                                 _p(shift, F32, "shift"), _p(scale, F32, "scale"), _p(pos, F32, "pos"),
+                                 0 if pos is None else pos.shape[0], _p(out, F32, "out"), _i32(frames_out, B, "lfr_cmvn: frames_out"),
+                                 B, T, out.shape[1], n_mels, int(m), int(n), float(xscale)), "f5e_lfr_cmvn_f32")
+    return out
+
+
+def fsmn(x: Tensor, w_t: Tensor, lengths: Optional[Tensor], out: Tensor, B: int, left: int, addend: Optional[Tensor] = None):
+    """f5e_fsmn_f32: the masked depthwise memory block.  x f32 [B * T, C] (a row-strided view, e.g. the v third of q | k | v),
+    w_t f32 [K, C], out / addend f32 [B * T, C] views (out may be addend, not x): out = conv_K(x masked) + x (+ addend) at
+    t < lengths[b]; addend (or zero) beyond."""
+    if x.ndim != 2 or w_t.ndim != 2 or B < 1 or x.shape[0] % B or x.shape[0] == 0 or w_t.shape[1] != x.shape[1] or \
+            out.shape != x.shape or (addend is not None and addend.shape != x.shape):
+        raise _C.F5EError(f"fsmn: x / out / addend [B * T, C], w_t [K, C] (got {tuple(x.shape)}, {tuple(out.shape)}, "
+                          f"{tuple(w_t.shape)}, B = {B}); there is no CPU path")
+    M, Cc = x.shape
+    xp, ldx = _rows(x, (F32,), "fsmn: x", Cc)
+    op, ldo = _rows(out, (F32,), "fsmn: out", Cc)
+    ap, lda = (None, 0) if addend is None else _rows(addend, (F32,), "fsmn: addend", Cc)
+    require_device()
+    check(lib().f5e_fsmn_f32(_stream(), xp, ldx, _p(w_t, F32, "w_t"), _len(lengths, B, "fsmn"), ap, lda, op, ldo, B, M // B, Cc,
+                             w_t.shape[0], int(left)), "f5e_fsmn_f32")
+    return out
+
+
+def mask_rows(x: Tensor, lengths: Tensor, B: int):
+    """f5e_mask_rows_f32: rows t >= lengths[b] of x f32 [B * T, C] (row-strided view) become zero, in place."""
+    if x.ndim != 2 or B < 1 or x.shape[0] % B or x.shape[0] == 0:
+        raise _C.F5EError(f"mask_rows: x [B * T, C] (got {tuple(x.shape)}, B = {B})")
+    xp, ldx = _rows(x, (F32,), "mask_rows: x", x.shape[1], vec=1)
+    require_device()
+    check(lib().f5e_mask_rows_f32(_stream(), xp, ldx, _len(lengths, B, "mask_rows"), B, x.shape[0] // B, x.shape[1]),
+          "f5e_mask_rows_f32")
+    return x
+
+
+def cif_alpha(logits: Tensor, lengths: Optional[Tensor], alpha: Tensor, n_out: Tensor, smooth: float = 1.0, noise: float = 0.0,
+              tail: float = 0.45):
+    """f5e_cif_alpha_f32: logits f32 [B, T] (contiguous) -> alpha f32 [B, T + 1] = relu(sigmoid * smooth - noise) at t < lengths[b],
+    ``tail`` at t = lengths[b], zero beyond; n_out i32 [B] = floor(sum alpha)."""
+    if logits.ndim != 2 or alpha.shape != (logits.shape[0], logits.shape[1] + 1):
+        raise _C.F5EError(f"cif_alpha: logits [B, T], alpha [B, T + 1] (got {tuple(logits.shape)}, {tuple(alpha.shape)})")
+    B, T = logits.shape
+    require_device()
+    check(lib().f5e_cif_alpha_f32(_stream(), _p(logits, F32, "logits"), 1, _len(lengths, B, "cif_alpha"), _p(alpha, F32, "alpha"),
+                                  T + 1, _i32(n_out, B, "cif_alpha: n_out"), B, T, float(smooth), float(noise), float(tail)),
+          "f5e_cif_alpha_f32")
+    return alpha, n_out
+
+
+def cif_fire_scratch(B: int, T: int, L_cap: int) -> int:
+    """Floats of scratch ``cif_fire`` needs: cur [B, T + 1] | pos [B, L_cap] (i32) | rem [B, L_cap]."""
+    return B * (T + 1) + 2 * B * L_cap
+
+
+def cif_fire(alpha: Tensor, h: Tensor, lengths: Optional[Tensor], out: Tensor, count: Tensor, scratch: Tensor,
+             n_limit: Optional[Tensor] = None, threshold: float = 1.0):
+    """f5e_cif_fire_f32: alpha f32 [B, T + 1] (``cif_alpha``), h f32 [B * T, D] (row-strided view) -> out f32 [B, L_cap, D]: the
+    emitted frames of the sequential integrate-and-fire loop, bit for bit; token k >= min(count[b], L_cap, n_limit[b]) is zero.
+    count i32 [B] = all fires of the row.  scratch f32 [>= cif_fire_scratch(B, T, L_cap)]; afterwards it holds cur | pos | rem."""
+    if alpha.ndim != 2 or h.ndim != 2 or out.ndim != 3 or out.shape[0] != alpha.shape[0] or out.shape[2] != h.shape[1] or \
+            h.shape[0] != alpha.shape[0] * (alpha.shape[1] - 1) or h.shape[0] == 0:
+        raise _C.F5EError(f"cif_fire: alpha [B, T + 1], h [B * T, D], out [B, L_cap, D] (got {tuple(alpha.shape)}, {tuple(h.shape)}, "
+                          f"{tuple(out.shape)}); there is no CPU path")
+    B, T, Lc, D = alpha.shape[0], alpha.shape[1] - 1, out.shape[1], h.shape[1]
+    hp, ldh = _rows(h, (F32,), "cif_fire: h", D, vec=1)
+    _flat(scratch, F32, "cif_fire: scratch", cif_fire_scratch(B, T, Lc))
+    _p(scratch, F32, "cif_fire: scratch")
+    base, fb = scratch.data_ptr(), 4
+    cur, pos, rem = base, base + fb * B * (T + 1), base + fb * (B * (T + 1) + B * Lc)
+    require_device()
+    check(lib().f5e_cif_fire_f32(_stream(), _p(alpha, F32, "alpha"), T + 1, hp, ldh, _len(lengths, B, "cif_fire"),
+                                 _len(n_limit, B, "cif_fire"), C.c_void_p(cur), C.c_void_p(pos), C.c_void_p(rem),
+                                 _i32(count, B, "cif_fire: count"), _p(out, F32, "out"), D, B, T, D, Lc, float(threshold)),
+          "f5e_cif_fire_f32")
+    return out, count
+
+
+def nar_pick(logits: Tensor, n: Optional[Tensor], B: int, arg: Tensor, logp: Tensor, ids: Tensor, length: Tensor, score: Tensor,
+             sos: int = 1, eos: int = 2, blank: int = 0, pad: int = -1):
+    """f5e_nar_pick: logits f32 [B * L, V] (row-strided view) -> arg i32 [B * L] (argmax, lowest index on ties; -1 at k >= n[b]),
+    logp f32 [B * L] (its log-softmax value), ids i32 [B, L] (the args of k < n[b] other than sos / eos / blank, compacted,
+    padded with ``pad``), length i32 [B], score f32 [B] = sum of logp over k < n[b]."""
+    if logits.ndim != 2 or B < 1 or logits.shape[0] % B or logits.shape[0] == 0:
+        raise _C.F5EError(f"nar_pick: logits [B * L, V] (got {tuple(logits.shape)}, B = {B}); there is no CPU path")
+    R, V = logits.shape
+    L = R // B
+    lp_, ld = _rows(logits, (F32,), "nar_pick: logits", V, vec=1)
+    if ids.shape != (B, L):
+        raise _C.F5EError(f"nar_pick: ids must be [{B}, {L}]")
+    require_device()
+    check(lib().f5e_nar_pick(_stream(), lp_, ld, _len(n, B, "nar_pick"), _i32(arg, R, "nar_pick: arg"),
+                             _flat(logp, F32, "nar_pick: logp", R), _p(ids, I32, "ids"), _i32(length, B, "nar_pick: length"),
+                             _flat(score, F32, "nar_pick: score", B), B, L, V, int(sos), int(eos), int(blank), int(pad)),
+          "f5e_nar_pick")
+    return ids, length, score
+
+
 def dit_forward(plan: "_C.DitPlan"):
     require_device()
     check(lib().f5e_dit_forward(_stream(), C.byref(plan)), "f5e_dit_forward")

@@ -1104,6 +1104,63 @@ F5E_API int f5e_lstm_f32(f5e_stream st, const float* xg, long long ldxg, const f
 F5E_API int f5e_score_mean(f5e_stream st, const float* hid, long long ldh, const float* w2, const float* b2, const int* frames,
                    float* frame_scores, float* out, int B, int T, int F, float scale, float offset);
 
+/* ---------------------------------------------------------------- Paraformer (csrc/paraformer.hip) ------------ */
+/* funasr's paraformer-zh, the Chinese recogniser of the reference's WER (eval/utils_eval.py:472-482): the LFR + CMVN front
+ * behind f5e_kaldi_fbank, the FSMN memory block of the SANM attention, the CIF predictor and the pick of the non-autoregressive
+ * decoder.  The projections, norms, convolutions-as-GEMM and attentions are f5e_gemm_f32 / f5e_layernorm / f5e_im2col /
+ * f5e_mha_f32.  fp32, channels-last, per-row lengths DEVICE int [B] clamped to [0, T] (NULL: every row is full).  No
+ * allocation, no synchronisation, nothing read back, no atomics: capturable, a replay gives the bits of the eager run.  Every
+ * product and sum is rounded on its own (no fused multiply-add). */
+
+/* Low frame rate + CMVN + the encoder's input scale and position table in one pass, each step rounded separately:
+ *   out[b][i][j n_mels + c] = ((fbank[b][f][c] + shift[k]) * scale[k]) * xscale + pos[i][k],  k = j n_mels + c,
+ *   f = clamp(n i + j - (m - 1) / 2, 0, T_b - 1)   for i < T'_b = ceil(T_b / n), ZERO for T'_b <= i < Tp,
+ * i.e. (m - 1) / 2 copies of frame 0 in front, the last frame repeated behind.  fbank f32 [B][T][n_mels]; shift, scale f32
+ * [m n_mels]; pos f32 [pos_rows >= Tp][m n_mels] or NULL; out f32 [B][Tp][m n_mels], Tp >= ceil(T / n).  T_b = count[b]
+ * (hop == 0: frames) or kaldi's snip_edges frame count of count[b] samples, 0 below win, else 1 + (count[b] - win) / hop
+ * (hop > 0); NULL: T.  frames_out (NULL to skip) int [B] receives T'_b.  No frame at or beyond T_b is read. */
+F5E_API int f5e_lfr_cmvn_f32(f5e_stream st, const float* fbank, const int* count, int win, int hop, const float* shift,
+                     const float* scale, const float* pos, int pos_rows, float* out, int* frames_out, int B, int T, int Tp,
+                     int n_mels, int m, int n, float xscale);
+
+/* The masked depthwise memory block (FSMN) of the SANM attention and of the decoder:
+ *   out[b][t][c] = sum_{j < K} w_t[j][c] x[b][t + j - left][c] + x[b][t][c]  (+ addend[b][t][c])   for t < len[b],
+ *   out[b][t][c] = addend[b][t][c] (or 0 without an addend)                                        for t >= len[b],
+ * a tap outside [0, len[b]) contributing nothing: it never reads a frame at or past the row's length nor the neighbouring batch
+ * row.  x, addend, out f32 [B * T][>= C] with their own row strides (x may be the v third of a q | k | v buffer); w_t f32 [K][C]
+ * (Conv1d weight [C][1][K] transposed).  out may be addend itself, not x.  C and the strides multiples of 4, operands 16-byte
+ * aligned, 1 <= K <= 256, 0 <= left < K. */
+F5E_API int f5e_fsmn_f32(f5e_stream st, const float* x, int ldx, const float* w_t, const int* len, const float* addend, int ld_add,
+                 float* out, int ldo, int B, int T, int C, int K, int left);
+
+/* x[b][t][0 .. C) = 0 for t >= len[b], in place; x f32 [B * T][ldx >= C]. */
+F5E_API int f5e_mask_rows_f32(f5e_stream st, float* x, int ldx, const int* len, int B, int T, int C);
+
+/* CIF weights: alpha[b][t] = max(sigmoid(logits[b T + t]) * smooth - noise, 0) for t < len[b], `tail` at t = len[b] (the tail
+ * step), 0 beyond; alpha f32 [B][ld_alpha >= T + 1], logits one float every ld_logits.  n_out int [B] = floor(sum_t alpha[b][t]),
+ * summed in double in a fixed order. */
+F5E_API int f5e_cif_alpha_f32(f5e_stream st, const float* logits, int ld_logits, const int* len, float* alpha, int ld_alpha,
+                      int* n_out, int B, int T, float smooth, float noise, float tail);
+
+/* Continuous integrate-and-fire.  Launch 1, one thread per row over steps t = 0 .. len[b] (len[b] + 1 dependent fp32 additions):
+ *   comp = 1 - integrate; integrate += alpha_t; fire = integrate >= threshold; if fire: integrate -= 1; cur_t = fire ? comp : alpha_t
+ * recording cur f32 [B][ld_alpha], and per fire k < L_cap its step pos int [B][L_cap] and remainder rem f32 [B][L_cap] = alpha_t -
+ * cur_t; count int [B] = ALL fires of the row.  Launch 2, per (row, token k, channel): frame = rem_{k-1} h[pos_{k-1}] (0 for
+ * k = 0), then frame += cur_t h_t for t = pos_{k-1} + 1 .. pos_k in time order, product and sum rounded separately: the bits of
+ * the sequential loop for equal alpha and h.  h f32 [B * T][ldh >= D] is read only at t < len[b]; the step t = len[b] has h = 0.
+ * out f32 [B][L_cap][ldo >= D]: token k < min(count[b], L_cap, n_limit[b]) (n_limit DEVICE int [B] or NULL), ZERO beyond. */
+F5E_API int f5e_cif_fire_f32(f5e_stream st, const float* alpha, int ld_alpha, const float* h, int ldh, const int* len,
+                     const int* n_limit, float* cur, int* pos, float* rem, int* count, float* out, int ldo, int B, int T, int D,
+                     int L_cap, float threshold);
+
+/* The pick of the non-autoregressive decoder.  Launch 1, one wave per token row r = b L + k with k < n[b], ONE pass over
+ * logits[r][0 .. V) (row stride ld; logits or log-probabilities alike): arg[r] = argmax (lowest index on ties) and logp[r] = its
+ * log-softmax value; rows k >= n[b] get -1 and 0.  Launch 2, one wave per utterance: ids int [B][L] = the arg of tokens k < n[b]
+ * other than sos, eos and blank, in order, padded with `pad`; len_out int [B] their count; score f32 [B] = sum_{k < n[b]} logp.
+ * n DEVICE int [B] clamped to [0, L] (NULL: L). */
+F5E_API int f5e_nar_pick(f5e_stream st, const float* logits, long long ld, const int* n, int* arg, float* logp, int* ids,
+                 int* len_out, float* score, int B, int L, int V, int sos, int eos, int blank, int pad);
+
 /* ---------------------------------------------------------------- hipGraph capture --------------------------- */
 F5E_API int f5e_graph_begin(f5e_stream st);
 F5E_API int f5e_graph_end(f5e_stream st, void** graph_exec_out);

@@ -138,6 +138,13 @@ SIGNATURES = {
     "f5e_cif_alpha_f32": [_P, _P, _I, _P, _P, _I, _P, _I, _I, _F, _F, _F],
     "f5e_cif_fire_f32": [_P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F],
     "f5e_nar_pick": [_P, _P, _LL, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I],
+    "f5e_rmsnorm_f32": [_P, _P, _I, _P, _P, _I, _I, _I, _F],
+    "f5e_swiglu_f32": [_P, _P, _I, _P, _I, _I, _I],
+    "f5e_llm_embed_f32": [_P, _P, _P, _P, _I, _I, _I],
+    "f5e_llm_embed_w16": [_P, _P, _P, _I, _P, _I, _I, _I],
+    "f5e_gqa_rope_append_f32": [_P, _P, _I, _P, _P, _LL, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F],
+    "f5e_gqa_rope_decode_dev_f32": [_P, _P, _I, _P, _P, _LL, _I, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _F],
+    "f5e_llm_pick_dev": [_P, _P, _LL, _P, _I, _I, _P, _P, _P, _P, _I, _I, _P, _I, _F, _F, _I, _F, _P, _I, _I, _P, _P, _P, _P, _P],
     "f5e_dit_forward": [_P, _P],
     "f5e_sample_loop": [_P, _P],
     "f5e_workspace_bytes": [_P, _P],

@@ -2655,3 +2655,166 @@ class Graph:
             self.destroy()
         except Exception:
             pass
+
+
+# ---- the Qwen2 chat model's kernels (csrc/llm.hip) ----
+
+LLM_MAX_TOP_K = 64
+LLM_MAX_POS = 4096
+
+
+def rmsnorm_f32(x: Tensor, w: Tensor, eps: float, out: Optional[Tensor] = None) -> Tensor:
+    """out[m] = (x[m] * rsqrt(mean(x[m]^2) + eps)) * w (f5e_rmsnorm_f32): x, out f32 [M, >= D] row-strided views (row strides
+    multiples of 4, 16-byte aligned; out may be x), w f32 [D], D a multiple of 4, at most 8192.  One wave per row."""
+    if not isinstance(x, Tensor) or x.ndim != 2 or w.ndim != 1:
+        raise _C.F5EError("rmsnorm_f32: x [M, D] and w [D]; there is no CPU path")
+    M, D = x.shape[0], w.shape[0]
+    xp, ldx = _rows(x, (F32,), "rmsnorm_f32: x", D)
+    out = torch.empty(M, D, dtype=F32, device=x.device) if out is None else out
+    if out.ndim != 2 or out.shape[0] != M:
+        raise _C.F5EError(f"rmsnorm_f32: out must be [{M}, >= {D}]")
+    op, ldo = _rows(out, (F32,), "rmsnorm_f32: out", D)
+    require_device()
+    check(lib().f5e_rmsnorm_f32(_stream(), xp, ldx, _vec(w, F32, "rmsnorm_f32: w", (D,), align=16), op, ldo, M, D, float(eps)),
+          "f5e_rmsnorm_f32")
+    return out
+
+
+def swiglu_f32(gu: Tensor, out: Optional[Tensor] = None, I: Optional[int] = None) -> Tensor:
+    """out[m, i] = silu(gu[m, i]) * gu[m, I + i] (f5e_swiglu_f32): gu f32 [M, >= 2 I] (gate | up), out f32 [M, >= I]."""
+    if not isinstance(gu, Tensor) or gu.ndim != 2:
+        raise _C.F5EError("swiglu_f32: gu [M, 2 I]; there is no CPU path")
+    M = gu.shape[0]
+    I = gu.shape[1] // 2 if I is None else int(I)
+    gp, ld = _rows(gu, (F32,), "swiglu_f32: gu", 2 * I)
+    out = torch.empty(M, I, dtype=F32, device=gu.device) if out is None else out
+    if out.ndim != 2 or out.shape[0] != M:
+        raise _C.F5EError(f"swiglu_f32: out must be [{M}, >= {I}]")
+    op, ldo = _rows(out, (F32,), "swiglu_f32: out", I)
+    require_device()
+    check(lib().f5e_swiglu_f32(_stream(), gp, ld, op, ldo, M, I), "f5e_swiglu_f32")
+    return out
+
+
+def llm_embed(ids: Tensor, emb: Tensor, out: Tensor) -> Tensor:
+    """out[i] = emb[ids[i]], widened exactly (f5e_llm_embed_f32 / f5e_llm_embed_w16 by ``emb.dtype``): ids i32 [n] on the device
+    (clamped to the table; the decode step passes ``last``), emb f32 / fp16 / bf16 [V, D], out f32 [n, D], contiguous."""
+    if not isinstance(ids, Tensor) or ids.ndim != 1 or emb.ndim != 2 or out.ndim != 2:
+        raise _C.F5EError("llm_embed: ids [n], emb [V, D] and out [n, D]; there is no CPU path")
+    n, (V, D) = ids.shape[0], emb.shape
+    if n < 1 or tuple(out.shape) != (n, D) or D % 4:
+        raise _C.F5EError(f"llm_embed: ids {tuple(ids.shape)}, emb {tuple(emb.shape)}, out {tuple(out.shape)}: out must be [n, D] "
+                          f"and D a multiple of 4")
+    if emb.dtype != F32 and emb.dtype not in W16_TYPES:
+        raise _C.F5EError(f"llm_embed: emb must be f32, fp16 or bf16 (got {emb.dtype})")
+    for t, nm in ((emb, "emb"), (out, "out")):
+        if t.is_cuda and t.data_ptr() % (8 if t.dtype in W16_TYPES else 16):
+            raise _C.F5EError(f"llm_embed: {nm} must be 16-byte aligned (a 16-bit emb: 8-byte)")
+    ip, ep, op = _p(ids, I32, "llm_embed: ids"), _p(emb, None, "llm_embed: emb"), _p(out, F32, "llm_embed: out")
+    require_device()
+    if emb.dtype == F32:
+        check(lib().f5e_llm_embed_f32(_stream(), ip, ep, op, n, D, V), "f5e_llm_embed_f32")
+    else:
+        check(lib().f5e_llm_embed_w16(_stream(), ip, ep, W16_TYPES[emb.dtype], op, n, D, V), "f5e_llm_embed_w16")
+    return out
+
+
+def _gqa_common(name: str, qkv: Tensor, kc: Tensor, vc: Tensor, cos: Tensor, sin: Tensor, heads: int, kv_heads: int, rows: int,
+                begin: Optional[Tensor], out: Optional[Tensor]):
+    if not isinstance(qkv, Tensor) or qkv.ndim != 2 or kc.ndim != 3 or kc.shape != vc.shape or kc.stride() != vc.stride():
+        raise _C.F5EError(f"{name}: qkv [rows, >= (H + 2 Hkv) dk] and kc, vc [R, P, Hkv dk] with equal strides; there is no CPU path")
+    R, P, Dkv = kc.shape
+    for t, nm in ((kc, "kc"), (vc, "vc")):
+        if not t.is_cuda or t.dtype != F32 or t.stride(2) != 1:
+            raise _C.F5EError(f"{name}: {nm} must be an f32 GPU tensor with unit channel stride")
+    heads, kv_heads = int(heads), int(kv_heads)
+    if kv_heads < 1 or heads % kv_heads or Dkv % kv_heads:
+        raise _C.F5EError(f"{name}: kv_heads = {kv_heads} must divide heads = {heads} and the caches' {Dkv} channels")
+    dk = Dkv // kv_heads
+    D = heads * dk
+    if cos.ndim != 2 or cos.shape != sin.shape or cos.shape[1] != dk // 2 or cos.shape[0] < P:
+        raise _C.F5EError(f"{name}: cos, sin must be f32 [>= {P}, {dk // 2}] (got {tuple(cos.shape)}, {tuple(sin.shape)})")
+    pos_stride = kc.stride(1) if P > 1 else max(Dkv, kc.stride(1))
+    row_stride = kc.stride(0) if R > 1 else max(kc.stride(0), (P - 1) * pos_stride + Dkv)
+    for t in (kc, vc):
+        have = t.untyped_storage().nbytes() // 4 - t.storage_offset()
+        if pos_stride < Dkv or row_stride < (P - 1) * pos_stride + Dkv or have < (R - 1) * row_stride + (P - 1) * pos_stride + Dkv \
+                or pos_stride % 4 or row_stride % 4 or t.data_ptr() % 16:
+            raise _C.F5EError(f"{name}: cache strides ({row_stride}, {pos_stride}) must be multiples of 4 spanning "
+                              f"[{R}, {P}, {Dkv}] inside the storage, kc and vc 16-byte aligned")
+    if qkv.shape[0] != rows * R:
+        raise _C.F5EError(f"{name}: qkv has {qkv.shape[0]} rows, {R} * {rows} are needed")
+    qp, ldq = _rows(qkv, (F32,), f"{name}: qkv", D + 2 * Dkv)
+    bp = None if begin is None else _vec(begin, I32, f"{name}: begin", (R,))
+    cp = _vec(cos, F32, f"{name}: cos", cos.shape, align=16)
+    sp = _vec(sin, F32, f"{name}: sin", sin.shape, align=16)
+    out = torch.empty(R * rows, D, dtype=F32, device=qkv.device) if out is None else out
+    if out.ndim != 2 or tuple(out.shape) != (R * rows, D):
+        raise _C.F5EError(f"{name}: out must be [{R * rows}, {D}]")
+    op, ldo = _rows(out, (F32,), f"{name}: out", D)
+    require_device()
+    front = (_stream(), qp, ldq, C.c_void_p(kc.data_ptr()), C.c_void_p(vc.data_ptr()), row_stride, pos_stride, bp, cp, sp,
+             cos.shape[0], op, ldo, R)
+    return front, out, P, dk
+
+
+def gqa_rope_append_f32(qkv: Tensor, kc: Tensor, vc: Tensor, cos: Tensor, sin: Tensor, U: int, p0: int, heads: int, kv_heads: int,
+                        scale: float, begin: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """Causal attention of U new positions behind p0 cached ones with rotary positions and grouped heads
+    (f5e_gqa_rope_append_f32): qkv f32 [R * U, >= (H + 2 Hkv) dk] packed q | k | v, kc / vc f32 [R, Umax, Hkv dk] views of the
+    layer's caches, cos / sin f32 [>= Umax, dk / 2], begin i32 [R] on the device or None -> out f32 [R * U, H dk].  Slots
+    [r, p0:p0 + U] receive the rotated keys and the values; nothing else is written, nothing at or beyond p0 is read."""
+    U, p0 = int(U), int(p0)
+    if U < 1 or p0 < 0 or kc.ndim != 3 or p0 + U > kc.shape[1]:
+        raise _C.F5EError(f"gqa_rope_append_f32: need U = {U} >= 1 new positions from p0 = {p0} >= 0 inside the cached ones")
+    front, out, P, dk = _gqa_common("gqa_rope_append_f32", qkv, kc, vc, cos, sin, heads, kv_heads, U, begin, out)
+    check(lib().f5e_gqa_rope_append_f32(*front, U, P, int(heads), int(kv_heads), dk, p0, float(scale)), "f5e_gqa_rope_append_f32")
+    return out
+
+
+def gqa_rope_decode_dev_f32(qkv: Tensor, kc: Tensor, vc: Tensor, cos: Tensor, sin: Tensor, rec: Tensor, heads: int, kv_heads: int,
+                            scale: float, begin: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """One position from the step record (f5e_gqa_rope_decode_dev_f32): qkv f32 [R, >= (H + 2 Hkv) dk], kc / vc f32
+    [R, P, Hkv dk], rec i32 [8] on the device -> out f32 [R, H dk].  p = rec[0] clamped to [0, P - 1]; slot [r, p] receives the
+    step's rotated key and its value.  The launch does not depend on p."""
+    front, out, P, dk = _gqa_common("gqa_rope_decode_dev_f32", qkv, kc, vc, cos, sin, heads, kv_heads, 1, begin, out)
+    check(lib().f5e_gqa_rope_decode_dev_f32(*front, P, int(heads), int(kv_heads), dk, _rec(rec, "gqa_rope_decode_dev_f32"),
+                                            float(scale)), "f5e_gqa_rope_decode_dev_f32")
+    return out
+
+
+def llm_pick_dev(logits: Tensor, tokens: Tensor, last: Tensor, done: Tensor, alive: Tensor, rec: Tensor, *, eos, pad: int,
+                 do_sample: bool = False, penalty: float = 1.0, temperature: float = 1.0, top_k: int = 1, top_p: float = 1.0,
+                 begin: Optional[Tensor] = None, row_key: Optional[Tensor] = None, serial: Optional[Tensor] = None,
+                 keep_id: Optional[Tensor] = None, keep_p: Optional[Tensor] = None, keep_n: Optional[Tensor] = None,
+                 V: Optional[int] = None) -> Tensor:
+    """f5e_llm_pick_dev: repetition penalty over tokens[r, begin[r]:p + 1], then the arg max (``do_sample`` False) or
+    temperature, top-k, top-p and an inverse-CDF draw keyed by (seed, row_key[r], serial[r], p), at the step record's position;
+    then ``alive`` and p += 1.  ``eos``: up to 4 ids; a done row writes ``pad``.  keep_id i32 / keep_p f32 [R, 64], keep_n i32
+    [R]: the survivors, for the parity tests."""
+    if not isinstance(logits, Tensor) or logits.ndim != 2 or tokens.ndim != 2 or tokens.shape[0] != logits.shape[0]:
+        raise _C.F5EError("llm_pick_dev: logits [R, >= V] and tokens [R, >= 2]; there is no CPU path")
+    R = logits.shape[0]
+    V = logits.shape[1] if V is None else int(V)
+    if V > logits.shape[1]:
+        raise _C.F5EError(f"llm_pick_dev: V = {V} exceeds the {logits.shape[1]} columns of logits")
+    if last.shape != (R,) or done.shape != (R,) or alive.numel() != 1:
+        raise _C.F5EError(f"llm_pick_dev: last [{R}], done [{R}], alive [1]")
+    eos = [int(e) for e in ([eos] if isinstance(eos, int) else eos)]
+    if len(eos) > 4:
+        raise _C.F5EError(f"llm_pick_dev: at most 4 eos ids (got {len(eos)})")
+    lp, ld = _rows(logits, (F32,), "llm_pick_dev: logits", max(V, 1), vec=1)
+    tp, ld_tok = _rows(tokens, (I32,), "llm_pick_dev: tokens", 2, vec=1)
+    bp = None if begin is None else _vec(begin, I32, "llm_pick_dev: begin", (R,))
+    if do_sample and (row_key is None or serial is None or row_key.shape != (R,) or serial.shape != (R,)):
+        raise _C.F5EError(f"llm_pick_dev: sampling needs row_key [{R}] and serial [{R}]")
+    kid = None if keep_id is None else _vec(keep_id, I32, "llm_pick_dev: keep_id", (R, LLM_MAX_TOP_K))
+    kp = None if keep_p is None else _vec(keep_p, F32, "llm_pick_dev: keep_p", (R, LLM_MAX_TOP_K))
+    kn = None if keep_n is None else _vec(keep_n, I32, "llm_pick_dev: keep_n", (R,))
+    eos_arr = (C.c_int * max(len(eos), 1))(*eos)
+    require_device()
+    check(lib().f5e_llm_pick_dev(_stream(), lp, ld, tp, ld_tok, tokens.shape[1], bp, _p(last, I32, "last"), _p(done, I32, "done"),
+                                 _p(alive, I32, "alive"), R, V, _rec(rec, "llm_pick_dev"), 1 if do_sample else 0, float(penalty),
+                                 float(temperature), int(top_k), float(top_p), C.cast(eos_arr, C.c_void_p), len(eos), int(pad),
+                                 _p(row_key, I32, "row_key"), _p(serial, I32, "serial"), kid, kp, kn), "f5e_llm_pick_dev")
+    return last

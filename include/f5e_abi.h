@@ -1161,6 +1161,70 @@ F5E_API int f5e_cif_fire_f32(f5e_stream st, const float* alpha, int ld_alpha, co
 F5E_API int f5e_nar_pick(f5e_stream st, const float* logits, long long ld, const int* n, int* arg, float* logp, int* ids,
                  int* len_out, float* score, int B, int L, int V, int sos, int eos, int blank, int pad);
 
+/* ---------------------------------------------------------------- Qwen2 chat model (csrc/llm.hip) -------------- */
+/* What a Qwen2-style decoder-only language model needs around f5e_gemm_f32_w16 (prefill) and f5e_gemm_f32_w16_skinny (decode):
+ * DESIGN 4s.  fp32 throughout.  No allocation, no synchronisation, no floating-point atomics, no workgroup waits for another;
+ * every reduction runs in a fixed order, so a launch is bit-reproducible, capturable, and a row's result does not depend on
+ * how many rows the call has.  What changes per token is read on the device: ids, `last`, and the step record `rec` of the
+ * Whisper step (DEVICE i32 [8], 16-byte aligned: rec[0] = p, rec[2] / rec[3] = the seed's low / high word). */
+
+/* y[m][:] = (x[m][:] * rsqrt(mean(x[m][:]^2) + eps)) * w, the products in that order (Qwen2RMSNorm in fp32).  x f32 [M][ldx],
+ * w f32 [D], out f32 [M][ldo]; out may be x.  One wave per row.  D % 4 == 0, strides multiples of 4 floats, 16-byte aligned
+ * (else F5E_ERR_BAD_SHAPE); D <= 8192 (else F5E_ERR_UNSUPPORTED). */
+F5E_API int f5e_rmsnorm_f32(f5e_stream st, const float* x, int ldx, const float* w, float* out, int ldo, int M, int D, float eps);
+/* out[m][i] = silu(gu[m][i]) * gu[m][I + i], silu(x) = x / (1 + expf(-x)) with the accurate expf.  gu f32 [M][ld >= 2 I] (the
+ * fused gate | up projection), out f32 [M][ldo >= I]; I % 4 == 0, strides multiples of 4 floats, 16-byte aligned. */
+F5E_API int f5e_swiglu_f32(f5e_stream st, const float* gu, int ld, float* out, int ldo, int M, int I);
+/* out[i][:] = emb[ids[i]][:] for i < n, widened exactly (csrc/w_load.h).  ids DEVICE i32 [n], clamped to the table; emb
+ * [table_rows][D] f32 (16-byte aligned) or fp16 / bf16 (wtype = F5E_W_*, 8-byte aligned); out f32 [n][D], D % 4 == 0.  The ids
+ * are read on the device, so the decode step's form is this call with ids = last and n = R: it needs no position. */
+F5E_API int f5e_llm_embed_f32(f5e_stream st, const int* ids, const float* emb, float* out, int n, int D, int table_rows);
+F5E_API int f5e_llm_embed_w16(f5e_stream st, const int* ids, const void* emb, int wtype, float* out, int n, int D, int table_rows);
+/* Attention with rotary positions and grouped heads.  qkv f32 [rows][ld_qkv >= (H + 2 Hkv) dk] packed q | k | v; kc / vc the
+ * layer's f32 caches, element (r, j, c) at r*row_stride + j*pos_stride + c, c < Hkv*dk; begin DEVICE i32 [R] or NULL: the
+ * row's left padding; cos / sin f32 [max_pos][dk/2], max_pos >= the cached positions.  Query head h uses key/value head
+ * h / (H / Hkv).  Position j of row r is rotated at pos = max(j - begin[r], 0):
+ *   x'[d] = x[d] cos[pos][d] - x[d + dk/2] sin[pos][d] (d < dk/2), x[d] cos[pos][d - dk/2] + x[d - dk/2] sin[pos][d - dk/2]
+ * (otherwise); two products and one addition per element.  K is filed in the cache rotated, V bit for bit.
+ * Limits: dk in {32, 64, 128}, 1 <= H / Hkv <= 8, at most 4096 cached positions (else F5E_ERR_UNSUPPORTED); strides multiples
+ * of 4 floats, pointers 16-byte aligned, R, H <= 65535 (else F5E_ERR_BAD_SHAPE).  A row's output equals its R = 1 call's.
+ *
+ * f5e_gqa_rope_append_f32: the U new positions p0 .. p0+U-1 (row r*U + u of qkv / out) behind p0 cached ones, with the masking,
+ * containment and read / write rules of f5e_attn_append_f32 (begin clamped to [0, p0 + U]; cached keys from the caches, new keys
+ * from qkv under the causal mask; only slots [r][p0 .. p0+U-1] are written and only slots below p0 read; a query below begin[r]
+ * gives exact zeros) on its wave tile.  p0 = 0 is the prefill, p0 > 0 the next turn of a conversation.
+ *
+ * f5e_gqa_rope_decode_dev_f32: one position p = clamp(rec[0], 0, P - 1), qkv / out f32 [R][..].  Grid (Hkv, R), independent of
+ * p: one workgroup serves the H / Hkv query heads of its group and reads every cached element once for all of them; keys are
+ * split over the waves of its 512 threads, maxima, sums and partial outputs merged through LDS in a fixed order.  begin
+ * clamped to [0, p].
+ * Slot [r][p] receives the step's key (rotated) and value; no other slot is written. */
+F5E_API int f5e_gqa_rope_append_f32(f5e_stream st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                            int pos_stride, const int* begin, const float* cos, const float* sin, int max_pos, float* out,
+                            int ldo, int R, int U, int Umax, int H, int Hkv, int dk, int p0, float scale);
+F5E_API int f5e_gqa_rope_decode_dev_f32(f5e_stream st, const float* qkv, int ld_qkv, float* kc, float* vc, long long row_stride,
+                                int pos_stride, const int* begin, const float* cos, const float* sin, int max_pos, float* out,
+                                int ldo, int R, int P, int H, int Hkv, int dk, const int* rec, float scale);
+/* The pick of transformers' sampling call, one workgroup per row, the logits [R][ld >= V] read once, at
+ * p = clamp(rec[0], 0, n_tok - 2) (n_tok = the columns of a token row, ld_tok its stride):
+ *   1. repetition penalty: every class that occurs in tokens[r][begin[r] .. p] gets x < 0 ? x * penalty : x / penalty, once;
+ *   2. do_sample = 0: the lowest index among the maxima;
+ *   3. do_sample = 1: x / temperature; exactly the top_k largest survive (the lower id first on equal values:
+ *      TopKLogitsWarper keeps every class tied with the k-th); softmax over them; in ascending order of probability a survivor
+ *      is dropped while the cumulative sum up to and including it is <= 1 - top_p, never the largest (TopPLogitsWarper);
+ *      the first survivor, in descending order, whose sequential fp32 cumulative sum reaches u * total is drawn,
+ *      u = ((w >> 8) + 0.5) 2^-24 from word 0 of Philox4x32-10(counter = (0, p, serial[r], row_key[r]), key = the seed);
+ *   4. tokens[r][p + 1] and last[r] = the pick; done[r] 0 -> 1 on any of the n_eos <= 4 ids of the HOST array eos; a row that
+ *      is done writes `pad`; then one workgroup writes *alive = rows not done and rec[0] += 1.
+ * keep_id i32 [R][64], keep_p f32 [R][64], keep_n i32 [R] (each may be NULL): the survivors in descending order, their
+ * renormalised probabilities and their count (greedy: the pick, 1 and 1; a done row: count 0).  Nothing else is written.
+ * penalty >= 1, temperature > 0, 0 < top_p <= 1 (else F5E_ERR_BAD_SHAPE); 1 <= top_k <= min(64, V), 2 <= V <= 262144 (else
+ * F5E_ERR_UNSUPPORTED). */
+F5E_API int f5e_llm_pick_dev(f5e_stream st, const float* logits, long long ld, int* tokens, int ld_tok, int n_tok, const int* begin,
+                     int* last, int* done, int* alive, int R, int V, int* rec, int do_sample, float penalty, float temperature,
+                     int top_k, float top_p, const int* eos, int n_eos, int pad, const int* row_key, const int* serial,
+                     int* keep_id, float* keep_p, int* keep_n);
+
 /* ---------------------------------------------------------------- hipGraph capture --------------------------- */
 F5E_API int f5e_graph_begin(f5e_stream st);
 F5E_API int f5e_graph_end(f5e_stream st, void** graph_exec_out);

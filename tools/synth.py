@@ -269,3 +269,40 @@ def init_whisper_state(shapes: Dict[str, tuple], seed: int = 99, gain: float = 1
             fan_in = math.prod(shape[1:])
             out[name] = r * math.sqrt(gain / fan_in)
     return out
+
+
+def qwen2_config_fields(**kw) -> Dict:
+    """The config.json fields of Qwen2.5-3B-Instruct (public model card) that ``f5e_tts_amd.infer.qwen2.Qwen2Config.from_dict``
+    takes; ``kw`` overrides (fewer layers for quick runs)."""
+    f = dict(model_type="qwen2", vocab_size=151936, hidden_size=2048, num_hidden_layers=36, num_attention_heads=16,
+             num_key_value_heads=2, intermediate_size=11008, rms_norm_eps=1e-6, rope_theta=1000000.0, max_position_embeddings=32768,
+             tie_word_embeddings=True)
+    f.update(kw)
+    return f
+
+
+def init_qwen2_state(fields: Dict, seed: int = 77, device="cpu", dtype=torch.bfloat16) -> State:
+    """Seeded weights under ``Qwen2ForCausalLM``'s names for ``fields`` (``qwen2_config_fields``): matrices N(0, 1 / fan_in),
+    biases N(0, 0.02), norm weights 1 + N(0, 0.1), token embedding N(0, 0.02); matrices in ``dtype``, the rest fp32.  ``device``:
+    where the draws are made (3e9 parameters at full size; a GPU stream of draws differs from the CPU's)."""
+    g = torch.Generator(device=device).manual_seed(seed)
+    D, I, V = fields["hidden_size"], fields["intermediate_size"], fields["vocab_size"]
+    H, Hkv = fields["num_attention_heads"], fields["num_key_value_heads"]
+    dk = fields.get("head_dim") or D // H
+
+    def mat(n, k, std=None):
+        return (torch.randn(n, k, generator=g, device=device) * (std if std is not None else k ** -0.5)).to(dtype)
+
+    def vec(n, mean, std):
+        return mean + std * torch.randn(n, generator=g, device=device)
+    sd = {"model.embed_tokens.weight": mat(V, D, 0.02), "model.norm.weight": vec(D, 1.0, 0.1)}
+    if not fields.get("tie_word_embeddings"):
+        sd["lm_head.weight"] = mat(V, D)
+    for i in range(fields["num_hidden_layers"]):
+        p = f"model.layers.{i}."
+        for n, h in (("q", H), ("k", Hkv), ("v", Hkv)):
+            sd[p + f"self_attn.{n}_proj.weight"], sd[p + f"self_attn.{n}_proj.bias"] = mat(h * dk, D), vec(h * dk, 0.0, 0.02)
+        sd[p + "self_attn.o_proj.weight"] = mat(D, H * dk)
+        sd[p + "mlp.gate_proj.weight"], sd[p + "mlp.up_proj.weight"], sd[p + "mlp.down_proj.weight"] = mat(I, D), mat(I, D), mat(D, I)
+        sd[p + "input_layernorm.weight"], sd[p + "post_attention_layernorm.weight"] = vec(D, 1.0, 0.1), vec(D, 1.0, 0.1)
+    return sd
